@@ -39,6 +39,7 @@ FP32_VECTOR_PEAK_TFLOPS = 157.3                           # MI355X_MICROARCH.md:
 ALGO_FLOP_PER_SAMPLE = 445.0                              # flop per tuner input sample, 256 channels
 C3_FFT, C3_HOP = 65536, 32768                             # BASELINE config 3
 C3_BYTES_PER_FRAME = 12 * C3_FFT                          # 8 B in + 4 B dB out per bin
+DUMP_MAX_BYTES = 64 << 20                                 # --dump-outputs: at most this much in all
 
 
 def parse():
@@ -98,7 +99,17 @@ def parse():
                          "exits (faulthandler): a hang becomes an error that says where.  0 turns it off")
     ap.add_argument("--backend", default="nccl",
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo lets two ranks share one GPU in tests)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c2: write what the timed path computed in its last step -- rank 0's channel IQ and audio of every "
+                         "channel (a fixed, seeded sample of the channels beyond %d MB) -- to DIR/<name>.npy.  The timed "
+                         "stream then starts from the tuner's stream-start state (wr_tuner_seek), so the same arguments give "
+                         "the same outputs from run to run" % (DUMP_MAX_BYTES >> 20))
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.workload != "c2":
+        ap.error("--dump-outputs: only the c2 workload writes its outputs")
+    return args
 
 
 def _hip_runtime():
@@ -793,6 +804,29 @@ def run_c5(args, torch, dist, rank, world, device_index, local_rank=0, have=1):
     return out
 
 
+def dump_outputs(tuner, channels, n, dirpath):
+    """--dump-outputs: the last block's channel IQ [channel][2 * frames] (interleaved re, im) and audio
+    [channel][frames] as float32, and the channel numbers they belong to (float64).  A tuner whose outputs
+    exceed DUMP_MAX_BYTES writes a sample of its channels, drawn with a fixed seed."""
+    import numpy as np
+    from webradio_amd import capi
+    iq0 = tuner.fetch(0, capi.WR_STAGE_CHAN_IQ, 2 * n)         # (a block of n frames has fewer at either rate)
+    au0 = tuner.fetch(0, capi.WR_STAGE_AUDIO, n)
+    per_channel = (iq0.size + au0.size) * 4
+    keep = max(1, min(channels, (DUMP_MAX_BYTES - 8 * channels) // per_channel))
+    chans = np.arange(channels) if keep == channels else \
+        np.sort(np.random.default_rng(0).choice(channels, keep, replace=False))
+    iq = np.empty((keep, iq0.size), np.float32)
+    audio = np.empty((keep, au0.size), np.float32)
+    for i, ch in enumerate(chans):
+        iq[i] = tuner.fetch(int(ch), capi.WR_STAGE_CHAN_IQ, iq0.size)
+        audio[i] = tuner.fetch(int(ch), capi.WR_STAGE_AUDIO, au0.size)
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, "chan_iq.npy"), iq)
+    np.save(os.path.join(dirpath, "audio.npy"), audio)
+    np.save(os.path.join(dirpath, "channels.npy"), chans.astype(np.float64))
+
+
 def finish(out, dist, gpus):
     """The JSON line is the LAST line the job writes: RCCL prints its version banner through C stdio
     when NCCL_DEBUG=VERSION is set (it is on the GPU boxes); every rank pushes that out, the ranks
@@ -954,6 +988,12 @@ def main():
     # (an event record between two launches costs the stream ~10 us: as few pairs as the stride allows -- at the driver's 20 steps
     # ONE pair around the five launches, recorded before the first and behind the last)
     stride = max(1, min(args.profile_stride, n_launches))
+    if args.dump_outputs:
+        # the state the warm-up and the timed settling left depends on how many steps they took: start the stream over
+        # (phase 0, empty histories) with the block that precedes blocks[0] in the resident stream, untimed -- a seek
+        # still pending would keep the first timed block out of the streaming launch
+        tuner.seek(0)
+        tuner.submit_device(blocks[nb - 1], n)
     tuner.flush()
     if tuner.stream_info()[2]:                           # (not with --warmup 0 --settle-ms 0: nothing to fetch yet)
         tuner.fetch(0, capi.WR_STAGE_AUDIO, n * B)       # a fetch looks at the launch the settling steps left closed: its count is in
@@ -974,6 +1014,8 @@ def main():
     a = tuner.fetch(0, capi.WR_STAGE_AUDIO, n * B)
     assert a.size and a.size % (n // 400 // 5) == 0 and bool((a == a).all()) and float(abs(a).max()) > 0.0
     long_blocks = tuner.stream_long_blocks() - long0     # (the fetch above looked at the closed launch: the count is in)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tuner, args.channels, n, args.dump_outputs)
 
     # the same job the other ways the library can run it, outside the headline's timed region: a kernel launch per block
     # (r01-r04's like-for-like figure) and four held blocks per launch (r02-r04's headline: up to 120 ms of added audio latency)

@@ -49,3 +49,13 @@ def test_ranks_that_share_a_gpu_over_rccl_are_an_error_not_a_measurement():
     two = [dict(same[0]), dict(same[1], pci_bus_id="0000:15:00.0", device_index=1)]
     recs, distinct = bench.gather_ranks(FakeDist(two), 2, two[0], "nccl")
     assert distinct
+
+
+@pytest.mark.parametrize("extra,says", [(["--steps", "0"], b"--steps must be >= 1"),
+                                        (["--workload", "c5", "--dump-outputs", "out"], b"only the c2 workload")],
+                         ids=["no-steps", "c5-dump"])
+def test_arguments_that_cannot_be_measured_are_refused(extra, says):
+    """Before any GPU is looked for: --steps is the number of timed steps and must be one at least, and --dump-outputs
+    writes the C2 workload's outputs only."""
+    p = _proc.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, cwd=ROOT, check=False, timeout=60)
+    assert p.returncode == 2 and says in p.stderr, p.stderr[-2000:]

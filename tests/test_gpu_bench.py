@@ -112,18 +112,24 @@ def _check_ranks(j, world, backend):
     assert max(r["seconds"] for r in rk) <= j["ms_per_step"] * j["steps"] / 1e3 * 1.001 + 1e-6
 
 
+# Ranks that share the one GPU of the test box, beside this process (which holds it through the `dev` fixture): no more
+# than six processes may have a GPU open at once, so the multi-rank path is walked at four ranks, not a node's eight.
+SHARED_GPU_RANKS = 4
+
+
 @pytest.mark.parametrize("workload", ["c2", "c5"])
-def test_eight_rank_line_on_one_gpu(workload):
-    """BASELINE configs 4 and 5 as far as a one-GPU box can walk them: EIGHT ranks started by bench.py itself (file store,
-    gloo: they share the GPU), each with its own 256-channel tuner (c2) or its chunks of the one stream and a halo from its
-    ring neighbour (c5).  The line carries eight rank records."""
+def test_multi_rank_line_on_one_gpu(workload):
+    """BASELINE configs 4 and 5 as far as a one-GPU box can walk them: SHARED_GPU_RANKS ranks started by bench.py itself
+    (file store, gloo: they share the GPU), each with its own 256-channel tuner (c2) or its chunks of the one stream and a
+    halo from its ring neighbour (c5).  The line carries a rank record for each of them."""
     extra = ["--workload", "c5"] if workload == "c5" else []
-    out = _proc.output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
+    world = SHARED_GPU_RANKS
+    out = _proc.output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
                         "--backend", "gloo", "--settle-ms", "20", "--resident-blocks", "4", "--spawn-timeout", "400",
                         "--rdzv-timeout", "200"] + extra, cwd=ROOT, env=_plain_env(), timeout=460)
     j = _line(out)
-    assert j["n_gpus"] == 8 and j["steps"] == 3
-    _check_ranks(j, 8, "gloo")
+    assert j["n_gpus"] == world and j["steps"] == 3
+    _check_ranks(j, world, "gloo")
     if workload == "c5":
         assert all(r["ring_exchanges"] >= 3 for r in j["ranks"])
 
@@ -273,3 +279,27 @@ def test_c5_halo_through_the_native_ring():
     j = _line(out)
     assert j["n_gpus"] == 1 and j["config"]["halo"] == "ring" and "wr_ring" in j["config"]["workload"]
     assert j["config"]["ring_exchanges"] == 3 + 1 + 1
+
+
+def test_dump_outputs_are_the_last_steps_and_repeat(tmp_path):
+    """--dump-outputs writes the last timed step's channel IQ and audio of every channel; the same arguments give the same
+    arrays whatever the untimed settling took (the timed stream starts from the stream-start state), and --steps picks
+    which block is the last one."""
+    import numpy as np
+
+    def run(d, steps, settle_ms):
+        out = _proc.output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1",
+                            "--settle-ms", str(settle_ms), "--no-cpu-baseline", "--no-secondary",
+                            "--dump-outputs", str(tmp_path / d)], cwd=ROOT, timeout=300)
+        assert _line(out)["steps"] == steps
+        return {k: np.load(str(tmp_path / d / (k + ".npy"))) for k in ("chan_iq", "audio", "channels")}
+
+    a, b, c = run("a", 5, 0), run("b", 5, 40), run("c", 6, 0)
+    assert a["chan_iq"].dtype == np.float32 and a["chan_iq"].shape == (256, 2 * 10_000)
+    assert a["audio"].dtype == np.float32 and a["audio"].shape == (256, 2_000)
+    assert np.array_equal(a["channels"], np.arange(256, dtype=np.float64))
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert bool(np.isfinite(a["chan_iq"]).all()) and float(np.abs(a["audio"]).max()) > 0.0
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert not np.array_equal(a["chan_iq"], c["chan_iq"])
