@@ -304,7 +304,7 @@ int wr_chan_set_state(wr_tuner *tuner, int chan, unsigned int phase, const float
  * by at least twice their channel filter's length is staged sparsely -- only the frames under the taps and the block's
  * tail cross PCIe, read by a kernel on the device's stream (see wr_stage_windows_from_host); like any copy out of
  * page-locked memory it is asynchronous: the block must stay untouched until wr_dev_wait_uploads / wr_dev_sync.
- * $WR_HOST_SPARSE=0: the whole block, as before.  wr_tuner_last_staging says how the last WR_HOST block travelled:
+ * wr_tuner_last_staging says how the last WR_HOST block travelled:
  * 0 none yet, 1 copied whole, 2 staged sparsely, 3 (r06) streamed: a wr_tuner_submit_u8 block out of page-locked memory
  * under wr_tuner_set_streaming(tuner, 2) -- its bytes cross PCIe as a DMA copy on the library's upload stream and the
  * streaming launch's doorbell is rung by a stream memory operation behind them; nothing waits, and the block must stay
@@ -359,7 +359,7 @@ int wr_tuner_fetch_audio_all(wr_tuner *tuner, float *out_host, size_t out_capaci
  * decimations are not queued (fetch per channel then).  depth 0 frees the ring.
  * r04: a deferred post stage writes its audio into the slot ITSELF (the slot is page-locked host memory mapped into the
  * device's address space; the kernel stores every sample there as well as in device memory), so the block is in the ring
- * when its launch has run and no copy is enqueued behind it ($WR_RING_DIRECT=0: the copy, as before). */
+ * when its launch has run and no copy is enqueued behind it. */
 int wr_tuner_audio_ring(wr_tuner *tuner, unsigned int depth);
 /* oldest block not yet released: waits for its copy, then channel slot s (wr_chan_slot) is at
  * (*audio_host) + s * (*chan_stride), *frames floats each; *seq counts submits from 0 (gaps =

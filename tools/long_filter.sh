@@ -9,8 +9,6 @@ for l in 128 256; do
 	q "QT_L1=$l"
 	q "QT_L2=$l"
 	q "QT_L2=$l QT_KEEP=1"
-	q "QT_L2=$l WR_POST_FLUSH_RUN=1"
-	q "QT_L2=$l WR_POST_FLUSH_RUN=2"
 done
 q "QT_KEEP=1"
 q "QT_L1B=64"

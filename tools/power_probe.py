@@ -1,6 +1,5 @@
 """What the package draws (rocm-smi, sampled from a thread every 0.2 s) while the GPU runs: nothing; the streaming launch back to
-back (C2, 400-block launches); the same with the post stage's body switched off (WR_STREAM_DBG=1: results wrong); the isolated
-tap mix (tools/ubench_tap, built by hand: see its first line); a plain HBM copy.  -> profiles/r06_power.txt
+back (C2, 400-block launches); the isolated tap mix (tools/ubench_tap, built by hand: see its first line); a plain HBM copy.  -> profiles/r06_power.txt
     python tools/power_probe.py"""
 import sys, time, os, subprocess, threading, re
 sys.path.insert(0, '.')
@@ -38,15 +37,6 @@ while time.perf_counter() - t0 < 12.0:
     t.flush(); torch.cuda.synchronize(); reps += 1
 t1 = time.perf_counter()
 marks.append(("stream", (t1 - t0) / (reps * K) * 1e6, t1))
-os.environ["WR_STREAM_DBG"] = "1"
-t0 = time.perf_counter(); reps = 0
-while time.perf_counter() - t0 < 8.0:
-    for i in range(K):
-        t.submit_device(blocks[i % nb], n)
-    t.flush(); torch.cuda.synchronize(); reps += 1
-t1 = time.perf_counter()
-marks.append(("stream, no post body", (t1 - t0) / (reps * K) * 1e6, t1))
-del os.environ["WR_STREAM_DBG"]
 t.destroy()
 if os.path.exists("tools/ubench_tap"):
     for _ in range(5):

@@ -1,5 +1,8 @@
-"""-DSTREAM_TL build, WR_STREAM_DBG=16: when does each block of a K-block stream finish, from the launch's first instruction?"""
+"""When does each block of a K-block stream finish, from the launch's first instruction?  Needs a library built with
+-DSTREAM_TL in place of the product library:
+    make -C webradio_amd/csrc clean && make -C webradio_amd/csrc WR_DEFS=-DSTREAM_TL"""
 import sys, time, os
+os.environ.setdefault("WR_STREAM_TL", "1")        # the library then hands the stream launch its timeline buffer
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, ctypes, numpy as np
 from webradio_amd import capi, synth

@@ -1,5 +1,6 @@
 """Per-wave timeline of k_tuner_ddc at C2 (development aid): needs a library built with
--DDDC_TIMELINE (tools/mkvariant.sh tl -DDDC_TIMELINE) in place of the product library."""
+-DDDC_TIMELINE in place of the product library:
+    make -C webradio_amd/csrc clean && make -C webradio_amd/csrc WR_DEFS=-DDDC_TIMELINE"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -883,17 +883,9 @@ extern "C" int wr_u8_to_f32_from_host(wr_dev *d, const uint8_t *in_host, float *
 	}
 	std::lock_guard<std::mutex> up_guard(*d->upload_lock);         /* the ring of tails: calls may come from several threads */
 	/* The bytes come over with the DMA engine and are converted out of device memory.  (r03 tried the kernel reading
-	 * host memory itself, WR_U8_ZEROCOPY=1: one launch and 47 GB/s -- but kernels running beside it take up to ten times
+	 * host memory itself: one launch and 47 GB/s -- but kernels running beside it take up to ten times
 	 * as long, k_tuner_post 14 -> 107 us, a 32 MB device copy 13 -> 146 us: its reads, microseconds each, sit in the
 	 * same L2 / fabric queues as everybody's HBM traffic.  A DMA copy does not go through them.) */
-	static const bool zerocopy = getenv("WR_U8_ZEROCOPY") && atoi(getenv("WR_U8_ZEROCOPY")) != 0;
-	if (zerocopy) {
-		unsigned long long n = 0;
-		if (int rc = upload_ahead_begin(d, (void *)out_dev, &n))
-			return rc;
-		HIP_TRY(wrk_u8_to_f32(d->up_stream, (const uint8_t *)mapped, out_dev, count));
-		return upload_ahead_end(d);
-	}
 	/* Only the COPY runs on the upload stream, into one of two raw buffers in turn; the conversion follows on the device's
 	 * stream once the copy's event has fired.  So the copies of consecutive blocks follow each other on the link without
 	 * a kernel in between (the upload stream waits for nothing but the conversion that last read the raw buffer it is about
@@ -939,25 +931,6 @@ extern "C" int wr_stage_windows_from_host(wr_dev *d, const void *in_host, int is
 	}
 	HIP_TRY(wrk_stage_windows(d->stream, mapped, is_u8 != 0, out_dev, nframes, period, length, tail_frames));
 	return upload_mark(d, d->stream);                  /* the host buffer is free again when the kernel has read it */
-}
-
-static bool host_sparse_enabled()
-{
-	static const bool on = !(getenv("WR_HOST_SPARSE") && atoi(getenv("WR_HOST_SPARSE")) == 0);
-	return on;
-}
-
-static bool lazy_seek_enabled()
-{
-	static const bool on = !(getenv("WR_LAZY_SEEK") && atoi(getenv("WR_LAZY_SEEK")) == 0);
-	return on;
-}
-
-/* WR_LONG_ROTATE=0: channel filters of 128 / 256 taps take the reference's arithmetic in every nco mode (r03's first version) */
-static bool long_rot_enabled()
-{
-	static const bool on = !(getenv("WR_LONG_ROTATE") && atoi(getenv("WR_LONG_ROTATE")) == 0);
-	return on;
 }
 
 /* ------------------------------------------------------------------ tuner -- */
@@ -2017,7 +1990,7 @@ static int tuner_submit_now(wr_tuner *t, const void *iq, size_t nframes, int whe
 		 * whole: the staging kernel brings over the frames under the taps and the tail (wr_stage_windows_from_host says
 		 * which), as floats whatever the source format.  Pageable memory, mixed shapes, dense windows: the copy, as before. */
 		bool sparse = false;
-		if (nframes && host_sparse_enabled() && !(((uintptr_t)iq | (uintptr_t)t->in_stage) & 15u)) {
+		if (nframes && !(((uintptr_t)iq | (uintptr_t)t->in_stage) & 15u)) {
 			unsigned int sd = 0, sl = 0;
 			bool same = true;
 			for (const Group *g : t->groups) {
@@ -2174,7 +2147,7 @@ static int tuner_submit_now(wr_tuner *t, const void *iq, size_t nframes, int whe
 			/* a channel filter of 128 or 256 taps: the plain kernel with the reference's arithmetic (wr_kernels.hip:
 			 * k_tuner_ddc_long), which also rolls phase and mixed history; r04: its ROTATE form carries the previous block's post stage like the 64-tap kernel */
 			HIP_TRY(wrk_tuner_ddc_long(st, L, g->dev, g->l1, d->table, d->num_cus,
-			                           t->nco_mode != WR_NCO_EXACT && g->long_uniform && long_rot_enabled(), g->long_one, d->hi_cs, d->lo_cs,
+			                           t->nco_mode != WR_NCO_EXACT && g->long_uniform, g->long_one, d->hi_cs, d->lo_cs,
 			                           g->post_pending ? &g->post_args : nullptr, &rode));
 		else
 			HIP_TRY(wrk_tuner_ddc(st, L, Gs, t->nco_mode == WR_NCO_ROTATE ? d->table_turn : d->table, d->hi_cs, d->lo_cs,
@@ -2208,7 +2181,7 @@ static int tuner_submit_now(wr_tuner *t, const void *iq, size_t nframes, int whe
 		 * fused pass -- deferred to the next launch where that launch can carry it. */
 		/* (r04: a group with a long channel filter defers too where its launch can carry a post stage: the ROTATE kernel,
 		 * every lane group on one long filter) */
-		const bool long_rides = g->l1 > WR_FIR_LENGTH && g->long_uniform && long_rot_enabled();
+		const bool long_rides = g->l1 > WR_FIR_LENGTH && g->long_uniform;
 		/* (r05: an audio filter of 128 / 256 taps -- k_tuner_post<D2, 2 | 4> -- goes out on its own behind the DDC: the
 		 * workgroups that ride are compiled for 64 taps) */
 		/* (r05: a group with a second channel stage defers as well -- its post stage reads chan_iq2, which the NEXT block's
@@ -2475,13 +2448,6 @@ static int stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, boo
 	HIP_TRY(wrk_stream_geometry(g->d2, groups, d->num_cus, &n_ddc, &n_post));
 	if (!n_ddc || !n_post)
 		return WR_OK;
-	if (getenv("WR_STREAM_NPOST")) {                        /* (development: another split of the resident workgroups) */
-		const unsigned int np = (unsigned int)atoi(getenv("WR_STREAM_NPOST"));
-		if (np >= 1u && np < n_ddc + n_post - 8u) {
-			n_ddc = n_ddc + n_post - np;
-			n_post = np;
-		}
-	}
 	/* (each on its own: an allocation that failed last time is tried again, never skipped because an earlier one stands) */
 	if (!s.ctl)
 		HIP_TRY(hipHostMalloc((void **)&s.ctl, sizeof(WrStreamCtl), hipHostMallocMapped | hipHostMallocCoherent));
@@ -2540,8 +2506,7 @@ static int stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, boo
 	A.wait_ticks = (unsigned long long)WR_STREAM_WAIT_MS * 100000ull;
 	A.n_ddc = n_ddc;
 	A.n_post = n_post;
-	A.dbg = getenv("WR_STREAM_DBG") ? (unsigned int)atoi(getenv("WR_STREAM_DBG")) : 0u;
-	if (A.dbg & 16u) {
+	if (getenv("WR_STREAM_TL") && atoi(getenv("WR_STREAM_TL"))) {      /* the timeline of a -DSTREAM_TL build */
 		static unsigned long long *tlbuf = nullptr;
 		if (!tlbuf)
 			HIP_TRY(hipHostMalloc((void **)&tlbuf, 8192 * 8 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
@@ -2555,7 +2520,7 @@ static int stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, boo
 	A.k1 = (unsigned int)k1;
 	A.d1 = g->d1;
 	A.is_u8 = u8 ? 1u : 0u;
-	A.ext = (s.ext || (getenv("WR_STREAM_EXT") && atoi(getenv("WR_STREAM_EXT")))) ? 1u : 0u;
+	A.ext = s.ext ? 1u : 0u;
 	A.slots = g->slots;
 	A.groups = groups;
 	for (unsigned int gi = 0; gi < groups; ++gi)
@@ -3000,13 +2965,6 @@ static Group *single_group(wr_tuner *t)
 	return g;
 }
 
-/* queue the copy of one block's audio, right behind the kernel that produces it */
-static bool ring_direct_enabled()
-{
-	static const bool on = !(getenv("WR_RING_DIRECT") && atoi(getenv("WR_RING_DIRECT")) == 0);
-	return on;
-}
-
 /* r04: the post stage whose arguments are being put together (a deferred one: it is launched later, riding in the next
  * block's launch or by a flush) may write its audio straight into the ring slot its block will be queued in -- the next
  * one to fill, which stays the next one until that block's own ring_push: pushes come in block order and this group is
@@ -3016,7 +2974,7 @@ static bool ring_direct_enabled()
  * copy if a slot is free by then), or page-locked memory that cannot be had. */
 static float *ring_reserve(wr_tuner *t, Group *g, size_t k2, unsigned int used)
 {
-	if (t->ring.empty() || !ring_direct_enabled())
+	if (t->ring.empty())
 		return nullptr;
 	std::lock_guard<std::mutex> lk(t->ring_lock);
 	if (single_group(t) != g || t->ring_count == t->ring.size())
@@ -3290,9 +3248,8 @@ extern "C" int wr_tuner_seek(wr_tuner *t, unsigned long long frame)
 		/* Lazily where the group's launch can take it (one channel-filter stage of up to 64 taps): nothing is launched
 		 * here, the next submit's DDC computes the phase in closed form and reads all-zero state sets, and the post
 		 * stage of the chunk before, if it is still waiting, rides in that launch as usual -- a time-sharded stream
-		 * (BASELINE config 5) then costs ONE launch per chunk instead of three (seek, DDC, post stage).
-		 * WR_LAZY_SEEK=0: as before. */
-		const bool lazy = !g->d1b && g->l1 <= WR_FIR_LENGTH && lazy_seek_enabled();
+		 * (BASELINE config 5) then costs ONE launch per chunk instead of three (seek, DDC, post stage). */
+		const bool lazy = !g->d1b && g->l1 <= WR_FIR_LENGTH;
 		if (!lazy && g->post_pending) {
 			/* a post stage still waiting for the next submit would write ITS end-of-block state over ours */
 			HIP_TRY(wrk_tuner_post_args(st, g->post_args));
@@ -3541,7 +3498,7 @@ extern "C" int wr_spectrum_push(wr_spectrum *s, const float *iq, size_t nframes,
 		/* WHERE it is kept: in page-locked HOST memory, brought there by the DMA engine.  A device-to-device copy is a copy
 		 * KERNEL on this runtime, and a kernel queued beside an open launch is trouble: dispatched while the launch still
 		 * fills the chip it holds workgroup slots the launch's own workgroups wait for, and its waves, behind spinning waves
-		 * of a higher priority, may never finish -- the launch then runs into its deadline (measured: tools/scratch/fe_loop.py,
+		 * of a higher priority, may never finish -- the launch then runs into its deadline (measured:
 		 * 12 of 12 at the device stream's priority, 2 of 8 at the lowest).  Copies of 16 KB or less are kernels too
 		 * (GPU_FORCE_BLIT_COPY_SIZE), so at least 4096 frames (32 KB) of the block's end travel. */
 		const size_t MINF = 4096;

@@ -229,24 +229,16 @@ __device__ __forceinline__ void nt_store2(float2 *p, float2 v)
 
 /* write-through (sc1) stores: data that the NEXT launch reads (pass 1's intermediate) or nothing on the chip reads again
  * (the dB rows) leave the L2 as they are written, not at the end-of-kernel release.  r03, 121 frames on one box: pass 1
- * 25.6 -> 23.8 us, pass 2 16.9 -> 16.5 us (profiles/r03_fft_pass1_ablation.txt, section 4; FFT_PLAIN_STORE restores the old) */
+ * 25.6 -> 23.8 us, pass 2 16.9 -> 16.5 us (profiles/r03_fft_pass1_ablation.txt, section 4) */
 __device__ __forceinline__ void wt_store2(float2 *p, float2 v)
 {
-#ifdef FFT_PLAIN_STORE
-	*p = v;
-#else
 	union { float2 f; unsigned long long u; } cv;
 	cv.f = v;
 	__hip_atomic_store((unsigned long long *)p, cv.u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 }
 __device__ __forceinline__ void wt_store1(float *p, float v)
 {
-#ifdef FFT_PLAIN_STORE
-	*p = v;
-#else
 	__hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 }
 
 #define F256_S 272        /* LDS row stride (float2): 16 x 16 plus 16 -> conflict-free exchanges */
@@ -282,18 +274,12 @@ k_fft64k_pass1(const float2 *__restrict__ iq, size_t hop, const float *__restric
 #pragma unroll
 		for (int a = 0; a < 16; ++a)
 			nx[a] = x[(a * 16u + t) * 256u + col];
-#ifdef FFT_P1_PLAIN_WINDOW
-#pragma unroll
-		for (int a = 0; a < 16; ++a)
-			wv[a] = window[(a * 16u + t) * 256u + col];
-#else
 		const float4 *wp = (const float4 *)window_p1 + (size_t)blockIdx.x * 1024u + threadIdx.x;   /* [tile][a / 4][thread] */
 #pragma unroll
 		for (int q = 0; q < 4; ++q) {
 			const float4 w4 = wp[q * 256u];
 			wv[4 * q] = w4.x, wv[4 * q + 1] = w4.y, wv[4 * q + 2] = w4.z, wv[4 * q + 3] = w4.w;
 		}
-#endif
 	}
 #pragma unroll 1
 	for (unsigned int fi = 0; fi < FPW; ++fi) {
@@ -361,11 +347,7 @@ k_fft64k_pass2(const float2 *__restrict__ work, const float2 *__restrict__ tw256
 		const unsigned int t = threadIdx.x & 15u, r = threadIdx.x >> 4;
 #pragma unroll
 		for (int a = 0; a < 16; ++a)
-#ifdef FFT_P2_NT
-			v[a] = nt_load2(&win[(a * 256u + row0 + r) * 16u + t]);
-#else
 			v[a] = win[(a * 256u + row0 + r) * 16u + t];   /* column a*16 + t of row row0 + r (tiled, see pass 1) */
-#endif
 		fft16(v);
 		__syncthreads();                               /* the table */
 #pragma unroll
@@ -388,11 +370,7 @@ k_fft64k_pass2(const float2 *__restrict__ work, const float2 *__restrict__ tw256
 			if (bins)
 				bins[fbase + k] = v[kh];
 			if (db) {
-#ifdef FFT_P2_NT
-				__builtin_nontemporal_store(to_db(v[kh], scaledb), &db[fbase + ((k + 32768u) & 65535u)]);
-#else
 				wt_store1(&db[fbase + ((k + 32768u) & 65535u)], to_db(v[kh], scaledb));
-#endif
 			}
 		}
 	}
@@ -456,13 +434,6 @@ hipError_t wrk_bins_to_db(hipStream_t st, const float *bins, unsigned int n, flo
 #define FFT64K_P1_LONG_MIN 96u
 static int fft64k_p1_fpw(size_t batch)
 {
-	static int forced = -1;
-	if (forced < 0) {
-		const char *v = getenv("WR_FFT_P1_FPW");           /* 1, 2, 4: frames per pass-1 workgroup whatever the batch */
-		forced = v ? atoi(v) : 0;
-	}
-	if (forced == 1 || forced == 2 || forced == 4)
-		return forced;
 	return batch >= FFT64K_P1_LONG_MIN ? 4 : 1;
 }
 

@@ -202,14 +202,12 @@ hipError_t wrk_gather_rows(hipStream_t st, const float *src, size_t rows, size_t
  * its last channel-IQ row is out, whether or not another block follows (dsp/dspblock.cxx:169-212: a block's output
  * leaves within its own run()).  See k_tuner_stream in wr_kernels.hip. ---- */
 #define WR_STREAM_MAXJ   WR_STREAM_MAX_BLOCKS             /* blocks one streaming launch takes at most (the host then opens the next) */
-#ifndef WR_STREAM_RING
 #define WR_STREAM_RING   6u                /* blocks of channel IQ the ring between the DDC waves and the post stage holds.  r06: 6,
                                               not 8 -- the launch runs at the package's power limit (profiles/r06_power.txt) and the
                                               channel IQ's way to memory and back is a seventh of what it spends; 123 MB of ring
                                               (C2) beside the input windows stay in the 256 MB Infinity Cache where 164 MB did not
                                               quite: 29.8-30.0 against 30.5-30.7 us per block, 33.0-33.9 against 34.2-34.4 at the
                                               driver's 20 steps, two boxes; 5 and 4 leave the DDC too little room to run ahead */
-#endif
 struct WrStreamDesc {                      /* one submitted block */
 	unsigned long long cur;                /* device address of its frames (float pairs, or byte pairs) */
 	unsigned long long audio_host;         /* mapped page-locked ring slot that takes its audio too, or 0 */
@@ -265,8 +263,8 @@ struct WrStreamArgs {
 	unsigned long long  idle_ticks;        /* 100 MHz ticks without a bell after which the launch closes itself */
 	unsigned long long  wait_ticks;        /* ... any other wait may take before it gives up (an error) */
 	unsigned int        n_ddc, n_post;     /* workgroups per role; one more rings the bell */
-	unsigned int        dbg;               /* development switches (WR_STREAM_DBG): results are wrong with any of them set */
-	unsigned long long *tl;                /* WR_STREAM_DBG & 16: [wave][8] cycle counts of the DDC waves (development aid) */
+	unsigned long long *tl;                /* -DSTREAM_TL builds with WR_STREAM_TL=1: [wave][8] cycle counts of the DDC waves
+	                                          (development aid; wr_debug_stream_tl) */
 	unsigned long long  cur0, audio0;      /* block 0's descriptor (the launch exists because of it): here, not copied to
 	                                          device memory ahead of the launch -- two small copies on the stream cost the
 	                                          open 25 us; the bell wave puts it into WrStreamDev for whoever needs it later */

@@ -39,7 +39,7 @@ typedef __attribute__((address_space(3))) v4f lds_v4f;
 #define WR_CONSTANT __attribute__((address_space(4)))
 
 #ifdef DDC_TIMELINE
-/* development aid (tools/mkvariant.sh ... -DDDC_TIMELINE): per-wave s_memtime stamps of k_tuner_ddc */
+/* development aid (make WR_DEFS=-DDDC_TIMELINE): per-wave s_memtime stamps of k_tuner_ddc */
 #define TL_SLOTS 12
 __device__ unsigned long long g_ddc_tl[16384 * TL_SLOTS];
 extern "C" int wr_debug_timeline(unsigned long long *out, size_t n)
@@ -393,7 +393,6 @@ __device__ __forceinline__ void horner_close(v2f &y, v2f A, v2f cs)
  * falls as it gets through its units: whoever is behind goes first. */
 __device__ __forceinline__ void wave_prio(unsigned int level)
 {
-#ifndef DDC_NO_PRIO
 	if (level >= 3u)
 		__builtin_amdgcn_s_setprio(3);
 	else if (level == 2u)
@@ -402,13 +401,10 @@ __device__ __forceinline__ void wave_prio(unsigned int level)
 		__builtin_amdgcn_s_setprio(1);
 	else
 		__builtin_amdgcn_s_setprio(0);
-#endif
 }
 
-#ifndef ROT_SEG
 #define ROT_SEG 64                       /* measured on MI355X, C2: 16 -> 4.5e-8 / 40.9 us, 32 -> 6.7e-8 / 39.5 us,
                                             64 -> 1.2e-7 / 38.4 us (worst |IQ - bit-exact path| on +-0.4 signals / kernel) */
-#endif
 #define ROT_Q   (WR_FIR_LENGTH / ROT_SEG)
 #define SLOW_CH 4                          /* taps per memory round of the block-boundary paths */
 
@@ -484,16 +480,12 @@ __device__ __forceinline__ float2 input_frame(const float2 *__restrict__ cur, co
  *                 the last 63 demod outputs (audio filter history) and the last channel
  *                 frame (Demodulator::prev_i/q), into the other ping-pong set.
  */
-#ifndef POST_TK
 #define POST_TK 16u
-#endif
 #define POST_B 4u
-#ifndef POST_LB
 #define POST_LB 5u                       /* rows whose loads a wave of the stage phase has in flight together (measured
                                             at C2, us per block at 1 / 4 blocks per launch: 3 rows 34.7 / 30.5, 5 rows
                                             34.0 / 29.7, 6 rows 35.0 / 31.3, 9 rows 35.7 / 31.0 -- more rows, more
                                             registers: spills) */
-#endif
 #define POST_THREADS 512u
 /* What leaves the audio filter for the sink: af_gain and squelch (the reference has the two fields
  * and no code behind them, receiverhandler.cxx:112,118-119,127), then the sink's scale.
@@ -646,13 +638,7 @@ __device__ __forceinline__ void post_role(const WrPostArgs &A, unsigned int bx, 
 				 * block's first and last): the loads of POST_LB rows go out together, nothing to
 				 * decide per row -- the stage phase is a chain of memory round trips, and one per
 				 * row made the post workgroups the last to finish */
-#ifdef POST_SMALL_READS
-				/* (development, results wrong: every tile reads the same few hundred rows -- what the channel IQ's way back
-				 * from memory costs, profiles/r06_power.txt) */
-				const float2 *__restrict__ src = chan_iq + ((r0 - HIST) & 127u) * slots + s;
-#else
 				const float2 *__restrict__ src = chan_iq + (r0 - HIST) * slots + s;
-#endif
 				for (unsigned int r = beg; r < end; r += POST_LB) {
 					float2 z[POST_LB + 1u];
 					z[0] = src[((size_t)r - 1u) * slots];
@@ -801,28 +787,19 @@ k_tuner_post(WrPostArgs A)
 /* LDS plan of k_tuner_ddc: [0, 128 KiB) the two replicated NCO tables (SPLIT only),
  * then one private 2 x 512 B sample window per wave (double buffered across units). */
 #define DDC_TABLE_BYTES   (2u * WR_SPLIT_N * 32u * 8u)
-#ifndef DDC_WAVES
 #define DDC_WAVES         16u
-#endif
-#ifndef DDC_ROTATE_WGS_PER_CU
-#define DDC_ROTATE_WAVES      8u
-#define DDC_ROTATE_WGS_PER_CU 4u
-#endif
+#define DDC_ROTATE_WAVES      8u          /* every ROTATE variant (folded or per-lane taps): 8-wave workgroups, */
+#define DDC_ROTATE_WGS_PER_CU 4u          /* four per CU */
 #define DDC_LDS_BYTES     (DDC_TABLE_BYTES + DDC_WAVES * 2u * 512u)
-#ifndef DDC_LTAPS_SMALL
-#define DDC_LTAPS_SMALL 1                  /* the per-lane-taps ROTATE variant in 8-wave workgroups, four per CU, like the fast one */
-#endif
-#ifndef DDC_DEAL_WAYS
 #define DDC_DEAL_WAYS 2u                   /* measured at C2, us per block at 1 / 4 blocks per launch: in order (and as
                                               many workgroups as make the units come out even) 37.6 / 32.8, 2 ways
                                               36.8 / 32.0, 4 ways 37.0 / 32.0, 8 ways 38.5 / 32.0 */
-#endif
 
 /* PD2 > 0: workgroups n_ddc.. of the grid run the post stage (audio decimation PD2) of the
  * PREVIOUS block -- see post_role and wr_capi.hip: the two have nothing to do with each other
  * except that they share the CUs, the post stage's latency-bound phases filling in between the
  * DDC's arithmetic.  Their dependency is the kernel boundary before this launch. */
-/* r03: with DDC_ROLES the ROTATE kernel with folded taps splits its workgroups into roles:
+/* r03: the ROTATE kernel with folded taps splits its workgroups into roles:
  *   [0, n_ddc)               the persistent DDC waves: output frames kslow .. k1-1, whose 64-frame windows lie
  *                            inside this block -- ONE lean loop in the kernel itself, nothing else in its registers
  *   [n_ddc, n_ddc + n_bnd)   one wave per (lane group, frame k < kslow): the first ceil(63 / D1) frames of the
@@ -830,12 +807,6 @@ k_tuner_post(WrPostArgs A)
  *   [n_ddc + n_bnd, ...)     the previous block's post stage (PD2 != 0)
  * Everything but the lean loop is ddc_body, which the lean kernel reaches through a real call (its register
  * allocation is its own).  Kernels without roles (kslow = n_bnd = 0) ARE ddc_body: one generic loop. */
-#ifndef DDC_ROLES
-#define DDC_ROLES 1
-#endif
-#ifndef DDC_NG2
-#define DDC_NG2 1                          /* two lane groups per wave of the lean loop where the launch allows */
-#endif
 #define DDC_PARAMS \
 	const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u8, const float2 *__restrict__ hist, \
 	float2 *__restrict__ hist_next, size_t nframes, size_t k1, unsigned int d1, unsigned int slots, unsigned int groups, \
@@ -855,11 +826,7 @@ k_tuner_post(WrPostArgs A)
 /* the channel's phase at the block's first frame: kept from the block before, or -- the launch right after a
  * wr_tuner_seek (`seek_on`; the histories it reads are all-zero sets then) -- frame * step mod 2^32 in closed form
  * (downconverter.cxx:103), `seek_lo` = the frame's low 32 bits */
-#ifdef DDC_NO_LAZY_SEEK                          /* (timing comparisons only) */
-#define DDC_PHASE(s_) (phase[s_])
-#else
 #define DDC_PHASE(s_) (seek_on ? step[s_] * seek_lo : phase[s_])
-#endif
 #define DDC_ROLE_ALL      0                /* no roles: every frame, the state roll, the riding post stage */
 #define DDC_ROLE_BOUNDARY 1                /* one block-boundary unit per wave (or the post stage, by workgroup index) */
 #define DDC_ROLE_ROLL     2                /* the end-of-block state roll only */
@@ -953,7 +920,7 @@ ddc_body(DDC_PARAMS, v2f *lds, const int role)
 		wpg = k1u;                                       /* one unit, then out of the loop */
 	} else if (k >= wpg) {
 		k = k1u;                                         /* the few waves left over stay idle */
-	} else if (!LTAPS && DDC_DEAL_WAYS > 1u) {
+	} else if (!LTAPS) {
 		/* A wave that starts at k does ceil((k1 - k) / wpg) units: the low starts one more than the
 		 * high ones.  Neighbouring waves take their starts from DDC_DEAL_WAYS different parts of
 		 * [0, wpg) in turn, so that every workgroup -- and with it every SIMD: its waves go round
@@ -993,12 +960,8 @@ ddc_body(DDC_PARAMS, v2f *lds, const int role)
 	/* the window of the NEXT unit is fetched while this one is computed: its global-load
 	 * latency would otherwise sit in front of every unit */
 	float2 xnext = make_float2(0.0f, 0.0f);
-#ifndef DDC_PREFETCH1
-#define DDC_PREFETCH2 1                                 /* measured at C2: 38.1 -> 37.5 us */
-#endif
-#ifdef DDC_PREFETCH2
-	float2 xnext2 = make_float2(0.0f, 0.0f);         /* the unit after the next: an HBM + TLB miss can outlast a unit */
-#endif
+	float2 xnext2 = make_float2(0.0f, 0.0f);         /* the unit after the next: an HBM + TLB miss can outlast a unit
+	                                                    (measured at C2: 38.1 -> 37.5 us) */
 	const unsigned int s = g * 64u + lane;
 	if (k < k1u) {
 		{
@@ -1025,10 +988,8 @@ ddc_body(DDC_PARAMS, v2f *lds, const int role)
 			}
 		}
 		xnext = window_sample(k);
-#ifdef DDC_PREFETCH2
 		if (k + wpg < k1u)
 			xnext2 = window_sample(k + wpg);
-#endif
 	}
 
 	TL(2);                                                   /* per-channel state loaded (issued) */
@@ -1070,17 +1031,12 @@ ddc_body(DDC_PARAMS, v2f *lds, const int role)
 			for (int q = 0; q < ROT_Q; ++q)
 				csq[q] = nco<NCO>(P0 + (unsigned int)(q * ROT_SEG + ROT_SEG - 1) * st, table, hi_l, lo_l);
 		}
-#ifdef DDC_PREFETCH2
 		/* (the copy waits for the load issued one unit ago: the second slot buys little more than the
 		 * first.  Alternating two slots in a loop unrolled by two -- no copy -- spills under the
 		 * 64-VGPR bound and was slower, r02) */
 		xnext = xnext2;
 		if (kn + wpg < k1u)
 			xnext2 = window_sample(kn + wpg);
-#else
-		if (kn < k1u)
-			xnext = window_sample(kn);
-#endif
 		/* (per lane: lanes of channels with different filters read different copies of the window) */
 		const v2f *wbase = win + (buf * nset + mysel) * 64u;
 		const lds_v2f *w = (const lds_v2f *)wbase;
@@ -1276,9 +1232,6 @@ ddc_body(DDC_PARAMS, v2f *lds, const int role)
 			}
 		}
 		if (fl & PHASE_FLAG_ACTIVE) {
-#ifdef DDC_PLAIN_STORE
-			chan_iq[(size_t)k * slots + s] = make_float2(acc.x, acc.y);
-#else
 			/* Written once, read by the NEXT launch: a write-through (sc1) store streams the 20 MB of
 			 * channel IQ out while the taps run.  As plain stores they sat dirty in the L2s until the
 			 * end-of-kernel release wrote them back -- several microseconds in which nothing computes
@@ -1287,7 +1240,6 @@ ddc_body(DDC_PARAMS, v2f *lds, const int role)
 			cv.f = acc;
 			__hip_atomic_store((unsigned long long *)&chan_iq[(size_t)k * slots + s], cv.u, __ATOMIC_RELAXED,
 			                   __HIP_MEMORY_SCOPE_AGENT);
-#endif
 		}
 		k = kn;
 		TL(3u + tl_unit);                                    /* unit done (store issued) */
@@ -1359,9 +1311,7 @@ ddc_body(DDC_PARAMS, v2f *lds, const int role)
  * everything but the state roll away.  As a real call (tried) the kernel needs 936 bytes of stack per lane
  * for the 35 arguments and the call-clobbered registers: half a gigabyte of scratch for a full grid, which
  * the runtime then allocates and frees around EVERY dispatch -- 61 us per launch instead of 35.) */
-#ifndef DDC_RD
 #define DDC_RD 1                           /* lean loop: 16-byte window reads issued ahead of the taps, per stage */
-#endif
 
 /* NG: lane groups (recurrences) per wave of the lean loop.  The ROTATE tap is a chain -- every Horner step
  * waits for the one before it, and the carry travels add -> VCC -> select -> FMA -- so ONE recurrence per wave
@@ -1371,12 +1321,10 @@ ddc_body(DDC_PARAMS, v2f *lds, const int role)
  * groups at the same output frame: they share the window and every one of its LDS reads.  NG = 2 takes an even
  * number of lane groups that all use ONE and the same channel filter (the host says: WrTunerLaunch::one_filter)
  * and 80 registers (6 waves per SIMD); otherwise NG = 1, as before. */
-#ifndef DDC_NG2_WAVES_PER_EU
 #define DDC_NG2_WAVES_PER_EU 6u
-#endif
 template <int NCO, bool UTAPS, unsigned int NG> struct DdcOcc {
 	static constexpr unsigned int per_eu = (NG == 2u) ? DDC_NG2_WAVES_PER_EU
-	                                       : (NCO == WR_NCO_ROTATE && (UTAPS || DDC_LTAPS_SMALL)) ? DDC_ROTATE_WGS_PER_CU * DDC_ROTATE_WAVES / 4u
+	                                       : (NCO == WR_NCO_ROTATE) ? DDC_ROTATE_WGS_PER_CU * DDC_ROTATE_WAVES / 4u
 	                                       : DDC_WAVES / 4u;
 };
 
@@ -1399,7 +1347,7 @@ k_tuner_ddc(const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u8,
             unsigned int seek_on, unsigned int seek_lo)
 {
 	extern __shared__ v2f lds[];                /* see DDC_LDS_BYTES */
-	constexpr bool ROLES = DDC_ROLES && NCO == WR_NCO_ROTATE && UTAPS;
+	constexpr bool ROLES = NCO == WR_NCO_ROTATE && UTAPS;
 	static_assert(NG == 1u || (NG == 2u && ROLES), "two recurrences per wave: the lean loop only");
 	if constexpr (!ROLES) {
 		ddc_body<NCO, UTAPS, PD2>(DDC_PASS, lds, DDC_ROLE_ALL);
@@ -1448,11 +1396,10 @@ k_tuner_ddc(const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u8,
 	if (k >= wpg) {
 		k = k1u;                                         /* the few waves left over stay idle */
 	} else {
-		if (DDC_DEAL_WAYS > 1u) {                        /* long and short waves to every workgroup: see ddc_body */
-			const unsigned int r = k % DDC_DEAL_WAYS, q = k / DDC_DEAL_WAYS;
-			const unsigned int fl_ = wpg / DDC_DEAL_WAYS, rem = wpg % DDC_DEAL_WAYS;
-			k = r * fl_ + (r < rem ? r : rem) + q;
-		}
+		/* long and short waves to every workgroup: see ddc_body */
+		const unsigned int r = k % DDC_DEAL_WAYS, q = k / DDC_DEAL_WAYS;
+		const unsigned int fl_ = wpg / DDC_DEAL_WAYS, rem = wpg % DDC_DEAL_WAYS;
+		k = r * fl_ + (r < rem ? r : rem) + q;
 		k += kslow;                                      /* behind the block-boundary frames */
 		if (k > k1u)
 			k = k1u;
@@ -1558,20 +1505,14 @@ k_tuner_ddc(const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u8,
 				xr[0][r] = w4[b][r];
 #pragma unroll
 			for (int t = 0; t < NST; ++t) {
-#ifndef DDC_ABL_NOLDS
 				if (t + 1 < NST) {
 #pragma unroll
 					for (int r = 0; r < RD; ++r)
 						xr[(t + 1) & 1][r] = w4[b][(t + 1) * RD + r];
 				}
-#endif
 #pragma unroll
 				for (int r = 0; r < RD; ++r) {
-#ifdef DDC_ABL_NOLDS                                           /* (timing experiments only: results are wrong) */
-					const v4f x2 = {xo.x, xo.y, xo.y, xo.x};
-#else
 					const v4f x2 = xr[t & 1][r];
-#endif
 #pragma unroll
 					for (int jj = 0; jj < 2; ++jj) {
 						const int j = 2 * (t * RD + r) + jj;
@@ -1583,14 +1524,10 @@ k_tuner_ddc(const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u8,
 									F[c] += fstep[c];       /* a segment starts afresh: no turn */
 								A[c] = u;
 							} else {
-#ifdef DDC_ABL_NOSEL
-								horner_step(A[c], rot0[c].x, rot0[c].y, u);
-#else
 								unsigned int F2;
 								const bool carry = __builtin_uadd_overflow(F[c], fstep[c], &F2);
 								F[c] = F2;
 								horner_step(A[c], carry ? rot1[c].x : rot0[c].x, carry ? rot1[c].y : rot0[c].y, u);
-#endif
 							}
 							if (j % ROT_SEG == ROT_SEG - 1)
 								Aq[c][j / ROT_SEG] = A[c];
@@ -1621,14 +1558,10 @@ k_tuner_ddc(const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u8,
 #pragma unroll
 			for (unsigned int c = 0; c < NG; ++c) {
 				if (fl[c] & PHASE_FLAG_ACTIVE) {
-#ifdef DDC_PLAIN_STORE
-					out[c][(size_t)k * slots] = make_float2(acc[c].x, acc[c].y);
-#else
 					union { v2f f; unsigned long long u; } cv;
 					cv.f = acc[c];
 					__hip_atomic_store((unsigned long long *)&out[c][(size_t)k * slots], cv.u, __ATOMIC_RELAXED,
 					                   __HIP_MEMORY_SCOPE_AGENT);             /* write-through: see ddc_body */
-#endif
 				}
 				Pk[c] += dP[c];
 			}
@@ -2505,8 +2438,8 @@ long wrk_tune_ng2_min_passes(long value, bool set)
 }
 
 template <int NCO, bool UTAPS> struct DdcGeom {
-	static constexpr unsigned int waves = (NCO == WR_NCO_ROTATE && (UTAPS || DDC_LTAPS_SMALL)) ? DDC_ROTATE_WAVES : DDC_WAVES;
-	static constexpr unsigned int wgs_per_cu = (NCO == WR_NCO_ROTATE && (UTAPS || DDC_LTAPS_SMALL)) ? DDC_ROTATE_WGS_PER_CU
+	static constexpr unsigned int waves = (NCO == WR_NCO_ROTATE) ? DDC_ROTATE_WAVES : DDC_WAVES;
+	static constexpr unsigned int wgs_per_cu = (NCO == WR_NCO_ROTATE) ? DDC_ROTATE_WGS_PER_CU
 	                                           : (NCO == WR_NCO_EXACT) ? 2u : 1u;
 };
 
@@ -2518,7 +2451,7 @@ static hipError_t launch_ddc(hipStream_t st, const WrTunerLaunch &L, const WrGro
                              const WrPostArgs *post, unsigned long long gsel = 0, bool whole = true)
 {
 	constexpr unsigned int W = DdcGeom<NCO, UTAPS>::waves;
-	if constexpr (NG == 1u && DDC_ROLES && DDC_NG2 && NCO == WR_NCO_ROTATE && UTAPS) {
+	if constexpr (NG == 1u && NCO == WR_NCO_ROTATE && UTAPS) {
 		/* two lane groups per wave (see k_tuner_ddc: NG) where the launch allows: an even number of lane groups, at
 		 * most 16, all on one and the same channel filter */
 		unsigned int n = 0;
@@ -2584,17 +2517,15 @@ static hipError_t launch_ddc(hipStream_t st, const WrTunerLaunch &L, const WrGro
 		unsigned int fit = (unsigned int)((160u * 1024u) / lds);
 		if (fit < wgs_per_cu)
 			wgs_per_cu = fit;
-#ifndef POST_RESERVE
-#define POST_RESERVE 1u
-#endif
+		constexpr unsigned int POST_RESERVE = 1u;
 		wgs_per_cu = (wgs_per_cu > POST_RESERVE) ? wgs_per_cu - POST_RESERVE : 1u;
 		post_wgs = (post->ntiles + 1u) * post->groups;
 	}
 	/* launched even for a block too short to yield a channel-rate frame: workgroup 0 still
 	 * advances the NCO (downconverter.cxx:103 runs per input frame) and rolls the histories */
-	/* (DDC_ROLES) the first ceil(63 / D1) output frames of the block reach into the previous one: they go to
+	/* (ROLES) the first ceil(63 / D1) output frames of the block reach into the previous one: they go to
 	 * n_bnd workgroups of their own, one wave per (lane group, frame), and the persistent waves share the rest */
-	constexpr bool ROLES = DDC_ROLES && NCO == WR_NCO_ROTATE && UTAPS;
+	constexpr bool ROLES = NCO == WR_NCO_ROTATE && UTAPS;
 	unsigned int kslow = 0, n_bnd = 0;
 	if (ROLES && L.k1) {
 		kslow = (WR_HIST + L.d1 - 1u) / L.d1;
@@ -2606,17 +2537,7 @@ static hipError_t launch_ddc(hipStream_t st, const WrTunerLaunch &L, const WrGro
 	unsigned int wgs = (unsigned int)((units + W - 1) / W);
 	const unsigned int cap = (unsigned int)num_cus * wgs_per_cu;
 	if (wgs > cap) {
-#if DDC_DEAL_WAYS > 1u
 		wgs = cap;                                     /* every slot: the kernel evens the units out (DDC_DEAL_WAYS) */
-#else
-		/* as many workgroups as make the units come out EVEN: with every slot filled (6 144 waves for
-		 * C2's 40 000 units: 6.5 units per wave) half the waves take one unit more than the others
-		 * and run the last round at half occupancy; 715 of the 768 workgroups give every wave seven */
-		const size_t rounds = (units + (size_t)cap * W - 1) / ((size_t)cap * W);
-		wgs = (unsigned int)((units + (size_t)W * rounds - 1) / ((size_t)W * rounds));
-		if (wgs > cap)
-			wgs = cap;
-#endif
 	}
 	if (NCO == WR_NCO_ROTATE && !UTAPS) {
 		/* per-lane taps live in LDS, one lane group per WORKGROUP: a whole number of
@@ -2778,13 +2699,9 @@ WrPostArgs wrk_post_args(const WrTunerLaunch &L, const WrGroupDev &G)
 	/* tiles per workgroup: as long a run as still leaves every CU a few workgroups */
 	{
 		const unsigned int all = A.tiles * (L.slots_used / 64u);
-#ifdef POST_RUN
-		A.run = POST_RUN;
-#else
 		/* measured at C2 (500 tiles a block), us per block: 1 block per launch, run 1 / 2 / 4:
 		 * 38.3 / 37.1 / 38.0; 4 blocks per launch: 33.6 / 32.3 / 32.2 */
 		A.run = all >= 1536u ? 4u : all >= 384u ? 2u : 1u;
-#endif
 	}
 	A.ntiles = (A.tiles + A.run - 1u) / A.run;
 	A.taps2 = G.taps2;
@@ -2845,11 +2762,10 @@ hipError_t wrk_tuner_post_args(hipStream_t st, const WrPostArgs &A0)
 	{
 		/* ... unless there are tiles enough to fill the chip several times over anyway (the flush behind a launch of
 		 * several blocks): runs of tiles then save the rows two neighbouring tiles share from being loaded and
-		 * demodulated twice (59 of 139 at D2 = 5) -- WR_POST_FLUSH_RUN overrides */
-		static const int forced = getenv("WR_POST_FLUSH_RUN") ? atoi(getenv("WR_POST_FLUSH_RUN")) : 0;
+		 * demodulated twice (59 of 139 at D2 = 5) */
 		const unsigned int all = A.tiles * A.groups;
-		A.run = forced > 0 ? (unsigned int)forced : all >= 4096u ? 2u : 1u;   /* C2, four blocks: 43.6 / 33.6 / 36.0 us at runs of 1 / 2 / 4 */
-		if (forced <= 0 && A.nseg == 4u && all >= 384u)
+		A.run = all >= 4096u ? 2u : 1u;   /* C2, four blocks: 43.6 / 33.6 / 36.0 us at runs of 1 / 2 / 4 */
+		if (A.nseg == 4u && all >= 384u)
 			A.run = 2u;     /* 256 taps: a tile stages 331 rows for its 80 new ones (D2 = 5) and one workgroup fits a CU --
 			                   C2 (500 tiles), us per block all in at runs of 1 / 2 / 4: 93 / 83 / 104 (128 taps: 62 / 69 / 79),
 			                   profiles/r05_long_filter.txt */

@@ -140,9 +140,7 @@ __device__ __forceinline__ bool stream_wait_count(const WrStreamArgs &S, const u
 
 /* how many of a closed stream's last blocks hand their post-stage tasks out by ticket (measured: 2, 4, 6 end a 20-block stream
  * 36-38, 38-40, 38-41 us behind its last channel-IQ row -- what is left is the last block's own post stage) */
-#ifndef STREAM_DRAIN_BLOCKS
 #define STREAM_DRAIN_BLOCKS 2u
-#endif
 /* ---- the bell ---- */
 /* ---- the watcher: the second wave of the bell's workgroup.  It adds up the DDC waves' arrivals for the next block (a
  * shard per lane) and says so in ONE word (ddc_ready); it sees the post workgroups arrive and says, IN ORDER, which blocks
@@ -321,14 +319,14 @@ __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigne
 {
 	constexpr unsigned int D2 = PD2 ? PD2 : 1u;
 	constexpr unsigned int NEED = (POST_TK - 1u) * D2 + WR_FIR_LENGTH;
-	wave_prio((S.dbg & 0x4000u) ? ((S.dbg >> 12) & 3u) : 3u);
+	wave_prio(3u);
 	if (threadIdx.x >= POST_THREADS)
 		return;
 	const unsigned int wave = st_rfl(threadIdx.x >> 6);
 	const unsigned int waves_per_wg = POST_THREADS / 64u;
 #ifdef STREAM_TL
 	if (threadIdx.x == 0 && S.tl && !helper)
-		S.tl[(6000u + p) * 8u + 7u] = 12345ull + S.dbg;
+		S.tl[(6000u + p) * 8u + 7u] = 12345ull;
 #endif
 
 	/* block 0's frames whose windows reach into the block before the stream: one wave per (lane group, frame), with the
@@ -347,7 +345,7 @@ __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigne
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 		if (ub / S.groups < S.kslow && (threadIdx.x & 63u) == 0u)
 			__hip_atomic_fetch_add(&S.sdev->ddc_done[0][ub % WR_STREAM_SHARDS][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		wave_prio((S.dbg & 0x4000u) ? ((S.dbg >> 12) & 3u) : 3u);
+		wave_prio(3u);
 		__syncthreads();                                 /* the role's LDS (tables, windows) is the post stage's from here on */
 	}
 
@@ -386,11 +384,7 @@ __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigne
 			 * to four side by side (`rot` below), and in the drain, where tasks go by ticket to whoever asks, it is not a
 			 * given (ADVICE r05).  ONE 8-byte load says both. */
 			if (ok) {
-#ifndef STREAM_NO_AUDIO_WAIT
 				const unsigned int need_hi = j >= 4u ? j - 3u : 0u;
-#else
-				const unsigned int need_hi = 0u;
-#endif
 				const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
 				unsigned int spins = 0;
 				for (;;) {
@@ -415,7 +409,6 @@ __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigne
 			unsigned int drain = helper ? 1u : 0u;
 			if (ok) {
 				ah = j ? st_ld64(&S.sdev->desc[j].audio_host) : S.audio0;
-				if (!(S.dbg & 8u))
 				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 				if (!helper) {
 					/* (read behind the acquire: a block from drain_from on is seen as such by every workgroup that begins it) */
@@ -463,11 +456,7 @@ __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigne
 		 * blocks: BASELINE config 1 has 32 tasks a block) the post stages of consecutive blocks run side by side on
 		 * different workgroups instead of queueing behind each other on the same ones -- a block's post stage is a
 		 * chain of memory round trips, 18-20 us whatever its size */
-#ifndef STREAM_NO_ROT
 		const unsigned int rot = (unsigned int)(((unsigned long long)j * tasks) % S.n_post);
-#else
-		const unsigned int rot = 0u;                        /* (timing comparisons only) */
-#endif
 		for (unsigned int t = p >= rot ? p - rot : p + S.n_post - rot;; t += S.n_post) {
 			if (drain) {
 				/* (the stream's last blocks: tasks by ticket, the idle DDC workgroups beside the post workgroups) */
@@ -478,16 +467,13 @@ __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigne
 			}
 			if (t >= tasks_j)
 				break;
-			if (!(S.dbg & 1u))
 			post_role<D2, false>(A, t % A.ntiles, t / A.ntiles, stage, tile, modes);
 			__syncthreads();                             /* the next task's first phase rewrites `modes` and the stage */
 			++mine;
 		}
 		/* (the barrier above: every wave's stores are issued; `sh` is free again) */
 		if (threadIdx.x == 0 && mine) {
-			if (S.dbg & 2u)
-				;
-			else if (ah)
+			if (ah)
 				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "");          /* the ring slot is the host's: system scope */
 			else
 				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -506,7 +492,7 @@ __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigne
 #endif
 	}
 #ifdef STREAM_TL
-	if (threadIdx.x == 0 && S.tl && (S.dbg & 16u) && !helper) {
+	if (threadIdx.x == 0 && S.tl && !helper) {
 		S.tl[(6000u + p) * 8u + 0u] = pt_wait;
 		S.tl[(6000u + p) * 8u + 1u] = pt_sync;
 		S.tl[(6000u + p) * 8u + 2u] = pt_n;
@@ -672,11 +658,7 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 				const unsigned short b2 = ((const __attribute__((address_space(1))) unsigned short *)base)[idx];
 				dst = make_float2(__builtin_bit_cast(float, (unsigned int)b2), 0.0f);
 			} else {
-#ifdef STREAM_WINDOW_NT
-				const v2f x2 = __builtin_nontemporal_load((const __attribute__((address_space(1))) v2f *)base + idx);
-#else
 				const v2f x2 = ((const __attribute__((address_space(1))) v2f *)base)[idx];
-#endif
 				dst = make_float2(x2.x, x2.y);
 			}
 			++ahead;
@@ -710,7 +692,7 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 		/* one unit from LDS buffer b; `xo` holds the NEXT unit's window sample (on its way or landed) if ahead >= 2 */
 		unsigned long long tl_taps = 0, tl_rest = 0, tl_wait = 0, tl_units = 0, tl_ring = 0, tl_ringn = 0, tl_epochs = 0;
 #ifdef STREAM_TL
-		const bool tl_on = (S.dbg & 16u) != 0u;
+		const bool tl_on = S.tl != nullptr;
 #else
 		constexpr bool tl_on = false;                     /* (s_memtime is a scalar memory instruction: even behind a branch it
 		                                                     makes every LDS wait of the tap loop a wait for everything) */
@@ -732,7 +714,7 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 				const unsigned long long pg = __hip_atomic_load(&S.sdev->progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 				const unsigned int dr = st_rfl((unsigned int)pg), pr = st_rfl((unsigned int)(pg >> 32));
 				lead = j > dr ? j - dr : 0u;
-				if (!(S.dbg & 4u) && j + 1u >= WR_STREAM_RING && pr < j - WR_STREAM_RING + 2u) {
+				if (j + 1u >= WR_STREAM_RING && pr < j - WR_STREAM_RING + 2u) {
 					const unsigned long long tw0 = tl_on ? __builtin_amdgcn_s_memtime() : 0ull;
 					tell();
 					if (!stream_wait_count(S, (const unsigned int *)&S.sdev->progress + 1, j - WR_STREAM_RING + 2u)) {
@@ -808,9 +790,6 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 				asm volatile("" : "+v"(acc[c].x), "+v"(acc[c].y));
 			}
 			const unsigned long long tl1 = tl_on ? __builtin_amdgcn_s_memtime() : 0ull;
-#ifdef STREAM_REST_PRIO
-			wave_prio(STREAM_REST_PRIO);
-#endif
 			/* the next unit's window (requested two units ago), if there is a next unit ... */
 			if (ahead >= 2u)
 				to_lds(xo, b ^ 1);
@@ -826,28 +805,11 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 			const size_t row = (size_t)(j % WR_STREAM_RING) * k1s + k;
 #pragma unroll
 			for (unsigned int c = 0; c < NG; ++c) {
-#ifdef STREAM_FEW_IQ_STORES
-				/* (development, results wrong: one wave in 64 writes its rows -- what the channel IQ's way to memory costs) */
-				if ((fl[c] & PHASE_FLAG_ACTIVE) && !(wid & 63u)) {
-#else
 				if (fl[c] & PHASE_FLAG_ACTIVE) {
-#endif
 					union { v2f f; unsigned long long u; } cv;
 					cv.f = acc[c];
-#ifdef STREAM_IQ_STORE_POLICY
-					/* (development: other cache policies for the channel IQ's stores -- 1: sc1 nt, 2: sc0 sc1, 3: sc0 sc1 nt; profiles/r06_power.txt) */
-#if STREAM_IQ_STORE_POLICY == 1
-#define STREAM_IQ_ST "global_store_dwordx2 %0, %1, off sc1 nt"
-#elif STREAM_IQ_STORE_POLICY == 2
-#define STREAM_IQ_ST "global_store_dwordx2 %0, %1, off sc0 sc1"
-#else
-#define STREAM_IQ_ST "global_store_dwordx2 %0, %1, off sc0 sc1 nt"
-#endif
-					asm volatile(STREAM_IQ_ST :: "v"(&out[c][row * S.slots]), "v"(cv.u) : "memory");
-#else
 					__hip_atomic_store((unsigned long long *)&out[c][row * S.slots], cv.u, __ATOMIC_RELAXED,
 					                   __HIP_MEMORY_SCOPE_AGENT);             /* write-through: see ddc_body */
-#endif
 				}
 				Pk[c] += dP[c];
 			}
@@ -1108,11 +1070,6 @@ hipError_t wrk_tuner_stream(hipStream_t st, const WrStreamArgs &A0, void *ev_sta
 	       ((A.post.tiles + A.post.run - 1u) / A.post.run) * A.post.groups > A.n_post / 4u &&
 	       ((A.post.tiles + A.post.run - 1u) / A.post.run) * A.post.groups <= A.n_post / 2u)
 		++A.post.run;
-	if (const char *e = getenv("WR_STREAM_POST_RUN")) {      /* (development: tiles per post-stage task) */
-		const unsigned int r = (unsigned int)atoi(e);
-		if (r >= min_run && r <= 16u)
-			A.post.run = r;
-	}
 	A.post.ntiles = (A.post.tiles + A.post.run - 1u) / A.post.run;
 	/* the stream's last blocks (tasks by ticket, the DDC workgroups helping): the shortest runs -- what ends a closed stream is
 	 * the latency of its last tasks (secondary.frontend's launch-per-block mode: 123 against 134 us with the long runs) */
