@@ -311,7 +311,8 @@ int wr_chan_set_state(wr_tuner *tuner, int chan, unsigned int phase, const float
  * untouched until wr_dev_wait_uploads (as for any asynchronous upload).  wr_tuner_stream_host_blocks counts them.  The
  * WHOLE block crosses the link that way (sparse staging brings over a sixth at BASELINE config 2), and whatever else the
  * caller queues on the upload stream in front of a block (wr_dev_upload_ahead, wr_u8_to_f32_from_host) holds its doorbell
- * up: copies of 16 KB or less are copy kernels on this runtime and do not start beside an open launch. */
+ * up: copies of 16 KB or less are copy kernels on this runtime and do not start beside an open launch -- for the same reason a
+ * block of 16 KB or less (8192 frames) is not streamed this way: it goes the ordinary way. */
 int wr_tuner_last_staging(wr_tuner *tuner, int *how);
 int wr_tuner_submit(wr_tuner *tuner, const float *iq, size_t nframes, int where);
 /* the same for a block in the RTL-SDR byte format (unsigned 8-bit interleaved IQ, what

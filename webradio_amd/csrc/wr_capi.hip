@@ -2279,6 +2279,7 @@ static int tuner_submit_now(wr_tuner *t, const void *iq, size_t nframes, int whe
 #define WR_STREAM_IDLE_MS   500           /* the launch closes itself when the doorbell has been silent this long */
 #define WR_STREAM_STALE_MS  100           /* ... and the host does not ring a launch it has left alone this long: it opens a new one */
 #define WR_STREAM_WAIT_MS  2000           /* deadline of every other wait inside the launch (an error) */
+#define WR_STREAM_HOST_MIN_BYTES (16u << 10)   /* a host byte block streams only if it is larger than this (stream_host_u8) */
 
 static unsigned long long *g_stream_tl = nullptr;
 extern "C" int wr_debug_stream_tl(unsigned long long *out, size_t n)
@@ -2583,7 +2584,18 @@ static int stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, boo
 	 * or more -- it is NOT copied from the doorbell here: that copy would run when the stream gets to it, by which time
 	 * the host may have rung again, and the bell, finding the higher count already in device memory, would never bring
 	 * the descriptors over that go with it) */
-	HIP_TRY(hipMemsetAsync(s.sdev, 0, offsetof(WrStreamDev, desc), st));
+	if (s.ext) {
+		/* A launch that takes blocks out of host memory: WrStreamDev::ready_up is NOT part of this fill.  Its doorbells are
+		 * written on the UPLOAD stream, which does not wait for the device's: with small blocks the first of them could land
+		 * before this fill runs, and the fill would wipe the count (the launch then never sees the block).  stream_host_u8
+		 * zeroes ready_up on the upload stream instead, behind block 0's copy and ahead of raw_ev -- before every doorbell of
+		 * this launch by the upload stream's order, and before the launch starts by the wait on raw_ev. */
+		HIP_TRY(hipMemsetAsync(s.sdev, 0, offsetof(WrStreamDev, ready_up), st));
+		const size_t after = offsetof(WrStreamDev, ready_up) + sizeof(unsigned int);
+		HIP_TRY(hipMemsetAsync((char *)s.sdev + after, 0, offsetof(WrStreamDev, desc) - after, st));
+	} else {
+		HIP_TRY(hipMemsetAsync(s.sdev, 0, offsetof(WrStreamDev, desc), st));
+	}
 	A.cur0 = s.desc[0].cur;
 	A.audio0 = s.desc[0].audio_host;
 
@@ -2636,6 +2648,11 @@ static int stream_host_u8(wr_tuner *t, const uint8_t *bytes, size_t nframes, boo
 		return WR_OK;                                       /* pageable: the copy would be staged by the runtime, synchronously */
 	}
 	const size_t need = nframes * 2;
+	/* A copy of WR_STREAM_HOST_MIN_BYTES or less is a copy KERNEL on this runtime (GPU_FORCE_BLIT_COPY_SIZE), and a kernel does
+	 * not start beside the open launch (see stream_bell): the block's doorbell, queued behind its copy, would never ring and the
+	 * launch would close itself with the block untaken.  Such a block goes the ordinary way. */
+	if (need <= WR_STREAM_HOST_MIN_BYTES)
+		return WR_OK;
 	const bool follows = s.live && s.ext && stream_follows(t, nframes, WR_DEVICE, true);
 	if (need > s.raw_cap) {
 		if (s.live)
@@ -2654,12 +2671,16 @@ static int stream_host_u8(wr_tuner *t, const uint8_t *bytes, size_t nframes, boo
 		s.raw_cap = need;
 	}
 	const unsigned int slot = (unsigned int)(s.raw_next & 3u);
-	if (s.live && s.raw_gen[slot] == s.gen && s.ctl->done <= s.raw_idx[slot] + 1u) {
-		/* the buffer's last tenant -- four blocks back in this very launch -- and the block behind it, whose first windows reach
-		 * into its tail, are not through yet (a caller far ahead of the GPU): wait for their audio, which comes behind the
-		 * last read of their frames */
+	/* the buffer's last tenant and the block behind it, whose first windows reach into its tail, must be through before the copy
+	 * below is queued: their audio (WrStreamCtl::done) comes behind the last read of their frames.  The tenant may be four
+	 * blocks back in the live launch (a caller far ahead of the GPU), or a block of a launch that has been CLOSED but may still
+	 * be running (s.unchecked: nobody has waited for the device's stream since the stop) -- the copy is on the upload stream,
+	 * which does not wait for the device's, so only this wait orders the launch's last read of the buffer before the new
+	 * bytes.  A closed launch ends with done == count, so the block behind the tenant is waited for only if it was rung. */
+	const unsigned int through = s.raw_idx[slot] + 2u < s.count ? s.raw_idx[slot] + 2u : s.count;
+	if ((s.live || s.unchecked) && s.raw_gen[slot] == s.gen && s.ctl->done < through) {
 		const auto t0 = std::chrono::steady_clock::now();
-		while (s.ctl->done <= s.raw_idx[slot] + 1u && !s.ctl->err)
+		while (s.ctl->done < through && !s.ctl->err)
 			if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(4 * WR_STREAM_WAIT_MS))
 				return fail(WR_ERR_HIP, "streaming launch: block %u did not finish", s.raw_idx[slot] + 1u);
 	}
@@ -2686,6 +2707,13 @@ static int stream_host_u8(wr_tuner *t, const uint8_t *bytes, size_t nframes, boo
 	/* this block opens a launch (or, if it cannot, goes the ordinary way out of the device copy): either waits for the copy */
 	if (!s.raw_ev)
 		HIP_TRY(hipEventCreateWithFlags(&s.raw_ev, hipEventDisableTiming));
+	/* the doorbell's device-side twin starts from zero for the launch this block may open (see stream_open): written on the
+	 * upload stream, behind everything a launch before this one rang there and ahead of this launch's own doorbells.  (A
+	 * launch that was closed and may still run ignores it: its count is final in WrStreamCtl::ready, stream_close.)  A stream
+	 * memory operation, not a fill kernel: see stream_bell. */
+	if (!s.sdev)
+		HIP_TRY(hipMalloc((void **)&s.sdev, sizeof(WrStreamDev)));
+	HIP_TRY(hipStreamWriteValue32(d->up_stream, &s.sdev->ready_up, 0u, 0));
 	HIP_TRY(hipEventRecord(s.raw_ev, d->up_stream));
 	HIP_TRY(hipStreamWaitEvent(d->stream, s.raw_ev, 0));
 	s.ext = true;
