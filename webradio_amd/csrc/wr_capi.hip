@@ -2426,8 +2426,17 @@ static int stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, boo
 		if (int rc = group_upload(t, g))
 			return rc;
 	const unsigned int used = group_slots_used(g), groups = used / 64u;
-	if (!g->one_filter || !groups || groups > 16u)
+	if (!groups || groups > 16u)
 		return WR_OK;
+	/* every lane group on at most WR_TAPSETS distinct 64-tap channel filters (receiverhandler.cxx:130-137: a passband per
+	 * receiver); `kmax` of them at most in one lane group.  A group with more takes the per-lane-taps kernel: the ordinary way */
+	const unsigned long long used_mask = (1ull << groups) - 1ull;
+	if ((g->fewsets_mask & used_mask) != used_mask)
+		return WR_OK;
+	unsigned int kmax = 1;
+	for (unsigned int gi = 0; gi < groups; ++gi)
+		if (g->nsets[gi] > kmax)
+			kmax = g->nsets[gi];
 	if (int rc = dev_settle_stream(d))                      /* another tuner's launch in this context */
 		return rc;
 	{
@@ -2446,7 +2455,7 @@ static int stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, boo
 			return rc;
 	const size_t k1 = nframes / g->d1, k2 = k1 / g->d2;
 	unsigned int n_ddc = 0, n_post = 0;
-	HIP_TRY(wrk_stream_geometry(g->d2, groups, d->num_cus, &n_ddc, &n_post));
+	HIP_TRY(wrk_stream_geometry(g->d2, groups, kmax, g->one_filter, d->num_cus, &n_ddc, &n_post));
 	if (!n_ddc || !n_post)
 		return WR_OK;
 	/* (each on its own: an allocation that failed last time is tried again, never skipped because an earlier one stands) */
@@ -2491,7 +2500,7 @@ static int stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, boo
 	L.uniform_mask = g->uniform_mask;
 	L.uniform2_mask = g->uniform2_mask;
 	L.fewsets_mask = g->fewsets_mask;
-	L.one_filter = 1;
+	L.one_filter = g->one_filter ? 1 : 0;
 	memcpy(L.nsets, g->nsets, sizeof(L.nsets));
 	L.audio_scale = t->audio_scale;
 	L.use_gain = g->use_gain ? 1 : 0;
@@ -2556,6 +2565,8 @@ static int stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, boo
 	A.dem[0] = g->dev.dem[0];
 	A.dem[1] = g->dev.dem[1];
 	A.parity0 = g->parity;
+	A.kmax = kmax;
+	A.one_filter = g->one_filter ? 1u : 0u;
 
 	/* the doorbell as the launch finds it: block 0 rung */
 	++s.gen;

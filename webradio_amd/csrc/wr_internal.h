@@ -275,6 +275,9 @@ struct WrStreamArgs {
 	unsigned int        slots, groups;     /* row stride of the per-slot arrays; lane groups in use */
 	unsigned long long  gmap0, gmap1;      /* which lane groups (as k_tuner_ddc) */
 	unsigned int        kslow;             /* output frames of a block whose window reaches into the block before */
+	unsigned int        kmax;              /* the most distinct channel filters a lane group of the launch mixes, 1..WR_TAPSETS
+	                                          (it and one_filter fill alignment holes: no other field moves, nor does the
+	                                          kernel's argument block grow) */
 	/* the DDC's state (WrGroupDev), set `sp` read, set `sp ^ 1` written at exit */
 	const float        *hist;              /* tuner input history [63][2] before block 0 */
 	float              *hist_next;
@@ -295,10 +298,12 @@ struct WrStreamArgs {
 	const float        *prev_iq[2];
 	float              *dem[2];
 	int                 parity0;           /* set block 0 reads */
+	unsigned int        one_filter;        /* ONE channel filter for every channel (WrTunerLaunch::one_filter) */
 };
 #define WR_STREAM_ERR_WAIT   1u            /* a wait inside the launch ran into `wait_ticks` */
 /* workgroups the launch needs co-resident (it sizes its roles to them); 0 = this launch shape cannot stream */
-hipError_t wrk_stream_geometry(unsigned int d2, unsigned int groups, int num_cus, unsigned int *n_ddc, unsigned int *n_post);
+hipError_t wrk_stream_geometry(unsigned int d2, unsigned int groups, unsigned int kmax, bool one_filter, int num_cus,
+                               unsigned int *n_ddc, unsigned int *n_post);
 hipError_t wrk_tuner_stream(hipStream_t st, const WrStreamArgs &A, void *ev_start, void *ev_stop);
 
 /* ---- FFT (wr_fft.hip) ---- */

@@ -9,9 +9,10 @@
  * 3 us before the first tap at C2), and a ragged end in which the last waves run on a part-empty chip -- 4.6 us of
  * a 32 us block.  Here the grid is resident for the whole stream:
  *
- *   workgroups [0, n_ddc)            the DDC waves of k_tuner_ddc's lean loop (ROTATE NCO, one channel filter, NG lane
- *                                    groups per wave), walking the output frames of block 0, 1, 2, ... as ONE sequence
- *                                    -- a wave's units are every wpg-th frame of the STREAM, so the units come out even
+ *   workgroups [0, n_ddc)            the DDC waves of k_tuner_ddc's lean loop (ROTATE NCO, NG lane groups per wave: two
+ *                                    on ONE channel filter, or one lane group with up to TS = WR_TAPSETS distinct ones,
+ *                                    a window copy per filter -- stream_ddc), walking the output frames of block 0, 1,
+ *                                    2, ... as ONE sequence -- a wave's units are every wpg-th frame of the STREAM, so the units come out even
  *                                    over the stream, not per block.  Channel IQ goes to a ring of WR_STREAM_RING blocks.
  *   workgroups [n_ddc, n_ddc+n_post) the post stage (post_role: demodulator + audio filter), block by block: block j
  *                                    as soon as all of its channel-IQ rows are out and block j-1's post stage has left
@@ -314,7 +315,7 @@ __device__ __forceinline__ void stream_bell(const WrStreamArgs &S)
 }
 
 /* ---- the post stage, block by block ---- */
-template <unsigned int PD2>
+template <unsigned int PD2, unsigned int TS>
 __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigned int p, v2f *lds, const bool helper)
 {
 	constexpr unsigned int D2 = PD2 ? PD2 : 1u;
@@ -338,7 +339,7 @@ __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigne
 		                                   (const float2 *)S.hist, (float2 *)S.hist_next, (size_t)S.nframes, (size_t)S.k1, S.d1,
 		                                   S.slots, S.groups, S.phase, S.step, (const float2 *)S.hist_cs, S.flags, S.phase_next,
 		                                   (float2 *)S.hist_cs_next, (const float2 *)S.hist_lo, (float2 *)S.hist_lo_next, S.taps1,
-		                                   (const float4 *)S.rot, S.taps1u, S.tapsel, 1u, (float2 *)S.ring, S.table,
+		                                   (const float4 *)S.rot, S.taps1u, S.tapsel, TS == 1u ? 1u : S.kmax, (float2 *)S.ring, S.table,
 		                                   (const float2 *)S.hi_cs, (const float2 *)S.lo_cs, S.n_ddc, S.post, S.gmap0, S.gmap1, 0,
 		                                   S.kslow, 0x40000000u, 0u, 0u, lds, DDC_ROLE_BOUNDARY);
 		const unsigned int ub = p * waves_per_wg + wave;
@@ -514,10 +515,15 @@ __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigne
 	}
 }
 
-/* ---- the DDC waves ---- */
-template <unsigned int NG>
+/* ---- the DDC waves ----
+ * TS: tap sets per lane group the instance provides for.  TS = 1: one channel filter per lane group (NG = 2: ONE for
+ * both lane groups of a wave).  TS = WR_TAPSETS (NG = 1 only): up to that many distinct channel filters in a lane group,
+ * S.kmax of them at most in this launch -- as k_tuner_ddc's lean loop, the window goes to LDS once per filter, tap *
+ * sample, and a lane reads the copy made with ITS filter (WrGroupDev::tapsel): the same products, the same bits. */
+template <unsigned int NG, unsigned int TS>
 __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 {
+	static_assert(TS == 1u || (TS == WR_TAPSETS && NG == 1u), "several channel filters: one lane group per wave");
 	constexpr int NCO = WR_NCO_ROTATE;
 	const unsigned int lane = threadIdx.x & 63u;
 	const unsigned int wave = st_rfl(threadIdx.x >> 6);
@@ -534,7 +540,8 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 	}
 	__syncthreads();
 	const v2f *hi_l = lds, *lo_l = lds + WR_SPLIT_N;
-	v2f *win = lds + 2u * WR_SPLIT_N + wave * 128u;          /* one channel filter: one window copy, double buffered */
+	const unsigned int nset = TS == 1u ? 1u : S.kmax;        /* window copies per buffer, double buffered: [buffer][set][64] */
+	v2f *win = lds + 2u * WR_SPLIT_N + wave * (128u * nset);
 	const unsigned int k1s = S.k1, d1 = S.d1;
 	const unsigned int nwaves = S.n_ddc * waves_per_wg;
 	const unsigned int gsets = S.groups / NG;                /* sets of NG lane groups that share a wave */
@@ -569,13 +576,17 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 			dP[c] = wpg * d1 * stv[c];
 			out[c] = (float2 *)S.ring + s;
 		}
-		const float hlane = S.taps1u[((size_t)g0 * WR_TAPSETS) * 64u + lane];   /* lane j holds the tap of window sample j */
+		float hlane[TS];                                  /* lane j holds the tap of window sample j, per tap set */
+#pragma unroll
+		for (unsigned int q = 0; q < TS; ++q)
+			hlane[q] = (TS == 1u || q < nset) ? S.taps1u[((size_t)g0 * WR_TAPSETS + q) * 64u + lane] : 0.0f;
+		const unsigned int mysel = TS == 1u ? 0u : (unsigned int)S.tapsel[g0 * 64u + lane];   /* this lane's tap set */
 		const lds_v4f *w4[2];
 		v2f *wst[2];
 #pragma unroll
 		for (int b = 0; b < 2; ++b) {
-			w4[b] = (const lds_v4f *)(win + (unsigned int)b * 64u);
-			wst[b] = win + (unsigned int)b * 64u + lane;
+			w4[b] = (const lds_v4f *)(win + ((unsigned int)b * nset + mysel) * 64u);
+			wst[b] = win + (unsigned int)b * nset * 64u + lane;
 		}
 		/* where the wave computes (block j, frame k of it) and where it fetches (two units ahead) */
 		unsigned int j = 0, k = (unsigned int)q0;
@@ -674,7 +685,10 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 				const unsigned int bits = __builtin_bit_cast(unsigned int, raw.x);
 				xf = make_float2(((float)(bits & 255u) - 128.0f) / 128.0f, ((float)((bits >> 8) & 255u) - 128.0f) / 128.0f);
 			}
-			wst[b][0] = (v2f){hlane * xf.x, hlane * xf.y};
+#pragma unroll
+			for (unsigned int q = 0; q < TS; ++q)
+				if (TS == 1u || q < nset)
+					wst[b][q * 64u] = (v2f){hlane[q] * xf.x, hlane[q] * xf.y};
 		};
 		unsigned int cnt = 0, pend_j = 0, pend_cnt = 0;   /* lane-group units done in block j / to be signalled for pend_j */
 		unsigned int jring = 0xFFFFFFFFu;                 /* block whose ring rows are known to be free */
@@ -923,7 +937,7 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 	}
 }
 
-template <unsigned int PD2, unsigned int NG>
+template <unsigned int PD2, unsigned int NG, unsigned int TS>
 __global__ void __launch_bounds__(DDC_ROTATE_WAVES * 64u) __attribute__((amdgpu_waves_per_eu(DDC_NG2_WAVES_PER_EU)))
 k_tuner_stream(const WrStreamArgs S)
 {
@@ -934,11 +948,11 @@ k_tuner_stream(const WrStreamArgs S)
 	}
 	const bool ddc = blockIdx.x < S.n_ddc;
 	if (ddc) {
-		stream_ddc<NG>(S, lds);
+		stream_ddc<NG, TS>(S, lds);
 		__syncthreads();                                    /* every wave is behind its last block and the state roll: the
 		                                                       workgroup's LDS is free, and so is the workgroup (stream_post) */
 	}
-	stream_post<PD2>(S, ddc ? blockIdx.x : blockIdx.x - S.n_ddc, lds, ddc);
+	stream_post<PD2, TS>(S, ddc ? blockIdx.x : blockIdx.x - S.n_ddc, lds, ddc);
 }
 
 /* post-stage tiles per workgroup for a launch that may keep `max_post` post workgroups resident */
@@ -950,38 +964,51 @@ static unsigned int stream_post_run(unsigned int tiles, unsigned int groups, uns
 	return run;
 }
 
-static size_t stream_lds_bytes(unsigned int d2)
+/* LDS per workgroup: the post stage's stage and tile, or the DDC's NCO tables and window copies -- `nset` per buffer, two
+ * buffers per wave (the block-boundary role inside the post workgroups lays its windows out the same way) */
+static size_t stream_lds_bytes(unsigned int d2, unsigned int nset)
 {
 	const size_t need = (size_t)(POST_TK - 1u) * d2 + WR_FIR_LENGTH;
 	const size_t post_lds = (need * 64u + POST_TK * 65u + 64u + 16u) * sizeof(float);
-	const size_t ddc_lds = (size_t)DDC_ROTATE_WAVES * 2u * 512u + 2u * WR_SPLIT_N * 8u;
+	const size_t ddc_lds = (size_t)DDC_ROTATE_WAVES * 2u * 512u * nset + 2u * WR_SPLIT_N * 8u;
 	return post_lds > ddc_lds ? post_lds : ddc_lds;
 }
 
-template <unsigned int PD2, unsigned int NG>
+/* Which k_tuner_stream<PD2, NG, TS> a launch takes.  ONE channel filter for the whole tuner and an even number of lane
+ * groups: NG = 2 (two lane groups share a wave's window and its reads).  Otherwise one lane group per wave: TS = 1 while
+ * every lane group has a single channel filter (its own: hlane comes from the wave's lane group), TS = WR_TAPSETS
+ * when a lane group mixes several.  (Two lane groups with different filters do not share a wave: NG = 2 stays the
+ * one-filter shape, the one the headline runs, instruction for instruction.) */
+static void stream_shape(unsigned int groups, unsigned int kmax, bool one_filter, unsigned int *ng, unsigned int *ts)
+{
+	*ng = (one_filter && !(groups & 1u)) ? 2u : 1u;
+	*ts = kmax > 1u ? WR_TAPSETS : 1u;
+}
+
+template <unsigned int PD2, unsigned int NG, unsigned int TS>
 static hipError_t stream_occupancy(size_t lds, int *per_cu)
 {
 	static bool attr_done[WR_MAX_DEVICES];
 	if (lds > 64 * 1024) {
-		hipError_t e = allow_lds((const void *)k_tuner_stream<PD2, NG>, lds, attr_done);
+		hipError_t e = allow_lds((const void *)k_tuner_stream<PD2, NG, TS>, lds, attr_done);
 		if (e != hipSuccess)
 			return e;
 	}
-	return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_tuner_stream<PD2, NG>, (int)(DDC_ROTATE_WAVES * 64u), lds);
+	return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_tuner_stream<PD2, NG, TS>, (int)(DDC_ROTATE_WAVES * 64u), lds);
 }
 
-template <unsigned int NG>
+template <unsigned int NG, unsigned int TS>
 static hipError_t stream_occupancy_d2(unsigned int d2, size_t lds, int *per_cu)
 {
 	switch (d2) {
-	case 1: return stream_occupancy<1, NG>(lds, per_cu);
-	case 2: return stream_occupancy<2, NG>(lds, per_cu);
-	case 3: return stream_occupancy<3, NG>(lds, per_cu);
-	case 4: return stream_occupancy<4, NG>(lds, per_cu);
-	case 5: return stream_occupancy<5, NG>(lds, per_cu);
-	case 6: return stream_occupancy<6, NG>(lds, per_cu);
-	case 8: return stream_occupancy<8, NG>(lds, per_cu);
-	case 10: return stream_occupancy<10, NG>(lds, per_cu);
+	case 1: return stream_occupancy<1, NG, TS>(lds, per_cu);
+	case 2: return stream_occupancy<2, NG, TS>(lds, per_cu);
+	case 3: return stream_occupancy<3, NG, TS>(lds, per_cu);
+	case 4: return stream_occupancy<4, NG, TS>(lds, per_cu);
+	case 5: return stream_occupancy<5, NG, TS>(lds, per_cu);
+	case 6: return stream_occupancy<6, NG, TS>(lds, per_cu);
+	case 8: return stream_occupancy<8, NG, TS>(lds, per_cu);
+	case 10: return stream_occupancy<10, NG, TS>(lds, per_cu);
 	default: return hipErrorInvalidValue;
 	}
 }
@@ -989,15 +1016,20 @@ static hipError_t stream_occupancy_d2(unsigned int d2, size_t lds, int *per_cu)
 /* How many workgroups of the streaming launch a device holds at once, split into roles.  Every workgroup of the
  * launch must be resident (they wait for one another): the grid is never larger than what the occupancy query
  * admits, capped at three per CU (what 80 registers and eight waves per workgroup give; the query can be one too
- * generous near a register-file edge, MI355X_MICROARCH.md "Residency"). */
-hipError_t wrk_stream_geometry(unsigned int d2, unsigned int groups, int num_cus, unsigned int *n_ddc, unsigned int *n_post)
+ * generous near a register-file edge, MI355X_MICROARCH.md "Residency").  `kmax`: the most channel filters a lane group
+ * of the launch mixes; `one_filter`: one for the whole tuner (stream_shape). */
+hipError_t wrk_stream_geometry(unsigned int d2, unsigned int groups, unsigned int kmax, bool one_filter, int num_cus,
+                               unsigned int *n_ddc, unsigned int *n_post)
 {
 	*n_ddc = *n_post = 0;
-	if (!wrk_tuner_post_supported(d2) || !groups || groups > 16u)
+	if (!wrk_tuner_post_supported(d2) || !groups || groups > 16u || !kmax || kmax > WR_TAPSETS)
 		return hipSuccess;
-	const size_t lds = stream_lds_bytes(d2);
+	unsigned int ng, ts;
+	stream_shape(groups, kmax, one_filter, &ng, &ts);
+	const size_t lds = stream_lds_bytes(d2, ts == 1u ? 1u : kmax);
 	int per_cu = 0;
-	hipError_t e = (groups & 1u) ? stream_occupancy_d2<1>(d2, lds, &per_cu) : stream_occupancy_d2<2>(d2, lds, &per_cu);
+	hipError_t e = ts != 1u ? stream_occupancy_d2<1, WR_TAPSETS>(d2, lds, &per_cu)
+	               : ng == 1u ? stream_occupancy_d2<1, 1>(d2, lds, &per_cu) : stream_occupancy_d2<2, 1>(d2, lds, &per_cu);
 	if (e != hipSuccess)
 		return e;
 	if (per_cu > 3)
@@ -1011,38 +1043,38 @@ hipError_t wrk_stream_geometry(unsigned int d2, unsigned int groups, int num_cus
 	return hipSuccess;
 }
 
-template <unsigned int PD2, unsigned int NG>
+template <unsigned int PD2, unsigned int NG, unsigned int TS>
 static hipError_t launch_stream(hipStream_t st, const WrStreamArgs &A, void *ev_start, void *ev_stop)
 {
-	const size_t lds = stream_lds_bytes(PD2);
+	const size_t lds = stream_lds_bytes(PD2, TS == 1u ? 1u : A.kmax);
 	static bool attr_done[WR_MAX_DEVICES];
 	if (lds > 64 * 1024) {
-		hipError_t e = allow_lds((const void *)k_tuner_stream<PD2, NG>, lds, attr_done);
+		hipError_t e = allow_lds((const void *)k_tuner_stream<PD2, NG, TS>, lds, attr_done);
 		if (e != hipSuccess)
 			return e;
 	}
 	const unsigned int grid = A.n_ddc + A.n_post + 1u;
 	if (ev_start || ev_stop) {
-		hipExtLaunchKernelGGL((k_tuner_stream<PD2, NG>), dim3(grid), dim3(DDC_ROTATE_WAVES * 64u), (uint32_t)lds, st,
+		hipExtLaunchKernelGGL((k_tuner_stream<PD2, NG, TS>), dim3(grid), dim3(DDC_ROTATE_WAVES * 64u), (uint32_t)lds, st,
 		                      (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 0u, A);
 		return hipGetLastError();
 	}
-	k_tuner_stream<PD2, NG><<<grid, DDC_ROTATE_WAVES * 64u, lds, st>>>(A);
+	k_tuner_stream<PD2, NG, TS><<<grid, DDC_ROTATE_WAVES * 64u, lds, st>>>(A);
 	return hipGetLastError();
 }
 
-template <unsigned int NG>
+template <unsigned int NG, unsigned int TS>
 static hipError_t launch_stream_d2(hipStream_t st, const WrStreamArgs &A, void *ev_start, void *ev_stop)
 {
 	switch (A.post.d2) {
-	case 1: return launch_stream<1, NG>(st, A, ev_start, ev_stop);
-	case 2: return launch_stream<2, NG>(st, A, ev_start, ev_stop);
-	case 3: return launch_stream<3, NG>(st, A, ev_start, ev_stop);
-	case 4: return launch_stream<4, NG>(st, A, ev_start, ev_stop);
-	case 5: return launch_stream<5, NG>(st, A, ev_start, ev_stop);
-	case 6: return launch_stream<6, NG>(st, A, ev_start, ev_stop);
-	case 8: return launch_stream<8, NG>(st, A, ev_start, ev_stop);
-	case 10: return launch_stream<10, NG>(st, A, ev_start, ev_stop);
+	case 1: return launch_stream<1, NG, TS>(st, A, ev_start, ev_stop);
+	case 2: return launch_stream<2, NG, TS>(st, A, ev_start, ev_stop);
+	case 3: return launch_stream<3, NG, TS>(st, A, ev_start, ev_stop);
+	case 4: return launch_stream<4, NG, TS>(st, A, ev_start, ev_stop);
+	case 5: return launch_stream<5, NG, TS>(st, A, ev_start, ev_stop);
+	case 6: return launch_stream<6, NG, TS>(st, A, ev_start, ev_stop);
+	case 8: return launch_stream<8, NG, TS>(st, A, ev_start, ev_stop);
+	case 10: return launch_stream<10, NG, TS>(st, A, ev_start, ev_stop);
 	default: return hipErrorInvalidValue;
 	}
 }
@@ -1080,8 +1112,13 @@ hipError_t wrk_tuner_stream(hipStream_t st, const WrStreamArgs &A0, void *ev_sta
 	 * go round them -- and do NOT go to the DDC: its waves share the stream's frames evenly and wait for one another at the
 	 * ring's end, so the launch runs at the pace of the fullest SIMD, r05) */
 	(void)tasks;
-	const unsigned int ng = (A.groups & 1u) ? 1u : 2u;
+	if (!A.kmax || A.kmax > WR_TAPSETS)
+		return hipErrorInvalidValue;
+	unsigned int ng, ts;
+	stream_shape(A.groups, A.kmax, A.one_filter != 0u, &ng, &ts);
 	if ((size_t)A.n_ddc * DDC_ROTATE_WAVES < A.groups / ng)
 		return hipErrorInvalidValue;
-	return ng == 2u ? launch_stream_d2<2>(st, A, ev_start, ev_stop) : launch_stream_d2<1>(st, A, ev_start, ev_stop);
+	if (ts != 1u)
+		return launch_stream_d2<1, WR_TAPSETS>(st, A, ev_start, ev_stop);
+	return ng == 2u ? launch_stream_d2<2, 1>(st, A, ev_start, ev_stop) : launch_stream_d2<1, 1>(st, A, ev_start, ev_stop);
 }
