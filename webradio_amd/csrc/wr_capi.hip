@@ -945,6 +945,40 @@ static unsigned int group_slots_used(const Group *g)
 	return ((hi + WR_LANES - 1) / WR_LANES) * WR_LANES;
 }
 
+/* a rate group's view for the kernels of one block of `nframes` frames at `cur` (float IQ) or `cur_u8` (RTL-SDR bytes):
+ * what tuner_submit_now hands k_tuner_ddc and the post stage, and stream_open the streaming launch.  No events. */
+static WrTunerLaunch group_launch(const wr_tuner *t, const Group *g, const float *cur, const uint8_t *cur_u8,
+                                  size_t nframes)
+{
+	WrTunerLaunch L;
+	L.cur = cur;
+	L.cur_u8 = cur_u8;
+	L.hist = t->in_hist[t->in_par];
+	L.hist_next = t->in_hist[t->in_par ^ 1];
+	L.parity = g->parity;
+	L.sp = g->sp;
+	L.cb = g->cb;
+	L.nframes = nframes;
+	L.d1 = g->d1;
+	L.d2 = g->d2;
+	L.slots = g->slots;
+	L.slots_used = group_slots_used(g);
+	L.k1 = nframes / g->d1;                 /* dspblock.cxx:177-178 */
+	L.k2 = L.k1 / g->d2;
+	L.k2max = g->k2max;
+	L.nco_mode = t->nco_mode;
+	L.uniform_mask = g->uniform_mask;
+	L.uniform2_mask = g->uniform2_mask;
+	L.fewsets_mask = g->fewsets_mask;
+	L.one_filter = g->one_filter ? 1 : 0;
+	memcpy(L.nsets, g->nsets, sizeof(L.nsets));
+	L.audio_scale = t->audio_scale;
+	L.use_gain = g->use_gain ? 1 : 0;
+	L.use_squelch = g->use_squelch ? 1 : 0;
+	L.ev_start = L.ev_stop = nullptr;
+	return L;
+}
+
 static void group_free(Group *g)
 {
 	if (!g)
@@ -1819,6 +1853,20 @@ static int prof_drain(wr_tuner *t, size_t keep)
 	return WR_OK;
 }
 
+/* room for one more event pair at t->ev[t->ev_used]: the pairs recorded so far are drained first, unless a group's
+ * start event is still waiting for its stop (ev_used odd) */
+static int prof_reserve_pair(wr_tuner *t)
+{
+	if (int rc = (t->ev_used & 1) ? WR_OK : prof_drain(t, 64))
+		return rc;
+	while (t->ev.size() < t->ev_used + 2) {
+		hipEvent_t e;
+		HIP_TRY(hipEventCreate(&e));
+		t->ev.push_back(e);
+	}
+	return WR_OK;
+}
+
 extern "C" int wr_tuner_profile(wr_tuner *t, int enable)
 {
 	if (!t)
@@ -1970,6 +2018,17 @@ static int tuner_submit(wr_tuner *t, const void *iq, size_t nframes, int where, 
 	return tuner_submit_now(t, iq, nframes, where, u8);
 }
 
+/* the host's mirror of the phase advance the kernels wrote into the other state set: `frames` input frames on
+ * (downconverter.cxx:103), mod 2^32 */
+static void advance_phases(wr_tuner *t, unsigned long long frames)
+{
+	for (Chan &c : t->chans) {
+		if (!c.in_use || c.group < 0)
+			continue;
+		c.phaseL += (unsigned int)frames * c.stepL;
+	}
+}
+
 static int tuner_submit_now(wr_tuner *t, const void *iq, size_t nframes, int where, bool u8)
 {
 	if (!t || (nframes && !iq))
@@ -2059,41 +2118,10 @@ static int tuner_submit_now(wr_tuner *t, const void *iq, size_t nframes, int whe
 			if (rc)
 				return rc;
 		}
-		WrTunerLaunch L;
-		L.cur = cur;
-		L.cur_u8 = cur_u8;
-		L.hist = t->in_hist[t->in_par];
-		L.hist_next = t->in_hist[t->in_par ^ 1];
-		L.parity = g->parity;
-		L.sp = g->sp;
-		L.cb = g->cb;
-		L.nframes = nframes;
-		L.d1 = g->d1;
-		L.d2 = g->d2;
-		L.slots = g->slots;
-		L.slots_used = group_slots_used(g);
-		L.k1 = nframes / g->d1;                 /* dspblock.cxx:177-178 */
-		L.k2 = L.k1 / g->d2;
-		L.k2max = g->k2max;
-		L.nco_mode = t->nco_mode;
-		L.uniform_mask = g->uniform_mask;
-		L.uniform2_mask = g->uniform2_mask;
-		L.fewsets_mask = g->fewsets_mask;
-		L.one_filter = g->one_filter ? 1 : 0;
-		memcpy(L.nsets, g->nsets, sizeof(L.nsets));
-		L.audio_scale = t->audio_scale;
-		L.use_gain = g->use_gain ? 1 : 0;
-		L.use_squelch = g->use_squelch ? 1 : 0;
-		L.ev_start = L.ev_stop = nullptr;
+		WrTunerLaunch L = group_launch(t, g, cur, cur_u8, nframes);
 		if (prof_now || group_first) {
-			int rc = (t->ev_used & 1) ? WR_OK : prof_drain(t, 64);
-			if (rc)
+			if (int rc = prof_reserve_pair(t))
 				return rc;
-			while (t->ev.size() < t->ev_used + 2) {
-				hipEvent_t e;
-				HIP_TRY(hipEventCreate(&e));
-				t->ev.push_back(e);
-			}
 		}
 		if (prof_now) {
 			L.ev_start = t->ev[t->ev_used];     /* stamped by the launch itself (wrk_tuner_ddc) */
@@ -2244,12 +2272,7 @@ static int tuner_submit_now(wr_tuner *t, const void *iq, size_t nframes, int whe
 		++t->launches_marked;
 	}
 
-	/* host mirror of the phase advance k_tuner_ddc wrote into the other state set */
-	for (Chan &c : t->chans) {
-		if (!c.in_use || c.group < 0)
-			continue;
-		c.phaseL += (unsigned int)nframes * c.stepL;
-	}
+	advance_phases(t, nframes);
 	t->submitted = true;
 	return WR_OK;
 }
@@ -2267,10 +2290,10 @@ static int tuner_submit_now(wr_tuner *t, const void *iq, size_t nframes, int whe
  * own state is advanced by as many blocks at the close.  Same bits as one launch per block (tests/test_gpu_stream.py).
  *
  * Requirements, checked at the open (a submit that does not meet them goes the ordinary way): WR_NCO_ROTATE; one
- * rate group; at most 1024 channels, all on ONE 64-tap channel filter; no second channel stage; an audio decimation
- * the fused post stage has (1..6, 8, 10); whole audio frames per block; no kept demodulator rows, no seek pending, no
- * launch marks.  A block's memory must stay untouched until the NEXT block's audio is complete (the first frames of
- * a block read the last 63 of the one before in place).
+ * rate group; at most 1024 channels on 64-tap channel filters, at most WR_TAPSETS distinct ones in each lane group of 64
+ * channel slots; no second channel stage; an audio decimation the fused post stage has (1..6, 8, 10); whole audio
+ * frames per block; no kept demodulator rows, no seek pending, no launch marks.  A block's memory must stay untouched
+ * until the NEXT block's audio is complete (the first frames of a block read the last 63 of the one before in place).
  *
  * A caller that waits for the device's stream by other means (hipStreamSynchronize on a stream it handed to
  * wr_dev_open, torch.cuda.synchronize()) should call wr_tuner_flush first: an open launch that nobody rings ends by
@@ -2480,32 +2503,7 @@ static int stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, boo
 	hipStream_t st = d->stream;
 
 	/* the launch's view of the group: what tuner_submit_now hands k_tuner_ddc and the post stage for one block */
-	WrTunerLaunch L;
-	L.cur = u8 ? nullptr : (const float *)iq;
-	L.cur_u8 = u8 ? (const uint8_t *)iq : nullptr;
-	L.hist = t->in_hist[t->in_par];
-	L.hist_next = t->in_hist[t->in_par ^ 1];
-	L.parity = g->parity;
-	L.sp = g->sp;
-	L.cb = g->cb;
-	L.nframes = nframes;
-	L.d1 = g->d1;
-	L.d2 = g->d2;
-	L.slots = g->slots;
-	L.slots_used = used;
-	L.k1 = k1;
-	L.k2 = k2;
-	L.k2max = g->k2max;
-	L.nco_mode = t->nco_mode;
-	L.uniform_mask = g->uniform_mask;
-	L.uniform2_mask = g->uniform2_mask;
-	L.fewsets_mask = g->fewsets_mask;
-	L.one_filter = g->one_filter ? 1 : 0;
-	memcpy(L.nsets, g->nsets, sizeof(L.nsets));
-	L.audio_scale = t->audio_scale;
-	L.use_gain = g->use_gain ? 1 : 0;
-	L.use_squelch = g->use_squelch ? 1 : 0;
-	L.ev_start = L.ev_stop = nullptr;
+	const WrTunerLaunch L = group_launch(t, g, u8 ? nullptr : (const float *)iq, u8 ? (const uint8_t *)iq : nullptr, nframes);
 
 	WrStreamArgs A;
 	memset(&A, 0, sizeof(A));
@@ -2612,15 +2610,10 @@ static int stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, boo
 
 	void *ev0 = nullptr, *ev1 = nullptr;
 	if (t->profiling) {
-		/* one event pair for the whole launch, stamped by the dispatch itself */
-		if (int rc = (t->ev_used & 1) ? WR_OK : prof_drain(t, 64))
-			return rc;
+		/* one event pair for the whole launch, stamped by the dispatch itself (none while a group's start event is open) */
 		if (!(t->ev_used & 1)) {
-			while (t->ev.size() < t->ev_used + 2) {
-				hipEvent_t e;
-				HIP_TRY(hipEventCreate(&e));
-				t->ev.push_back(e);
-			}
+			if (int rc = prof_reserve_pair(t))
+				return rc;
 			ev0 = t->ev[t->ev_used];
 			ev1 = t->ev[t->ev_used + 1];
 		}
@@ -2787,11 +2780,7 @@ static int stream_close(wr_tuner *t)
 	g->audio_cur = (int)((g->audio_cur + (J - 1u)) & 3u);
 	g->dev.audio = g->dev.audio_set[g->audio_cur];
 	t->in_par ^= 1;
-	for (Chan &c : t->chans) {
-		if (!c.in_use || c.group < 0)
-			continue;
-		c.phaseL += (unsigned int)((unsigned long long)s.nframes * J) * c.stepL;
-	}
+	advance_phases(t, (unsigned long long)s.nframes * J);
 	t->submitted = true;
 	return WR_OK;
 }

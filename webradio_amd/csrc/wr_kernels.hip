@@ -25,6 +25,7 @@
 
 #include <atomic>
 #include <cstdlib>
+#include <type_traits>
 
 #include <hip/hip_ext.h>
 
@@ -401,6 +402,17 @@ __device__ __forceinline__ void wave_prio(unsigned int level)
 		__builtin_amdgcn_s_setprio(1);
 	else
 		__builtin_amdgcn_s_setprio(0);
+}
+
+/* the ROTATE NCO's tables to LDS, for the whole workgroup: hi_cs at [0, WR_SPLIT_N), lo_cs behind it */
+__device__ __forceinline__ void rot_tables_to_lds(v2f *lds, const float2 *hi_cs, const float2 *lo_cs)
+{
+	for (unsigned int e = threadIdx.x; e < WR_SPLIT_N; e += blockDim.x) {
+		const float2 hv = hi_cs[e], lv = lo_cs[e];
+		lds[e] = (v2f){hv.x, hv.y};
+		lds[WR_SPLIT_N + e] = (v2f){lv.x, lv.y};
+	}
+	__syncthreads();
 }
 
 #define ROT_SEG 64                       /* measured on MI355X, C2: 16 -> 4.5e-8 / 40.9 us, 32 -> 6.7e-8 / 39.5 us,
@@ -862,12 +874,7 @@ ddc_body(DDC_PARAMS, v2f *lds, const int role)
 		}
 		__syncthreads();
 	} else if (NCO == WR_NCO_ROTATE) {
-		for (unsigned int e = threadIdx.x; e < WR_SPLIT_N; e += blockDim.x) {
-			const float2 hv = hi_cs[e], lv = lo_cs[e];
-			lds[e] = (v2f){hv.x, hv.y};
-			lds[WR_SPLIT_N + e] = (v2f){lv.x, lv.y};
-		}
-		__syncthreads();
+		rot_tables_to_lds(lds, hi_cs, lo_cs);
 	}
 	const v2f *hi_l = (NCO == WR_NCO_ROTATE) ? lds : lds + (lane & 31u);
 	const v2f *lo_l = (NCO == WR_NCO_ROTATE) ? lds + WR_SPLIT_N : lds + WR_SPLIT_N * 32u + (lane & 31u);
@@ -1328,6 +1335,175 @@ template <int NCO, bool UTAPS, unsigned int NG> struct DdcOcc {
 	                                       : DDC_WAVES / 4u;
 };
 
+/* ---- the lean loop's pieces, shared by k_tuner_ddc and the streaming launch (stream_ddc): a wave computes one output
+ * frame of NG lane groups per unit ---- */
+
+/* per recurrence c < NG (lane group gs * NG + c of the launch's map): one coalesced load each (WrGroupDev::rot, ...),
+ * all independent of one another.  `phase0(s)`: slot s's phase at frame 0; `f0`: the wave's first unit's first window
+ * frame (mod 2^32); the phase of a unit's first window frame then advances by addition, wpg * d1 frames per unit. */
+template <unsigned int NG> struct LeanRec {
+	unsigned int Pk[NG], fstep[NG], dP[NG], stv[NG];
+	int fl[NG];
+	v2f rot0[NG], rot1[NG];                              /* the two possible turns per frame */
+	float2 *out[NG];
+	unsigned int g0;                                     /* recurrence 0's lane group */
+};
+
+template <unsigned int NG, class Phase0>
+__device__ __forceinline__ LeanRec<NG> lean_rec(const Phase0 &phase0, const unsigned int *step, const int *flags,
+                                                const float4 *rot, float2 *out, unsigned long long gmap0,
+                                                unsigned long long gmap1, unsigned int gs, unsigned int lane,
+                                                unsigned int f0, unsigned int wpg, unsigned int d1)
+{
+	LeanRec<NG> R;
+	R.g0 = 0;
+#pragma unroll
+	for (unsigned int c = 0; c < NG; ++c) {
+		const unsigned int gl = gs * NG + c;
+		const unsigned int g = (unsigned int)(((gl < 8u ? gmap0 : gmap1) >> ((gl & 7u) * 8u)) & 255u);
+		const unsigned int s = g * 64u + lane;
+		if (c == 0)
+			R.g0 = g;
+		const unsigned int p0 = phase0(s);
+		R.stv[c] = step[s];
+		R.fl[c] = flags[s];
+		const float4 r4 = rot[s];
+		R.rot0[c] = (v2f){r4.x, r4.y};
+		R.rot1[c] = (v2f){r4.z, r4.w};
+		R.fstep[c] = R.stv[c] << 16;
+		R.Pk[c] = p0 + f0 * R.stv[c];                    /* phase of the unit's first window frame */
+		R.dP[c] = wpg * d1 * R.stv[c];
+		R.out[c] = out + s;
+	}
+	return R;
+}
+
+/* a lane's part of the wave's two window buffers (`win`: [buffer][tap set][64], `nset` copies per buffer).  TS: the tap
+ * sets the instance provides for -- 1: one channel filter per lane group; WR_TAPSETS: a lane group with up to `nset`
+ * distinct ones, the window going to LDS once per filter, tap * sample, and every lane reading the copy made with ITS
+ * filter (WrGroupDev::tapsel). */
+template <unsigned int TS> struct LeanWin {
+	float hlane[TS];                                     /* lane j holds the tap of window sample j, per tap set */
+	unsigned int nset;
+	const lds_v4f *w4[2];                                /* this lane's copy, as the unit reads it */
+	v2f *wst[2];                                         /* where this lane's sample goes, copy 0 */
+
+	/* a window sample as loaded (two floats, or the two bytes of the RTL-SDR format in .x: converted here, where it is
+	 * used, (u8 - 128) / 128 as io/rtlsdrtuner.cxx:106 -- nothing waits at the load) to buffer b, once per tap set */
+	__device__ __forceinline__ void to_lds(const float2 raw, const int b, const bool u8) const
+	{
+		float2 xf = raw;
+		if (u8) {
+			const unsigned int bits = __builtin_bit_cast(unsigned int, raw.x);
+			xf = make_float2(((float)(bits & 255u) - 128.0f) / 128.0f, ((float)((bits >> 8) & 255u) - 128.0f) / 128.0f);
+		}
+#pragma unroll
+		for (unsigned int q = 0; q < TS; ++q)
+			if (TS == 1u || q < nset)
+				wst[b][q * 64u] = (v2f){hlane[q] * xf.x, hlane[q] * xf.y};
+	}
+};
+
+template <unsigned int TS>
+__device__ __forceinline__ LeanWin<TS> lean_win(const float *taps1u, const int *tapsel, unsigned int g0, unsigned int lane,
+                                                unsigned int nset, v2f *win)
+{
+	LeanWin<TS> W;
+	W.nset = nset;
+	const unsigned int mysel = TS == 1u ? 0u : (unsigned int)tapsel[g0 * 64u + lane];   /* this lane's tap set */
+#pragma unroll
+	for (unsigned int q = 0; q < TS; ++q)
+		W.hlane[q] = (TS == 1u || q < nset) ? taps1u[((size_t)g0 * WR_TAPSETS + q) * 64u + lane] : 0.0f;
+#pragma unroll
+	for (int b = 0; b < 2; ++b) {
+		W.w4[b] = (const lds_v4f *)(win + ((unsigned int)b * nset + mysel) * 64u);
+		W.wst[b] = win + (unsigned int)b * nset * 64u + lane;
+	}
+	return W;
+}
+
+/* One unit's taps: the ROTATE recurrences of NG lane groups over the window at `w` (tap * sample), each closed by the
+ * LO of its segment's last frame (see ROT_SEG) -- the arithmetic of one output frame, for every path that runs it. */
+template <unsigned int NG> struct AccN {
+	v2f v[NG];
+};
+
+template <unsigned int NG>
+__device__ __forceinline__ AccN<NG> rotate_unit(const lds_v4f *w, const LeanRec<NG> &R, const float *table,
+                                                const v2f *hi_l, const v2f *lo_l)
+{
+	v2f csq[NG][ROT_Q];
+	unsigned int F[NG];
+	AccN<NG> acc;
+	v2f A[NG], Aq[NG][ROT_Q];
+#pragma unroll
+	for (unsigned int c = 0; c < NG; ++c) {
+#pragma unroll
+		for (int q = 0; q < ROT_Q; ++q)
+			csq[c][q] = nco<WR_NCO_ROTATE>(R.Pk[c] + (unsigned int)(q * ROT_SEG + ROT_SEG - 1) * R.stv[c], table, hi_l, lo_l);
+		F[c] = R.Pk[c] << 16;                            /* the 16 fraction bits, left-aligned */
+		acc.v[c] = (v2f){0.0f, 0.0f};
+		A[c] = (v2f){0.0f, 0.0f};
+	}
+	/* the window comes back DDC_RD x 16 bytes (2 taps each) ahead of the arithmetic */
+	constexpr int RD = DDC_RD, NST = WR_FIR_LENGTH / 2 / RD;
+	v4f xr[2][RD];
+#pragma unroll
+	for (int r = 0; r < RD; ++r)
+		xr[0][r] = w[r];
+#pragma unroll
+	for (int t = 0; t < NST; ++t) {
+		if (t + 1 < NST) {
+#pragma unroll
+			for (int r = 0; r < RD; ++r)
+				xr[(t + 1) & 1][r] = w[(t + 1) * RD + r];
+		}
+#pragma unroll
+		for (int r = 0; r < RD; ++r) {
+			const v4f x2 = xr[t & 1][r];
+#pragma unroll
+			for (int jj = 0; jj < 2; ++jj) {
+				const int j = 2 * (t * RD + r) + jj;
+				const v2f u = jj ? (v2f){x2.z, x2.w} : (v2f){x2.x, x2.y};
+#pragma unroll
+				for (unsigned int c = 0; c < NG; ++c) {
+					if (j % ROT_SEG == 0) {
+						if (j)
+							F[c] += R.fstep[c];          /* a segment starts afresh: no turn */
+						A[c] = u;
+					} else {
+						unsigned int F2;
+						const bool carry = __builtin_uadd_overflow(F[c], R.fstep[c], &F2);
+						F[c] = F2;
+						horner_step(A[c], carry ? R.rot1[c].x : R.rot0[c].x, carry ? R.rot1[c].y : R.rot0[c].y, u);
+					}
+					if (j % ROT_SEG == ROT_SEG - 1 && j / ROT_SEG + 1 < ROT_Q)
+						Aq[c][j / ROT_SEG] = A[c];     /* (the last segment closes on A itself, below) */
+				}
+			}
+		}
+		/* nothing crosses a stage: left alone, the scheduler hoists all 32 window reads of a unit to its top (128
+		 * registers of them) and spills them -- and the optimiser, for which the carries and selects of ALL taps depend
+		 * on nothing but the phase, may compute them first and sink the multiply-adds to where the result is used: the
+		 * recurrence is pinned stage by stage */
+#pragma unroll
+		for (unsigned int c = 0; c < NG; ++c)
+			asm volatile("" : "+v"(A[c].x), "+v"(A[c].y), "+v"(F[c]));
+		__builtin_amdgcn_sched_barrier(0);
+	}
+#pragma unroll
+	for (unsigned int c = 0; c < NG; ++c) {
+#pragma unroll
+		for (int q = 0; q < ROT_Q; ++q)
+			horner_close(acc.v[c], q + 1 < ROT_Q ? Aq[c][q] : A[c], csq[c][q]);
+		/* (the result is needed HERE: its only use is the caller's store under `if (active)`, and the optimiser would
+		 * sink the whole recurrence into that branch, behind the window writes -- leaving the unit's 32 window reads on
+		 * their own at its top, 128 registers wide) */
+		asm volatile("" : "+v"(acc.v[c].x), "+v"(acc.v[c].y));
+	}
+	return acc;
+}
+
 template <int NCO, bool UTAPS, unsigned int PD2, unsigned int NG>
 __global__ void __launch_bounds__(DDC_WAVES * 64u) __attribute__((amdgpu_waves_per_eu(DdcOcc<NCO, UTAPS, NG>::per_eu)))
 k_tuner_ddc(const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u8,
@@ -1373,14 +1549,10 @@ k_tuner_ddc(const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u8,
 	const unsigned int wid = blockIdx.x * waves_per_wg + wave;
 	TL(0);
 	wave_prio(3u);                                           /* the prologue's loads go out at once */
-	for (unsigned int e = threadIdx.x; e < WR_SPLIT_N; e += blockDim.x) {
-		const float2 hv = hi_cs[e], lv = lo_cs[e];
-		lds[e] = (v2f){hv.x, hv.y};
-		lds[WR_SPLIT_N + e] = (v2f){lv.x, lv.y};
-	}
-	__syncthreads();
+	rot_tables_to_lds(lds, hi_cs, lo_cs);
 	const v2f *hi_l = lds, *lo_l = lds + WR_SPLIT_N;
-	const unsigned int nset = (NG == 2u) ? 1u : kmax;
+	constexpr unsigned int TS = (NG == 2u) ? 1u : WR_TAPSETS;   /* (NG = 2: one channel filter for both lane groups) */
+	const unsigned int nset = (TS == 1u) ? 1u : kmax;
 	v2f *win = lds + 2u * WR_SPLIT_N + wave * (128u * nset);
 	if (whole && blockIdx.x == 0 && wave == 0 && lane < WR_HIST) {
 		const size_t f = nframes + lane;            /* frame index in [hist | cur]: the tuner's next input history */
@@ -1407,51 +1579,15 @@ k_tuner_ddc(const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u8,
 	const unsigned int my_units = (k < k1u) ? (k1u - k + wpg - 1u) / wpg : 0u;
 	unsigned int tl_unit = 0;
 	if (k < k1u) {
-		/* per recurrence: one coalesced load each (WrGroupDev::rot, taps1u), all independent of one another */
-		unsigned int Pk[NG], fstep[NG], dP[NG], stv[NG];
-		int fl[NG];
-		v2f rot0[NG], rot1[NG];                          /* the two possible turns per frame */
-		float2 *out[NG];
-		unsigned int g0 = 0, s0 = 0;
-#pragma unroll
-		for (unsigned int c = 0; c < NG; ++c) {
-			const unsigned int gl = gs * NG + c;
-			const unsigned int g = (unsigned int)(((gl < 8u ? gmap0 : gmap1) >> ((gl & 7u) * 8u)) & 255u);
-			const unsigned int s = g * 64u + lane;
-			if (c == 0) {
-				g0 = g;
-				s0 = s;
-			}
-			const unsigned int p0 = DDC_PHASE(s);
-			stv[c] = step[s];
-			fl[c] = flags[s];
-			const float4 r4 = rot[s];
-			rot0[c] = (v2f){r4.x, r4.y};
-			rot1[c] = (v2f){r4.z, r4.w};
-			fstep[c] = stv[c] << 16;
-			Pk[c] = p0 + (unsigned int)((size_t)k * d1 - WR_HIST) * stv[c];   /* phase of the unit's first window frame */
-			dP[c] = wpg * d1 * stv[c];
-			out[c] = chan_iq + s;
-		}
-		const unsigned int mysel = (NG == 2u) ? 0u : (unsigned int)tapsel[s0];   /* which of the group's tap sets this lane's channel uses */
-		float hlane[WR_TAPSETS];                              /* lane j holds the tap of window sample j, per tap set */
-#pragma unroll
-		for (int q = 0; q < WR_TAPSETS; ++q)
-			hlane[q] = ((unsigned int)q < nset) ? taps1u[((size_t)g0 * WR_TAPSETS + q) * 64u + lane] : 0.0f;
-		const lds_v4f *w4[2];
-		v2f *wst[2];
-#pragma unroll
-		for (int b = 0; b < 2; ++b) {
-			w4[b] = (const lds_v4f *)(win + ((unsigned int)b * nset + mysel) * 64u);
-			wst[b] = win + (unsigned int)b * nset * 64u + lane;
-		}
+		LeanRec<NG> R = lean_rec<NG>([&](unsigned int s) { return DDC_PHASE(s); }, step, flags, rot, chan_iq, gmap0, gmap1,
+		                             gs, lane, (unsigned int)((size_t)k * d1 - WR_HIST), wpg, d1);
+		const LeanWin<TS> W = lean_win<TS>(taps1u, tapsel, R.g0, lane, nset, win);
 		const size_t dn = (size_t)wpg * d1;
 		/* window sample `lane` of unit kk is frame kk * d1 - 63 + lane >= 0, inside the block; past the
 		 * wave's last unit the index stays where it is (a load nobody uses, and no branch around it) */
 		const size_t nlast = (size_t)(k + (my_units - 1u) * wpg) * d1 - WR_HIST + lane;
 		size_t nx = (size_t)k * d1 - WR_HIST + lane;
-		/* (a frame travels as loaded -- two floats, or the two bytes of the RTL-SDR format in .x -- and is
-		 * converted where it is used, (u8 - 128) / 128 as io/rtlsdrtuner.cxx:106: nothing waits at the load) */
+		/* (a frame travels as loaded: LeanWin::to_lds) */
 		auto fetch = [&]() __attribute__((always_inline)) -> float2 {
 			float2 v;
 			if (cur_u8) {
@@ -1463,20 +1599,10 @@ k_tuner_ddc(const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u8,
 			nx = (nx + dn <= nlast) ? nx + dn : nlast;
 			return v;
 		};
-		auto to_lds = [&](const float2 raw, const int b) __attribute__((always_inline)) {
-			float2 xf = raw;
-			if (cur_u8) {
-				const unsigned int bits = __builtin_bit_cast(unsigned int, raw.x);
-				xf = make_float2(((float)(bits & 255u) - 128.0f) / 128.0f, ((float)((bits >> 8) & 255u) - 128.0f) / 128.0f);
-			}
-#pragma unroll
-			for (int q = 0; q < WR_TAPSETS; ++q)
-				if ((unsigned int)q < nset)
-					wst[b][q * 64] = (v2f){hlane[q] * xf.x, hlane[q] * xf.y};
-		};
+		const bool u8 = cur_u8 != nullptr;
 		float2 xa = fetch();                              /* unit 0 */
 		float2 xb = fetch();                              /* unit 1 */
-		to_lds(xa, 0);
+		W.to_lds(xa, 0, u8);
 		xa = fetch();                                     /* unit 2 */
 		TL(2);
 		/* one unit from LDS buffer b; `xo` holds the NEXT unit's window sample (on its way or landed) */
@@ -1485,85 +1611,18 @@ k_tuner_ddc(const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u8,
 				const unsigned int q = (4u * tl_unit) / my_units;   /* 0..3: see wave_prio */
 				wave_prio(q >= 3u ? 0u : 2u - q + 0u);
 			}
-			v2f csq[NG][ROT_Q];
-			unsigned int F[NG];
-			v2f acc[NG], A[NG], Aq[NG][ROT_Q];
-#pragma unroll
-			for (unsigned int c = 0; c < NG; ++c) {
-#pragma unroll
-				for (int q = 0; q < ROT_Q; ++q)
-					csq[c][q] = nco<NCO>(Pk[c] + (unsigned int)(q * ROT_SEG + ROT_SEG - 1) * stv[c], table, hi_l, lo_l);
-				F[c] = Pk[c] << 16;                   /* the 16 fraction bits, left-aligned */
-				acc[c] = (v2f){0.0f, 0.0f};
-				A[c] = (v2f){0.0f, 0.0f};
-			}
-			/* the window comes back DDC_RD x 16 bytes (2 taps each) ahead of the arithmetic */
-			constexpr int RD = DDC_RD, NST = WR_FIR_LENGTH / 2 / RD;
-			v4f xr[2][RD];
-#pragma unroll
-			for (int r = 0; r < RD; ++r)
-				xr[0][r] = w4[b][r];
-#pragma unroll
-			for (int t = 0; t < NST; ++t) {
-				if (t + 1 < NST) {
-#pragma unroll
-					for (int r = 0; r < RD; ++r)
-						xr[(t + 1) & 1][r] = w4[b][(t + 1) * RD + r];
-				}
-#pragma unroll
-				for (int r = 0; r < RD; ++r) {
-					const v4f x2 = xr[t & 1][r];
-#pragma unroll
-					for (int jj = 0; jj < 2; ++jj) {
-						const int j = 2 * (t * RD + r) + jj;
-						const v2f u = jj ? (v2f){x2.z, x2.w} : (v2f){x2.x, x2.y};
-#pragma unroll
-						for (unsigned int c = 0; c < NG; ++c) {
-							if (j % ROT_SEG == 0) {
-								if (j)
-									F[c] += fstep[c];       /* a segment starts afresh: no turn */
-								A[c] = u;
-							} else {
-								unsigned int F2;
-								const bool carry = __builtin_uadd_overflow(F[c], fstep[c], &F2);
-								F[c] = F2;
-								horner_step(A[c], carry ? rot1[c].x : rot0[c].x, carry ? rot1[c].y : rot0[c].y, u);
-							}
-							if (j % ROT_SEG == ROT_SEG - 1)
-								Aq[c][j / ROT_SEG] = A[c];
-						}
-					}
-				}
-				/* nothing crosses a stage: left alone, the scheduler hoists all 32 window reads of a unit to
-				 * its top (128 registers of them) and spills them -- and the optimiser, for which the carries and
-				 * selects of ALL taps depend on nothing but the phase, may compute them first and sink the
-				 * multiply-adds to where the result is used: the recurrence is pinned stage by stage */
-#pragma unroll
-				for (unsigned int c = 0; c < NG; ++c)
-					asm volatile("" : "+v"(A[c].x), "+v"(A[c].y), "+v"(F[c]));
-				__builtin_amdgcn_sched_barrier(0);
-			}
-#pragma unroll
-			for (unsigned int c = 0; c < NG; ++c) {
-#pragma unroll
-				for (int q = 0; q < ROT_Q; ++q)
-					horner_close(acc[c], Aq[c][q], csq[c][q]);
-				/* (the result is needed HERE: its only use is the store under `if (active)` below, and the
-				 * optimiser would sink the whole recurrence into that branch, behind the window writes --
-				 * leaving the unit's 32 window reads on their own at its top, 128 registers wide) */
-				asm volatile("" : "+v"(acc[c].x), "+v"(acc[c].y));
-			}
+			const AccN<NG> acc = rotate_unit<NG>(W.w4[b], R, table, hi_l, lo_l);
 			/* the next unit's window (requested two units ago), this unit's result, the request after next */
-			to_lds(xo, b ^ 1);
+			W.to_lds(xo, b ^ 1, u8);
 #pragma unroll
 			for (unsigned int c = 0; c < NG; ++c) {
-				if (fl[c] & PHASE_FLAG_ACTIVE) {
+				if (R.fl[c] & PHASE_FLAG_ACTIVE) {
 					union { v2f f; unsigned long long u; } cv;
-					cv.f = acc[c];
-					__hip_atomic_store((unsigned long long *)&out[c][(size_t)k * slots], cv.u, __ATOMIC_RELAXED,
+					cv.f = acc.v[c];
+					__hip_atomic_store((unsigned long long *)&R.out[c][(size_t)k * slots], cv.u, __ATOMIC_RELAXED,
 					                   __HIP_MEMORY_SCOPE_AGENT);             /* write-through: see ddc_body */
 				}
-				Pk[c] += dP[c];
+				R.Pk[c] += R.dP[c];
 			}
 			xo = fetch();
 			k += wpg;
@@ -1756,12 +1815,7 @@ k_tuner_ddc_long_rot(const float2 *__restrict__ cur, const uchar2 *__restrict__ 
 	v2f *hi_l = (v2f *)long_rot_lds, *lo_l = hi_l + WR_SPLIT_N;
 	v2f (*winl)[2][64] = (v2f (*)[2][64])(lo_l + WR_SPLIT_N);
 	float (*hseg)[64] = (float (*)[64])(winl + LONG_ROT_WAVES);
-	for (unsigned int e = threadIdx.x; e < WR_SPLIT_N; e += blockDim.x) {
-		const float2 hv = hi_cs[e], lv = lo_cs[e];
-		hi_l[e] = (v2f){hv.x, hv.y};
-		lo_l[e] = (v2f){lv.x, lv.y};
-	}
-	__syncthreads();
+	rot_tables_to_lds(hi_l, hi_cs, lo_cs);
 	const unsigned int lane = threadIdx.x & 63u;
 	const unsigned int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const unsigned int segs = len / 64u, hl = len - 1u, gsets = groups / NG;
@@ -1876,6 +1930,36 @@ k_ddc_long_roll(const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u
 	               (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
 }
 
+/* The audio decimations the post stage is built for (anything else takes the two-kernel path): 1..6, and 8 and 10 --
+ * 256 k -> 32 k (BASELINE config 1), 240 k -> 24 k, 480 k -> 48 k.  Calls f with the run-time d2 as a compile-time
+ * constant (std::integral_constant<unsigned int, D2>); any other d2: hipErrorInvalidValue. */
+template <class F>
+static hipError_t with_post_d2(unsigned int d2, F &&f)
+{
+	switch (d2) {
+	case 1: return f(std::integral_constant<unsigned int, 1u>());
+	case 2: return f(std::integral_constant<unsigned int, 2u>());
+	case 3: return f(std::integral_constant<unsigned int, 3u>());
+	case 4: return f(std::integral_constant<unsigned int, 4u>());
+	case 5: return f(std::integral_constant<unsigned int, 5u>());
+	case 6: return f(std::integral_constant<unsigned int, 6u>());
+	case 8: return f(std::integral_constant<unsigned int, 8u>());
+	case 10: return f(std::integral_constant<unsigned int, 10u>());
+	default: return hipErrorInvalidValue;
+	}
+}
+
+bool wrk_tuner_post_supported(unsigned int d2)
+{
+	return with_post_d2(d2, [](auto) { return hipSuccess; }) == hipSuccess;
+}
+
+/* LDS of a post-stage workgroup (post_role): the staged rows of (POST_TK - 1) d2 + 64 nseg frames, the tile, the modes */
+static size_t post_lds_bytes(unsigned int d2, unsigned int nseg)
+{
+	return (((size_t)(POST_TK - 1u) * d2 + WR_FIR_LENGTH * nseg) * 64u + POST_TK * 65u + 64u) * sizeof(float);
+}
+
 hipError_t wrk_tuner_ddc_long(hipStream_t st, const WrTunerLaunch &L, const WrGroupDev &G, unsigned int len,
                               const float *table_dev, int num_cus, bool rotate, bool rotate_one_filter, const float *hi_dev,
                               const float *lo_dev, const WrPostArgs *post, bool *post_taken)
@@ -1913,39 +1997,29 @@ hipError_t wrk_tuner_ddc_long(hipStream_t st, const WrTunerLaunch &L, const WrGr
 		rolled = true;
 		size_t lds = LONG_ROT_LDS;
 		if (ride) {
-			const size_t need = ((size_t)((POST_TK - 1u) * d2r + WR_FIR_LENGTH) * 64u + POST_TK * 65u + 64u) * sizeof(float);
+			const size_t need = post_lds_bytes(d2r, 1u);
 			if (need > lds)
 				lds = need;
 			if (post_taken)
 				*post_taken = true;
 		}
-#define LONG_ROT_LAUNCH(NG_, PD2_) \
-		hipExtLaunchKernelGGL((k_tuner_ddc_long_rot<NG_, PD2_>), dim3(wgs_r + post_wgs + roll_wgs), dim3(LONG_ROT_WAVES * 64u), (uint32_t)lds, st, \
-		                      e0, e1, 0u, (const float2 *)L.cur, (const uchar2 *)L.cur_u8, L.k1, L.d1, len, L.slots, groups, \
-		                      (const unsigned int *)G.phase[L.sp], (const unsigned int *)G.step, (const int *)G.flags, \
-		                      (const float4 *)G.rot, (const float *)G.taps1L, (const float2 *)hi_dev, (const float2 *)lo_dev, \
-		                      (float2 *)G.chan_iq[L.cb], (const float2 *)G.mixhist[L.sp], wgs_r, pa, post_wgs, L.nframes, \
-		                      G.phase[L.sp ^ 1], (float2 *)G.mixhist[L.sp ^ 1], table_dev)
-#define LONG_ROT_BY_D2(NG_) \
-		switch (d2r) { \
-		case 0: LONG_ROT_LAUNCH(NG_, 0u); break; \
-		case 1: LONG_ROT_LAUNCH(NG_, 1u); break; \
-		case 2: LONG_ROT_LAUNCH(NG_, 2u); break; \
-		case 3: LONG_ROT_LAUNCH(NG_, 3u); break; \
-		case 4: LONG_ROT_LAUNCH(NG_, 4u); break; \
-		case 5: LONG_ROT_LAUNCH(NG_, 5u); break; \
-		case 6: LONG_ROT_LAUNCH(NG_, 6u); break; \
-		case 8: LONG_ROT_LAUNCH(NG_, 8u); break; \
-		case 10: LONG_ROT_LAUNCH(NG_, 10u); break; \
-		default: return hipErrorInvalidValue; \
-		}
-		if (two) {
-			LONG_ROT_BY_D2(2u)
-		} else {
-			LONG_ROT_BY_D2(1u)
-		}
-#undef LONG_ROT_BY_D2
-#undef LONG_ROT_LAUNCH
+		auto launch = [&](auto NG_) {
+			auto go = [&](auto PD2_) {
+				hipExtLaunchKernelGGL((k_tuner_ddc_long_rot<decltype(NG_)::value, decltype(PD2_)::value>),
+				                      dim3(wgs_r + post_wgs + roll_wgs), dim3(LONG_ROT_WAVES * 64u), (uint32_t)lds, st, e0, e1, 0u,
+				                      (const float2 *)L.cur, (const uchar2 *)L.cur_u8, L.k1, L.d1, len, L.slots, groups,
+				                      (const unsigned int *)G.phase[L.sp], (const unsigned int *)G.step, (const int *)G.flags,
+				                      (const float4 *)G.rot, (const float *)G.taps1L, (const float2 *)hi_dev, (const float2 *)lo_dev,
+				                      (float2 *)G.chan_iq[L.cb], (const float2 *)G.mixhist[L.sp], wgs_r, pa, post_wgs, L.nframes,
+				                      G.phase[L.sp ^ 1], (float2 *)G.mixhist[L.sp ^ 1], table_dev);
+				return hipSuccess;
+			};
+			return d2r ? with_post_d2(d2r, go) : go(std::integral_constant<unsigned int, 0u>());
+		};
+		const hipError_t e = two ? launch(std::integral_constant<unsigned int, 2u>())
+		                         : launch(std::integral_constant<unsigned int, 1u>());
+		if (e != hipSuccess)
+			return e;
 	}
 	const bool prof_exact = L.ev_start && L.ev_stop && !exact_done;
 	const size_t units = exact_done ? 0 : k_exact * groups;
@@ -2510,8 +2584,7 @@ static hipError_t launch_ddc(hipStream_t st, const WrTunerLaunch &L, const WrGro
 		 * persist).  Measured at C2, kernel duration (r02: per-slot turns, priorities by progress,
 		 * post workgroups at priority 3): 1 slot 38.2 us, 2 slots 39.7, 3 slots 49.8 (the DDC
 		 * starves); DDC + post as two launches: 31.3 + 15.2 + gap. */
-		constexpr unsigned int NEED = (POST_TK - 1u) * (PD2 ? PD2 : 1u) + WR_FIR_LENGTH;
-		const size_t post_lds = ((size_t)NEED * 64u + POST_TK * 65u + 64u) * sizeof(float);
+		const size_t post_lds = post_lds_bytes(PD2, 1u);
 		if (post_lds > lds)
 			lds = post_lds;
 		unsigned int fit = (unsigned int)((160u * 1024u) / lds);
@@ -2591,17 +2664,11 @@ static hipError_t launch_ddc_riding(unsigned int d2, hipStream_t st, const WrTun
                                     const WrPostArgs *post, unsigned long long gsel, bool whole)
 {
 	constexpr bool R = NCO == WR_NCO_ROTATE;
-	switch (d2) {
-	case 1: return launch_ddc<NCO, UTAPS, (R ? 1u : 0u)>(st, L, G, table_dev, hi_dev, lo_dev, num_cus, post, gsel, whole);
-	case 2: return launch_ddc<NCO, UTAPS, (R ? 2u : 0u)>(st, L, G, table_dev, hi_dev, lo_dev, num_cus, post, gsel, whole);
-	case 3: return launch_ddc<NCO, UTAPS, (R ? 3u : 0u)>(st, L, G, table_dev, hi_dev, lo_dev, num_cus, post, gsel, whole);
-	case 4: return launch_ddc<NCO, UTAPS, (R ? 4u : 0u)>(st, L, G, table_dev, hi_dev, lo_dev, num_cus, post, gsel, whole);
-	case 5: return launch_ddc<NCO, UTAPS, (R ? 5u : 0u)>(st, L, G, table_dev, hi_dev, lo_dev, num_cus, post, gsel, whole);
-	case 6: return launch_ddc<NCO, UTAPS, (R ? 6u : 0u)>(st, L, G, table_dev, hi_dev, lo_dev, num_cus, post, gsel, whole);
-	case 8: return launch_ddc<NCO, UTAPS, (R ? 8u : 0u)>(st, L, G, table_dev, hi_dev, lo_dev, num_cus, post, gsel, whole);
-	case 10: return launch_ddc<NCO, UTAPS, (R ? 10u : 0u)>(st, L, G, table_dev, hi_dev, lo_dev, num_cus, post, gsel, whole);
-	default: return hipErrorInvalidValue;      /* (wrk_tuner_post_supported keeps other decimations away) */
-	}
+	/* (wrk_tuner_post_supported keeps other decimations away) */
+	return with_post_d2(d2, [&](auto D2) {
+		return launch_ddc<NCO, UTAPS, (R ? decltype(D2)::value : 0u)>(st, L, G, table_dev, hi_dev, lo_dev, num_cus, post, gsel,
+		                                                             whole);
+	});
 }
 
 template <int NCO>
@@ -2726,9 +2793,9 @@ static hipError_t launch_post(hipStream_t st, const WrPostArgs &A)
 	dim3 grid(A.ntiles + 1u, A.groups);
 	/* (an audio filter of 128 / 256 taps: 2 / 4 segments of 64, post_role) */
 	if (A.nseg == 2u || A.nseg == 4u) {
-		const size_t lds = (((size_t)(POST_TK - 1u) * D2 + WR_FIR_LENGTH * A.nseg) * 64u + POST_TK * 65u + 64u) * sizeof(float);
+		const size_t lds = post_lds_bytes(D2, A.nseg);
 		static bool attr2[WR_MAX_DEVICES], attr4[WR_MAX_DEVICES];
-		const size_t lds_max = (((size_t)(POST_TK - 1u) * D2 + WR_FIR_LENGTH * 4u) * 64u + POST_TK * 65u + 64u) * sizeof(float);
+		const size_t lds_max = post_lds_bytes(D2, 4u);
 		hipError_t e = A.nseg == 2u ? allow_lds((const void *)k_tuner_post<D2, 2u>, lds_max, attr2)
 		                            : allow_lds((const void *)k_tuner_post<D2, 4u>, lds_max, attr4);
 		if (e != hipSuccess)
@@ -2742,13 +2809,6 @@ static hipError_t launch_post(hipStream_t st, const WrPostArgs &A)
 	else
 		return hipErrorInvalidValue;
 	return hipGetLastError();
-}
-
-/* audio decimations k_tuner_post is instantiated for (anything else takes the two-kernel path): 1..6, and 8 and 10
- * -- 256 k -> 32 k (BASELINE config 1), 240 k -> 24 k, 480 k -> 48 k */
-bool wrk_tuner_post_supported(unsigned int d2)
-{
-	return (d2 >= 1 && d2 <= 6) || d2 == 8 || d2 == 10;
 }
 
 hipError_t wrk_tuner_post_args(hipStream_t st, const WrPostArgs &A0)
@@ -2771,17 +2831,7 @@ hipError_t wrk_tuner_post_args(hipStream_t st, const WrPostArgs &A0)
 			                   profiles/r05_long_filter.txt */
 	}
 	A.ntiles = (A.tiles + A.run - 1u) / A.run;
-	switch (A.d2) {
-	case 1: return launch_post<1>(st, A);
-	case 2: return launch_post<2>(st, A);
-	case 3: return launch_post<3>(st, A);
-	case 4: return launch_post<4>(st, A);
-	case 5: return launch_post<5>(st, A);
-	case 6: return launch_post<6>(st, A);
-	case 8: return launch_post<8>(st, A);
-	case 10: return launch_post<10>(st, A);
-	default: return hipErrorInvalidValue;
-	}
+	return with_post_d2(A.d2, [&](auto D2) { return launch_post<decltype(D2)::value>(st, A); });
 }
 
 hipError_t wrk_tuner_post(hipStream_t st, const WrTunerLaunch &L, const WrGroupDev &G)

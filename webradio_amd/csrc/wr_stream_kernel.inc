@@ -33,10 +33,12 @@
  * the stream on its own when the doorbell has been silent for idle_ticks (a caller that synchronises the stream behind
  * the library's back waits that long, no longer).
  *
- * Bits: the lean loop's arithmetic per output frame is k_tuner_ddc's (same functions, same order); frames of blocks
- * j >= 1 whose windows reach into block j-1 take the SAME path with the window read from two places -- the step cannot
- * change inside a stream (a setter closes it), so no kept turns are needed -- which is what "bits do not depend on
- * where the block boundaries fall" (DESIGN.md 4) promises; tests/test_gpu_stream.py holds it to that.
+ * Bits: the lean loop's arithmetic per output frame is k_tuner_ddc's, literally: both call the same functions of
+ * wr_kernels.hip -- lean_rec (a lane's recurrences), lean_win (its taps and window buffers; LeanWin::to_lds), rotate_unit
+ * (one output frame's taps) and rot_tables_to_lds.  Frames of blocks j >= 1 whose windows reach into block j-1 take
+ * the SAME path with the window read from two places -- the step cannot change inside a stream (a setter closes it), so
+ * no kept turns are needed -- which is what "bits do not depend on where the block boundaries fall" (DESIGN.md 4)
+ * promises; tests/test_gpu_stream.py holds it to that.
  */
 
 __device__ __forceinline__ unsigned int st_rfl(unsigned int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -530,15 +532,7 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 	const unsigned int waves_per_wg = blockDim.x >> 6;
 	const unsigned int wid = blockIdx.x * waves_per_wg + wave;
 	wave_prio(3u);                                           /* the prologue's loads go out at once */
-	{
-		const float2 *hi_cs = (const float2 *)S.hi_cs, *lo_cs = (const float2 *)S.lo_cs;
-		for (unsigned int e = threadIdx.x; e < WR_SPLIT_N; e += blockDim.x) {
-			const float2 hv = hi_cs[e], lv = lo_cs[e];
-			lds[e] = (v2f){hv.x, hv.y};
-			lds[WR_SPLIT_N + e] = (v2f){lv.x, lv.y};
-		}
-	}
-	__syncthreads();
+	rot_tables_to_lds(lds, (const float2 *)S.hi_cs, (const float2 *)S.lo_cs);
 	const v2f *hi_l = lds, *lo_l = lds + WR_SPLIT_N;
 	const unsigned int nset = TS == 1u ? 1u : S.kmax;        /* window copies per buffer, double buffered: [buffer][set][64] */
 	v2f *win = lds + 2u * WR_SPLIT_N + wave * (128u * nset);
@@ -551,43 +545,11 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 	unsigned int known = 1;                          /* block 0 is there from the start */
 	bool closed = false;
 	if (iw < wpg) {
-		unsigned int Pk[NG], fstep[NG], dP[NG], stv[NG];
-		int fl[NG];
-		v2f rot0[NG], rot1[NG];
-		float2 *out[NG];
-		unsigned int g0 = 0;
 		/* the wave's first output frame, as a frame of the STREAM: behind block 0's boundary frames */
 		const unsigned long long q0 = (unsigned long long)S.kslow + iw;
-#pragma unroll
-		for (unsigned int c = 0; c < NG; ++c) {
-			const unsigned int gl = gs * NG + c;
-			const unsigned int g = (unsigned int)(((gl < 8u ? S.gmap0 : S.gmap1) >> ((gl & 7u) * 8u)) & 255u);
-			const unsigned int s = g * 64u + lane;
-			if (c == 0)
-				g0 = g;
-			const unsigned int p0 = S.phase[s];
-			stv[c] = S.step[s];
-			fl[c] = S.flags[s];
-			const float4 r4 = ((const float4 *)S.rot)[s];
-			rot0[c] = (v2f){r4.x, r4.y};
-			rot1[c] = (v2f){r4.z, r4.w};
-			fstep[c] = stv[c] << 16;
-			Pk[c] = p0 + (unsigned int)(q0 * d1 - WR_HIST) * stv[c];    /* phase of the unit's first window frame (mod 2^32) */
-			dP[c] = wpg * d1 * stv[c];
-			out[c] = (float2 *)S.ring + s;
-		}
-		float hlane[TS];                                  /* lane j holds the tap of window sample j, per tap set */
-#pragma unroll
-		for (unsigned int q = 0; q < TS; ++q)
-			hlane[q] = (TS == 1u || q < nset) ? S.taps1u[((size_t)g0 * WR_TAPSETS + q) * 64u + lane] : 0.0f;
-		const unsigned int mysel = TS == 1u ? 0u : (unsigned int)S.tapsel[g0 * 64u + lane];   /* this lane's tap set */
-		const lds_v4f *w4[2];
-		v2f *wst[2];
-#pragma unroll
-		for (int b = 0; b < 2; ++b) {
-			w4[b] = (const lds_v4f *)(win + ((unsigned int)b * nset + mysel) * 64u);
-			wst[b] = win + (unsigned int)b * nset * 64u + lane;
-		}
+		LeanRec<NG> R = lean_rec<NG>([&](unsigned int s) { return S.phase[s]; }, S.step, S.flags, (const float4 *)S.rot,
+		                             (float2 *)S.ring, S.gmap0, S.gmap1, gs, lane, (unsigned int)(q0 * d1 - WR_HIST), wpg, d1);
+		const LeanWin<TS> W = lean_win<TS>(S.taps1u, S.tapsel, R.g0, lane, nset, win);
 		/* where the wave computes (block j, frame k of it) and where it fetches (two units ahead) */
 		unsigned int j = 0, k = (unsigned int)q0;
 		while (k >= k1s) {
@@ -679,17 +641,6 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 				++jf;
 			}
 		};
-		auto to_lds = [&](const float2 raw, const int b) __attribute__((always_inline)) {
-			float2 xf = raw;
-			if (u8) {
-				const unsigned int bits = __builtin_bit_cast(unsigned int, raw.x);
-				xf = make_float2(((float)(bits & 255u) - 128.0f) / 128.0f, ((float)((bits >> 8) & 255u) - 128.0f) / 128.0f);
-			}
-#pragma unroll
-			for (unsigned int q = 0; q < TS; ++q)
-				if (TS == 1u || q < nset)
-					wst[b][q * 64u] = (v2f){hlane[q] * xf.x, hlane[q] * xf.y};
-		};
 		unsigned int cnt = 0, pend_j = 0, pend_cnt = 0;   /* lane-group units done in block j / to be signalled for pend_j */
 		unsigned int jring = 0xFFFFFFFFu;                 /* block whose ring rows are known to be free */
 		/* everything this wave has finished and not said yet: the block it left last (all of its stores are waited for) */
@@ -712,7 +663,6 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 		                                                     makes every LDS wait of the tap loop a wait for everything) */
 #endif
 		unsigned int lead = 0;                            /* blocks this wave is ahead of the slowest one (as of its entry into block j) */
-		unsigned int nunits = 0;                          /* units this wave has done */
 		auto unit = [&](float2 &xo, const int b) __attribute__((always_inline)) {
 			const unsigned long long tl0 = tl_on ? __builtin_amdgcn_s_memtime() : 0ull;
 			if (j != jring) {
@@ -750,63 +700,11 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 				/* ... and within a block it falls as the wave gets through it (quarters of the block's frames) */
 				wave_prio(lead <= 1u ? 2u : lead <= 3u ? 1u : 0u);
 			}
-			v2f csq[NG];
-			unsigned int F[NG];
-			v2f acc[NG], A[NG];
-#pragma unroll
-			for (unsigned int c = 0; c < NG; ++c) {
-				csq[c] = nco<NCO>(Pk[c] + (unsigned int)(WR_FIR_LENGTH - 1) * stv[c], S.table, hi_l, lo_l);
-				F[c] = Pk[c] << 16;                   /* the 16 fraction bits, left-aligned */
-				acc[c] = (v2f){0.0f, 0.0f};
-				A[c] = (v2f){0.0f, 0.0f};
-			}
-			constexpr int RD = DDC_RD, NST = WR_FIR_LENGTH / 2 / RD;
-			v4f xr[2][RD];
-#pragma unroll
-			for (int r = 0; r < RD; ++r)
-				xr[0][r] = w4[b][r];
-#pragma unroll
-			for (int t = 0; t < NST; ++t) {
-				if (t + 1 < NST) {
-#pragma unroll
-					for (int r = 0; r < RD; ++r)
-						xr[(t + 1) & 1][r] = w4[b][(t + 1) * RD + r];
-				}
-#pragma unroll
-				for (int r = 0; r < RD; ++r) {
-					const v4f x2 = xr[t & 1][r];
-#pragma unroll
-					for (int jj = 0; jj < 2; ++jj) {
-						const int jt = 2 * (t * RD + r) + jj;
-						const v2f u = jj ? (v2f){x2.z, x2.w} : (v2f){x2.x, x2.y};
-#pragma unroll
-						for (unsigned int c = 0; c < NG; ++c) {
-							if (jt == 0) {
-								A[c] = u;                   /* the recurrence starts afresh: no turn */
-							} else {
-								unsigned int F2;
-								const bool carry = __builtin_uadd_overflow(F[c], fstep[c], &F2);
-								F[c] = F2;
-								horner_step(A[c], carry ? rot1[c].x : rot0[c].x, carry ? rot1[c].y : rot0[c].y, u);
-							}
-						}
-					}
-				}
-				/* (pinned stage by stage: see k_tuner_ddc) */
-#pragma unroll
-				for (unsigned int c = 0; c < NG; ++c)
-					asm volatile("" : "+v"(A[c].x), "+v"(A[c].y), "+v"(F[c]));
-				__builtin_amdgcn_sched_barrier(0);
-			}
-#pragma unroll
-			for (unsigned int c = 0; c < NG; ++c) {
-				horner_close(acc[c], A[c], csq[c]);
-				asm volatile("" : "+v"(acc[c].x), "+v"(acc[c].y));
-			}
+			const AccN<NG> acc = rotate_unit<NG>(W.w4[b], R, S.table, hi_l, lo_l);
 			const unsigned long long tl1 = tl_on ? __builtin_amdgcn_s_memtime() : 0ull;
 			/* the next unit's window (requested two units ago), if there is a next unit ... */
 			if (ahead >= 2u)
-				to_lds(xo, b ^ 1);
+				W.to_lds(xo, b ^ 1, u8);
 			unsigned long long tl2 = 0;
 			if (tl_on) {
 				asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -819,16 +717,15 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 			const size_t row = (size_t)(j % WR_STREAM_RING) * k1s + k;
 #pragma unroll
 			for (unsigned int c = 0; c < NG; ++c) {
-				if (fl[c] & PHASE_FLAG_ACTIVE) {
+				if (R.fl[c] & PHASE_FLAG_ACTIVE) {
 					union { v2f f; unsigned long long u; } cv;
-					cv.f = acc[c];
-					__hip_atomic_store((unsigned long long *)&out[c][row * S.slots], cv.u, __ATOMIC_RELAXED,
+					cv.f = acc.v[c];
+					__hip_atomic_store((unsigned long long *)&R.out[c][row * S.slots], cv.u, __ATOMIC_RELAXED,
 					                   __HIP_MEMORY_SCOPE_AGENT);             /* write-through: see ddc_body */
 				}
-				Pk[c] += dP[c];
+				R.Pk[c] += R.dP[c];
 			}
 			--ahead;
-			++nunits;
 			cnt += NG;
 			k += wpg;
 			if (k >= k1s) {
@@ -859,7 +756,7 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 			++tl_epochs;
 			try_fetch(xa);                                /* unit 0 (there: the wait above) */
 			try_fetch(xb);                                /* unit 1 */
-			to_lds(xa, 0);
+			W.to_lds(xa, 0, u8);
 			try_fetch(xa);                                /* unit 2 */
 			wave_prio(2u);                                /* (set again at every block the wave enters) */
 			while (ahead) {
@@ -968,8 +865,7 @@ static unsigned int stream_post_run(unsigned int tiles, unsigned int groups, uns
  * buffers per wave (the block-boundary role inside the post workgroups lays its windows out the same way) */
 static size_t stream_lds_bytes(unsigned int d2, unsigned int nset)
 {
-	const size_t need = (size_t)(POST_TK - 1u) * d2 + WR_FIR_LENGTH;
-	const size_t post_lds = (need * 64u + POST_TK * 65u + 64u + 16u) * sizeof(float);
+	const size_t post_lds = post_lds_bytes(d2, 1u) + 16u * sizeof(float);     /* (+ stream_post's `sh` words) */
 	const size_t ddc_lds = (size_t)DDC_ROTATE_WAVES * 2u * 512u * nset + 2u * WR_SPLIT_N * 8u;
 	return post_lds > ddc_lds ? post_lds : ddc_lds;
 }
@@ -997,22 +893,6 @@ static hipError_t stream_occupancy(size_t lds, int *per_cu)
 	return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_tuner_stream<PD2, NG, TS>, (int)(DDC_ROTATE_WAVES * 64u), lds);
 }
 
-template <unsigned int NG, unsigned int TS>
-static hipError_t stream_occupancy_d2(unsigned int d2, size_t lds, int *per_cu)
-{
-	switch (d2) {
-	case 1: return stream_occupancy<1, NG, TS>(lds, per_cu);
-	case 2: return stream_occupancy<2, NG, TS>(lds, per_cu);
-	case 3: return stream_occupancy<3, NG, TS>(lds, per_cu);
-	case 4: return stream_occupancy<4, NG, TS>(lds, per_cu);
-	case 5: return stream_occupancy<5, NG, TS>(lds, per_cu);
-	case 6: return stream_occupancy<6, NG, TS>(lds, per_cu);
-	case 8: return stream_occupancy<8, NG, TS>(lds, per_cu);
-	case 10: return stream_occupancy<10, NG, TS>(lds, per_cu);
-	default: return hipErrorInvalidValue;
-	}
-}
-
 /* How many workgroups of the streaming launch a device holds at once, split into roles.  Every workgroup of the
  * launch must be resident (they wait for one another): the grid is never larger than what the occupancy query
  * admits, capped at three per CU (what 80 registers and eight waves per workgroup give; the query can be one too
@@ -1028,8 +908,11 @@ hipError_t wrk_stream_geometry(unsigned int d2, unsigned int groups, unsigned in
 	stream_shape(groups, kmax, one_filter, &ng, &ts);
 	const size_t lds = stream_lds_bytes(d2, ts == 1u ? 1u : kmax);
 	int per_cu = 0;
-	hipError_t e = ts != 1u ? stream_occupancy_d2<1, WR_TAPSETS>(d2, lds, &per_cu)
-	               : ng == 1u ? stream_occupancy_d2<1, 1>(d2, lds, &per_cu) : stream_occupancy_d2<2, 1>(d2, lds, &per_cu);
+	hipError_t e = with_post_d2(d2, [&](auto D2) {
+		constexpr unsigned int PD2 = decltype(D2)::value;
+		return ts != 1u ? stream_occupancy<PD2, 1, WR_TAPSETS>(lds, &per_cu)
+		       : ng == 1u ? stream_occupancy<PD2, 1, 1>(lds, &per_cu) : stream_occupancy<PD2, 2, 1>(lds, &per_cu);
+	});
 	if (e != hipSuccess)
 		return e;
 	if (per_cu > 3)
@@ -1061,22 +944,6 @@ static hipError_t launch_stream(hipStream_t st, const WrStreamArgs &A, void *ev_
 	}
 	k_tuner_stream<PD2, NG, TS><<<grid, DDC_ROTATE_WAVES * 64u, lds, st>>>(A);
 	return hipGetLastError();
-}
-
-template <unsigned int NG, unsigned int TS>
-static hipError_t launch_stream_d2(hipStream_t st, const WrStreamArgs &A, void *ev_start, void *ev_stop)
-{
-	switch (A.post.d2) {
-	case 1: return launch_stream<1, NG, TS>(st, A, ev_start, ev_stop);
-	case 2: return launch_stream<2, NG, TS>(st, A, ev_start, ev_stop);
-	case 3: return launch_stream<3, NG, TS>(st, A, ev_start, ev_stop);
-	case 4: return launch_stream<4, NG, TS>(st, A, ev_start, ev_stop);
-	case 5: return launch_stream<5, NG, TS>(st, A, ev_start, ev_stop);
-	case 6: return launch_stream<6, NG, TS>(st, A, ev_start, ev_stop);
-	case 8: return launch_stream<8, NG, TS>(st, A, ev_start, ev_stop);
-	case 10: return launch_stream<10, NG, TS>(st, A, ev_start, ev_stop);
-	default: return hipErrorInvalidValue;
-	}
 }
 
 /* `A.post` comes from wrk_post_args for ONE block of the stream; its tiling is redone here for the post workgroups
@@ -1118,7 +985,10 @@ hipError_t wrk_tuner_stream(hipStream_t st, const WrStreamArgs &A0, void *ev_sta
 	stream_shape(A.groups, A.kmax, A.one_filter != 0u, &ng, &ts);
 	if ((size_t)A.n_ddc * DDC_ROTATE_WAVES < A.groups / ng)
 		return hipErrorInvalidValue;
-	if (ts != 1u)
-		return launch_stream_d2<1, WR_TAPSETS>(st, A, ev_start, ev_stop);
-	return ng == 2u ? launch_stream_d2<2, 1>(st, A, ev_start, ev_stop) : launch_stream_d2<1, 1>(st, A, ev_start, ev_stop);
+	return with_post_d2(A.post.d2, [&](auto D2) {
+		constexpr unsigned int PD2 = decltype(D2)::value;
+		return ts != 1u ? launch_stream<PD2, 1, WR_TAPSETS>(st, A, ev_start, ev_stop)
+		       : ng == 2u ? launch_stream<PD2, 2, 1>(st, A, ev_start, ev_stop)
+		                  : launch_stream<PD2, 1, 1>(st, A, ev_start, ev_stop);
+	});
 }
