@@ -14,14 +14,17 @@
   RCCL ("nccl") by default.  N GPUs must be there: with fewer the job exits non-zero instead of
   quietly measuring one GPU (`--backend gloo` lets ranks share a GPU; that is for the tests).
 
-Prints ONE JSON line on rank 0 (see the contract in the task description) carrying
-`roofline` (dominant kernel, HIP-event timed inside the timed region) and, at N = 1,
-`cpu_baseline` (the oracle -- a scalar port of the reference CPU path -- timed on ALL host
-cores, one pipeline thread per core with its own subset of the receivers, and on one core,
-over a bounded sample of the same workload) and `secondary.c3` (BASELINE config 3: the
+Prints ONE JSON line on rank 0 carrying the headline and `roofline` (dominant kernel, HIP-event
+timed inside the timed region).  That is all a plain run does: set up, warm up, time the K steps,
+write --dump-outputs, print.  With --full, at N = 1, the line also carries what takes runs of its
+own, all of it after the timed steps: `cpu_baseline` (the oracle -- a scalar port of the reference
+CPU path -- timed on ALL host cores, one pipeline thread per core with its own subset of the
+receivers, and on one core, over a bounded sample of the same workload), `secondary.c2_*` (the same
+job a launch per block and four blocks per launch), `secondary.c3` (BASELINE config 3: the
 SpectrumSink waterfall, 65536-point FFT at 50 % overlap, off the same resident stream),
-`secondary.c1` (BASELINE config 1) and `secondary.host_fed` (the same C2 job through the C++ host
-classes with the block in HOST memory: the PCIe-inclusive rates -- reported beside `value`, never as it).
+`secondary.frontend` (C2 and C3 on the same blocks), `secondary.c1` (BASELINE config 1),
+`roofline.power` and `secondary.host_fed` (the same C2 job through the C++ host classes with the
+block in HOST memory: the PCIe-inclusive rates -- reported beside `value`, never as it).
 """
 import argparse
 import json
@@ -42,7 +45,7 @@ C3_BYTES_PER_FRAME = 12 * C3_FFT                          # 8 B in + 
 DUMP_MAX_BYTES = 64 << 20                                 # --dump-outputs: at most this much in all
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -60,8 +63,8 @@ def parse():
                     help="headline without wr_tuner_set_streaming: a kernel launch per step (or per --blocks-per-launch steps).  "
                          "Default: the streaming launch -- the tuner's blocks go to ONE persistent launch through a doorbell, a "
                          "block's audio is complete ~15 us after its last channel-rate frame whether or not another block follows "
-                         "(dspblock.cxx:169-212), same bits (tests/test_gpu_stream.py); the launch-per-block figures are "
-                         "reported as secondary.c2_one_launch_per_block / c2_four_blocks_per_launch")
+                         "(dspblock.cxx:169-212), same bits (tests/test_gpu_stream.py); --full reports the launch-per-block "
+                         "figures as secondary.c2_one_block_per_launch / c2_four_blocks_per_launch")
     ap.add_argument("--blocks-per-launch", type=int, default=1,
                     help="only with --no-stream: wr_tuner_set_blocks_per_launch, consecutive resident blocks the tuner holds and "
                          "launches as one (a step stays one 40 ms block; audio is delivered per launch, up to n - 1 blocks late)")
@@ -70,10 +73,14 @@ def parse():
                          "MI355X that was idle starts a kernel stream at a reduced clock and takes ~50 ms of continuous "
                          "load to reach its steady state (measured: the same launch 42-44 us in the first 6 ms, 34.4 us "
                          "from 45 ms on, profiles/r02_clock_ramp.txt).  0 turns it off")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="c2 at N = 1: after the headline, everything else the line can carry -- the same job the library's "
+                         "other ways, BASELINE configs 3 and 1, the FrontEnd, the host classes, the package's power draw "
+                         "(secondary.*, roofline.power) and the CPU baseline (cpu_baseline).  Off: the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
     ap.add_argument("--cpu-blocks", type=int, default=0,
-                    help="blocks of the all-cores CPU baseline (0: as many as take about 10-20 s)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C3 (SpectrumSink) measurement")
+                    help="blocks of --full's all-cores CPU baseline (0: as many as take about 10-20 s)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: leave out secondary.* and roofline.power")
     ap.add_argument("--profile-stride", type=int, default=64,
                     help="one HIP event pair around every n consecutive launches of the dominant kernel, at most all of the "
                          "timed region's (an event record between two launches costs the stream ~10 us; n = 1: every "
@@ -104,7 +111,7 @@ def parse():
                          "channel (a fixed, seeded sample of the channels beyond %d MB) -- to DIR/<name>.npy.  The timed "
                          "stream then starts from the tuner's stream-start state (wr_tuner_seek), so the same arguments give "
                          "the same outputs from run to run" % (DUMP_MAX_BYTES >> 20))
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be >= 1")
     if args.dump_outputs and args.workload != "c2":
@@ -1037,8 +1044,10 @@ def main():
         tuner.blocks_per_launch(B)
         return r
 
+    # everything below the headline needs --full: a plain run goes from its timed steps (and --dump-outputs) to the line
+    secondary = world == 1 and args.full and not args.no_secondary
     one = four = streamed = None
-    if world == 1 and not args.no_secondary:
+    if secondary:
         k1 = min(args.steps, 96) // 4 * 4 or 4
         if streaming or B > 1:
             one = other_mode(False, 1, k1)
@@ -1049,7 +1058,7 @@ def main():
 
     # BASELINE config 3 off the same resident stream, outside the timed region of the headline
     c3 = c1 = fe = pw = None
-    if world == 1 and not args.no_secondary:
+    if secondary:
         tuner.flush()
         torch.cuda.synchronize()
         c3 = c3_secondary(torch, dev, blocks, n, max(nb, min(args.steps, 60)), args.settle_ms)
@@ -1191,7 +1200,7 @@ def main():
             hf = host_fed_secondary()
             if hf is not None:
                 out["secondary"]["host_fed"] = hf
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # the reference's own classes on the host cores where oracle/_ref is there (kind "reference"), with the
             # oracle's port beside it; the port alone (kind "port") otherwise
             port = cpu_baseline(cfg, ifs, args.cpu_blocks)

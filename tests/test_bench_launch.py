@@ -51,6 +51,14 @@ def test_ranks_that_share_a_gpu_over_rccl_are_an_error_not_a_measurement():
     assert distinct
 
 
+def test_a_plain_run_is_not_full():
+    """Everything beyond the headline waits for --full: a plain `bench.py --gpus 1 --steps N --warmup W` is the headline."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert not bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"]).full
+    assert bench.parse(["--full"]).full
+
+
 @pytest.mark.parametrize("extra,says", [(["--steps", "0"], b"--steps must be >= 1"),
                                         (["--workload", "c5", "--dump-outputs", "out"], b"only the c2 workload")],
                          ids=["no-steps", "c5-dump"])

@@ -25,7 +25,7 @@ def _line(out):
 
 def test_single_gpu_line():
     out = _proc.output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "2",
-                                   "--cpu-blocks", "1"], cwd=ROOT, timeout=420)
+                        "--cpu-blocks", "1", "--full"], cwd=ROOT, timeout=420)
     j = _line(out)
     for k in REQUIRED + ["cpu_baseline"]:
         assert k in j, k
@@ -82,6 +82,27 @@ def test_single_gpu_line():
     assert fe["streaming_closed_per_block"]["streaming_launches"] == fe["blocks"]       # every waterfall batch closes the launch
     assert fe["streaming_newest_frame"]["streaming_launches"] <= fe["blocks"] // 5 + 1  # a poll does, a block does not
     assert fe["lazy"]["pushes_kept"] > 0 and fe["lazy"]["transformed_on_demand"] > 0
+
+
+def test_plain_run_is_the_headline_alone():
+    """Without --full the run sets up, warms up, times its steps and prints the line: the headline's keys mean what they do
+    with --full, and nothing that takes runs of its own (secondary.*, roofline.power, cpu_baseline) is measured.  Outside its
+    steps it spends at most 30 s, start to exit."""
+    import time
+    t0 = time.monotonic()
+    out = _proc.output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "2"],
+                       cwd=ROOT, timeout=300)
+    wall = time.monotonic() - t0
+    j = _line(out)
+    for k in REQUIRED:
+        assert k in j, k
+    for k in ("secondary", "cpu_baseline", "value_one_block_per_launch"):
+        assert k not in j, k
+    assert "power" not in j["roofline"]
+    assert j["n_gpus"] == 1 and j["steps"] == 40 and j["warmup"] == 2 and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert abs(j["value"] - 4.0e6 * 40 / (j["ms_per_step"] * 40 / 1e3) / 1e6) / j["value"] < 1e-3
+    assert j["config"]["streaming"] is True and j["roofline"]["launches_timed"] == 1
+    assert wall - (40 + 2) * j["ms_per_step"] / 1e3 <= 30.0, wall
 
 
 def test_two_rank_launch_path():

@@ -1,16 +1,16 @@
 #!/usr/bin/env python3
-"""profiles/<round>_bench_boxes.txt from the per-box files tools/bench_box.sh left in gpurun_out/ (one fresh lease each):
-the driver's invocation `python bench.py --steps 20 --warmup 5` on the boxes of the pool.
-    python tools/bench_boxes_table.py r06"""
+"""profiles/<round>_bench_boxes.txt from the per-box files tools/bench_box.sh left in <dir> (one fresh lease each):
+the driver's invocation `python bench.py --steps 20 --warmup 5`, with --full, on the boxes of the pool.
+    python tools/bench_boxes_table.py r06 <dir>"""
 import glob
 import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-rnd = sys.argv[1] if len(sys.argv) > 1 else "r06"
+rnd, src = sys.argv[1], sys.argv[2]
 rows = []
-for path in sorted(glob.glob(os.path.join(ROOT, "gpurun_out", "%s_box_*.json" % rnd))):
+for path in sorted(glob.glob(os.path.join(src, "%s_box_*.json" % rnd))):
     try:
         j = json.loads([l for l in open(path) if l.startswith("{")][-1])
     except Exception:
@@ -34,7 +34,7 @@ for path in sorted(glob.glob(os.path.join(ROOT, "gpurun_out", "%s_box_*.json" % 
         "u8_on": hf.get(("u8 ", "on time", "sparse")), "u8_late": hf.get(("u8 ", "one blo", "sparse")),
         "f32_on": hf.get(("f32", "on time", "sparse")), "f32_late": hf.get(("f32", "one blo", "sparse")),
     })
-out = ["python bench.py --steps 20 --warmup 5 --no-cpu-baseline, one fresh lease per row (tools/bench_box.sh; this table: tools/bench_boxes_table.py %s)" % rnd,
+out = ["python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline, one fresh lease per row (tools/bench_box.sh; this table: tools/bench_boxes_table.py %s)" % rnd,
        "`value` = the streaming launch: 20 blocks through ONE persistent launch, opened and closed inside the timed region",
        "box (UTC)          Gsps   us/step  the launch us    frac   launch/block Gsps  4 blocks/launch Gsps   C3 us (frac)    C1 us: launch / stream   "
        "FrontEnd us: launches+waterfall / stream closed / stream newest frame (+ per poll)   host classes ms per block: device late / (no stream) / on time | u8 on time / late | f32 on time / late"]

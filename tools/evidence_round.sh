@@ -10,7 +10,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 mkdir -p $O
 cd $R
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/${round}_bench_driver_flags.json 2> /dev/null
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/${round}_bench_driver_flags.json 2> /dev/null
 timeout 300 python bench.py --workload c5 --steps 30 --warmup 4 > $O/${round}_c5_1gpu.json 2> /dev/null
 timeout 300 python bench.py --workload c5 --halo ring --steps 30 --warmup 4 > $O/${round}_c5_1gpu_ring.json 2> /dev/null
 ( for src in f32 u8; do for late in 0 1 2; do

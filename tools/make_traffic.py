@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Writes profiles/traffic.json -- the HBM bytes per launch bench.py quotes in `roofline.traffic` -- from the PMC dumps of
-tools/profile_round.sh (gpurun_out/<round>_pmc_fetch_size.txt / _pmc_write_size.txt: FETCH_SIZE and WRITE_SIZE per kernel and
-launch shape, separate rocprofv3 --pmc passes).  No hand step: `python tools/make_traffic.py r05` (profile_round.sh calls it).
+tools/profile_round.sh (<dir>/<round>_pmc_fetch_size.txt / _pmc_write_size.txt: FETCH_SIZE and WRITE_SIZE per kernel and
+launch shape, separate rocprofv3 --pmc passes).  No hand step: `python tools/make_traffic.py r05 <dir>` (profile_round.sh calls it).
 
 Reading of the counters, settled in r05 on known byte counts (tools/ubench_fetch.hip, profiles/r05_fetch_calibration.txt):
 both are KB per launch; on gfx950 every read request the L2 sends to memory is 128 bytes and FETCH_SIZE tallies it at 64 --
@@ -14,7 +14,6 @@ import os
 import re
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LINE = re.compile(r"^(?:void )?(\S+?(?:<[^>]*>)?) \[(\d+) workgroups\] (\w+) mean=([0-9.]+) KB per launch \(n=(\d+)\)")
 ALGO_PER_BLOCK = 8.512 * 4.0e6
 
@@ -30,14 +29,13 @@ def read(path):
     return rows
 
 
-def main(rnd):
-    src = os.path.join(ROOT, "gpurun_out")
+def main(rnd, src):
     kb = 1024.0
     rule = ("2 x FETCH_SIZE + WRITE_SIZE: gfx950 tallies every 128-byte read request at 64 bytes, whatever the load's width "
             "(profiles/r05_fetch_calibration.txt: 0.500 x the bytes asked for with 4, 8 and 16 bytes per lane, streaming and in "
             "the DDC's windows); WRITE_SIZE as counted")
     out = {"round": rnd, "nco": "rotate", "fetch_rule": rule,
-           "made_by": "tools/make_traffic.py from gpurun_out/%s_pmc*_fetch_size.txt and _write_size.txt (tools/profile_round.sh)" % rnd}
+           "made_by": "tools/make_traffic.py from %s_pmc*_fetch_size.txt and _write_size.txt (tools/profile_round.sh)" % rnd}
     # the streaming launch: ONE launch of `blocks` blocks in its PMC pass (profile_round.sh: no warm-up, no settling steps)
     fs, ws = read(os.path.join(src, "%s_pmc_stream_fetch_size.txt" % rnd)), read(os.path.join(src, "%s_pmc_stream_write_size.txt" % rnd))
     st = [k for k in fs if k[0].startswith("k_tuner_stream") and k in ws]
@@ -50,7 +48,7 @@ def main(rnd):
                             "hbm_bytes_per_block": int(round(per)), "x_algorithmic": round(per / ALGO_PER_BLOCK, 3)}
     f, w = read(os.path.join(src, "%s_pmc_fetch_size.txt" % rnd)), read(os.path.join(src, "%s_pmc_write_size.txt" % rnd))
     # the riding DDC kernel (audio decimation 5, two lane groups per wave) in its two launch shapes: the larger grid is the
-    # four-block launch, the smaller the one-block launch (bench.py --no-stream; secondary.c2_* in the default run)
+    # four-block launch, the smaller the one-block launch (bench.py --no-stream; secondary.c2_* with --full)
     ddc = sorted([k for k in f if k[0].startswith("k_tuner_ddc<2, true, 5u") and k in w], key=lambda k: -k[1])
     if len(ddc) >= 2:
         four, one = ddc[0], ddc[-1]
@@ -85,4 +83,4 @@ def main(rnd):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "r06")
+    main(sys.argv[1], sys.argv[2])

@@ -1,23 +1,24 @@
 #!/bin/bash
-# Produces the rocprof evidence for bench.py's roofline numbers (run on the GPU box via gpurun):
-#   gpurun_out/<round>_bench.json            the bench line (C2 headline + secondary.c3 + cpu_baseline)
-#   gpurun_out/<round>_kernel_stats.csv      rocprofv3 --kernel-trace --stats of the same command (all launches: warm-up,
-#                                            clock settling and the timed steps)
-#   gpurun_out/<round>_kernel_stats_timed.csv   the same trace, the timed region's launches only
-#   gpurun_out/<round>_pmc_fetch_size.txt / _pmc_write_size.txt   FETCH_SIZE / WRITE_SIZE per kernel (separate passes)
+# Produces the rocprof evidence for bench.py's roofline numbers (run on an MI355X; OUT: the directory the evidence goes to):
+#   $OUT/<round>_bench.json            the bench line (bench.py --full: C2 headline + secondary.* + cpu_baseline)
+#   $OUT/<round>_kernel_stats.csv      rocprofv3 --kernel-trace --stats of bench.py --full (all launches: warm-up,
+#                                      clock settling, the timed steps and the secondary runs)
+#   $OUT/<round>_kernel_stats_timed.csv   the same trace, the timed region's launches only
+#   $OUT/<round>_pmc_fetch_size.txt / _pmc_write_size.txt   FETCH_SIZE / WRITE_SIZE per kernel (separate passes)
+#   OUT=<dir> bash tools/profile_round.sh <round>
 round=${1:-r06}
-R=$GRAFT_REPO_ROOT
-mkdir -p $R/gpurun_out
-cd $R && python bench.py > gpurun_out/${round}_bench.json 2> gpurun_out/${round}_bench.err
+R=$(cd "$(dirname "$0")/.." && pwd)
+mkdir -p "${OUT:?set OUT to the directory the evidence goes to}" && OUT=$(cd "$OUT" && pwd) && export OUT
+cd $R && python bench.py --full > $OUT/${round}_bench.json 2> $OUT/${round}_bench.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_$round
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$round -o $round -- python $R/bench.py --steps 60 --warmup 5 --no-cpu-baseline > /tmp/prof_$round.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$round -o $round -- python $R/bench.py --full --steps 60 --warmup 5 --no-cpu-baseline > /tmp/prof_$round.log 2>&1
 python3 - "$round" <<'PY'
 import csv, sys, os
-r = sys.argv[1]; R = os.environ['GRAFT_REPO_ROOT']
+r = sys.argv[1]; O = os.environ['OUT']
 src = '/tmp/prof_%s/%s_kernel_stats.csv' % (r, r)
 rows = list(csv.DictReader(open(src)))
-with open(R + '/gpurun_out/%s_kernel_stats.csv' % r, 'w') as f:
+with open(O + '/%s_kernel_stats.csv' % r, 'w') as f:
     w = csv.writer(f); w.writerow(['Name', 'Calls', 'TotalDurationNs', 'AverageNs', 'Percentage', 'MinNs', 'MaxNs'])
     for x in rows:
         name = x['Name']
@@ -30,7 +31,7 @@ PY
 # bench.py --settle-ms): the last 15 are reported beside the mean over all.
 python3 - "$round" <<'PY'
 import csv, sys, glob, os, collections
-r = sys.argv[1]; R = os.environ['GRAFT_REPO_ROOT']
+r = sys.argv[1]; O = os.environ['OUT']
 rows = []
 for f in glob.glob('/tmp/prof_%s/**/*kernel_trace.csv' % r, recursive=True):
     for x in csv.DictReader(open(f)):
@@ -42,7 +43,7 @@ g = collections.OrderedDict()
 for _, name, wgs, d in rows:
     if name.startswith('k_'):
         g.setdefault((name, wgs), []).append(d)
-with open(R + '/gpurun_out/%s_kernel_stats_timed.csv' % r, 'w') as f:
+with open(O + '/%s_kernel_stats_timed.csv' % r, 'w') as f:
     w = csv.writer(f); w.writerow(['Name', 'Workgroups', 'Calls', 'AverageNs', 'MinNs', 'MaxNs', 'Last15AverageNs'])
     for (name, wgs), d in sorted(g.items()):
         if len(d) < 3 and not name.startswith(('k_fft', 'k_tuner_stream')):
@@ -53,19 +54,19 @@ PY
 # the headline's kernel by itself: bench.py --no-secondary, every k_tuner_stream launch in order -- the warm-up's, the 100-block
 # streams of the clock settling, and LAST the timed region's one launch of 60 blocks (what bench.py's own events time)
 rm -rf /tmp/prof_${round}_s
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_${round}_s -o s -- python $R/bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-secondary > $R/gpurun_out/${round}_stream_bench.json 2>/tmp/prof_${round}_s.log
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_${round}_s -o s -- python $R/bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-secondary > $OUT/${round}_stream_bench.json 2>/tmp/prof_${round}_s.log
 python3 - "$round" <<'PY'
 import csv, sys, glob, os, json
-r = sys.argv[1]; R = os.environ['GRAFT_REPO_ROOT']
+r = sys.argv[1]; O = os.environ['OUT']
 rows = []
 for f in glob.glob('/tmp/prof_%s_s/**/*kernel_trace.csv' % r, recursive=True):
     for x in csv.DictReader(open(f)):
         if 'k_tuner_stream' in x['Kernel_Name']:
             rows.append((int(x['Start_Timestamp']), int(x['End_Timestamp']) - int(x['Start_Timestamp'])))
 rows.sort()
-line = [l for l in open(R + '/gpurun_out/%s_stream_bench.json' % r) if l.startswith('{')][-1]
+line = [l for l in open(O + '/%s_stream_bench.json' % r) if l.startswith('{')][-1]
 j = json.loads(line)
-with open(R + '/gpurun_out/%s_stream_launches.txt' % r, 'w') as f:
+with open(O + '/%s_stream_launches.txt' % r, 'w') as f:
     f.write('rocprofv3 --kernel-trace of `python bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-secondary`: every k_tuner_stream launch, in order, ns\n')
     f.write(' '.join(str(d) for _, d in rows) + '\n')
     last = rows[-1][1]
@@ -80,18 +81,18 @@ PY
 #             not care about the clock), so that bytes per launch / $SB = bytes per block
 #   ""      : bench.py --no-stream --blocks-per-launch 4 -- k_tuner_ddc in its four-block and (secondary) one-block shapes, the FFT passes
 SB=24
-echo $SB > $R/gpurun_out/${round}_pmc_stream_blocks.txt
+echo $SB > $OUT/${round}_pmc_stream_blocks.txt
 for variant in stream ""; do
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_$c
   if [ "$variant" = "stream" ]; then
     rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_$c -o p -- python $R/bench.py --steps $SB --warmup 0 --settle-ms 0 --no-secondary --no-cpu-baseline > /tmp/pmc_$c.log 2>&1
   else
-    rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_$c -o p -- python $R/bench.py --no-stream --blocks-per-launch 4 --steps 12 --warmup 2 --no-cpu-baseline > /tmp/pmc_$c.log 2>&1
+    rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_$c -o p -- python $R/bench.py --full --no-stream --blocks-per-launch 4 --steps 12 --warmup 2 --no-cpu-baseline > /tmp/pmc_$c.log 2>&1
   fi
   python3 - "$c" "$round" "$variant" <<'PY'
 import csv, sys, glob, collections, os
-c, r, variant = sys.argv[1], sys.argv[2], sys.argv[3]; R = os.environ['GRAFT_REPO_ROOT']
+c, r, variant = sys.argv[1], sys.argv[2], sys.argv[3]; O = os.environ['OUT']
 acc = collections.defaultdict(list)
 for f in glob.glob('/tmp/pmc_%s/**/*counter_collection.csv' % c, recursive=True):
     for row in csv.DictReader(open(f)):
@@ -100,7 +101,7 @@ for f in glob.glob('/tmp/pmc_%s/**/*counter_collection.csv' % c, recursive=True)
         if k.startswith(('k_', 'void k_')):
             acc['%s [%d workgroups]' % (k, wgs)].append(float(row['Counter_Value']))
 name = '%s_pmc_%s%s.txt' % (r, 'stream_' if variant else '', c.lower())
-with open(R + '/gpurun_out/' + name, 'w') as out:
+with open(O + '/' + name, 'w') as out:
     for k, v in sorted(acc.items()):
         if len(v) < 3 and 'k_fft' not in k and 'k_tuner_stream' not in k:
             continue
@@ -109,5 +110,5 @@ PY
 done
 done
 # profiles/traffic.json (what bench.py quotes as roofline.traffic) from the two PMC dumps: no hand step
-python3 $R/tools/make_traffic.py $round
-cat $R/gpurun_out/${round}_bench.json | cut -c1-600; grep -E "k_tuner|k_fft" $R/gpurun_out/${round}_kernel_stats.csv; cat $R/gpurun_out/${round}_kernel_stats_timed.csv; cat $R/gpurun_out/${round}_pmc_*.txt
+python3 $R/tools/make_traffic.py $round $OUT
+cat $OUT/${round}_bench.json | cut -c1-600; grep -E "k_tuner|k_fft" $OUT/${round}_kernel_stats.csv; cat $OUT/${round}_kernel_stats_timed.csv; cat $OUT/${round}_pmc_*.txt
