@@ -979,7 +979,7 @@ def test_stream_past_max_blocks(dev, oracle):
                         check_blocks=set(range(0, 4)) | set(range(edge - 3, nblk)))
 
 
-HOST_STREAM_MIN_BYTES = 16 << 10              # wr_capi.hip WR_STREAM_HOST_MIN_BYTES: a host byte block streams if larger
+HOST_STREAM_MIN_BYTES = 16 << 10              # wr_capi_internal.h WR_STREAM_HOST_MIN_BYTES: a host byte block streams if larger
 
 
 def test_host_byte_stream_submit_ahead_without_flush(dev, oracle, page_locked):

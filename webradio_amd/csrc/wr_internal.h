@@ -1,5 +1,5 @@
 /*
- * wr_internal.h -- internal C++ interface between the C ABI (wr_capi.hip), the host
+ * wr_internal.h -- internal C++ interface between the C ABI (wr_dev.hip, wr_tuner*.hip, wr_spectrum.hip), the host
  * design math (wr_design.cpp) and the kernels (wr_kernels.hip, wr_fft.hip).
  * Not installed; the public boundary is include/webradio_amd.h.
  */
@@ -20,7 +20,7 @@
                                               receivers of one tuner mostly share a passband (radio.cxx:78-79),
                                               the UI lets each choose its own (receiverhandler.cxx:130-137) */
 
-/* ---- what other translation units need of a wr_dev (wr_capi.hip) ---- */
+/* ---- what other translation units need of a wr_dev (wr_dev.hip, wr_tuner.hip) ---- */
 int         wrc_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));   /* sets wr_last_error() */
 int         wrc_dev_index(const wr_dev *dev);
 hipStream_t wrc_dev_stream(const wr_dev *dev);
@@ -82,7 +82,7 @@ struct WrGroupDev {
 	float        *audio_set[4]; /* four arrays of that shape, `audio` one of them: inside a streaming launch the blocks' post stages store
 	                               by turns (block j into set member (first + j) mod 4), so that blocks whose post-stage tasks run side by
 	                               side never store into the same array; the stream's close makes the array its last block wrote
-	                               `audio` (wr_capi.hip: stream_close) */
+	                               `audio` (wr_tuner_stream.hip: wrc_stream_close) */
 	/* taps of the group's audio filter and of its second channel stage: 64, or 128 / 256 (the rate group is keyed by
 	 * them; dem then carries l2 - 1 history rows, iq2_hist l1b - 1, taps2 / taps1b l2 / l1b rows) */
 	unsigned int  l2 = 64, l1b = 64;
@@ -112,7 +112,7 @@ struct WrTunerLaunch {
 	int          one_filter;           /* every channel of the rate group uses ONE and the same channel filter */
 	void        *ev_start, *ev_stop;   /* hipEvent_t pair the DDC launch itself stamps (profiling), or NULL */
 	bool         seeking = false;      /* the first block after wr_tuner_seek: phase = frame * step in closed form, the state sets
-	                                      handed to the launch are all-zero ones (wr_capi.hip: seek_pending) */
+	                                      handed to the launch are all-zero ones (wr_tuner.hip: seek_pending) */
 	unsigned int seek_lo = 0;          /* the frame's low 32 bits */
 };
 
