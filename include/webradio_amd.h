@@ -459,7 +459,10 @@ int wr_tuner_set_blocks_per_launch(wr_tuner *tuner, unsigned int nblocks);
  *   Taken up by: WR_NCO_ROTATE tuners with one rate group, at most 1024 channels with 64-tap channel filters, at most 4
  * distinct ones in every lane group of 64 channel slots (a passband per receiver streams as long as no lane group mixes
  * more than 4; a channel-filter setter closes the launch like any setter, and the next block opens another if the new
- * filters still qualify), no second channel stage, an audio decimation of 1..6, 8 or 10, blocks of whole audio frames, no kept demodulator rows
+ * filters still qualify), no second channel stage, an audio decimation of 1..6, 8 or 10, an audio filter of 64 or 128 taps
+ * (wr_chan_set_filter_n) or of 256 taps with an audio decimation of 1..3 (beyond it the launch has no room for its window:
+ * a launch per block, as before), blocks of whole audio frames that hold at least as many channel-rate frames as the audio
+ * filter has taps, no kept demodulator rows
  * (wr_tuner_keep_stages), no launch marks.  Any other submit goes the ordinary way, silently: wr_tuner_stream_info
  * tells which happened.
  *   Rules for the caller: a block's memory stays untouched until the NEXT block's audio is complete (or the launch is

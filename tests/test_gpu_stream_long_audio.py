@@ -1,0 +1,348 @@
+"""-m gpu: the streaming launch (k_tuner_stream) for tuners whose receivers have an audio filter of 128 or 256 taps.
+
+LowPass::_firLength is a run-time value (dsp/lowpass.cxx:38-39); the tuner builds a 128- or 256-tap audio filter as 2 or 4
+segments of 64 taps (post_role<D2, false, NSEG>), which tests/test_gpu_f4.py holds to the oracle on the launch-per-block
+path.  k_tuner_stream<PD2, NG, TS, NSEG> takes such a tuner too: 128 taps at every audio decimation the launch has,
+256 taps up to an audio decimation of 3 (beyond it the post stage's window leaves a CU room for one workgroup and the
+tuner keeps its launch per block: DESIGN.md 3.6).  A block must hold L2 channel-rate frames at least: L2 - 1 rows of
+history for the block behind it and the frame in front of them.
+
+Every case asserts the exact stream_info() tuple (a silent fall-back to a launch per block fails), the SAME BITS as one
+launch per block on a fresh tuner (every block's audio on every receiver, the last block's channel IQ, every receiver's
+state), and holds probe receivers of all four demodulators in every lane group to the oracle's chain with an L2-tap audio
+filter (test_gpu_f4.OracleChain), within that file's ROTATE bounds: channel IQ 1e-6; audio 2e-6 x sum|h2| for AM, USB
+and LSB (|.| and the Re / Im sums are 2-Lipschitz in the channel IQ, then the linear filter), AUDIO_ATOL x sum|h2| for FM
+as the stream tests have it."""
+import numpy as np
+import pytest
+
+from webradio_amd import capi, synth
+from webradio_amd.device import Tuner
+from test_gpu_f4 import OracleChain
+from test_gpu_stream import (AUDIO_ATOL, DECIMATION_RATES, IQ_ATOL, MODES, POST_TK, _carriers, _drain, _lane_groups,
+                             _passbands, _probes, _same_bits, _spread_ifs)
+
+pytestmark = pytest.mark.gpu
+
+LINEAR_ATOL = 2e-6                            # test_gpu_f4.py's ROTATE bound for AM / USB / LSB audio, per unit of sum|h2|
+LANE_CASES = {"odd": 130, "even": 70}         # 3 and 2 lane groups of 64, the last one ragged
+# the audio decimations a launch must take, by audio filter length (wr_stream_kernel.inc: with_stream_nseg)
+STREAMED_D2 = {128: sorted(DECIMATION_RATES), 256: [1, 2, 3]}
+
+
+def _k2_for(l2, d2, k2=100):
+    """about 100 audio frames a block -- more where the block would otherwise hold fewer than L2 channel-rate frames"""
+    return max(k2, -(-l2 // d2) + 5)
+
+
+def _play_long(dev, fs, crate, arate, ifs, l2, blocks, stream, submit, between=None, apbs=None, cpbs=None):
+    """test_gpu_stream._play with an audio filter of l2 taps on every receiver (fir_lengths=(64, l2)) and, with `apbs` /
+    `cpbs`, an audio / a channel passband per receiver; `stream` may be a callable(t, b) that says per block whether to
+    stream it (the state hand-over case).  Returns _play's dict."""
+    nch = len(ifs)
+    t = Tuner(dev, fs, nch, max(n for _, n in blocks), capi.WR_NCO_ROTATE)
+    cpb, apb = _passbands(fs, crate, arate)
+    chans = [t.add_receiver(f, cpbs[c] if cpbs else cpb, crate, MODES[c % 4], apbs[c] if apbs else apb, arate,
+                            fir_lengths=(64, l2))
+             for c, f in enumerate(ifs)]
+    t.audio_ring(len(blocks))
+    if not callable(stream):
+        t.streaming(stream)
+    got = []
+    for b, (off, n) in enumerate(blocks):
+        if between is not None:
+            got += between(t, chans, b)
+        if callable(stream):
+            stream(t, b)
+        submit(t, b, off, n)
+    info = t.stream_info()
+    t.flush()
+    got += _drain(t, len(blocks) - len(got))
+    k1 = blocks[-1][1] * crate // fs
+    out = dict(got=got, info=info, slots=[t.slot(c) for c in chans],
+               iq=[t.fetch(c, capi.WR_STAGE_CHAN_IQ, 2 * k1) for c in chans], state=[t.state(c) for c in chans])
+    t.destroy()
+    return out
+
+
+def _against_the_chain(oracle, fs, crate, arate, ifs, l2, host_blocks, run, probes, apbs=None, every_group=True,
+                       cpbs=None):
+    """the probes' audio of every block and the last block's channel IQ against the oracle's mixer -> LowPass(64, D1) ->
+    demodulator -> LowPass(l2, D2) chain; every demodulator is probed in every lane group, and a carrier is heard"""
+    nch = len(ifs)
+    d1, d2 = fs // crate, crate // arate
+    omode = {capi.WR_FM: oracle.FM, capi.WR_USB: oracle.USB, capi.WR_AM: oracle.AM, capi.WR_LSB: oracle.LSB}
+    if every_group:
+        # (receiver c sits in slot c; a ragged last lane group may be too short to hold all four)
+        assert run["slots"] == list(range(nch))
+        assert {(c // 64, c % 4) for c in probes} == {(c // 64, c % 4) for c in range(nch)}
+    cpb_all, apb = _passbands(fs, crate, arate)
+    loudest = 0.0
+    for c in probes:
+        pb2 = apbs[c] if apbs else apb
+        cpb = cpbs[c] if cpbs else cpb_all
+        assert oracle.lowpass_maxbin(cpb, fs) >= 1 and oracle.lowpass_maxbin_n(l2, pb2, crate) >= 1     # (filters that pass something)
+        rx = OracleChain(oracle, fs, ifs[c], 64, cpb, d1, omode[MODES[c % 4]], l2, pb2, d2)
+        gain2 = max(1.0, float(np.abs(oracle.lowpass_design(pb2, crate, l2)).sum()))
+        tol = (AUDIO_ATOL if MODES[c % 4] == capi.WR_FM else LINEAR_ATOL) * gain2
+        wc = None
+        for b, iq in enumerate(host_blocks):
+            wa, wc, _ = rx.run(iq)
+            ga = run["got"][b][1][run["slots"][c]]
+            err = float(np.abs(ga - wa).max()) if ga.shape == wa.shape else None
+            assert err is not None and err <= tol, (c, b, err, tol)
+            loudest = max(loudest, float(np.abs(wa).max()))
+        err = float(np.abs(run["iq"][c] - wc).max()) if run["iq"][c].shape == wc.shape else None
+        assert err is not None and err <= IQ_ATOL, (c, err)
+    assert loudest > 1e-3, loudest
+
+
+def _group_probes(nch):
+    """all four demodulators in every lane group (the ragged last one too), and test_gpu_stream's probes: the FM ones carry
+    the carriers"""
+    out = set(_probes(nch))
+    for g in range(_lane_groups(nch)):
+        top = min(64 * g + 63, nch - 1)
+        for m in range(4):
+            mine = [c for c in range(64 * g, top + 1) if c % 4 == m]
+            if mine:
+                out.add(mine[len(mine) // 2])
+    return sorted(out)
+
+
+def _stream_vs_blocks(dev, oracle, l2, fs, crate, arate, nch, n, nblk, expect, u8=False):
+    """nblk blocks of n frames out of device memory, streamed and with a launch per block: the exact stream_info() tuple
+    (`expect`: one tuple, or a set of admissible ones), the same bits, the probes against the oracle.  Returns the streamed
+    run."""
+    import torch
+    ifs = _spread_ifs(fs, nch)
+    iq = synth.fm_stream(nblk * n, fs, _carriers(ifs), amp=0.1)
+    if u8:
+        raw = np.clip(np.rint(iq * 128.0 + 128.0), 0, 255).astype(np.uint8)
+        iq = oracle.u8_to_float(raw)                       # what the tuner sees (io/rtlsdrtuner.cxx:106)
+        x = torch.from_numpy(raw).cuda()
+    else:
+        x = torch.from_numpy(iq).cuda()
+    torch.cuda.synchronize()
+    blocks = [(b * n, n) for b in range(nblk)]
+    views = [x[2 * off: 2 * (off + m)] for off, m in blocks]
+
+    def submit(t, b, off, m):
+        (t.submit_u8_device if u8 else t.submit_device)(views[b], m)
+
+    one = _play_long(dev, fs, crate, arate, ifs, l2, blocks, False, submit)
+    many = _play_long(dev, fs, crate, arate, ifs, l2, blocks, True, submit)
+    assert one["info"] == (False, 0, 0)
+    print("stream_info", l2, crate // arate, nch, n, many["info"])
+    if isinstance(expect, tuple):
+        assert many["info"] == expect, many["info"]
+    else:
+        assert many["info"] in expect, many["info"]
+    _same_bits(one, many)
+    _against_the_chain(oracle, fs, crate, arate, ifs, l2, [iq[2 * off: 2 * (off + m)] for off, m in blocks], many,
+                       _group_probes(nch))
+    return many
+
+
+INSTANCES = [(l2, pd2, lanes) for l2 in sorted(STREAMED_D2) for pd2 in STREAMED_D2[l2] for lanes in LANE_CASES]
+
+
+@pytest.mark.parametrize("l2,pd2,lanes", INSTANCES, ids=[f"L2={a}-PD2={p}-{l}" for a, p, l in INSTANCES])
+def test_long_audio_filter_streams_at_every_instance(dev, oracle, l2, pd2, lanes):
+    """k_tuner_stream<PD2, NG, 1, L2 / 64> for NG in {1, 2}: 128 taps at every audio decimation the launch has, 256 taps at
+    1, 2 and 3 -- five blocks of about 100 audio frames through ONE launch, 2 and 3 lane groups with a ragged last"""
+    fs, crate = DECIMATION_RATES[pd2]
+    nch = LANE_CASES[lanes]
+    d1 = fs // crate
+    k2 = _k2_for(l2, pd2)
+    assert k2 * pd2 >= l2
+    _stream_vs_blocks(dev, oracle, l2, fs, crate, crate // pd2, nch, k2 * pd2 * d1, 5, (True, 1, 5))
+
+
+def test_256_taps_at_an_audio_decimation_of_5(dev, oracle):
+    """256 taps from an audio decimation of 4 on: the post stage's window (89 KB at D2 = 5) leaves a CU's LDS room for one
+    workgroup.  Such a tuner either streams (a launch built with a narrower tile) or keeps its launch per block --
+    nothing in between -- and gives the same bits and the oracle's audio either way."""
+    fs, crate = DECIMATION_RATES[5]
+    nblk = 4
+    _stream_vs_blocks(dev, oracle, 256, fs, crate, crate // 5, 130, 100 * 5 * (fs // crate), nblk,
+                      {(True, 1, nblk), (False, 0, 0)})
+
+
+# id: (audio taps, audio decimation, audio frames per block, does it stream)
+EDGE_CASES = {
+    "L2=128-smallest": (128, 5, 26, True),                # k1 = 130: the smallest multiple of D2 that is >= L2
+    "L2=128-below": (128, 5, 25, False),                  # k1 = 125: the largest below it
+    "L2=256-smallest": (256, 3, 86, True),                # k1 = 258
+    "L2=256-below": (256, 3, 85, False),                  # k1 = 255
+    "L2=256-exactly": (256, 1, 256, True),                # k1 = L2: sixteen whole tiles, the history is the whole block before
+    "L2=256-one-short": (256, 1, 255, False),
+    "L2=128-one-tile-exactly": (128, 8, 16, True),        # k1 = L2 = 128 and ONE tile of 16 audio frames
+    "L2=128-one-tile": (128, 10, 16, True),               # k1 = 160: one tile
+    "L2=128-ragged-tile": (128, 5, 57, True),             # 3 tiles and 9 frames
+    "L2=256-ragged-tile": (256, 2, 135, True),            # 8 tiles and 7 frames
+}
+
+
+@pytest.mark.parametrize("case", list(EDGE_CASES))
+def test_long_audio_filter_block_edges(dev, oracle, case):
+    """A block streams from L2 channel-rate frames on (L2 - 1 rows of history for the block behind it and the frame in
+    front of them) -- the smallest multiple of D2 that is, and the largest that is not, which takes a launch per block and
+    gives the right bits; a ragged last tile; a block of one tile."""
+    l2, pd2, k2, streams = EDGE_CASES[case]
+    fs, crate = DECIMATION_RATES[pd2]
+    k1 = k2 * pd2
+    assert (k1 >= l2) == streams
+    if "smallest" in case or "exactly" in case:
+        assert k1 - pd2 < l2 <= k1
+    if "below" in case or "one-short" in case:
+        assert k1 < l2 <= k1 + pd2
+    if "ragged" in case:
+        assert k2 > POST_TK and k2 % POST_TK
+    if "one-tile" in case:
+        assert k2 == POST_TK
+    nblk = 4
+    _stream_vs_blocks(dev, oracle, l2, fs, crate, crate // pd2, 70, k1 * (fs // crate), nblk,
+                      (True, 1, nblk) if streams else (False, 0, 0))
+
+
+@pytest.mark.parametrize("l2,pd2", [(128, 5), (256, 3)])
+def test_long_audio_filter_state_goes_both_ways(dev, oracle, l2, pd2):
+    """One tuner: two blocks with a launch each, flush(), two blocks streamed, flush(), one block with a launch of its own --
+    against five blocks with a launch each.  The stream's block 0 takes its L2 - 1 rows of history from the tuner's state
+    (dem_hist), its second block from the channel-IQ ring (chan_prev), and the closing state task leaves L2 - 1 rows and
+    the last channel frame for the launch behind it."""
+    import torch
+    fs, crate = DECIMATION_RATES[pd2]
+    arate, nch, nblk = crate // pd2, 130, 5
+    n = _k2_for(l2, pd2, 60) * pd2 * (fs // crate)
+    ifs = _spread_ifs(fs, nch)
+    iq = synth.fm_stream(nblk * n, fs, _carriers(ifs), amp=0.1)
+    x = torch.from_numpy(iq).cuda()
+    torch.cuda.synchronize()
+    blocks = [(b * n, n) for b in range(nblk)]
+    views = [x[2 * off: 2 * (off + m)] for off, m in blocks]
+    seen = {}
+
+    def submit(t, b, off, m):
+        t.submit_device(views[b], m)
+
+    def phases(t, b):
+        if b in (2, 4):
+            if b == 4:
+                seen["streamed"] = t.stream_info()
+            t.flush()
+            t.streaming(b == 2)
+
+    one = _play_long(dev, fs, crate, arate, ifs, l2, blocks, False, submit)
+    many = _play_long(dev, fs, crate, arate, ifs, l2, blocks, phases, submit)
+    assert one["info"] == (False, 0, 0)
+    assert seen["streamed"] == (True, 1, 2), seen
+    assert many["info"] == (False, 1, 2), many["info"]
+    _same_bits(one, many)
+    _against_the_chain(oracle, fs, crate, arate, ifs, l2, [iq[2 * off: 2 * (off + m)] for off, m in blocks], many,
+                       _group_probes(nch))
+
+
+@pytest.mark.parametrize("l2,pd2", [(128, 5), (256, 2)])
+def test_an_audio_passband_per_receiver_and_setters_between_blocks(dev, oracle, l2, pd2):
+    """Half of lane group 0 has an audio passband of its own: that group's taps come per lane (WrPostArgs::uni2 clear),
+    lane groups 1 and 2 share one filter each and read it through the scalar cache (uni2 set).  A retune and a change of
+    mode between blocks close the launch at their block boundary, and the next block opens another -- the counts of
+    test_gpu_stream_filters.test_filter_setters_mid_stream."""
+    import torch
+    fs, crate = DECIMATION_RATES[pd2]
+    arate, nch, nblk = crate // pd2, 130, 6
+    n = _k2_for(l2, pd2, 60) * pd2 * (fs // crate)
+    ifs = _spread_ifs(fs, nch)
+    _, apb = _passbands(fs, crate, arate)
+    apbs = [apb // 2 if c < 32 else apb for c in range(nch)]
+    assert oracle.lowpass_maxbin_n(l2, apb // 2, crate) >= 1
+    assert not np.array_equal(oracle.lowpass_design(apb // 2, crate, l2), oracle.lowpass_design(apb, crate, l2))
+    retuned, remoded = 70, 9                     # lane group 1 (shared filter) and lane group 0 (per-lane taps)
+    iq = synth.fm_stream(nblk * n, fs, _carriers(ifs), amp=0.1)
+    x = torch.from_numpy(iq).cuda()
+    torch.cuda.synchronize()
+    blocks = [(b * n, n) for b in range(nblk)]
+    views = [x[2 * off: 2 * (off + m)] for off, m in blocks]
+
+    def submit(t, b, off, m):
+        t.submit_device(views[b], m)
+
+    def run(stream):
+        seen = {}
+
+        def between(t, chans, b):
+            if b in (2, 4):
+                seen[b] = t.stream_info()
+                if b == 2:
+                    t.set_if(chans[retuned], ifs[retuned] + 777)
+                else:
+                    t.set_mode(chans[remoded], capi.WR_AM)
+            return []
+
+        return _play_long(dev, fs, crate, arate, ifs, l2, blocks, stream, submit, between=between, apbs=apbs), seen
+
+    one, seen1 = run(False)
+    many, seen = run(True)
+    assert one["info"] == (False, 0, 0) and all(v == (False, 0, 0) for v in seen1.values())
+    assert seen[2] == (True, 1, 2), seen            # blocks 0, 1: one launch
+    assert seen[4] == (True, 2, 4), seen            # blocks 2, 3: the retune closed it, block 2 opened the second
+    assert many["info"] == (True, 3, 6), many["info"]   # blocks 4, 5: behind the change of mode, a third
+    _same_bits(one, many)
+    probes = [c for c in _group_probes(nch) if c not in (retuned, remoded)]
+    assert {apbs[c] for c in probes} == {apb // 2, apb}
+    _against_the_chain(oracle, fs, crate, arate, ifs, l2, [iq[2 * off: 2 * (off + m)] for off, m in blocks], many, probes,
+                       apbs=apbs, every_group=False)
+
+
+def test_long_audio_filter_streams_byte_blocks(dev, oracle):
+    """the RTL-SDR byte format (io/rtlsdrtuner.cxx:106) out of device memory, 128 taps at D2 = 8 (BASELINE config 1's
+    decimations)"""
+    fs, crate = DECIMATION_RATES[8]
+    _stream_vs_blocks(dev, oracle, 128, fs, crate, crate // 8, 70, 100 * 8 * (fs // crate), 4, (True, 1, 4), u8=True)
+
+
+# audio taps: (audio decimation, receivers, distinct channel passbands per lane group, how they are laid out)
+MIXED_CHANNEL_FILTERS = {128: [(5, 130, 4, "spread"), (10, 70, 3, "staggered"), (1, 200, 2, "spread")],
+                         256: [(3, 130, 4, "staggered"), (1, 70, 2, "spread"), (2, 200, 3, "spread")]}
+MIXED_CASES = [(l2,) + c for l2 in sorted(MIXED_CHANNEL_FILTERS) for c in MIXED_CHANNEL_FILTERS[l2]]
+
+
+@pytest.mark.parametrize("l2,pd2,nch,k,layout", MIXED_CASES, ids=[f"L2={c[0]}-PD2={c[1]}-{c[3]}-filters" for c in MIXED_CASES])
+def test_long_audio_filter_with_channel_passbands_per_receiver(dev, oracle, l2, pd2, nch, k, layout):
+    """k_tuner_stream<PD2, 1, WR_TAPSETS, L2 / 64>: 2, 3 and 4 distinct channel passbands across the lanes of a lane group
+    (receiverhandler.cxx:130-137; tests/test_gpu_stream_filters.py's layouts) on a tuner whose audio filters have 128 or
+    256 taps -- a window copy per channel filter in the DDC waves, the long window in the post stage.  One launch, the
+    bits of a launch per block, every distinct channel passband probed against the oracle's chain."""
+    import torch
+    from test_gpu_stream_filters import _pb, _sets_per_group, _spread, _staggered
+    fs, crate = DECIMATION_RATES[pd2]
+    arate, nblk = crate // pd2, 4
+    bins = (_spread if layout == "spread" else _staggered)(nch, k)
+    sets = _sets_per_group(bins)
+    assert max(sets) == k > 1 and (layout == "spread" or len(set(sets)) > 1), sets
+    cpbs = [_pb(fs, m) for m in bins]
+    n = _k2_for(l2, pd2, 60) * pd2 * (fs // crate)
+    ifs = _spread_ifs(fs, nch)
+    iq = synth.fm_stream(nblk * n, fs, _carriers(ifs), amp=0.1)
+    x = torch.from_numpy(iq).cuda()
+    torch.cuda.synchronize()
+    blocks = [(b * n, n) for b in range(nblk)]
+    views = [x[2 * off: 2 * (off + m)] for off, m in blocks]
+
+    def submit(t, b, off, m):
+        t.submit_device(views[b], m)
+
+    one = _play_long(dev, fs, crate, arate, ifs, l2, blocks, False, submit, cpbs=cpbs)
+    many = _play_long(dev, fs, crate, arate, ifs, l2, blocks, True, submit, cpbs=cpbs)
+    assert one["info"] == (False, 0, 0)
+    assert many["info"] == (True, 1, nblk), many["info"]
+    _same_bits(one, many)
+    probes = _group_probes(nch)
+    for m in sorted(set(bins)):                        # every distinct channel passband, by a linear demodulator too
+        probes += [c for c in range(nch) if bins[c] == m and c % 4 != 0][:1]
+    probes = sorted(set(probes))
+    assert {bins[c] for c in probes} == set(bins)
+    _against_the_chain(oracle, fs, crate, arate, ifs, l2, [iq[2 * off: 2 * (off + m)] for off, m in blocks], many, probes,
+                       cpbs=cpbs)

@@ -50,8 +50,8 @@ struct WrGroupDev {
 	int          *flags;        /* bit0: slot active (host-written only) */
 	int          *mode;         /* wr_mode, or -1 for an idle slot (what the post-DDC kernels test) */
 	float        *taps1;        /* [64][slots] channel-filter taps, taps1[j*slots+s] = coeff[j] */
-	float        *taps2;        /* [64][slots] audio-filter taps */
-	float        *taps2u;       /* [lane groups][64] the group's one audio filter, where its channels share one
+	float        *taps2;        /* [l2][slots] audio-filter taps (l2 = 64, or 128 / 256: below) */
+	float        *taps2u;       /* [lane groups][l2] the group's one audio filter, where its channels share one
 	                               (WrTunerLaunch::uniform2_mask) */
 	/* what a DDC wave needs before its first tap, laid out so that it is ONE coalesced load each (a
 	 * wave that gathers them -- 64 tap rows, four table entries per lane -- queues 320 cache-line
@@ -144,7 +144,7 @@ struct WrPostArgs {
 	unsigned int run;            /* consecutive tiles one workgroup takes */
 	unsigned int ntiles;         /* workgroups per lane group = ceil(tiles / run), plus the one that writes the state */
 	const float *taps2;
-	const float *taps2u;         /* [groups][64], read through the scalar cache */
+	const float *taps2u;         /* [groups][64 nseg], read through the scalar cache */
 	unsigned long long uni2;     /* bit g: lane group g's channels share one audio filter (taps2u) */
 	float       *audio;
 	size_t       k2max;
@@ -160,9 +160,9 @@ struct WrPostArgs {
 	size_t       host_stride;
 	unsigned int nseg = 1;       /* the audio filter's taps / 64: 1, or 2 / 4 (dem_hist then has 127 / 255 rows, taps2 128 / 256,
 	                                taps2u [groups][taps]) */
-	const float *chan_prev = nullptr;   /* r05 (the streaming launch): the channel IQ of the block BEFORE this one, [k1][slots][2], k1 >= 64 --
-	                                the 63 rows of audio-filter history and the demodulator's previous frame are then made from
-	                                ITS last 64 rows (the same operations on the same frames: the same bits) instead of read
+	const float *chan_prev = nullptr;   /* r05 (the streaming launch): the channel IQ of the block BEFORE this one, [k1][slots][2], k1 >= 64 nseg --
+	                                the 64 nseg - 1 rows of audio-filter history and the demodulator's previous frame are then made from
+	                                ITS last 64 nseg rows (the same operations on the same frames: the same bits) instead of read
 	                                from dem_hist / prev_iq, so that a block's post stage does not wait for the one before */
 };
 /* `post` (optional): the post stage of the PREVIOUS block, run by extra workgroups of the same
@@ -302,8 +302,9 @@ struct WrStreamArgs {
 };
 #define WR_STREAM_ERR_WAIT   1u            /* a wait inside the launch ran into `wait_ticks` */
 /* workgroups the launch needs co-resident (it sizes its roles to them); 0 = this launch shape cannot stream */
-hipError_t wrk_stream_geometry(unsigned int d2, unsigned int groups, unsigned int kmax, bool one_filter, int num_cus,
-                               unsigned int *n_ddc, unsigned int *n_post);
+/* (`nseg`: the audio filter's taps / 64 -- 1, 2, or 4 up to an audio decimation of 3) */
+hipError_t wrk_stream_geometry(unsigned int d2, unsigned int groups, unsigned int kmax, bool one_filter, unsigned int nseg,
+                               int num_cus, unsigned int *n_ddc, unsigned int *n_post);
 hipError_t wrk_tuner_stream(hipStream_t st, const WrStreamArgs &A, void *ev_start, void *ev_stop);
 
 /* ---- FFT (wr_fft.hip) ---- */

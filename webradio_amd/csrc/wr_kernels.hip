@@ -590,7 +590,8 @@ __device__ __forceinline__ void post_role(const WrPostArgs &A, unsigned int bx, 
 			return;
 		const size_t first = k1;                        /* the last 63 (L - 1) rows of [history | current] */
 #pragma unroll
-		for (unsigned int r = row; r < HIST; r += NROW)      /* unrolled: one memory round, not eight */
+		for (unsigned int r = row; r < HIST; r += NROW)      /* unrolled: one memory round, not eight (64 taps; the 16 / 32 rounds of
+		                                                        127 / 255 rows stay a loop, which the compiler says so about) */
 			A.dem_hist_next[(size_t)r * slots + s] = post_row(chan_iq, k1, slots, s, m, prev_iq, dem_hist, first + r, chan_prev, HIST);
 		if (row == 0)
 			((float2 *)A.prev_next)[s] = k1 ? chan_iq[(size_t)(k1 - 1u) * slots + s] : prev_iq[s];

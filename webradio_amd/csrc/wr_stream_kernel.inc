@@ -317,11 +317,13 @@ __device__ __forceinline__ void stream_bell(const WrStreamArgs &S)
 }
 
 /* ---- the post stage, block by block ---- */
-template <unsigned int PD2, unsigned int TS>
+/* NSEG: the audio filter's taps / 64 (post_role): 1, or 2 / 4 for a filter of 128 / 256 taps -- the staged window and the
+ * history in front of a block grow to 64 NSEG - 1 rows, everything else is the 64-tap launch's */
+template <unsigned int PD2, unsigned int TS, unsigned int NSEG>
 __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigned int p, v2f *lds, const bool helper)
 {
 	constexpr unsigned int D2 = PD2 ? PD2 : 1u;
-	constexpr unsigned int NEED = (POST_TK - 1u) * D2 + WR_FIR_LENGTH;
+	constexpr unsigned int NEED = (POST_TK - 1u) * D2 + WR_FIR_LENGTH * NSEG;
 	wave_prio(3u);
 	if (threadIdx.x >= POST_THREADS)
 		return;
@@ -432,9 +434,9 @@ __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigne
 		known = sh[3];
 		if (!go)
 			break;
-		/* Block j's tiles.  The rows in front of the block -- the audio filter's 63 rows of history, the demodulator's
-		 * previous frame -- come from the tuner's state for block 0 and, for every later block, from the last 64
-		 * channel-IQ rows of the block before, which are still in the ring (WrPostArgs::chan_prev): a block's post
+		/* Block j's tiles.  The rows in front of the block -- the audio filter's 63 (64 NSEG - 1) rows of history, the
+		 * demodulator's previous frame -- come from the tuner's state for block 0 and, for every later block, from the last
+		 * 64 NSEG channel-IQ rows of the block before, which are still in the ring (WrPostArgs::chan_prev): a block's post
 		 * stage waits for its own channel IQ and for nothing else, so the post workgroups need not move in step. */
 		WrPostArgs A = S.post;
 		A.chan_iq = S.ring + (size_t)(j % WR_STREAM_RING) * S.k1 * S.slots * 2u;
@@ -470,7 +472,7 @@ __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigne
 			}
 			if (t >= tasks_j)
 				break;
-			post_role<D2, false>(A, t % A.ntiles, t / A.ntiles, stage, tile, modes);
+			post_role<D2, false, NSEG>(A, t % A.ntiles, t / A.ntiles, stage, tile, modes);
 			__syncthreads();                             /* the next task's first phase rewrites `modes` and the stage */
 			++mine;
 		}
@@ -502,8 +504,9 @@ __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigne
 	}
 #endif
 	/* The stream is closed and this workgroup has done its share of every block: what the LAST block leaves behind per
-	 * lane group -- the last 63 demodulator outputs, the last channel frame (post_role's state task) -- goes to the
-	 * other ping-pong set, once.  (Every post workgroup has seen ddc_ready reach the last block: its rows are there.) */
+	 * lane group -- the last 63 (64 NSEG - 1) demodulator outputs, the last channel frame (post_role's state task) -- goes
+	 * to the other ping-pong set, once: what a launch per block reads as its history, whatever the filter's length.
+	 * (Every post workgroup has seen ddc_ready reach the last block: its rows are there.) */
 	if (!helper && p < S.post.groups && known && known <= WR_STREAM_MAXJ) {
 		const unsigned int jl = known - 1u;
 		WrPostArgs A = S.post;
@@ -513,7 +516,7 @@ __device__ __forceinline__ void stream_post(const WrStreamArgs &S, const unsigne
 		A.dem_hist = S.dem[S.parity0];
 		A.prev_next = const_cast<float *>(S.prev_iq[S.parity0 ^ 1]);
 		A.dem_hist_next = S.dem[S.parity0 ^ 1];
-		post_role<D2, false>(A, A.ntiles, p, stage, tile, modes);
+		post_role<D2, false, NSEG>(A, A.ntiles, p, stage, tile, modes);
 	}
 }
 
@@ -834,7 +837,7 @@ __device__ __forceinline__ void stream_ddc(const WrStreamArgs &S, v2f *lds)
 	}
 }
 
-template <unsigned int PD2, unsigned int NG, unsigned int TS>
+template <unsigned int PD2, unsigned int NG, unsigned int TS, unsigned int NSEG>
 __global__ void __launch_bounds__(DDC_ROTATE_WAVES * 64u) __attribute__((amdgpu_waves_per_eu(DDC_NG2_WAVES_PER_EU)))
 k_tuner_stream(const WrStreamArgs S)
 {
@@ -849,7 +852,7 @@ k_tuner_stream(const WrStreamArgs S)
 		__syncthreads();                                    /* every wave is behind its last block and the state roll: the
 		                                                       workgroup's LDS is free, and so is the workgroup (stream_post) */
 	}
-	stream_post<PD2, TS>(S, ddc ? blockIdx.x : blockIdx.x - S.n_ddc, lds, ddc);
+	stream_post<PD2, TS, NSEG>(S, ddc ? blockIdx.x : blockIdx.x - S.n_ddc, lds, ddc);
 }
 
 /* post-stage tiles per workgroup for a launch that may keep `max_post` post workgroups resident */
@@ -862,10 +865,12 @@ static unsigned int stream_post_run(unsigned int tiles, unsigned int groups, uns
 }
 
 /* LDS per workgroup: the post stage's stage and tile, or the DDC's NCO tables and window copies -- `nset` per buffer, two
- * buffers per wave (the block-boundary role inside the post workgroups lays its windows out the same way) */
-static size_t stream_lds_bytes(unsigned int d2, unsigned int nset)
+ * buffers per wave (the block-boundary role inside the post workgroups lays its windows out the same way).  EVERY
+ * workgroup of the launch reserves it (LDS is per kernel, not per role), so an audio filter of `nseg` x 64 taps decides how
+ * many workgroups a CU's 160 KB hold: at D2 = 5, 40 064 / 56 448 / 89 216 B for 64 / 128 / 256 taps (DESIGN.md 3.6) */
+static size_t stream_lds_bytes(unsigned int d2, unsigned int nset, unsigned int nseg)
 {
-	const size_t post_lds = post_lds_bytes(d2, 1u) + 16u * sizeof(float);     /* (+ stream_post's `sh` words) */
+	const size_t post_lds = post_lds_bytes(d2, nseg) + 16u * sizeof(float);     /* (+ stream_post's `sh` words) */
 	const size_t ddc_lds = (size_t)DDC_ROTATE_WAVES * 2u * 512u * nset + 2u * WR_SPLIT_N * 8u;
 	return post_lds > ddc_lds ? post_lds : ddc_lds;
 }
@@ -881,37 +886,76 @@ static void stream_shape(unsigned int groups, unsigned int kmax, bool one_filter
 	*ts = kmax > 1u ? WR_TAPSETS : 1u;
 }
 
-template <unsigned int PD2, unsigned int NG, unsigned int TS>
-static hipError_t stream_occupancy(size_t lds, int *per_cu)
+/* The audio filter lengths a launch is built for, by audio decimation: 64 and 128 taps at every one, 256 taps up to
+ * D2 = 3 -- from D2 = 4 on a 256-tap window is 85 KB and more, ONE workgroup per CU, and a launch needs two (a DDC and a post
+ * workgroup: wrk_stream_geometry): those tuners keep their launch per block, and no kernel is built for them. */
+#define STREAM_NSEG4_MAX_D2 3u
+static bool stream_nseg_supported(unsigned int d2, unsigned int nseg)
+{
+	return nseg == 1u || nseg == 2u || (nseg == 4u && d2 <= STREAM_NSEG4_MAX_D2);
+}
+/* calls f with the run-time nseg as a compile-time constant; a length the launch is not built for: hipErrorInvalidValue */
+template <unsigned int PD2, class F>
+static hipError_t with_stream_nseg(unsigned int nseg, F &&f)
+{
+	if (nseg == 1u)
+		return f(std::integral_constant<unsigned int, 1u>());
+	if (nseg == 2u)
+		return f(std::integral_constant<unsigned int, 2u>());
+	if constexpr (PD2 <= STREAM_NSEG4_MAX_D2)
+		if (nseg == 4u)
+			return f(std::integral_constant<unsigned int, 4u>());
+	return hipErrorInvalidValue;
+}
+
+/* An instance's dynamic LDS above 64 KB must be allowed once per device (allow_lds remembers that it has been): the MOST
+ * the instance can ask for -- TS window copies per buffer -- not what this launch asks for.  With the current request a
+ * tuner whose lane groups came to mix more channel filters later (kmax up, more window copies) kept the limit of its first
+ * launch.  The 64-tap instances stay under 64 KB whatever kmax and never get here. */
+template <unsigned int PD2, unsigned int NG, unsigned int TS, unsigned int NSEG>
+static hipError_t stream_allow_lds(size_t lds)
 {
 	static bool attr_done[WR_MAX_DEVICES];
-	if (lds > 64 * 1024) {
-		hipError_t e = allow_lds((const void *)k_tuner_stream<PD2, NG, TS>, lds, attr_done);
-		if (e != hipSuccess)
-			return e;
-	}
-	return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_tuner_stream<PD2, NG, TS>, (int)(DDC_ROTATE_WAVES * 64u), lds);
+	if (lds <= 64 * 1024)
+		return hipSuccess;
+	return allow_lds((const void *)k_tuner_stream<PD2, NG, TS, NSEG>, stream_lds_bytes(PD2, TS, NSEG), attr_done);
+}
+
+template <unsigned int PD2, unsigned int NG, unsigned int TS, unsigned int NSEG>
+static hipError_t stream_occupancy(size_t lds, int *per_cu)
+{
+	hipError_t e = stream_allow_lds<PD2, NG, TS, NSEG>(lds);
+	if (e != hipSuccess)
+		return e;
+	return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_tuner_stream<PD2, NG, TS, NSEG>, (int)(DDC_ROTATE_WAVES * 64u), lds);
 }
 
 /* How many workgroups of the streaming launch a device holds at once, split into roles.  Every workgroup of the
  * launch must be resident (they wait for one another): the grid is never larger than what the occupancy query
  * admits, capped at three per CU (what 80 registers and eight waves per workgroup give; the query can be one too
  * generous near a register-file edge, MI355X_MICROARCH.md "Residency").  `kmax`: the most channel filters a lane group
- * of the launch mixes; `one_filter`: one for the whole tuner (stream_shape). */
-hipError_t wrk_stream_geometry(unsigned int d2, unsigned int groups, unsigned int kmax, bool one_filter, int num_cus,
-                               unsigned int *n_ddc, unsigned int *n_post)
+ * of the launch mixes; `one_filter`: one for the whole tuner (stream_shape); `nseg`: the audio filter's taps / 64.
+ * An audio filter of 128 taps (and one of 256 up to D2 = 3) leaves a CU's LDS room for TWO workgroups, not three: one DDC
+ * workgroup per CU instead of two, the post stage's slot as before.  Fewer than two: no launch (256 taps from D2 = 4 on). */
+hipError_t wrk_stream_geometry(unsigned int d2, unsigned int groups, unsigned int kmax, bool one_filter, unsigned int nseg,
+                               int num_cus, unsigned int *n_ddc, unsigned int *n_post)
 {
 	*n_ddc = *n_post = 0;
-	if (!wrk_tuner_post_supported(d2) || !groups || groups > 16u || !kmax || kmax > WR_TAPSETS)
+	if (!wrk_tuner_post_supported(d2) || !stream_nseg_supported(d2, nseg) || !groups || groups > 16u || !kmax ||
+	    kmax > WR_TAPSETS)
 		return hipSuccess;
 	unsigned int ng, ts;
 	stream_shape(groups, kmax, one_filter, &ng, &ts);
-	const size_t lds = stream_lds_bytes(d2, ts == 1u ? 1u : kmax);
+	const size_t lds = stream_lds_bytes(d2, ts == 1u ? 1u : kmax, nseg);
 	int per_cu = 0;
 	hipError_t e = with_post_d2(d2, [&](auto D2) {
 		constexpr unsigned int PD2 = decltype(D2)::value;
-		return ts != 1u ? stream_occupancy<PD2, 1, WR_TAPSETS>(lds, &per_cu)
-		       : ng == 1u ? stream_occupancy<PD2, 1, 1>(lds, &per_cu) : stream_occupancy<PD2, 2, 1>(lds, &per_cu);
+		return with_stream_nseg<PD2>(nseg, [&](auto NS) {
+			constexpr unsigned int NSEG = decltype(NS)::value;
+			return ts != 1u ? stream_occupancy<PD2, 1, WR_TAPSETS, NSEG>(lds, &per_cu)
+			       : ng == 1u ? stream_occupancy<PD2, 1, 1, NSEG>(lds, &per_cu)
+			                  : stream_occupancy<PD2, 2, 1, NSEG>(lds, &per_cu);
+		});
 	});
 	if (e != hipSuccess)
 		return e;
@@ -926,23 +970,20 @@ hipError_t wrk_stream_geometry(unsigned int d2, unsigned int groups, unsigned in
 	return hipSuccess;
 }
 
-template <unsigned int PD2, unsigned int NG, unsigned int TS>
+template <unsigned int PD2, unsigned int NG, unsigned int TS, unsigned int NSEG>
 static hipError_t launch_stream(hipStream_t st, const WrStreamArgs &A, void *ev_start, void *ev_stop)
 {
-	const size_t lds = stream_lds_bytes(PD2, TS == 1u ? 1u : A.kmax);
-	static bool attr_done[WR_MAX_DEVICES];
-	if (lds > 64 * 1024) {
-		hipError_t e = allow_lds((const void *)k_tuner_stream<PD2, NG, TS>, lds, attr_done);
-		if (e != hipSuccess)
-			return e;
-	}
+	const size_t lds = stream_lds_bytes(PD2, TS == 1u ? 1u : A.kmax, NSEG);
+	hipError_t e = stream_allow_lds<PD2, NG, TS, NSEG>(lds);
+	if (e != hipSuccess)
+		return e;
 	const unsigned int grid = A.n_ddc + A.n_post + 1u;
 	if (ev_start || ev_stop) {
-		hipExtLaunchKernelGGL((k_tuner_stream<PD2, NG, TS>), dim3(grid), dim3(DDC_ROTATE_WAVES * 64u), (uint32_t)lds, st,
+		hipExtLaunchKernelGGL((k_tuner_stream<PD2, NG, TS, NSEG>), dim3(grid), dim3(DDC_ROTATE_WAVES * 64u), (uint32_t)lds, st,
 		                      (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 0u, A);
 		return hipGetLastError();
 	}
-	k_tuner_stream<PD2, NG, TS><<<grid, DDC_ROTATE_WAVES * 64u, lds, st>>>(A);
+	k_tuner_stream<PD2, NG, TS, NSEG><<<grid, DDC_ROTATE_WAVES * 64u, lds, st>>>(A);
 	return hipGetLastError();
 }
 
@@ -985,10 +1026,16 @@ hipError_t wrk_tuner_stream(hipStream_t st, const WrStreamArgs &A0, void *ev_sta
 	stream_shape(A.groups, A.kmax, A.one_filter != 0u, &ng, &ts);
 	if ((size_t)A.n_ddc * DDC_ROTATE_WAVES < A.groups / ng)
 		return hipErrorInvalidValue;
+	/* (a block shorter than the audio filter has no L2 - 1 rows of history for the block behind it: wrc_stream_open) */
+	if (A.k1 < WR_FIR_LENGTH * A.post.nseg)
+		return hipErrorInvalidValue;
 	return with_post_d2(A.post.d2, [&](auto D2) {
 		constexpr unsigned int PD2 = decltype(D2)::value;
-		return ts != 1u ? launch_stream<PD2, 1, WR_TAPSETS>(st, A, ev_start, ev_stop)
-		       : ng == 2u ? launch_stream<PD2, 2, 1>(st, A, ev_start, ev_stop)
-		                  : launch_stream<PD2, 1, 1>(st, A, ev_start, ev_stop);
+		return with_stream_nseg<PD2>(A.post.nseg, [&](auto NS) {
+			constexpr unsigned int NSEG = decltype(NS)::value;
+			return ts != 1u ? launch_stream<PD2, 1, WR_TAPSETS, NSEG>(st, A, ev_start, ev_stop)
+			       : ng == 2u ? launch_stream<PD2, 2, 1, NSEG>(st, A, ev_start, ev_stop)
+			                  : launch_stream<PD2, 1, 1, NSEG>(st, A, ev_start, ev_stop);
+		});
 	});
 }

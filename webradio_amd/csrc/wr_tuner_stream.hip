@@ -19,8 +19,10 @@
  *
  * Requirements, checked at the open (a submit that does not meet them goes the ordinary way): WR_NCO_ROTATE; one
  * rate group; at most 1024 channels on 64-tap channel filters, at most WR_TAPSETS distinct ones in each lane group of 64
- * channel slots; no second channel stage; an audio decimation the fused post stage has (1..6, 8, 10); whole audio
- * frames per block; no kept demodulator rows, no seek pending, no launch marks.  A block's memory must stay untouched
+ * channel slots; no second channel stage; an audio decimation the fused post stage has (1..6, 8, 10); an audio filter of
+ * 64 or 128 taps, or of 256 up to an audio decimation of 3 (beyond it the post stage's window leaves a CU's LDS room for
+ * one workgroup, and a launch needs two: DESIGN.md 3.6); blocks of at least as many channel-rate frames as the audio filter
+ * has taps; whole audio frames per block; no kept demodulator rows, no seek pending, no launch marks.  A block's memory must stay untouched
  * until the NEXT block's audio is complete (the first frames of a block read the last 63 of the one before in place).
  *
  * A caller that waits for the device's stream by other means (hipStreamSynchronize on a stream it handed to
@@ -143,10 +145,16 @@ int wrc_stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, bool *
 	if (t->nco_mode != WR_NCO_ROTATE || !t->defer_post || t->mark_launches || (t->keep_mask & (1u << WR_STAGE_DEMOD)))
 		return WR_OK;
 	Group *g = wrc_single_group(t);
-	if (!g || g->l1 != WR_FIR_LENGTH || g->l2 != WR_FIR_LENGTH || g->d1b || g->seek_pending || !wrk_tuner_post_supported(g->d2))
+	if (!g || g->l1 != WR_FIR_LENGTH || g->d1b || g->seek_pending || !wrk_tuner_post_supported(g->d2))
 		return WR_OK;
-	/* (64 channel-rate frames per block at least: a block's post stage takes its history from the block before) */
-	if (nframes < (size_t)WR_FIR_LENGTH * g->d1 || nframes % ((size_t)g->d1 * g->d2) || nframes / g->d1 > 0x3FFFFFFFu)
+	/* an audio filter of 64, 128 or 256 taps: 1, 2 or 4 segments of 64 in the post stage (wrk_stream_geometry says which of
+	 * them a launch has room for) */
+	if (g->l2 != WR_FIR_LENGTH && g->l2 != 2u * WR_FIR_LENGTH && g->l2 != 4u * WR_FIR_LENGTH)
+		return WR_OK;
+	const unsigned int nseg = g->l2 / WR_FIR_LENGTH;
+	/* (as many channel-rate frames per block as the audio filter has taps, 64 at least: a block's post stage takes its
+	 * L2 - 1 rows of history and the frame in front of them from the block before) */
+	if (nframes < (size_t)g->l2 * g->d1 || nframes % ((size_t)g->d1 * g->d2) || nframes / g->d1 > 0x3FFFFFFFu)
 		return WR_OK;
 	if (wrc_dev_bind(d))
 		return WR_ERR_HIP;
@@ -185,7 +193,7 @@ int wrc_stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, bool *
 			return rc;
 	const size_t k1 = nframes / g->d1, k2 = k1 / g->d2;
 	unsigned int n_ddc = 0, n_post = 0;
-	HIP_TRY(wrk_stream_geometry(g->d2, groups, kmax, g->one_filter, d->num_cus, &n_ddc, &n_post));
+	HIP_TRY(wrk_stream_geometry(g->d2, groups, kmax, g->one_filter, nseg, d->num_cus, &n_ddc, &n_post));
 	if (!n_ddc || !n_post)
 		return WR_OK;
 	/* (each on its own: an allocation that failed last time is tried again, never skipped because an earlier one stands) */
@@ -263,7 +271,7 @@ int wrc_stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, bool *
 	A.ring = s.ring;
 	for (int i = 0; i < 4; ++i)
 		A.audio_bufs[i] = g->dev.audio_set[(g->audio_cur + i) & 3];
-	A.post = wrk_post_args(L, g->dev);
+	A.post = wrk_post_args(L, g->dev);                      /* (nseg, and taps2u [lane groups][L2], with it) */
 	A.post.host_stride = k2;                                /* the ring's rows lie back to back (RingSlot::stride = frames) */
 	A.prev_iq[0] = g->dev.prev_iq[0];
 	A.prev_iq[1] = g->dev.prev_iq[1];
