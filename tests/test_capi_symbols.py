@@ -120,7 +120,7 @@ def test_product_never_touches_oracle():
     bad = []
     for d, _, files in os.walk(os.path.join(ROOT, "webradio_amd")):
         for f in files:
-            if f.endswith((".py", ".h", ".hip", ".cpp", ".cxx", "Makefile")):
+            if f.endswith((".py", ".h", ".hip", ".inc", ".cpp", ".cxx", "Makefile")):
                 text = open(os.path.join(d, f), errors="replace").read()
                 if re.search(r"wr_oracle|wro_|oracle/|libwr_ref", text):
                     bad.append(os.path.join(d, f))

@@ -809,7 +809,7 @@ k_tuner_post(WrPostArgs A)
                                               36.8 / 32.0, 4 ways 37.0 / 32.0, 8 ways 38.5 / 32.0 */
 
 /* PD2 > 0: workgroups n_ddc.. of the grid run the post stage (audio decimation PD2) of the
- * PREVIOUS block -- see post_role and wr_capi.hip: the two have nothing to do with each other
+ * PREVIOUS block -- see post_role and wr_tuner.hip: the two have nothing to do with each other
  * except that they share the CUs, the post stage's latency-bound phases filling in between the
  * DDC's arithmetic.  Their dependency is the kernel boundary before this launch. */
 /* r03: the ROTATE kernel with folded taps splits its workgroups into roles:
@@ -1961,6 +1961,22 @@ static size_t post_lds_bytes(unsigned int d2, unsigned int nseg)
 	return (((size_t)(POST_TK - 1u) * d2 + WR_FIR_LENGTH * nseg) * 64u + POST_TK * 65u + 64u) * sizeof(float);
 }
 
+/* Launch `kernel`, stamping the launch's own start / stop events where the caller gave any.  Profiling (both events; with
+ * two launches per rate group the first takes the start, the last the stop) or a caller that wants to wait for THIS launch
+ * from another stream (the stop event alone, wr_tuner_mark_launches): the launch stamps the events with the dispatch's own
+ * start and end, as rocprof sees them -- events recorded around it would add their own barrier packets.  No event: a plain
+ * launch.  The arguments are converted to the kernel's parameter types here, once for both forms. */
+template <class... Params, class... Args>
+static void launch_stamped(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st, void *ev_start,
+                           void *ev_stop, const Args &...args)
+{
+	if (ev_start || ev_stop)
+		hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, st, (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 0u,
+		                      static_cast<Params>(args)...);
+	else
+		kernel<<<grid, block, lds, st>>>(static_cast<Params>(args)...);
+}
+
 hipError_t wrk_tuner_ddc_long(hipStream_t st, const WrTunerLaunch &L, const WrGroupDev &G, unsigned int len,
                               const float *table_dev, int num_cus, bool rotate, bool rotate_one_filter, const float *hi_dev,
                               const float *lo_dev, const WrPostArgs *post, bool *post_taken)
@@ -2029,33 +2045,22 @@ hipError_t wrk_tuner_ddc_long(hipStream_t st, const WrTunerLaunch &L, const WrGr
 		const unsigned int cap = (unsigned int)num_cus * 8u;
 		if (wgs > cap)
 			wgs = cap;
-		if (prof_exact)
-			/* profiling: the filter kernel's own start and end (the roll behind it is not in the bracket) */
-			hipExtLaunchKernelGGL(k_tuner_ddc_long, dim3(wgs), dim3(256), 0, st, (hipEvent_t)L.ev_start, (hipEvent_t)L.ev_stop, 0u,
-			                      (const float2 *)L.cur, (const uchar2 *)L.cur_u8, L.nframes, k_exact, L.d1, len, L.slots, groups,
-			                      (const unsigned int *)G.phase[L.sp], (const unsigned int *)G.step, (const int *)G.flags,
-			                      (const float *)G.taps1L, (const float2 *)G.mixhist[L.sp], table_dev, (float2 *)G.chan_iq[L.cb]);
-		else
-			k_tuner_ddc_long<<<wgs, 256, 0, st>>>((const float2 *)L.cur, (const uchar2 *)L.cur_u8, L.nframes, k_exact, L.d1, len,
-			                                      L.slots, groups, G.phase[L.sp], G.step, G.flags, G.taps1L,
-			                                      (const float2 *)G.mixhist[L.sp], table_dev, (float2 *)G.chan_iq[L.cb]);
+		/* profiling: the filter kernel's own start and end (the roll behind it is not in the bracket) */
+		launch_stamped(k_tuner_ddc_long, dim3(wgs), dim3(256), 0, st, prof_exact ? L.ev_start : nullptr,
+		               prof_exact ? L.ev_stop : nullptr, (const float2 *)L.cur, (const uchar2 *)L.cur_u8, L.nframes, k_exact, L.d1,
+		               len, L.slots, groups, G.phase[L.sp], G.step, G.flags, G.taps1L, (const float2 *)G.mixhist[L.sp], table_dev,
+		               (float2 *)G.chan_iq[L.cb]);
 	}
 	if (rolled)
 		return hipGetLastError();                           /* the ROTATE launch rolled the state itself */
 	const size_t total = (size_t)(len - 1u) * L.slots;
 	const unsigned int rwgs = (unsigned int)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256);
-	if (L.ev_start && L.ev_stop && !L.k1) {
-		/* profiling a block too short for an output frame: the roll is all there is */
-		hipExtLaunchKernelGGL(k_ddc_long_roll, dim3(rwgs), dim3(256), 0, st, (hipEvent_t)L.ev_start, (hipEvent_t)L.ev_stop, 0u,
-		                      (const float2 *)L.cur, (const uchar2 *)L.cur_u8, L.nframes, len, L.slots,
-		                      (const unsigned int *)G.phase[L.sp], (const unsigned int *)G.step, (const int *)G.flags,
-		                      G.phase[L.sp ^ 1], (const float2 *)G.mixhist[L.sp], (float2 *)G.mixhist[L.sp ^ 1], table_dev);
-		return hipGetLastError();
-	}
-	k_ddc_long_roll<<<rwgs, 256, 0, st>>>((const float2 *)L.cur, (const uchar2 *)L.cur_u8, L.nframes,
-	                                                            len, L.slots, G.phase[L.sp], G.step, G.flags, G.phase[L.sp ^ 1],
-	                                                            (const float2 *)G.mixhist[L.sp], (float2 *)G.mixhist[L.sp ^ 1],
-	                                                            table_dev);
+	/* profiling a block too short for an output frame: the roll is all there is */
+	const bool prof_roll = L.ev_start && L.ev_stop && !L.k1;
+	launch_stamped(k_ddc_long_roll, dim3(rwgs), dim3(256), 0, st, prof_roll ? L.ev_start : nullptr,
+	               prof_roll ? L.ev_stop : nullptr, (const float2 *)L.cur, (const uchar2 *)L.cur_u8, L.nframes, len, L.slots,
+	               G.phase[L.sp], G.step, G.flags, G.phase[L.sp ^ 1], (const float2 *)G.mixhist[L.sp],
+	               (float2 *)G.mixhist[L.sp ^ 1], table_dev);
 	return hipGetLastError();
 }
 
@@ -2632,28 +2637,13 @@ static hipError_t launch_ddc(hipStream_t st, const WrTunerLaunch &L, const WrGro
 			return e;
 	}
 	const WrPostArgs pa = post ? *post : WrPostArgs();
-	if (L.ev_start || L.ev_stop) {
-		/* profiling (both events; with two launches per rate group the first takes the start, the last the stop) or a caller that wants to wait for THIS launch from another stream (the stop event
-		 * alone, wr_tuner_mark_launches): the launch stamps the events with the dispatch's own start and end, as
-		 * rocprof sees them -- events recorded around it would add their own barrier packets */
-		hipExtLaunchKernelGGL((k_tuner_ddc<NCO, UTAPS, PD2, NG>), dim3(wgs + n_bnd + post_wgs), dim3(W * 64u), (uint32_t)lds, st,
-		                      (hipEvent_t)L.ev_start, (hipEvent_t)L.ev_stop, 0u,
-		                      (const float2 *)L.cur, (const uchar2 *)L.cur_u8, (const float2 *)L.hist, (float2 *)L.hist_next,
-		                      L.nframes, L.k1, L.d1, L.slots, ngroups, (const unsigned int *)G.phase[L.sp],
-		                      (const unsigned int *)G.step, (const float2 *)G.hist_cs[L.sp], (const int *)G.flags,
-		                      G.phase[L.sp ^ 1], (float2 *)G.hist_cs[L.sp ^ 1], (const float2 *)G.hist_lo[L.sp],
-		                      (float2 *)G.hist_lo[L.sp ^ 1], (const float *)G.taps1, (const float4 *)G.rot, (const float *)G.taps1u,
-		                      (const int *)G.tapsel, kmax, (float2 *)G.chan_iq[L.cb], table_dev,
-		                      (const float2 *)hi_dev, (const float2 *)lo_dev, wgs, pa, gmap[0], gmap[1], whole ? 1 : 0, kslow, n_bnd, L.seeking ? 1u : 0u, L.seek_lo);
-		return hipGetLastError();
-	}
-	k_tuner_ddc<NCO, UTAPS, PD2, NG><<<wgs + n_bnd + post_wgs, W * 64u, lds, st>>>(
-		(const float2 *)L.cur, (const uchar2 *)L.cur_u8, (const float2 *)L.hist, (float2 *)L.hist_next, L.nframes,
-		L.k1, L.d1,
-		L.slots, ngroups, G.phase[L.sp], G.step, (const float2 *)G.hist_cs[L.sp], G.flags, G.phase[L.sp ^ 1],
-		(float2 *)G.hist_cs[L.sp ^ 1], (const float2 *)G.hist_lo[L.sp], (float2 *)G.hist_lo[L.sp ^ 1], G.taps1,
-		(const float4 *)G.rot, G.taps1u, G.tapsel, kmax, (float2 *)G.chan_iq[L.cb], table_dev,
-		(const float2 *)hi_dev, (const float2 *)lo_dev, wgs, pa, gmap[0], gmap[1], whole ? 1 : 0, kslow, n_bnd, L.seeking ? 1u : 0u, L.seek_lo);
+	launch_stamped(k_tuner_ddc<NCO, UTAPS, PD2, NG>, dim3(wgs + n_bnd + post_wgs), dim3(W * 64u), lds, st, L.ev_start, L.ev_stop,
+	               (const float2 *)L.cur, (const uchar2 *)L.cur_u8, (const float2 *)L.hist, (float2 *)L.hist_next, L.nframes,
+	               L.k1, L.d1, L.slots, ngroups, G.phase[L.sp], G.step, (const float2 *)G.hist_cs[L.sp], G.flags,
+	               G.phase[L.sp ^ 1], (float2 *)G.hist_cs[L.sp ^ 1], (const float2 *)G.hist_lo[L.sp],
+	               (float2 *)G.hist_lo[L.sp ^ 1], G.taps1, (const float4 *)G.rot, G.taps1u, G.tapsel, kmax,
+	               (float2 *)G.chan_iq[L.cb], table_dev, (const float2 *)hi_dev, (const float2 *)lo_dev, wgs, pa, gmap[0], gmap[1],
+	               whole ? 1 : 0, kslow, n_bnd, L.seeking ? 1u : 0u, L.seek_lo);
 	return hipGetLastError();
 }
 
