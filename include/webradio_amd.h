@@ -49,6 +49,7 @@ extern "C" {
                                     6: wr_spectrum_lazy_info, wr_tuner_stream_host_blocks, wr_tuner_stream_long_blocks, wr_tuner_submit_count, WR_STREAM_MAX_BLOCKS added; wr_tuner_set_streaming
                                     takes 2 (byte blocks out of page-locked host memory stream too), wr_tuner_last_staging may say 3;
                                     wr_spectrum_push beside an open streaming launch keeps the frame and transforms it on demand.
+                                    Added to 6 later: wr_spectrum_create_real, wr_spectrum_channels, wr_spectrum_batch_db_rows.
                                     Nothing of an earlier version changed or removed */
 #define WR_FIR_LENGTH    64      /* dsp/lowpass.cxx:39  FIR_LENGTH */
 #define WR_TABLE_SIZE    65536   /* dsp/downconverter.cxx:35 LOOKUP_BITS 16 */
@@ -504,6 +505,17 @@ int wr_tuner_profile_read(wr_tuner *tuner, unsigned int *launches, double *mean_
  * successive transforms; 0 or fft_size = the reference's back-to-back frames
  * (spectrumsink.cxx:101-121); fft_size/2 = 50 % overlap (BASELINE config 3). */
 int wr_spectrum_create(wr_spectrum **spec, wr_dev *dev, unsigned int fft_size, unsigned int hop);
+/* The same sink for REAL samples, one float per frame: a receiver's audio, a Demodulator's output.  The reference leaves
+ * this open (io/spectrumsink.cxx:62-64: "Check number of channels, select appropriate plan", "Handle real->complex for
+ * spectrum of real signals"; :93-100 expects _channels = 1 to work once the plan is right).  The spectrum is what
+ * wr_spectrum_create's sink gives for the frames (x[n], 0): same window, same dB expression, fft_size values, the row
+ * symmetric about its middle -- computed as a transform of fft_size / 2 packed points and an untangle step, so half the
+ * input bytes and half the butterflies.  Every call below that counts frames counts samples on such a spectrum.
+ * A real spectrum is never kept aside beside an open streaming launch: a WR_DEVICE push closes the launch like any other
+ * call on the device. */
+int wr_spectrum_create_real(wr_spectrum **spec, wr_dev *dev, unsigned int fft_size, unsigned int hop);
+/* floats per frame: 2 (wr_spectrum_create) or 1 (wr_spectrum_create_real) */
+int wr_spectrum_channels(wr_spectrum *spec, unsigned int *channels);
 int wr_spectrum_destroy(wr_spectrum *spec);
 /* SpectrumSink::process (io/spectrumsink.cxx:88-123): append frames; every time a
  * frame is complete it is windowed and transformed.  Async for WR_DEVICE input.
@@ -532,10 +544,17 @@ int wr_spectrum_frames_done(wr_spectrum *spec, unsigned long *frames);
 int wr_spectrum_get_waterfall_row(wr_spectrum *spec, unsigned int width, int hold,
                                   float *db_row_host, uint8_t *palette_host);
 /* transform `nframes_fft` whole frames laid out back to back at a fixed hop in
- * device memory and write dB rows (waterfall): frame f starts at iq_dev + 2*f*hop.
+ * device memory and write dB rows (waterfall): frame f starts at iq_dev + 2*f*hop
+ * (a real spectrum: at iq_dev + f*hop).
  * db_dev receives nframes_fft rows of fft_size floats (fft-shifted). Async. */
 int wr_spectrum_batch_db(wr_spectrum *spec, const float *iq_dev, size_t nframes_fft,
                          float *db_dev);
+/* The same for rows: the first fft_size frames of each of `nrows` rows lying `row_stride` frames apart
+ * (row_stride >= fft_size, else WR_ERR_ARG) to nrows dB rows.  With wr_tuner_audio_dev's pointer and chan_stride on a
+ * real spectrum: the audio spectrum of every receiver of a block (which needs fft_size audio frames or more) in one
+ * launch sequence.  Async; closes an open streaming launch first, like wr_spectrum_batch_db. */
+int wr_spectrum_batch_db_rows(wr_spectrum *spec, const float *in_dev, size_t row_stride, size_t nrows,
+                              float *db_dev);
 
 #ifdef __cplusplus
 }

@@ -251,6 +251,7 @@ struct wr_tuner {
 struct wr_spectrum {
 	wr_dev *dev;
 	unsigned int n, hop;
+	unsigned int ch;           /* floats per frame: 2 (IQ) or 1 (real samples, wr_spectrum_create_real) */
 	WrFftPlan plan;
 	float *stage;              /* device stream buffer */
 	size_t stage_cap;          /* frames */

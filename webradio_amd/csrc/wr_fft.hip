@@ -16,6 +16,12 @@
  *               256 x 256 with one 512 KiB intermediate per frame, which stays in
  *               L2 / Infinity Cache between the passes.
  *
+ * Real input (one channel: a receiver's audio; the reference's FIXMEs at io/spectrumsink.cxx:62-64): the n samples are
+ * packed as m = n/2 complex points z[i] = (w[2i]*x[2i], w[2i+1]*x[2i+1]), the m-point transform Z runs on the machinery
+ * above, and the untangle step X[k] = E - i*W_n^k*O, E/O = (Z[k] +/- conj(Z[m-k]))/2, X[n-k] = conj(X[k]) gives the n bins.
+ *   n <= 16384 : one workgroup per frame, untangled out of the LDS result buffer.
+ *   n  > 16384 : four-step on m, then k_fft_untangle.
+ *
  * The window multiply is the reference's float multiply on the raw sample
  * (spectrumsink.cxx:109-112); the dB expression is the reference's float
  * expression (spectrumsink.cxx:127,137-138).
@@ -94,7 +100,95 @@ k_fft_single(const float2 *__restrict__ iq, size_t hop, unsigned int n,
 	}
 }
 
-/* four-step pass 1; grid = (n2/ct, frames) */
+/* a packed point of a real frame: samples 2i and 2i+1, windowed.  A frame starts at any float offset (any hop, pushes of
+ * any length), so the pair is one 8-byte load only where the frame happens to be 8-byte aligned. */
+__device__ __forceinline__ float2 real_pair(const float *__restrict__ x, bool aligned, const float *__restrict__ window,
+                                            unsigned int i)
+{
+	float2 v;
+	if (aligned)
+		v = *(const float2 *)(x + 2u * i);
+	else
+		v = make_float2(x[2u * i], x[2u * i + 1u]);
+	const float2 w = *(const float2 *)(window + 2u * i);
+	return make_float2(v.x * w.x, v.y * w.y);
+}
+
+/* bin k of a real frame of 2m samples from Z[k], Z[m-k] of its packed transform and w = W_2m^k, 0 < k < m */
+__device__ __forceinline__ float2 untangle(float2 zk, float2 zr, float2 w)
+{
+	const float2 e = make_float2(0.5f * (zk.x + zr.x), 0.5f * (zk.y - zr.y));   /* (Z[k] + conj(Z[m-k])) / 2 */
+	const float2 o = make_float2(0.5f * (zk.x - zr.x), 0.5f * (zk.y + zr.y));   /* (Z[k] - conj(Z[m-k])) / 2 */
+	const float2 t = cmul(o, w);
+	return make_float2(e.x + t.y, e.y - t.x);                                   /* E - i*W*O */
+}
+
+/* bins k and n-k of frame `fbase / n` (Hermitian completion), or their dB values at the shifted positions */
+__device__ __forceinline__ void put_real_bins(float2 *__restrict__ bins, float *__restrict__ db, size_t fbase,
+                                              unsigned int n, unsigned int k, float2 zk, float2 zr, float2 w, float scaledb)
+{
+	const unsigned int m = n >> 1;
+	if (k == 0) {
+		/* X[0] and X[m] are Re Z0 +/- Im Z0 */
+		const float2 x0 = make_float2(zk.x + zk.y, 0.0f), xm = make_float2(zk.x - zk.y, 0.0f);
+		if (bins) {
+			bins[fbase] = x0;
+			bins[fbase + m] = xm;
+		}
+		if (db) {
+			db[fbase + m] = to_db(x0, scaledb);
+			db[fbase] = to_db(xm, scaledb);
+		}
+		return;
+	}
+	const float2 v = untangle(zk, zr, w);
+	if (bins) {
+		bins[fbase + k] = v;
+		bins[fbase + n - k] = make_float2(v.x, -v.y);
+	}
+	if (db) {
+		const float d = to_db(v, scaledb);
+		db[fbase + m + k] = d;
+		db[fbase + m - k] = d;
+	}
+}
+
+/* a real frame of n <= 16384 samples whole in LDS (m = n/2 packed points); grid.x = frame, `hop` in floats */
+__global__ void __launch_bounds__(FFT_THREADS)
+k_fft_real_single(const float *__restrict__ in, size_t hop, unsigned int n,
+                  const float *__restrict__ window, const float2 *__restrict__ tw,
+                  float2 *__restrict__ bins, float *__restrict__ db, float scaledb)
+{
+	extern __shared__ float2 lds[];
+	const unsigned int m = n >> 1;
+	float2 *a = lds, *b = lds + m;
+	const size_t frame = blockIdx.x;
+	const float *x = in + frame * hop;
+	const bool aligned = ((size_t)x & 7u) == 0;
+	for (unsigned int i = threadIdx.x; i < m; i += FFT_THREADS)
+		a[i] = real_pair(x, aligned, window, i);
+	__syncthreads();
+	const float2 *r = lds_fft(a, b, m, 1, tw, 2, threadIdx.x);     /* (tw is the n-point table: every other entry) */
+	for (unsigned int k = threadIdx.x; k < m; k += FFT_THREADS)
+		put_real_bins(bins, db, frame * n, n, k, r[k], r[(m - k) & (m - 1)], tw[k], scaledb);
+}
+
+/* the untangle step behind pass 2 of a real frame's packed transform; grid = (m/256, frames) */
+__global__ void __launch_bounds__(FFT_THREADS)
+k_fft_untangle(const float2 *__restrict__ z, unsigned int n, const float2 *__restrict__ tw,
+               float2 *__restrict__ bins, float *__restrict__ db, float scaledb)
+{
+	const unsigned int m = n >> 1;
+	const unsigned int k = blockIdx.x * FFT_THREADS + threadIdx.x;
+	const size_t frame = blockIdx.y;
+	const float2 *zf = z + frame * m;
+	if (k < m)
+		put_real_bins(bins, db, frame * n, n, k, zf[k], zf[(m - k) & (m - 1)], tw[k], scaledb);
+}
+
+/* four-step pass 1; grid = (n2/ct, frames).  REAL: `iq` are floats, `hop` counts floats, the transform is the packed one
+ * of n1*n2 points and tw_n the table of TWICE that size */
+template <bool REAL>
 __global__ void __launch_bounds__(FFT_THREADS)
 k_fft_pass1(const float2 *__restrict__ iq, size_t hop, unsigned int n1, unsigned int n2,
             unsigned int ct, const float *__restrict__ window, const float2 *__restrict__ tw_sub,
@@ -105,14 +199,23 @@ k_fft_pass1(const float2 *__restrict__ iq, size_t hop, unsigned int n1, unsigned
 	float2 *a = lds, *b = lds + (size_t)n1 * ct;
 	const size_t frame = blockIdx.y;
 	const unsigned int col0 = blockIdx.x * ct;
-	const float2 *x = iq + frame * hop;
 	const unsigned int total = n1 * ct;
-	for (unsigned int e = threadIdx.x; e < total; e += FFT_THREADS) {
-		const unsigned int r = e / ct, c = e - r * ct;
-		const unsigned int idx = r * n2 + col0 + c;
-		const float2 v = x[idx];
-		const float w = window[idx];
-		a[e] = make_float2(v.x * w, v.y * w);
+	if (REAL) {
+		const float *x = (const float *)iq + frame * hop;
+		const bool aligned = ((size_t)x & 7u) == 0;
+		for (unsigned int e = threadIdx.x; e < total; e += FFT_THREADS) {
+			const unsigned int r = e / ct, c = e - r * ct;
+			a[e] = real_pair(x, aligned, window, r * n2 + col0 + c);
+		}
+	} else {
+		const float2 *x = iq + frame * hop;
+		for (unsigned int e = threadIdx.x; e < total; e += FFT_THREADS) {
+			const unsigned int r = e / ct, c = e - r * ct;
+			const unsigned int idx = r * n2 + col0 + c;
+			const float2 v = x[idx];
+			const float w = window[idx];
+			a[e] = make_float2(v.x * w, v.y * w);
+		}
 	}
 	__syncthreads();
 	const float2 *res = lds_fft(a, b, n1, ct, tw_sub, tw_sub_len / n1, threadIdx.x);
@@ -123,9 +226,9 @@ k_fft_pass1(const float2 *__restrict__ iq, size_t hop, unsigned int n1, unsigned
 		unsigned int m = col * k1;                      /* < n */
 		float2 w;
 		if (m < (n >> 1)) {
-			w = tw_n[m];
+			w = tw_n[REAL ? 2u * m : m];
 		} else {
-			const float2 t = tw_n[m - (n >> 1)];
+			const float2 t = tw_n[REAL ? 2u * (m - (n >> 1)) : m - (n >> 1)];
 			w = make_float2(-t.x, -t.y);
 		}
 		wout[(size_t)k1 * n2 + col] = cmul(res[e], w);
@@ -437,6 +540,65 @@ static int fft64k_p1_fpw(size_t batch)
 	return batch >= FFT64K_P1_LONG_MIN ? 4 : 1;
 }
 
+/* a real plan (P.channels == 1): P.n1 * P.n2 = P.n / 2, the packed transform's shape; `in` and `hop` in floats.  Of
+ * P.work's work_frames * n complex values the first half is the intermediate between the passes, the second the packed
+ * transform Z that the untangle step reads. */
+static hipError_t fft_frames_real(hipStream_t st, const WrFftPlan &P, const float *in, size_t hop, size_t nframes_fft,
+                                  float *bins_out, float *db_out, float scaledb)
+{
+	const unsigned int m = P.n >> 1;
+	hipError_t e;
+	if (P.n2 == 1) {
+		const size_t lds = (size_t)2 * m * sizeof(float2);
+		if (lds > 48 * 1024) {
+			e = hipFuncSetAttribute((const void *)k_fft_real_single, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+			if (e != hipSuccess)
+				return e;
+		}
+		k_fft_real_single<<<(unsigned int)nframes_fft, FFT_THREADS, lds, st>>>(
+			in, hop, P.n, P.window, (const float2 *)P.tw_n, (float2 *)bins_out, db_out, scaledb);
+		return hipGetLastError();
+	}
+	const unsigned int tw_sub_len = P.n1 > P.n2 ? P.n1 : P.n2;
+	unsigned int ct = 8192u / P.n1;
+	if (ct > 16)
+		ct = 16;
+	unsigned int rt = 8192u / P.n2;
+	if (rt > 16)
+		rt = 16;
+	const size_t lds1 = (size_t)2 * P.n1 * ct * sizeof(float2);
+	const size_t lds2 = (size_t)2 * P.n2 * rt * sizeof(float2);
+	e = hipFuncSetAttribute((const void *)k_fft_pass1<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
+	if (e != hipSuccess)
+		return e;
+	e = hipFuncSetAttribute((const void *)k_fft_pass2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+	if (e != hipSuccess)
+		return e;
+	float2 *zbuf = (float2 *)P.work + P.work_frames * m;
+	size_t done = 0;
+	while (done < nframes_fft) {
+		size_t batch = nframes_fft - done;
+		if (batch > P.work_frames)
+			batch = P.work_frames;
+		dim3 g1(P.n2 / ct, (unsigned int)batch);
+		k_fft_pass1<true><<<g1, FFT_THREADS, lds1, st>>>((const float2 *)(in + done * hop), hop, P.n1, P.n2, ct, P.window,
+		                                                 (const float2 *)P.tw_sub, tw_sub_len,
+		                                                 (const float2 *)P.tw_n, (float2 *)P.work);
+		dim3 g2(P.n1 / rt, (unsigned int)batch);
+		k_fft_pass2<<<g2, FFT_THREADS, lds2, st>>>((const float2 *)P.work, P.n1, P.n2, rt, (const float2 *)P.tw_sub,
+		                                           tw_sub_len, zbuf, (float *)nullptr, 0.0f);
+		dim3 g3(m / FFT_THREADS, (unsigned int)batch);
+		k_fft_untangle<<<g3, FFT_THREADS, 0, st>>>(zbuf, P.n, (const float2 *)P.tw_n,
+		                                           bins_out ? (float2 *)(bins_out + 2 * done * P.n) : (float2 *)nullptr,
+		                                           db_out ? db_out + done * P.n : (float *)nullptr, scaledb);
+		e = hipGetLastError();
+		if (e != hipSuccess)
+			return e;
+		done += batch;
+	}
+	return hipSuccess;
+}
+
 hipError_t wrk_fft_frames(hipStream_t st, const WrFftPlan &P, const float *iq, size_t hop,
                           size_t nframes_fft, float *bins_out, float *db_out)
 {
@@ -444,6 +606,8 @@ hipError_t wrk_fft_frames(hipStream_t st, const WrFftPlan &P, const float *iq, s
 		return hipSuccess;
 	const float scaledb = 20.0f * log10f((float)P.n);   /* spectrumsink.cxx:127 */
 	hipError_t e;
+	if (P.channels == 1)
+		return fft_frames_real(st, P, iq, hop, nframes_fft, bins_out, db_out, scaledb);
 	if (P.n2 == 1) {
 		const size_t lds = (size_t)2 * P.n * sizeof(float2);
 		if (lds > 48 * 1024) {
@@ -497,7 +661,7 @@ hipError_t wrk_fft_frames(hipStream_t st, const WrFftPlan &P, const float *iq, s
 		rt = 16;
 	const size_t lds1 = (size_t)2 * P.n1 * ct * sizeof(float2);
 	const size_t lds2 = (size_t)2 * P.n2 * rt * sizeof(float2);
-	e = hipFuncSetAttribute((const void *)k_fft_pass1, hipFuncAttributeMaxDynamicSharedMemorySize,
+	e = hipFuncSetAttribute((const void *)k_fft_pass1<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
 	                        (int)lds1);
 	if (e != hipSuccess)
 		return e;
@@ -512,9 +676,9 @@ hipError_t wrk_fft_frames(hipStream_t st, const WrFftPlan &P, const float *iq, s
 			batch = P.work_frames;
 		const float *src = iq + 2 * done * hop;
 		dim3 g1(P.n2 / ct, (unsigned int)batch);
-		k_fft_pass1<<<g1, FFT_THREADS, lds1, st>>>((const float2 *)src, hop, P.n1, P.n2, ct, P.window,
-		                                           (const float2 *)P.tw_sub, tw_sub_len,
-		                                           (const float2 *)P.tw_n, (float2 *)P.work);
+		k_fft_pass1<false><<<g1, FFT_THREADS, lds1, st>>>((const float2 *)src, hop, P.n1, P.n2, ct, P.window,
+		                                                  (const float2 *)P.tw_sub, tw_sub_len,
+		                                                  (const float2 *)P.tw_n, (float2 *)P.work);
 		dim3 g2(P.n1 / rt, (unsigned int)batch);
 		k_fft_pass2<<<g2, FFT_THREADS, lds2, st>>>(
 			(const float2 *)P.work, P.n1, P.n2, rt, (const float2 *)P.tw_sub, tw_sub_len,

@@ -310,14 +310,17 @@ hipError_t wrk_tuner_stream(hipStream_t st, const WrStreamArgs &A, void *ev_star
 /* ---- FFT (wr_fft.hip) ---- */
 struct WrFftPlan {
 	unsigned int n;             /* transform size */
-	unsigned int n1, n2;        /* n = n1*n2; n2 == 1 for single-pass */
+	unsigned int channels;      /* 2: IQ frames; 1: real samples, transformed as n/2 packed points and untangled */
+	unsigned int n1, n2;        /* n = n1*n2 (real: n/2 = n1*n2); n2 == 1 for single-pass */
 	float *tw_n;                /* [n/2][2] twiddles of the full size (device) */
 	float *tw_sub;              /* [max(n1,n2)/2][2] twiddles of the LDS sub-transforms (device) */
 	float *window;              /* [n] (device) */
 	float *window_p1;           /* 65536-point path: the window in the order pass 1's threads take it (wr_fft.hip), else NULL */
-	float *work;                /* [n][2] intermediate per frame in flight (device), batch-sized */
+	float *work;                /* [n][2] intermediate per frame in flight (device), batch-sized (real: half of it is the
+	                               intermediate, half the packed transform in front of the untangle step) */
 	size_t work_frames;
 };
+/* frame f starts `f * hop` frames (of P.channels floats) into `iq` */
 hipError_t wrk_fft_frames(hipStream_t st, const WrFftPlan &P, const float *iq, size_t hop,
                           size_t nframes_fft, float *bins_out /* or NULL */, float *db_out /* or NULL */);
 

@@ -16,10 +16,11 @@ static void plan_free(WrFftPlan &p)
 	memset(&p, 0, sizeof(p));
 }
 
-extern "C" int wr_spectrum_create(wr_spectrum **spec, wr_dev *dev, unsigned int fft_size, unsigned int hop)
+static int spectrum_create(wr_spectrum **spec, wr_dev *dev, unsigned int fft_size, unsigned int hop, unsigned int ch,
+                           const char *who)
 {
 	if (!spec || !dev)
-		return wrc_fail(WR_ERR_ARG, "wr_spectrum_create: bad argument");
+		return wrc_fail(WR_ERR_ARG, "%s: bad argument", who);
 	*spec = nullptr;
 	if (fft_size < 8 || fft_size > (1u << 20) || (fft_size & (fft_size - 1)))
 		return wrc_fail(WR_ERR_ARG, "size must be a power of 2 in [8, 1048576]");   /* spectrumsink.cxx:53-56 */
@@ -37,6 +38,7 @@ extern "C" int wr_spectrum_create(wr_spectrum **spec, wr_dev *dev, unsigned int 
 	s->dev = dev;
 	s->n = fft_size;
 	s->hop = hop;
+	s->ch = ch;
 	s->stage = nullptr;
 	s->stage_cap = 0;
 	s->pending = 0;
@@ -45,15 +47,18 @@ extern "C" int wr_spectrum_create(wr_spectrum **spec, wr_dev *dev, unsigned int 
 
 	WrFftPlan &p = s->plan;
 	p.n = fft_size;
-	if (fft_size <= 8192) {
-		p.n1 = fft_size;
+	p.channels = ch;
+	/* (real samples: the transform that runs is the packed one of fft_size / 2 points, wr_fft.hip) */
+	const unsigned int points = ch == 1 ? fft_size / 2 : fft_size;
+	if (points <= 8192) {
+		p.n1 = points;
 		p.n2 = 1;
 	} else {
 		unsigned int bits = 0;
-		while ((1u << bits) < fft_size)
+		while ((1u << bits) < points)
 			bits++;
 		p.n1 = 1u << ((bits + 1) / 2);
-		p.n2 = fft_size / p.n1;
+		p.n2 = points / p.n1;
 	}
 	const unsigned int sub = (p.n2 == 1) ? 0 : (p.n1 > p.n2 ? p.n1 : p.n2);
 	std::vector<float> tw(fft_size), win(fft_size), tws(sub ? sub : 2);
@@ -87,11 +92,30 @@ extern "C" int wr_spectrum_create(wr_spectrum **spec, wr_dev *dev, unsigned int 
 		if (sub && (e = hipMemcpy(p.tw_sub, tws.data(), sub * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
 	} while (0);
 	if (e != hipSuccess) {
-		int rc = wrc_fail(WR_ERR_HIP, "wr_spectrum_create: %s", hipGetErrorString(e));
+		int rc = wrc_fail(WR_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
 		wr_spectrum_destroy(s);
 		return rc;
 	}
 	*spec = s;
+	return WR_OK;
+}
+
+extern "C" int wr_spectrum_create(wr_spectrum **spec, wr_dev *dev, unsigned int fft_size, unsigned int hop)
+{
+	return spectrum_create(spec, dev, fft_size, hop, 2, "wr_spectrum_create");
+}
+
+/* the reference's FIXMEs at io/spectrumsink.cxx:62-64: one channel, the real-to-complex plan */
+extern "C" int wr_spectrum_create_real(wr_spectrum **spec, wr_dev *dev, unsigned int fft_size, unsigned int hop)
+{
+	return spectrum_create(spec, dev, fft_size, hop, 1, "wr_spectrum_create_real");
+}
+
+extern "C" int wr_spectrum_channels(wr_spectrum *s, unsigned int *channels)
+{
+	if (!s || !channels)
+		return wrc_fail(WR_ERR_ARG, "wr_spectrum_channels: bad argument");
+	*channels = s->ch;
 	return WR_OK;
 }
 
@@ -120,9 +144,9 @@ static int spectrum_stage_room(wr_spectrum *s, size_t frames, bool carry)
 		return WR_OK;
 	float *nb = nullptr;
 	const size_t cap = frames + s->n;
-	HIP_TRY(hipMalloc((void **)&nb, cap * 2 * sizeof(float)));
+	HIP_TRY(hipMalloc((void **)&nb, cap * s->ch * sizeof(float)));
 	if (carry && s->pending)
-		HIP_TRY(hipMemcpyAsync(nb, s->stage, s->pending * 2 * sizeof(float), hipMemcpyDeviceToDevice, s->dev->stream));
+		HIP_TRY(hipMemcpyAsync(nb, s->stage, s->pending * s->ch * sizeof(float), hipMemcpyDeviceToDevice, s->dev->stream));
 	HIP_TRY(wrc_dev_stream_sync(s->dev));                   /* (whatever still reads the old stage) */
 	if (s->stage)
 		HIP_TRY(hipFree(s->stage));
@@ -136,16 +160,17 @@ static int spectrum_compact(wr_spectrum *s, size_t from, size_t rest)
 {
 	wr_dev *d = s->dev;
 	hipStream_t st = d->stream;
+	const size_t ch = s->ch;
 	if (!rest)
 		return WR_OK;
 	if (rest <= from) {
-		HIP_TRY(hipMemcpyAsync(s->stage, s->stage + 2 * from, rest * 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+		HIP_TRY(hipMemcpyAsync(s->stage, s->stage + ch * from, rest * ch * sizeof(float), hipMemcpyDeviceToDevice, st));
 	} else {
 		SCRATCH_GUARD(d);
-		if (int rc = wrc_dev_scratch(d, rest * 2))
+		if (int rc = wrc_dev_scratch(d, rest * ch))
 			return rc;
-		HIP_TRY(hipMemcpyAsync(d->scratch, s->stage + 2 * from, rest * 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
-		HIP_TRY(hipMemcpyAsync(s->stage, d->scratch, rest * 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d->scratch, s->stage + ch * from, rest * ch * sizeof(float), hipMemcpyDeviceToDevice, st));
+		HIP_TRY(hipMemcpyAsync(s->stage, d->scratch, rest * ch * sizeof(float), hipMemcpyDeviceToDevice, st));
 	}
 	return WR_OK;
 }
@@ -255,7 +280,8 @@ extern "C" int wr_spectrum_push(wr_spectrum *s, const float *iq, size_t nframes,
 		return WR_ERR_HIP;
 	const bool inside = where == WR_DEVICE && s->pending + nframes >= s->n &&
 	                    ((s->pending + nframes - s->n) / s->hop) * s->hop >= s->pending;   /* the newest frame starts inside this block */
-	if (inside && d->streaming) {
+	if (inside && d->streaming && s->ch == 2) {
+		/* (IQ only: spectrum_defer's DMA thresholds are sized for tuner blocks; a real spectrum closes the launch) */
 		bool kept = false;
 		const int rc = spectrum_defer(s, iq, nframes, &kept);
 		if (rc || kept)
@@ -271,6 +297,7 @@ extern "C" int wr_spectrum_push(wr_spectrum *s, const float *iq, size_t nframes,
 	}
 	DEV_SETTLE(d);
 	hipStream_t st = d->stream;
+	const size_t ch = s->ch;                                /* floats per frame */
 	if (inside) {
 		/* A block that already lies in device memory and whose most recent complete frame starts INSIDE it (any block of
 		 * fftSize + hop frames or more; whatever was carried over belongs to frames nobody can observe,
@@ -280,12 +307,12 @@ extern "C" int wr_spectrum_push(wr_spectrum *s, const float *iq, size_t nframes,
 		 * block's tail only (r04: the host runtime's stagedTail). */
 		size_t nfft, first, rest;
 		spectrum_newest(s, nframes, &nfft, &first, &rest);
-		HIP_TRY(wrk_fft_frames(st, s->plan, iq + 2 * first, s->hop, 1, s->bins, nullptr));
+		HIP_TRY(wrk_fft_frames(st, s->plan, iq + ch * first, s->hop, 1, s->bins, nullptr));
 		s->frames_done += nfft;
 		if (rest) {
 			if (int rc = spectrum_stage_room(s, rest, false))
 				return rc;
-			HIP_TRY(hipMemcpyAsync(s->stage, iq + 2 * (first + s->hop), rest * 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+			HIP_TRY(hipMemcpyAsync(s->stage, iq + ch * (first + s->hop), rest * ch * sizeof(float), hipMemcpyDeviceToDevice, st));
 		}
 		s->pending = rest;
 		return WR_OK;
@@ -294,7 +321,7 @@ extern "C" int wr_spectrum_push(wr_spectrum *s, const float *iq, size_t nframes,
 	if (int rc = spectrum_stage_room(s, have, true))
 		return rc;
 	if (nframes)
-		HIP_TRY(hipMemcpyAsync(s->stage + 2 * s->pending, iq, nframes * 2 * sizeof(float),
+		HIP_TRY(hipMemcpyAsync(s->stage + ch * s->pending, iq, nframes * ch * sizeof(float),
 		                       where == WR_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
 	/* frames start every `hop`; the reference transforms each one but only the most
 	 * recent is observable through getSpectrum (spectrumsink.cxx:114-116,136-141) */
@@ -302,7 +329,7 @@ extern "C" int wr_spectrum_push(wr_spectrum *s, const float *iq, size_t nframes,
 	if (have >= s->n)
 		nfft = (have - s->n) / s->hop + 1;
 	if (nfft) {
-		const float *last = s->stage + 2 * (nfft - 1) * s->hop;
+		const float *last = s->stage + ch * (nfft - 1) * s->hop;
 		HIP_TRY(wrk_fft_frames(st, s->plan, last, s->hop, 1, s->bins, nullptr));
 		s->frames_done += nfft;
 		const size_t consumed = nfft * s->hop;
@@ -402,10 +429,9 @@ extern "C" int wr_spectrum_frames_done(wr_spectrum *s, unsigned long *frames)
 	return WR_OK;
 }
 
-extern "C" int wr_spectrum_batch_db(wr_spectrum *s, const float *iq_dev, size_t nframes_fft, float *db_dev)
+/* `nframes_fft` frames lying `stride` frames apart to dB rows (wr_spectrum_batch_db: the hop; _rows: the row stride) */
+static int spectrum_batch(wr_spectrum *s, const float *iq_dev, size_t stride, size_t nframes_fft, float *db_dev)
 {
-	if (!s || (nframes_fft && (!iq_dev || !db_dev)))
-		return wrc_fail(WR_ERR_ARG, "wr_spectrum_batch_db: bad argument");
 	if (wrc_dev_bind(s->dev))
 		return WR_ERR_HIP;
 	DEV_SETTLE(s->dev);
@@ -429,6 +455,22 @@ extern "C" int wr_spectrum_batch_db(wr_spectrum *s, const float *iq_dev, size_t 
 			p.work_frames = want;
 		}
 	}
-	HIP_TRY(wrk_fft_frames(s->dev->stream, s->plan, iq_dev, s->hop, nframes_fft, nullptr, db_dev));
+	HIP_TRY(wrk_fft_frames(s->dev->stream, s->plan, iq_dev, stride, nframes_fft, nullptr, db_dev));
 	return WR_OK;
+}
+
+extern "C" int wr_spectrum_batch_db(wr_spectrum *s, const float *iq_dev, size_t nframes_fft, float *db_dev)
+{
+	if (!s || (nframes_fft && (!iq_dev || !db_dev)))
+		return wrc_fail(WR_ERR_ARG, "wr_spectrum_batch_db: bad argument");
+	return spectrum_batch(s, iq_dev, s->hop, nframes_fft, db_dev);
+}
+
+extern "C" int wr_spectrum_batch_db_rows(wr_spectrum *s, const float *in_dev, size_t row_stride, size_t nrows, float *db_dev)
+{
+	if (!s || (nrows && (!in_dev || !db_dev)))
+		return wrc_fail(WR_ERR_ARG, "wr_spectrum_batch_db_rows: bad argument");
+	if (row_stride < s->n)
+		return wrc_fail(WR_ERR_ARG, "wr_spectrum_batch_db_rows: row_stride must not be less than fft_size");
+	return spectrum_batch(s, in_dev, row_stride, nrows, db_dev);
 }

@@ -288,14 +288,17 @@ class Tuner:
 
 
 class Spectrum:
-    """wr_spectrum: SpectrumSink (io/spectrumsink.h:44-68)."""
+    """wr_spectrum: SpectrumSink (io/spectrumsink.h:44-68).  real=True: one float per frame (a receiver's audio),
+    wr_spectrum_create_real -- pushes and batches then count samples."""
 
-    def __init__(self, dev, fft_size, hop=0):
+    def __init__(self, dev, fft_size, hop=0, real=False):
         self.dev = dev
         self.lib = dev.lib
         self.n = fft_size
+        self.ch = 1 if real else 2
         h = C.c_void_p()
-        check(self.lib.wr_spectrum_create(C.byref(h), dev.h, fft_size, hop))
+        create = self.lib.wr_spectrum_create_real if real else self.lib.wr_spectrum_create
+        check(create(C.byref(h), dev.h, fft_size, hop))
         self.h = h
 
     def destroy(self):
@@ -305,7 +308,7 @@ class Spectrum:
 
     def push_host(self, iq):
         iq = np.ascontiguousarray(iq, dtype=np.float32)
-        check(self.lib.wr_spectrum_push(self.h, ptr(iq), iq.size // 2, capi.WR_HOST))
+        check(self.lib.wr_spectrum_push(self.h, ptr(iq), iq.size // self.ch, capi.WR_HOST))
 
     def push_device(self, dev_ptr, nframes):
         check(self.lib.wr_spectrum_push(self.h, ptr(dev_ptr), nframes, capi.WR_DEVICE))
@@ -339,6 +342,15 @@ class Spectrum:
 
     def batch_db(self, iq_dev, nframes_fft, db_dev):
         check(self.lib.wr_spectrum_batch_db(self.h, ptr(iq_dev), nframes_fft, ptr(db_dev)))
+
+    def batch_db_rows(self, in_dev, row_stride, nrows, db_dev):
+        """dB rows of the first fft_size frames of `nrows` rows lying `row_stride` frames apart in device memory"""
+        check(self.lib.wr_spectrum_batch_db_rows(self.h, ptr(in_dev), row_stride, nrows, ptr(db_dev)))
+
+    def channels(self):
+        c = C.c_uint()
+        check(self.lib.wr_spectrum_channels(self.h, C.byref(c)))
+        return c.value
 
 
 class Ring:

@@ -43,6 +43,20 @@ bool SpectrumSink::init()
 	if (!dev)
 		return false;
 	_dev = dev;
+	/* upstream's FIXMEs (spectrumsink.cxx:62-64): check the number of channels, select the appropriate plan */
+	if (inputChannels() == 1) {
+		/* real samples: a Demodulator's output, a receiver's audio filter */
+		if (wr_spectrum_create_real(&_spec, dev, _fftSize, _hop) != WR_OK) {
+			LOG_ERROR("SpectrumSink: %s\n", wr_last_error());
+			_spec = NULL;
+			return false;
+		}
+		return true;
+	}
+	if (inputChannels() != 2) {
+		LOG_ERROR("SpectrumSink: %u channels (1 = real samples or 2 = IQ expected)\n", inputChannels());
+		return false;
+	}
 	if (wr_spectrum_create(&_spec, dev, _fftSize, _hop) != WR_OK) {
 		LOG_ERROR("SpectrumSink: %s\n", wr_last_error());
 		_spec = NULL;
@@ -61,10 +75,18 @@ void SpectrumSink::deinit()
 
 bool SpectrumSink::process(const vector<sample_t> &inBuffer, vector<sample_t> &outBuffer)
 {
-	/* like upstream this assumes IQ input (spectrumsink.cxx:93) */
 	std::lock_guard<std::mutex> g(_lock);
 	if (!_spec)
 		return false;
+	if (inputChannels() == 1) {
+		/* not fed by the tuner: no staged block, no staged tail -- the host vector, inBuffer.size() / inputChannels() frames */
+		if (wr_spectrum_push(_spec, inBuffer.data(), inBuffer.size(), WR_HOST) != WR_OK) {
+			LOG_ERROR("SpectrumSink: %s\n", wr_last_error());
+			return false;
+		}
+		return true;
+	}
+	/* two channels: IQ, as upstream assumes (spectrumsink.cxx:93) */
 	/* the receivers of the same tuner go first on the device's stream: their audio is what run() waits for */
 	wrhost::submitBatchFirst(this, inBuffer);
 	/* fed straight from the tuner: use the device copy every GPU consumer of it shares */

@@ -1,6 +1,8 @@
 /*
  * spectrumsink.h -- windowed-FFT spectrum sink.  Public surface of webradio's
  * src/io/spectrumsink.h:44-53 (fftSize/setFftSize/getSpectrum, default size 512).
+ * Two input channels: IQ, as upstream.  One: real samples (a Demodulator, a receiver's audio filter) -- upstream's
+ * FIXMEs at src/io/spectrumsink.cxx:62-64; getSpectrum() then gives the row the IQ sink would give for (x, 0).
  */
 #ifndef SPECTRUMSINK_H_
 #define SPECTRUMSINK_H_
