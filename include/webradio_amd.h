@@ -50,6 +50,7 @@ extern "C" {
                                     takes 2 (byte blocks out of page-locked host memory stream too), wr_tuner_last_staging may say 3;
                                     wr_spectrum_push beside an open streaming launch keeps the frame and transforms it on demand.
                                     Added to 6 later: wr_spectrum_create_real, wr_spectrum_channels, wr_spectrum_batch_db_rows.
+                                    Added to 6 later: wr_tuner_chan_spectra.
                                     Nothing of an earlier version changed or removed */
 #define WR_FIR_LENGTH    64      /* dsp/lowpass.cxx:39  FIR_LENGTH */
 #define WR_TABLE_SIZE    65536   /* dsp/downconverter.cxx:35 LOOKUP_BITS 16 */
@@ -556,6 +557,18 @@ int wr_spectrum_batch_db(wr_spectrum *spec, const float *iq_dev, size_t nframes_
 int wr_spectrum_batch_db_rows(wr_spectrum *spec, const float *in_dev, size_t row_stride, size_t nrows,
                               float *db_dev);
 
+/* The CHANNEL spectrum of every receiver of a tuner (a SpectrumSink connected to each Receiver's channel filter,
+ * io/spectrumsink.cxx:88-142 behind radio.cxx:68-76): for each channel slot the dB row (fft-shifted, wr_spectrum_get_db's
+ * expression) of channel-rate frames [first_frame, first_frame + fft_size) of WR_STAGE_CHAN_IQ of the last submit, in one
+ * launch.  Row of slot s (wr_chan_slot) at db_dev + s * fft_size; *slots (optional) = rows written (the group's slots in
+ * use, in whole lane groups of 64 as wr_tuner_fetch_audio_all counts them: at most max_channels rounded up to 64, and
+ * db_dev needs room for that many rows; rows of slots that hold no channel carry no meaning).
+ * `spec`: an IQ spectrum (wr_spectrum_create) of the tuner's wr_dev with fft_size <= 8192; its window and twiddle tables
+ * are used, its own frames (wr_spectrum_push, frames_done, bins) are left alone.  Like every getter it sends held blocks
+ * out, launches a pending post stage and closes an open streaming launch.  Async on the device's stream.
+ * WR_ERR_ARG: NULL arguments, a real spectrum, fft_size > 8192, first_frame + fft_size beyond the last submit's channel
+ * frames, a spectrum of another wr_dev.  WR_ERR_STATE: nothing submitted yet, several rate groups. */
+int wr_tuner_chan_spectra(wr_tuner *tuner, wr_spectrum *spec, size_t first_frame, float *db_dev, unsigned int *slots);
 #ifdef __cplusplus
 }
 #endif

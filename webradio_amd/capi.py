@@ -122,6 +122,7 @@ SIGNATURES = {
     "wr_spectrum_create_real": (C.c_int, [C.POINTER(_vp), _vp, _u32, _u32]),
     "wr_spectrum_channels": (C.c_int, [_vp, C.POINTER(_u32)]),
     "wr_spectrum_batch_db_rows": (C.c_int, [_vp, _vp, _sz, _sz, _vp]),
+    "wr_tuner_chan_spectra": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(C.c_uint)]),
 }
 
 

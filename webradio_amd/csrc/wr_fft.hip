@@ -100,6 +100,37 @@ k_fft_single(const float2 *__restrict__ iq, size_t hop, unsigned int n,
 	}
 }
 
+/* CT adjacent columns of a [rows][S] array of IQ frames (a tuner's channel IQ: one lane per channel slot), rows
+ * `first` ... `first + n - 1`: one n-point frame per column, all of them in LDS side by side as lds_fft wants them,
+ * a[i*CT + c].  grid.x = cols / ct: the first `cols` columns (the launcher's ct divides 64, cols is whole lane groups).  Load: adjacent lanes read
+ * adjacent slots of one row, ct * 8 bytes contiguous.  Store: the bin index runs fastest, so a wave writes runs of ONE
+ * dB row (whole 256-byte runs from n = 64 on) and reads LDS with a stride of ct points: the global stores are what is
+ * kept coalesced, the LDS reads take the bank conflicts (none at ct = 1). */
+__global__ void __launch_bounds__(FFT_THREADS)
+k_fft_cols(const float2 *__restrict__ iq, unsigned int S, unsigned int cols, size_t first, unsigned int n, unsigned int ct,
+           const float *__restrict__ window, const float2 *__restrict__ tw, float *__restrict__ db, float scaledb)
+{
+	extern __shared__ float2 lds[];
+	const unsigned int total = n * ct;
+	float2 *a = lds, *b = lds + total;
+	const unsigned int slot0 = blockIdx.x * ct;
+	const unsigned int lgct = 31u - (unsigned int)__builtin_clz(ct), lgn = 31u - (unsigned int)__builtin_clz(n);
+	const float2 *x = iq + first * S;
+	for (unsigned int e = threadIdx.x; e < total; e += FFT_THREADS) {
+		const unsigned int i = e >> lgct, slot = slot0 + (e & (ct - 1u));
+		const float2 v = slot < cols ? x[(size_t)i * S + slot] : make_float2(0.0f, 0.0f);
+		const float w = window[i];
+		a[e] = make_float2(v.x * w, v.y * w);               /* spectrumsink.cxx:109-112 */
+	}
+	__syncthreads();
+	const float2 *r = lds_fft(a, b, n, ct, tw, 1, threadIdx.x);
+	for (unsigned int e = threadIdx.x; e < total; e += FFT_THREADS) {
+		const unsigned int c = e >> lgn, k = e & (n - 1u), slot = slot0 + c;
+		if (slot < cols)
+			db[(size_t)slot * n + ((k + (n >> 1)) & (n - 1u))] = to_db(r[k * ct + c], scaledb);
+	}
+}
+
 /* a packed point of a real frame: samples 2i and 2i+1, windowed.  A frame starts at any float offset (any hop, pushes of
  * any length), so the pair is one 8-byte load only where the frame happens to be 8-byte aligned. */
 __device__ __forceinline__ float2 real_pair(const float *__restrict__ x, bool aligned, const float *__restrict__ window,
@@ -690,4 +721,39 @@ hipError_t wrk_fft_frames(hipStream_t st, const WrFftPlan &P, const float *iq, s
 		done += batch;
 	}
 	return hipSuccess;
+}
+
+/* columns per workgroup of k_fft_cols.  Workgroups first: measured at 256 columns (profiles/chan_spectra.txt), one column
+ * per workgroup -- 256 workgroups, 8-byte loads a row apart -- takes 5.2 us at n = 512 where 8 columns in 32 workgroups, 64-byte
+ * runs per row, take 17.4.  So columns are put side by side only where there are more of them than compute units, and
+ * then within what the LDS holds: both buffers within 128 KiB (n * ct <= 8192 points, k_fft_single's budget at 8192), at
+ * most 8 (64-byte runs).  A power of two: it divides 64. */
+static unsigned int fft_cols_ct(unsigned int n, unsigned int cols, int num_cus)
+{
+	unsigned int most = 8192u / n;
+	if (most > 8u)
+		most = 8u;
+	if (num_cus > 0 && most > cols / (unsigned int)num_cus)
+		most = cols / (unsigned int)num_cus;
+	unsigned int ct = 1;
+	while (2u * ct <= most)
+		ct *= 2u;
+	return ct;
+}
+
+hipError_t wrk_fft_cols(hipStream_t st, const WrFftPlan &P, const float *iq, unsigned int S, unsigned int cols, size_t first,
+                        float *db, int num_cus)
+{
+	if (P.channels != 2 || P.n2 != 1 || P.n < 8 || P.n > 8192 || !cols || cols % 64u || cols > S)
+		return hipErrorInvalidValue;
+	const unsigned int ct = fft_cols_ct(P.n, cols, num_cus);
+	const size_t lds = (size_t)2 * P.n * ct * sizeof(float2);
+	if (lds > 48 * 1024) {
+		hipError_t e = hipFuncSetAttribute((const void *)k_fft_cols, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		if (e != hipSuccess)
+			return e;
+	}
+	k_fft_cols<<<cols / ct, FFT_THREADS, lds, st>>>((const float2 *)iq, S, cols, first, P.n, ct, P.window, (const float2 *)P.tw_n, db,
+	                                             20.0f * log10f((float)P.n));
+	return hipGetLastError();
 }

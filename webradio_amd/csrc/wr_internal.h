@@ -324,6 +324,11 @@ struct WrFftPlan {
 hipError_t wrk_fft_frames(hipStream_t st, const WrFftPlan &P, const float *iq, size_t hop,
                           size_t nframes_fft, float *bins_out /* or NULL */, float *db_out /* or NULL */);
 
+/* the dB row (shifted) of rows [first, first + P.n) of the first `cols` columns of iq[rows][S][2], row of column s at
+ * db + s * P.n: IQ plans of at most 8192 points, cols <= S a multiple of 64 */
+hipError_t wrk_fft_cols(hipStream_t st, const WrFftPlan &P, const float *iq, unsigned int S, unsigned int cols, size_t first,
+                        float *db, int num_cus /* of the device: columns share a workgroup only beyond that many */);
+
 hipError_t wrk_bins_to_db(hipStream_t st, const float *bins, unsigned int n, float *db);
 hipError_t wrk_waterfall_row(hipStream_t st, const float *bins, unsigned int n, unsigned int width, int hold,
                              float *db_row, uint8_t *palette);

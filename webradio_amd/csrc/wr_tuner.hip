@@ -1526,6 +1526,44 @@ extern "C" int wr_tuner_audio_dev(wr_tuner *t, const float **audio_dev, size_t *
 	return WR_OK;
 }
 
+/* every receiver's CHANNEL spectrum out of the buffer wr_chan_fetch(WR_STAGE_CHAN_IQ) gathers one column of: the columns
+ * are transformed where they lie (k_fft_cols), one launch for the whole group */
+extern "C" int wr_tuner_chan_spectra(wr_tuner *t, wr_spectrum *spec, size_t first_frame, float *db_dev, unsigned int *slots)
+{
+	if (!t || !spec || !db_dev)
+		return wrc_fail(WR_ERR_ARG, "wr_tuner_chan_spectra: bad argument (NULL tuner, spectrum or db_dev)");
+	if (spec->ch != 2)
+		return wrc_fail(WR_ERR_ARG, "wr_tuner_chan_spectra: channel IQ needs an IQ spectrum, this one takes real samples");
+	if (spec->n > 8192)
+		return wrc_fail(WR_ERR_ARG, "wr_tuner_chan_spectra: fft_size %u is above 8192", spec->n);
+	if (spec->dev != t->dev)
+		return wrc_fail(WR_ERR_ARG, "wr_tuner_chan_spectra: the spectrum belongs to another device than the tuner");
+	if (int rc = wrc_settle_held(t))
+		return rc;
+	bool several = false;
+	Group *g = wrc_single_group(t, &several);
+	if (several)
+		return wrc_fail(WR_ERR_STATE, "tuner has several rate groups; fetch per channel instead");
+	if (!g || !t->submitted)
+		return wrc_fail(WR_ERR_STATE, "wr_tuner_chan_spectra: nothing submitted yet");
+	if (first_frame > g->last_k1 || spec->n > g->last_k1 - first_frame)
+		return wrc_fail(WR_ERR_ARG, "wr_tuner_chan_spectra: frames [%zu, %zu) reach beyond the last submit's %zu channel frames",
+		                first_frame, first_frame + spec->n, g->last_k1);
+	wr_dev *d = t->dev;
+	if (wrc_dev_bind(d))
+		return WR_ERR_HIP;
+	if (int rc = wrc_tuner_flush(t))
+		return rc;
+	const float *iq = t->stream.last_iq ? t->stream.last_iq : g->d1b ? g->dev.chan_iq2[g->last_cb] : g->dev.chan_iq[g->last_cb];
+	/* (the lane groups in use, as wr_tuner_fetch_audio_all counts them; the array's row stride is all of the group's slots) */
+	const unsigned int used = wrc_group_slots_used(g);
+	if (used)
+		HIP_TRY(wrk_fft_cols(d->stream, spec->plan, iq, g->slots, used, first_frame, db_dev, d->num_cus));
+	if (slots)
+		*slots = used;
+	return WR_OK;
+}
+
 extern "C" int wr_tuner_fetch_audio_all(wr_tuner *t, float *out_host, size_t out_capacity,
                                         size_t *chan_stride, size_t *frames, unsigned int *slots_used)
 {

@@ -100,6 +100,7 @@ class Tuner:
         check(self.lib.wr_tuner_create(C.byref(h), dev.h, input_rate, max_channels, max_block_frames, nco))
         self.h = h
         self.input_rate = input_rate
+        self.max_channels = max_channels
 
     def destroy(self):
         if self.h:
@@ -285,6 +286,24 @@ class Tuner:
         frames = C.c_size_t()
         check(self.lib.wr_tuner_audio_dev(self.h, C.byref(a), C.byref(stride), C.byref(frames)))
         return a.value, stride.value, frames.value
+
+    def chan_spectra(self, spec, first_frame=0, db_dev=None):
+        """Every receiver's CHANNEL spectrum in one launch (wr_tuner_chan_spectra): the dB row of channel-rate frames
+        [first_frame, first_frame + spec.n) of the last submit, row of slot s at s * spec.n.  With db_dev (room for
+        max_channels rounded up to 64 rows) the call is asynchronous and returns the rows written; without, it returns
+        them as an array [slots][spec.n]."""
+        slots = C.c_uint()
+        if db_dev is not None:
+            check(self.lib.wr_tuner_chan_spectra(self.h, spec.h, first_frame, ptr(db_dev), C.byref(slots)))
+            return slots.value
+        rows = (self.max_channels + 63) // 64 * 64
+        p = self.dev.malloc(rows * spec.n * 4)
+        try:
+            check(self.lib.wr_tuner_chan_spectra(self.h, spec.h, first_frame, C.c_void_p(p), C.byref(slots)))
+            out = self.dev.download(p, slots.value * spec.n)
+        finally:
+            self.dev.free(p)
+        return out.reshape(slots.value, spec.n)
 
 
 class Spectrum:

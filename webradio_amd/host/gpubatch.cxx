@@ -17,6 +17,8 @@
 #include "downconverter.h"
 #include "filetuner.h"
 #include "lowpass.h"
+#include "spectrumframing.h"
+#include "spectrumsink.h"
 
 namespace wrhost {
 
@@ -489,6 +491,13 @@ bool streamInfo(const DspBlock *block, bool *live, unsigned long long *launches,
 	return batch && batch->streamInfo(live, launches, blocks);
 }
 
+unsigned long long chanSpectraCalls(const DspBlock *block)
+{
+	DspSource *src = TunerBatch::rootSource(block);
+	TunerBatch *batch = src ? src->batch() : NULL;
+	return batch ? batch->chanSpectraCalls() : 0;
+}
+
 bool hostBlockValid(const DspBlock *block)
 {
 	DspSource *src = TunerBatch::rootSource(block);
@@ -538,7 +547,7 @@ TunerBatch::TunerBatch(DspSource *source, wr_dev *dev)
 	  _submitOk(false), _audioPtr(NULL), _ringHeld(false), _audioStride(0), _audioFrames(0), _audioSlots(0),
 	  _late(envUnsigned("WEBRADIO_AUDIO_LATE", 0) != 0), _lateDepth(envUnsigned("WEBRADIO_AUDIO_LATE", 0) >= 2 ? 2u : 1u),
 	  _lateQueued(false), _silence(false), _lateSeq(0), _pieces(envUnsigned("WEBRADIO_PIECES", 2)), _delivered(false), _partSeq0(0),
-	  _streaming(false)
+	  _streaming(false), _tapSeq(0), _tapCalls(0)
 {
 	if (_pieces < 1 || _late)
 		_pieces = 1;
@@ -594,14 +603,28 @@ Channel *TunerBatch::enrol(DownConverter *mixer)
 	if (!src || mixer->_consumers.size() != 1)
 		return NULL;
 	LowPass *f1 = dynamic_cast<LowPass *>(mixer->_consumers[0]);
-	if (!f1 || f1->_consumers.size() != 1)
+	if (!f1 || f1->_consumers.empty())
 		return NULL;
 	/* optionally a second LowPass before the demodulator: how the reference's own means cut a narrow
 	 * channel out of a fast stream (one 64-tap stage gives bin 0 below fs/128, lowpass.cxx:167) */
-	LowPass *f1b = dynamic_cast<LowPass *>(f1->_consumers[0]);
-	if (f1b && f1b->_consumers.size() != 1)
-		return NULL;
-	Demodulator *dm = dynamic_cast<Demodulator *>(f1b ? f1b->_consumers[0] : f1->_consumers[0]);
+	LowPass *f1b = f1->_consumers.size() == 1 ? dynamic_cast<LowPass *>(f1->_consumers[0]) : NULL;
+	/* the LAST channel stage feeds the demodulator and, beside it, any number of SpectrumSinks (a panadapter per listener:
+	 * the channel spectrum).  Those get no samples: they are served out of the channel IQ the tuner keeps (chanSpectrum) */
+	const LowPass *last = f1b ? f1b : f1;
+	Demodulator *dm = NULL;
+	std::vector<const SpectrumSink *> taps;
+	for (size_t n = 0; n < last->_consumers.size(); n++) {
+		DspBlock *c = last->_consumers[n];
+		if (Demodulator *d = dynamic_cast<Demodulator *>(c)) {
+			if (dm)
+				return NULL;
+			dm = d;
+		} else if (const SpectrumSink *sink = dynamic_cast<const SpectrumSink *>(c)) {
+			taps.push_back(sink);
+		} else {
+			return NULL;
+		}
+	}
 	if (!dm || dm->_consumers.size() != 1)
 		return NULL;
 	LowPass *f2 = dynamic_cast<LowPass *>(dm->_consumers[0]);
@@ -623,6 +646,10 @@ Channel *TunerBatch::enrol(DownConverter *mixer)
 		batch = new TunerBatch(src, dev);
 		src->setBatch(batch);
 	}
+
+	for (size_t n = 0; n < taps.size(); n++)
+		if (!batch->sinkQualifies(taps[n], f1, f1b))
+			return NULL;                         /* block by block, the sink fed samples: the reference's dataflow */
 
 	std::lock_guard<std::mutex> g(batch->_lock);
 	{
@@ -673,6 +700,8 @@ Channel *TunerBatch::enrol(DownConverter *mixer)
 			batch->_streaming = false;
 		batch->_lateQueued = false;
 		batch->_lateSeq = 0;
+		batch->_tapRows.clear();
+		batch->_tapSeq = 0;
 	}
 	int id = -1;
 	if (wr_chan_add(batch->_tuner, &id) != WR_OK) {
@@ -684,6 +713,7 @@ Channel *TunerBatch::enrol(DownConverter *mixer)
 	ch->id = id;
 	ch->slot = -1;
 	ch->lateSeq = ~0ull;
+	ch->tapTotal = ch->tapLast = 0;
 	ch->mixer = mixer;
 	ch->chanFilter = f1;
 	ch->chanFilter2 = f1b;
@@ -706,6 +736,120 @@ Channel *TunerBatch::enrol(DownConverter *mixer)
 	f1->elideOutput(true);
 	dm->elideOutput(true);
 	return ch;
+}
+
+/* the decimation a LowPass that has not been started yet will have off `rate` (LowPass::init, DspBlock::start) */
+static unsigned int decimationOff(unsigned int rate, unsigned int reqOutputRate, unsigned int reqDecimation, unsigned int *outRate)
+{
+	const unsigned int out = reqOutputRate ? reqOutputRate : (reqDecimation ? rate / reqDecimation : 0);
+	*outRate = out;
+	return out && out <= rate ? rate / out : 0;
+}
+
+/* May a SpectrumSink on the chain's last channel filter stay there while the chain is fused?  It is served the reference's
+ * most recent complete frame out of the LAST submit's channel IQ: at most 8192 points (wr_tuner_chan_spectra), and the
+ * smallest submit the batch makes for a source block -- the block, or one of WEBRADIO_PIECES parts of it -- holds
+ * fftSize + hop channel-rate frames, so that the frame always lies inside it (spectrumframing.h). */
+bool TunerBatch::sinkQualifies(const SpectrumSink *sink, const LowPass *f1, const LowPass *f1b) const
+{
+	const unsigned int n = sink->fftSize(), hop = sink->hop() ? sink->hop() : n;
+	if (n < 8 || n > 8192 || hop > n)
+		return false;
+	unsigned int rate1 = 0, rate2 = 0;
+	unsigned long d = decimationOff(_source->outputSampleRate(), f1->_reqOutputRate, f1->_reqDecimation, &rate1);
+	if (f1b)
+		d *= decimationOff(rate1, f1b->_reqOutputRate, f1b->_reqDecimation, &rate2);
+	if (!d)
+		return false;
+	const unsigned long smallest = (_source->blockSize() / 2) / _pieces / d;
+	return smallest >= (unsigned long)n + hop;
+}
+
+/* the block just submitted, in `parts` equal parts, as the channels' SpectrumSinks count it */
+void TunerBatch::countTapFrames(unsigned int nframes, unsigned int parts)
+{
+	for (size_t n = 0; n < _channels.size(); n++) {
+		Channel *c = _channels[n];
+		if (c->slot < 0 || !c->chanFilter->isRunning() || (c->chanFilter2 && !c->chanFilter2->isRunning()))
+			continue;
+		const unsigned long d = (unsigned long)c->chanFilter->decimation() * (c->chanFilter2 ? c->chanFilter2->decimation() : 1u);
+		c->tapLast = d ? (nframes / parts) / d : 0;          /* dspblock.cxx:177-178, stage after stage */
+		c->tapTotal += c->tapLast * parts;
+	}
+}
+
+unsigned long long TunerBatch::chanSpectraCalls()
+{
+	std::lock_guard<std::mutex> g(_lock);
+	return _tapCalls;
+}
+
+TunerBatch::Tap TunerBatch::chanSpectrum(const DspBlock *filter, wr_spectrum *spec, unsigned int fftSize, unsigned int hop,
+                                         float *magnitudes)
+{
+	DspSource *src = rootSource(filter);
+	TunerBatch *b = src ? src->batch() : NULL;
+	if (!b)
+		return TAP_NONE;
+	std::lock_guard<std::mutex> g(b->_lock);
+	/* (looked up in the batch's own list under its lock: withdraw() may be taking the chain out on another thread) */
+	const Channel *ch = NULL;
+	for (size_t n = 0; n < b->_channels.size() && !ch; n++)
+		if ((b->_channels[n]->chanFilter2 ? b->_channels[n]->chanFilter2 : b->_channels[n]->chanFilter) == filter)
+			ch = b->_channels[n];
+	if (!ch || !b->_tuner)
+		return TAP_NONE;
+	if (ch->slot < 0 || !ch->tapLast)
+		return TAP_NOTHING_YET;
+	unsigned long long first = 0;
+	switch (spectrumFrameStart(ch->tapTotal, fftSize, hop, ch->tapLast, &first)) {
+	case SPECTRUM_FRAME_NONE:
+		return TAP_NOTHING_YET;
+	case SPECTRUM_FRAME_AT:
+		break;
+	default:
+		/* (a block shorter than the source's block size: the frame began in the block before, which is gone) */
+		LOG_ERROR("SpectrumSink: the last block's %llu channel frames do not hold the most recent frame of %u\n",
+		          ch->tapLast, fftSize);
+		return TAP_FAILED;
+	}
+	if (b->_tapSeq != b->_lateSeq) {
+		b->_tapRows.clear();
+		b->_tapSeq = b->_lateSeq;
+	}
+	const TapRows *rows = NULL;
+	for (size_t n = 0; n < b->_tapRows.size() && !rows; n++)
+		if (b->_tapRows[n].n == fftSize && b->_tapRows[n].first == first)
+			rows = &b->_tapRows[n];
+	if (!rows) {
+		int top = 0;
+		for (size_t n = 0; n < b->_channels.size(); n++)
+			if (b->_channels[n]->slot > top)
+				top = b->_channels[n]->slot;
+		const size_t room = ((size_t)top / 64 + 1) * 64;             /* the lane groups in use */
+		TapRows fresh;
+		fresh.n = fftSize;
+		fresh.first = first;
+		fresh.slots = 0;
+		++b->_tapCalls;
+		if (!b->_tapDev.reserve(b->_dev, room * fftSize * sizeof(float)) ||
+		    wr_tuner_chan_spectra(b->_tuner, spec, (size_t)first, (float *)b->_tapDev.ptr, &fresh.slots) != WR_OK ||
+		    fresh.slots > room) {
+			LOG_ERROR("SpectrumSink: wr_tuner_chan_spectra: %s\n", wr_last_error());
+			return TAP_FAILED;
+		}
+		fresh.db.resize((size_t)fresh.slots * fftSize);
+		if (wr_dev_download(b->_dev, fresh.db.data(), b->_tapDev.ptr, fresh.db.size() * sizeof(float)) != WR_OK) {
+			LOG_ERROR("SpectrumSink: %s\n", wr_last_error());
+			return TAP_FAILED;
+		}
+		b->_tapRows.push_back(fresh);
+		rows = &b->_tapRows.back();
+	}
+	if ((unsigned int)ch->slot >= rows->slots)
+		return TAP_FAILED;
+	memcpy(magnitudes, rows->db.data() + (size_t)ch->slot * fftSize, fftSize * sizeof(float));
+	return TAP_SERVED;
 }
 
 /* DspBlock::connect on a block whose output the fusion had elided */
@@ -838,7 +982,8 @@ bool TunerBatch::submitOnce(const vector<sample_t> &tunerBuffer, unsigned int nf
 					return false;
 				}
 			if (parts == 1)
-				return afterSubmit(false);
+				return afterSubmit(false, nframes);
+			countTapFrames(nframes, parts);
 			++_lateSeq;
 			if (!_streaming)
 				wr_tuner_flush(_tuner);                     /* (a streaming launch's post stage starts by itself) */
@@ -869,6 +1014,7 @@ bool TunerBatch::submitOnce(const vector<sample_t> &tunerBuffer, unsigned int nf
 		}
 	}
 	if (P > 1) {
+		countTapFrames(nframes, P);
 		++_lateSeq;
 		wr_tuner_flush(_tuner);                 /* the last part's demodulator + audio filter: nothing rides behind it */
 		traceAdd(_source, 'S');
@@ -900,7 +1046,7 @@ bool TunerBatch::submitOnce(const vector<sample_t> &tunerBuffer, unsigned int nf
 		LOG_ERROR("wr_tuner_submit: %s\n", wr_last_error());
 		return false;
 	}
-	return afterSubmit(pushed);
+	return afterSubmit(pushed, nframes);
 }
 
 bool TunerBatch::streamInfo(bool *live, unsigned long long *launches, unsigned long long *blocks)
@@ -946,7 +1092,7 @@ bool TunerBatch::sparseWindows(unsigned int *period, unsigned int *length)
 }
 
 /* the block has been submitted (enqueued): bookkeeping, and this run()'s audio */
-bool TunerBatch::afterSubmit(bool pushed)
+bool TunerBatch::afterSubmit(bool pushed, unsigned int nframes)
 {
 	++_lateSeq;                            /* blocks submitted so far */
 	if (pushed)                            /* a filter change may have moved a channel to another rate group */
@@ -958,6 +1104,7 @@ bool TunerBatch::afterSubmit(bool pushed)
 				_channels[n]->lateSeq = _lateSeq;          /* this block is the first in that slot: the ring entry
 				                                              of the block before it is not this channel's */
 		}
+	countTapFrames(nframes, 1);
 	/* the graph hands this block's audio on within this very run(): no waiting for the next launch.
 	 * (WEBRADIO_AUDIO_LATE=2 hands out the audio of the block before the previous one: the demodulator and
 	 * audio filter of a block then ride in the NEXT block's launch, as in bench.py -- one launch per block.) */

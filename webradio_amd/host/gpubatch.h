@@ -15,6 +15,9 @@
  *     tuner buffer once and submits every channel; later process() calls of enrolled
  *     blocks in the same epoch are no-ops, except the audio LowPass, which copies its
  *     channel's audio out of the batch's single device-to-host transfer;
+ *   - SpectrumSinks on the last channel filter of such a chain (a panadapter per listener) do not end the fusion:
+ *     they receive no samples, and getSpectrum() is served from the channel IQ the tuner keeps of its last submit --
+ *     one wr_tuner_chan_spectra launch and one copy for all the sinks that ask about the same block;
  *   - blocks that are not part of such a chain run one kernel each (wr_mix,
  *     wr_fir_decimate, wr_demod) on their own host buffers.
  */
@@ -34,6 +37,7 @@
 class DownConverter;
 class LowPass;
 class Demodulator;
+class SpectrumSink;
 
 namespace wrhost {
 
@@ -56,6 +60,8 @@ bool hostBlockValid(const DspBlock *block);
 /* r06: did the tuner batch of `block`'s root source stream (a DeviceBlock source: wr_tuner_set_streaming)?  `live`: a launch is
  * open right now; `launches` / `blocks`: opened / taken so far.  false: no batch */
 bool streamInfo(const DspBlock *block, bool *live, unsigned long long *launches, unsigned long long *blocks);
+/* how many wr_tuner_chan_spectra calls the tuner batch of `block`'s root source has made (0: no batch) */
+unsigned long long chanSpectraCalls(const DspBlock *block);
 /* For a consumer of the source's block that is NOT part of the tuner batch (the SpectrumSink, which FrontEnd connects
  * first): have the batch submit this block now, before the consumer enqueues its own work -- the receivers' launches then
  * come first on the device's stream and the audio does not wait behind the spectrum's copy and transform (the batch
@@ -102,6 +108,9 @@ struct Channel {
 	bool dirty;                   /* parameters changed since the last submit */
 	unsigned long long lateSeq;   /* the first block (counted from 1) submitted with the channel in `slot`: an
 	                                 older ring entry's row `slot` is not this channel's (WEBRADIO_AUDIO_LATE) */
+	/* for the SpectrumSinks on the chain's last channel filter: the channel-rate frames (at the demodulator's input) the
+	 * tuner has been handed for this channel since it was enrolled, and how many of them the LAST submit brought */
+	unsigned long long tapTotal, tapLast;
 };
 
 class TunerBatch {
@@ -125,6 +134,14 @@ public:
 	static void markDirty(Channel *ch);
 
 	bool streamInfo(bool *live, unsigned long long *launches, unsigned long long *blocks);
+	/* SpectrumSink::getSpectrum of a sink whose producer `filter` is the last channel filter of an enrolled chain: the dB row
+	 * of the reference's most recent complete frame (spectrumframing.h), out of one wr_tuner_chan_spectra per (block,
+	 * fft size, first frame) whose rows are downloaded once for every sink that asks.  `spec`: the sink's own wr_spectrum
+	 * (its tables).  TAP_NONE: `filter` is in no batch -- the sink is fed samples and answers itself */
+	enum Tap { TAP_NONE, TAP_SERVED, TAP_NOTHING_YET, TAP_FAILED };
+	static Tap chanSpectrum(const DspBlock *filter, wr_spectrum *spec, unsigned int fftSize, unsigned int hop, float *magnitudes);
+	static bool tapped(const DspBlock *filter) { return filter && filter->gpuChannel() != NULL; }
+	unsigned long long chanSpectraCalls();
 	bool streaming() const { return _streaming; }
 	wr_dev *dev() const { return _dev; }
 	DspSource *source() const { return _source; }
@@ -137,9 +154,11 @@ private:
 	bool pushParams(Channel *ch);
 	unsigned int piecesFor(unsigned int nframes);
 	bool sparseWindows(unsigned int *period, unsigned int *length);
-	bool afterSubmit(bool pushed);
+	bool afterSubmit(bool pushed, unsigned int nframes);
 	bool collectParts(unsigned int parts);
 	void drainRing();
+	void countTapFrames(unsigned int nframes, unsigned int parts);
+	bool sinkQualifies(const SpectrumSink *sink, const LowPass *f1, const LowPass *f1b) const;
 
 	DspSource *_source;
 	wr_dev *_dev;
@@ -165,6 +184,17 @@ private:
 	unsigned long long _partSeq0;     /* the number the tuner gave the first part of the block collectParts is about to collect
 	                                     (wr_tuner_submit_count before the parts went out: the library's own count) */
 	bool _streaming;                  /* the source produces its blocks in device memory (DeviceBlock): wr_tuner_set_streaming */
+	/* channel spectra of the block submitted last (_lateSeq), one entry per (fft size, first frame) asked about */
+	struct TapRows {
+		unsigned int n;
+		unsigned long long first;
+		unsigned int slots;
+		std::vector<float> db;        /* [slots][n] */
+	};
+	std::vector<TapRows> _tapRows;
+	unsigned long long _tapSeq;       /* the block (_lateSeq) _tapRows belongs to */
+	unsigned long long _tapCalls;     /* wr_tuner_chan_spectra calls made */
+	DevBuf _tapDev;
 };
 
 } // namespace wrhost

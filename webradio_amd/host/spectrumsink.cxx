@@ -87,6 +87,17 @@ bool SpectrumSink::process(const vector<sample_t> &inBuffer, vector<sample_t> &o
 		return true;
 	}
 	/* two channels: IQ, as upstream assumes (spectrumsink.cxx:93) */
+	if (inBuffer.empty() && wrhost::TunerBatch::tapped(upstream()))
+		return true;                    /* on a channel filter inside the tuner batch: no samples, the batch counts the frames */
+	if (upstream() != wrhost::TunerBatch::rootSource(this)) {
+		/* behind a block that runs on its own (a channel filter outside the batch): its host output, nothing staged --
+		 * and what the SOURCE did with its host vector is no concern of this sink's */
+		if (wr_spectrum_push(_spec, inBuffer.data(), inBuffer.size() / 2, WR_HOST) != WR_OK) {
+			LOG_ERROR("SpectrumSink: %s\n", wr_last_error());
+			return false;
+		}
+		return true;
+	}
 	/* the receivers of the same tuner go first on the device's stream: their audio is what run() waits for */
 	wrhost::submitBatchFirst(this, inBuffer);
 	/* fed straight from the tuner: use the device copy every GPU consumer of it shares */
@@ -115,6 +126,12 @@ bool SpectrumSink::process(const vector<sample_t> &inBuffer, vector<sample_t> &o
 void SpectrumSink::getSpectrum(float *magnitudes)
 {
 	std::lock_guard<std::mutex> g(_lock);
-	if (_spec)
-		wr_spectrum_get_db(_spec, magnitudes);
+	if (!_spec)
+		return;
+	/* on a channel filter inside the tuner batch: the batch's one launch for every receiver's sink.  (Before the first
+	 * complete frame, or when it fails, the array is left as it is there too.) */
+	if (inputChannels() == 2 && wrhost::TunerBatch::tapped(upstream()) &&
+	    wrhost::TunerBatch::chanSpectrum(upstream(), _spec, _fftSize, _hop, magnitudes) != wrhost::TunerBatch::TAP_NONE)
+		return;
+	wr_spectrum_get_db(_spec, magnitudes);
 }

@@ -3,6 +3,8 @@
  * src/io/spectrumsink.h:44-53 (fftSize/setFftSize/getSpectrum, default size 512).
  * Two input channels: IQ, as upstream.  One: real samples (a Demodulator, a receiver's audio filter) -- upstream's
  * FIXMEs at src/io/spectrumsink.cxx:62-64; getSpectrum() then gives the row the IQ sink would give for (x, 0).
+ * On the last channel filter of a Receiver whose chain runs inside the tuner batch (gpubatch.h) the sink is handed no
+ * samples: getSpectrum() asks the batch, which transforms every receiver's channel IQ in one launch.
  */
 #ifndef SPECTRUMSINK_H_
 #define SPECTRUMSINK_H_
@@ -29,6 +31,7 @@ public:
 	/* extension: frames start every `hop` input frames (0 = back to back, the upstream
 	 * behaviour; fftSize/2 = the 50 % overlap waterfall) -- ignored while running */
 	void setHop(unsigned int hop);
+	unsigned int hop() const { return _hop; }
 
 	void getSpectrum(float *magnitudes);
 
