@@ -51,6 +51,7 @@ extern "C" {
                                     wr_spectrum_push beside an open streaming launch keeps the frame and transforms it on demand.
                                     Added to 6 later: wr_spectrum_create_real, wr_spectrum_channels, wr_spectrum_batch_db_rows.
                                     Added to 6 later: wr_tuner_chan_spectra.
+                                    Added to 6 later: wr_tuner_chan_levels, wr_iq_levels.
                                     Nothing of an earlier version changed or removed */
 #define WR_FIR_LENGTH    64      /* dsp/lowpass.cxx:39  FIR_LENGTH */
 #define WR_TABLE_SIZE    65536   /* dsp/downconverter.cxx:35 LOOKUP_BITS 16 */
@@ -195,6 +196,12 @@ unsigned long long wr_block_kernel_calls(void);
  * (host), updated on return. */
 int wr_demod(wr_dev *dev, int mode, const float *in_dev, size_t nframes,
              float *prev_io /* [2] host */, float *out_dev);
+
+/* The level of a plain block of IQ frames iq_dev[nframes][2] (a stand-alone Demodulator's input): *mean_host = the mean
+ * and *peak_host = the largest of e = i*i + q*q over the block, linear powers with full scale 1.0 (either may be NULL).
+ * wr_tuner_chan_levels' kernels on one column, so the same rule of summation and the same bits for the same frames.
+ * Synchronous; counted by wr_block_kernel_calls.  WR_ERR_ARG: NULL dev or iq_dev, nframes == 0. */
+int wr_iq_levels(wr_dev *dev, const float *iq_dev, size_t nframes, float *mean_host, float *peak_host);
 
 /* RTL-SDR byte format to float, (u8 - 128)/128 (io/rtlsdrtuner.cxx:106) */
 int wr_u8_to_f32(wr_dev *dev, const uint8_t *in_dev, float *out_dev, size_t count);
@@ -569,6 +576,31 @@ int wr_spectrum_batch_db_rows(wr_spectrum *spec, const float *in_dev, size_t row
  * WR_ERR_ARG: NULL arguments, a real spectrum, fft_size > 8192, first_frame + fft_size beyond the last submit's channel
  * frames, a spectrum of another wr_dev.  WR_ERR_STATE: nothing submitted yet, several rate groups. */
 int wr_tuner_chan_spectra(wr_tuner *tuner, wr_spectrum *spec, size_t first_frame, float *db_dev, unsigned int *slots);
+
+/* The SIGNAL LEVEL of every receiver of a tuner (an S-meter beside the squelch_threshold and af_gain the reference's REST
+ * interface names, web/receiverhandler.cxx:112,118-119): the level of WR_STAGE_CHAN_IQ of the last submit -- what the
+ * demodulator sees (dsp/demodulator.cxx:77-115) -- for every channel slot, from one launch sequence.  With
+ * e_m = i*i + q*q of channel frame m (two products and one sum, each rounded to float) and K1 = *frames:
+ *   mean_host[s]  = sum / (float)K1, a linear power with full scale 1.0.  THE SUM is taken in one order, whatever the
+ *                   device and whatever max_channels: frames oldest first in runs of 16 (r_j = e_16j + e_16j+1 + ...),
+ *                   the run sums in order in groups of 16 runs, i.e. 256 frames (c_h = r_16h + r_16h+1 + ...), the group
+ *                   sums in order (sum = c_0 + c_1 + ...); the last run and the last group are simply shorter; every
+ *                   partial starts from its first term (e is never -0, so starting from 0.0f would give the same bits).
+ *                   The same frames give the same bits everywhere, and a float restatement of the rule is bit-identical.
+ *   peak_host[s]  = the largest e_m.
+ *   muted_host[s] = how many of the *audio_frames audio frames of the block the squelch muted (wr_chan_set_squelch's
+ *                   test, the audio path's own expression: the sum from 0.0f of the e of the frame's d2 channel frames,
+ *                   oldest first, divided by (float)d2, below the threshold); 0 for an open squelch.  The thresholds are
+ *                   the ones the last submit's audio was made with: a wr_chan_set_squelch since then shows once a block
+ *                   has been submitted with it (a wr_tuner_seek uploads staged settings too).
+ * Each array holds *slots entries (the slots in use in whole lane groups of 64, as wr_tuner_fetch_audio_all and
+ * wr_tuner_chan_spectra count them: at most max_channels rounded up to 64); the entry of a channel is wr_chan_slot's,
+ * entries of slots that hold no channel carry no meaning.  Any of the three arrays, frames, audio_frames and slots may be
+ * NULL; all three arrays NULL is WR_ERR_ARG.  Like every getter it sends held blocks out, launches a pending post stage
+ * and closes an open streaming launch; then it copies the few bytes out and waits for them.  It changes nothing the next
+ * block depends on.  WR_ERR_STATE: nothing submitted yet, several rate groups. */
+int wr_tuner_chan_levels(wr_tuner *tuner, float *mean_host, float *peak_host, unsigned int *muted_host, size_t *frames,
+                         size_t *audio_frames, unsigned int *slots);
 #ifdef __cplusplus
 }
 #endif

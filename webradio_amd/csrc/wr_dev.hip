@@ -518,6 +518,30 @@ extern "C" int wr_demod(wr_dev *d, int mode, const float *in_dev, size_t nframes
 	return WR_OK;
 }
 
+/* the level of a plain block: wr_tuner_chan_levels' kernels on ONE column (S = 1, cols = 1) */
+extern "C" int wr_iq_levels(wr_dev *d, const float *iq_dev, size_t nframes, float *mean_host, float *peak_host)
+{
+	if (!d || !iq_dev || !nframes)
+		return wrc_fail(WR_ERR_ARG, "wr_iq_levels: bad argument (NULL dev or iq_dev, or no frames)");
+	g_block_kernel_calls.fetch_add(1, std::memory_order_relaxed);
+	DEV_SETTLE(d);
+	float got[3];
+	{
+		SCRATCH_GUARD(d);
+		if (int rc = wrc_dev_scratch(d, wrk_chan_levels_work(1, nframes)))
+			return rc;
+		const float *res = nullptr;
+		HIP_TRY(wrk_chan_levels(d->stream, iq_dev, 1, 1, nframes, 0, 0, nullptr, d->scratch, &res));
+		HIP_TRY(hipMemcpyAsync(got, res, sizeof(got), hipMemcpyDeviceToHost, d->stream));
+		HIP_TRY(wrc_dev_stream_sync(d));
+	}
+	if (mean_host)
+		*mean_host = got[0];
+	if (peak_host)
+		*peak_host = got[1];
+	return WR_OK;
+}
+
 extern "C" int wr_u8_to_f32(wr_dev *d, const uint8_t *in_dev, float *out_dev, size_t count)
 {
 	if (!d || (count && (!in_dev || !out_dev)))

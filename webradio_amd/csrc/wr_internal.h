@@ -1,6 +1,6 @@
 /*
  * wr_internal.h -- internal C++ interface between the C ABI (wr_dev.hip, wr_tuner*.hip, wr_spectrum.hip), the host
- * design math (wr_design.cpp) and the kernels (wr_kernels.hip, wr_fft.hip).
+ * design math (wr_design.cpp) and the kernels (wr_kernels.hip, wr_fft.hip, wr_levels.hip).
  * Not installed; the public boundary is include/webradio_amd.h.
  */
 #ifndef WR_INTERNAL_H_
@@ -328,6 +328,15 @@ hipError_t wrk_fft_frames(hipStream_t st, const WrFftPlan &P, const float *iq, s
  * db + s * P.n: IQ plans of at most 8192 points, cols <= S a multiple of 64 */
 hipError_t wrk_fft_cols(hipStream_t st, const WrFftPlan &P, const float *iq, unsigned int S, unsigned int cols, size_t first,
                         float *db, int num_cus /* of the device: columns share a workgroup only beyond that many */);
+
+/* ---- signal levels (wr_levels.hip) ---- */
+/* of the first `cols` columns of iq[k1][S][2]: *out = [3][cols] in `work` (room for wrk_chan_levels_work floats): the mean
+ * of e = i*i + q*q (summed in runs of 16, groups of 16 runs, in order: a function of k1 alone), its peak, and -- with
+ * `squelch` ([cols] thresholds as powers, 0 = open; else NULL) -- as unsigned the audio frames k < k2 that audio_out mutes
+ * (the mean of e over rows k*d2 .. k*d2 + d2 - 1 below the threshold), 0 without.  cols <= S, any cols */
+size_t     wrk_chan_levels_work(unsigned int cols, size_t k1);
+hipError_t wrk_chan_levels(hipStream_t st, const float *iq, size_t S, unsigned int cols, size_t k1, unsigned int d2, size_t k2,
+                           const float *squelch, float *work, const float **out);
 
 hipError_t wrk_bins_to_db(hipStream_t st, const float *bins, unsigned int n, float *db);
 hipError_t wrk_waterfall_row(hipStream_t st, const float *bins, unsigned int n, unsigned int width, int hold,

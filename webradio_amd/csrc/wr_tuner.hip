@@ -1564,6 +1564,56 @@ extern "C" int wr_tuner_chan_spectra(wr_tuner *t, wr_spectrum *spec, size_t firs
 	return WR_OK;
 }
 
+/* every receiver's signal level out of the same buffer: a pass over it where it lies (k_levels_part, k_levels_sum), the
+ * thresholds the group's device arrays hold -- the ones wrc_group_upload gave the last submit */
+extern "C" int wr_tuner_chan_levels(wr_tuner *t, float *mean_host, float *peak_host, unsigned int *muted_host, size_t *frames,
+                                    size_t *audio_frames, unsigned int *slots)
+{
+	if (!t || (!mean_host && !peak_host && !muted_host))
+		return wrc_fail(WR_ERR_ARG, "wr_tuner_chan_levels: bad argument (NULL tuner, or no array to fill)");
+	if (int rc = wrc_settle_held(t))
+		return rc;
+	bool several = false;
+	Group *g = wrc_single_group(t, &several);
+	if (several)
+		return wrc_fail(WR_ERR_STATE, "tuner has several rate groups; fetch per channel instead");
+	if (!g || !t->submitted)
+		return wrc_fail(WR_ERR_STATE, "wr_tuner_chan_levels: nothing submitted yet");
+	wr_dev *d = t->dev;
+	if (wrc_dev_bind(d))
+		return WR_ERR_HIP;
+	if (int rc = wrc_tuner_flush(t))
+		return rc;
+	const float *iq = t->stream.last_iq ? t->stream.last_iq : g->d1b ? g->dev.chan_iq2[g->last_cb] : g->dev.chan_iq[g->last_cb];
+	const unsigned int used = wrc_group_slots_used(g);
+	if (frames)
+		*frames = g->last_k1;
+	if (audio_frames)
+		*audio_frames = g->last_k2;
+	if (slots)
+		*slots = used;
+	if (!used)
+		return WR_OK;
+	std::vector<float> got((size_t)3 * used, 0.0f);
+	if (g->last_k1) {
+		SCRATCH_GUARD(d);
+		if (int rc = wrc_dev_scratch(d, wrk_chan_levels_work(used, g->last_k1)))
+			return rc;
+		const float *res = nullptr;
+		HIP_TRY(wrk_chan_levels(d->stream, iq, g->slots, used, g->last_k1, g->d2, g->last_k2,
+		                        g->use_squelch ? g->dev.squelch : nullptr, d->scratch, &res));
+		HIP_TRY(hipMemcpyAsync(got.data(), res, got.size() * sizeof(float), hipMemcpyDeviceToHost, d->stream));
+		TUNER_SYNC_CHECKED(t);
+	}
+	if (mean_host)
+		memcpy(mean_host, got.data(), used * sizeof(float));
+	if (peak_host)
+		memcpy(peak_host, got.data() + used, used * sizeof(float));
+	if (muted_host)
+		memcpy(muted_host, got.data() + 2u * used, used * sizeof(unsigned int));
+	return WR_OK;
+}
+
 extern "C" int wr_tuner_fetch_audio_all(wr_tuner *t, float *out_host, size_t out_capacity,
                                         size_t *chan_stride, size_t *frames, unsigned int *slots_used)
 {

@@ -89,6 +89,13 @@ class Device:
         self.free(dout)
         return out, prev
 
+    def iq_levels(self, p, nframes):
+        """(mean, peak) of i*i + q*q over the [nframes][2] float array at device pointer p (wr_iq_levels), as
+        numpy float32 scalars."""
+        mean, peak = C.c_float(), C.c_float()
+        check(self.lib.wr_iq_levels(self.h, C.c_void_p(p), nframes, C.byref(mean), C.byref(peak)))
+        return np.float32(mean.value), np.float32(peak.value)
+
 
 class Tuner:
     """wr_tuner: every Receiver chain of one tuner, evaluated by one launch sequence."""
@@ -304,6 +311,19 @@ class Tuner:
         finally:
             self.dev.free(p)
         return out.reshape(slots.value, spec.n)
+
+    def chan_levels(self):
+        """Every receiver's signal level at the demodulator's input, from the last submit's channel IQ
+        (wr_tuner_chan_levels): (mean, peak, muted, frames, audio_frames) -- mean and peak power (float32, full scale
+        1.0) and the audio frames the squelch muted (uint32), arrays indexed by slot (Tuner.slot)."""
+        rows = (self.max_channels + 63) // 64 * 64
+        mean, peak = np.zeros(rows, np.float32), np.zeros(rows, np.float32)
+        muted = np.zeros(rows, np.uint32)
+        frames, audio_frames, slots = C.c_size_t(), C.c_size_t(), C.c_uint()
+        check(self.lib.wr_tuner_chan_levels(self.h, ptr(mean), ptr(peak), ptr(muted), C.byref(frames),
+                                            C.byref(audio_frames), C.byref(slots)))
+        n = slots.value
+        return mean[:n], peak[:n], muted[:n], frames.value, audio_frames.value
 
 
 class Spectrum:

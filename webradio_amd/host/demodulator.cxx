@@ -4,14 +4,17 @@
  */
 #include "demodulator.h"
 
+#include <cmath>
+
 #include "debug.h"
 #include "gpubatch.h"
 
 Demodulator::Demodulator(const string &name)
 	: DspBlock(name, "AMDemod"), _mode(AM), _channel(NULL), _in(new wrhost::DevBuf()),
-	  _out(new wrhost::DevBuf())
+	  _out(new wrhost::DevBuf()), _levelWanted(false), _levelHave(false)
 {
 	_prev[0] = _prev[1] = 0.0f;
+	_level[0] = _level[1] = 0.0f;
 	/* index = enum value (demodulator.cxx:37-41) */
 	const char *names[] = { "AM", "FM", "USB", "LSB" };
 	for (int n = 0; n < (int)MAX_MODE; n++)
@@ -38,6 +41,32 @@ bool Demodulator::setModeString(const string &mode)
 			return true;
 		}
 	return false;
+}
+
+bool Demodulator::inputLevel(float *mean_dbfs, float *peak_dbfs)
+{
+	float mean = 0.0f, peak = 0.0f;
+	switch (wrhost::TunerBatch::chanLevel(this, &mean, &peak)) {
+	case wrhost::TunerBatch::TAP_SERVED:
+		break;
+	case wrhost::TunerBatch::TAP_NONE: {
+		/* stand-alone: process() measures from now on */
+		std::lock_guard<std::mutex> g(_levelLock);
+		_levelWanted = true;
+		if (!_levelHave)
+			return false;
+		mean = _level[0];
+		peak = _level[1];
+		break;
+	}
+	default:
+		return false;
+	}
+	if (mean_dbfs)
+		*mean_dbfs = (float)(10.0 * log10((double)mean));
+	if (peak_dbfs)
+		*peak_dbfs = (float)(10.0 * log10((double)peak));
+	return true;
 }
 
 bool Demodulator::init()
@@ -80,6 +109,22 @@ bool Demodulator::process(const vector<sample_t> &inBuffer, vector<sample_t> &ou
 			return false;
 		}
 		din = (const float *)_in->ptr;
+	}
+	bool wanted;
+	{
+		std::lock_guard<std::mutex> g(_levelLock);
+		wanted = _levelWanted;
+	}
+	if (wanted && nframes) {
+		float level[2];
+		if (wr_iq_levels(dev, din, nframes, &level[0], &level[1]) != WR_OK) {
+			LOG_ERROR("Demodulator: %s\n", wr_last_error());
+			return false;
+		}
+		std::lock_guard<std::mutex> g(_levelLock);
+		_level[0] = level[0];
+		_level[1] = level[1];
+		_levelHave = true;
 	}
 	if (wr_demod(dev, (int)_mode, din, nframes, _prev, (float *)_out->ptr) != WR_OK) {
 		LOG_ERROR("Demodulator: %s\n", wr_last_error());

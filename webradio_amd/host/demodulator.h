@@ -5,6 +5,7 @@
 #ifndef DEMODULATOR_H_
 #define DEMODULATOR_H_
 
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -34,6 +35,17 @@ public:
 	const string& modeString() const { return _modeNames[_mode]; }
 	bool setModeString(const string &mode);
 
+	/* extension (an S-meter beside the squelch_threshold and af_gain the reference's REST interface names,
+	 * web/receiverhandler.cxx:112,118-119): the level of the demodulator's most recent input block, 10 * log10 of the mean
+	 * and of the largest i*i + q*q in dBFS (computed on the host in double; a silent channel gives -inf, as the
+	 * spectrum's dB rows do).  Any thread.  false: nothing to report yet.
+	 *   Inside the tuner batch: the last submit's channel IQ -- with WEBRADIO_PIECES above 1 the block's LAST part --
+	 * measured for every receiver of the tuner by one wr_tuner_chan_levels per block; before the first submit false; a
+	 * call beside an open streaming launch closes it, as a channel-spectrum poll does.
+	 *   Stand-alone: the first call answers false and asks for the measurement; from the next process() on every block
+	 * is measured (wr_iq_levels) and the call answers with the latest.  A chain nobody asks costs nothing more. */
+	bool inputLevel(float *mean_dbfs, float *peak_dbfs);
+
 private:
 	bool init();
 	void deinit();
@@ -47,6 +59,9 @@ private:
 	wrhost::Channel*	_channel;
 	wrhost::DevBuf*	_in;
 	wrhost::DevBuf*	_out;
+	std::mutex		_levelLock;		/* the three below: inputLevel() may come from an HTTP thread, like the setters */
+	bool			_levelWanted, _levelHave;
+	float			_level[2];		/* mean, peak: linear */
 };
 
 #endif /* DEMODULATOR_H_ */

@@ -498,6 +498,13 @@ unsigned long long chanSpectraCalls(const DspBlock *block)
 	return batch ? batch->chanSpectraCalls() : 0;
 }
 
+unsigned long long chanLevelCalls(const DspBlock *block)
+{
+	DspSource *src = TunerBatch::rootSource(block);
+	TunerBatch *batch = src ? src->batch() : NULL;
+	return batch ? batch->chanLevelCalls() : 0;
+}
+
 bool hostBlockValid(const DspBlock *block)
 {
 	DspSource *src = TunerBatch::rootSource(block);
@@ -547,7 +554,7 @@ TunerBatch::TunerBatch(DspSource *source, wr_dev *dev)
 	  _submitOk(false), _audioPtr(NULL), _ringHeld(false), _audioStride(0), _audioFrames(0), _audioSlots(0),
 	  _late(envUnsigned("WEBRADIO_AUDIO_LATE", 0) != 0), _lateDepth(envUnsigned("WEBRADIO_AUDIO_LATE", 0) >= 2 ? 2u : 1u),
 	  _lateQueued(false), _silence(false), _lateSeq(0), _pieces(envUnsigned("WEBRADIO_PIECES", 2)), _delivered(false), _partSeq0(0),
-	  _streaming(false), _tapSeq(0), _tapCalls(0)
+	  _streaming(false), _tapSeq(0), _tapCalls(0), _lvSlots(0), _lvSeq(0), _lvCalls(0)
 {
 	if (_pieces < 1 || _late)
 		_pieces = 1;
@@ -702,6 +709,7 @@ Channel *TunerBatch::enrol(DownConverter *mixer)
 		batch->_lateSeq = 0;
 		batch->_tapRows.clear();
 		batch->_tapSeq = 0;
+		batch->_lvSeq = 0;
 	}
 	int id = -1;
 	if (wr_chan_add(batch->_tuner, &id) != WR_OK) {
@@ -849,6 +857,59 @@ TunerBatch::Tap TunerBatch::chanSpectrum(const DspBlock *filter, wr_spectrum *sp
 	if ((unsigned int)ch->slot >= rows->slots)
 		return TAP_FAILED;
 	memcpy(magnitudes, rows->db.data() + (size_t)ch->slot * fftSize, fftSize * sizeof(float));
+	return TAP_SERVED;
+}
+
+unsigned long long TunerBatch::chanLevelCalls()
+{
+	std::lock_guard<std::mutex> g(_lock);
+	return _lvCalls;
+}
+
+TunerBatch::Tap TunerBatch::chanLevel(const Demodulator *demod, float *mean, float *peak, unsigned int *muted)
+{
+	DspSource *src = rootSource(demod);
+	TunerBatch *b = src ? src->batch() : NULL;
+	if (!b)
+		return TAP_NONE;
+	std::lock_guard<std::mutex> g(b->_lock);
+	/* (looked up in the batch's own list under its lock, as chanSpectrum does) */
+	const Channel *ch = NULL;
+	for (size_t n = 0; n < b->_channels.size() && !ch; n++)
+		if (b->_channels[n]->demod == demod)
+			ch = b->_channels[n];
+	if (!ch || !b->_tuner)
+		return TAP_NONE;
+	if (ch->slot < 0 || !b->_lateSeq)
+		return TAP_NOTHING_YET;
+	if (b->_lvSeq != b->_lateSeq) {
+		int top = 0;
+		for (size_t n = 0; n < b->_channels.size(); n++)
+			if (b->_channels[n]->slot > top)
+				top = b->_channels[n]->slot;
+		const size_t room = ((size_t)top / 64 + 1) * 64;             /* the lane groups in use */
+		b->_lvMean.assign(room, 0.0f);
+		b->_lvPeak.assign(room, 0.0f);
+		b->_lvMuted.assign(room, 0u);
+		b->_lvSlots = 0;
+		b->_lvSeq = 0;
+		++b->_lvCalls;
+		size_t frames = 0;
+		if (wr_tuner_chan_levels(b->_tuner, b->_lvMean.data(), b->_lvPeak.data(), b->_lvMuted.data(), &frames, NULL,
+		                         &b->_lvSlots) != WR_OK || b->_lvSlots > room) {
+			LOG_ERROR("Demodulator: wr_tuner_chan_levels: %s\n", wr_last_error());
+			return TAP_FAILED;
+		}
+		if (!frames)
+			return TAP_NOTHING_YET;
+		b->_lvSeq = b->_lateSeq;
+	}
+	if ((unsigned int)ch->slot >= b->_lvSlots)
+		return TAP_FAILED;
+	*mean = b->_lvMean[ch->slot];
+	*peak = b->_lvPeak[ch->slot];
+	if (muted)
+		*muted = b->_lvMuted[ch->slot];
 	return TAP_SERVED;
 }
 

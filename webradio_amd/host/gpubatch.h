@@ -62,6 +62,8 @@ bool hostBlockValid(const DspBlock *block);
 bool streamInfo(const DspBlock *block, bool *live, unsigned long long *launches, unsigned long long *blocks);
 /* how many wr_tuner_chan_spectra calls the tuner batch of `block`'s root source has made (0: no batch) */
 unsigned long long chanSpectraCalls(const DspBlock *block);
+/* ... and how many wr_tuner_chan_levels calls (Demodulator::inputLevel of its enrolled receivers: one per block asked about) */
+unsigned long long chanLevelCalls(const DspBlock *block);
 /* For a consumer of the source's block that is NOT part of the tuner batch (the SpectrumSink, which FrontEnd connects
  * first): have the batch submit this block now, before the consumer enqueues its own work -- the receivers' launches then
  * come first on the device's stream and the audio does not wait behind the spectrum's copy and transform (the batch
@@ -142,6 +144,12 @@ public:
 	static Tap chanSpectrum(const DspBlock *filter, wr_spectrum *spec, unsigned int fftSize, unsigned int hop, float *magnitudes);
 	static bool tapped(const DspBlock *filter) { return filter && filter->gpuChannel() != NULL; }
 	unsigned long long chanSpectraCalls();
+	/* Demodulator::inputLevel of an enrolled chain's demodulator: the mean and peak power (linear, full scale 1.0) of its
+	 * input in the block submitted last -- with WEBRADIO_PIECES above 1 the block's last part -- out of ONE
+	 * wr_tuner_chan_levels per block, whose arrays are kept until the next block for every Demodulator that asks.
+	 * `muted` (optional): the audio frames of that submit the tuner's squelch muted.  TAP_NONE: `demod` is in no batch */
+	static Tap chanLevel(const Demodulator *demod, float *mean, float *peak, unsigned int *muted = NULL);
+	unsigned long long chanLevelCalls();
 	bool streaming() const { return _streaming; }
 	wr_dev *dev() const { return _dev; }
 	DspSource *source() const { return _source; }
@@ -195,6 +203,12 @@ private:
 	unsigned long long _tapSeq;       /* the block (_lateSeq) _tapRows belongs to */
 	unsigned long long _tapCalls;     /* wr_tuner_chan_spectra calls made */
 	DevBuf _tapDev;
+	/* signal levels of the block submitted last, by slot */
+	std::vector<float> _lvMean, _lvPeak;
+	std::vector<unsigned int> _lvMuted;
+	unsigned int _lvSlots;
+	unsigned long long _lvSeq;        /* the block (_lateSeq) they belong to; 0: none */
+	unsigned long long _lvCalls;      /* wr_tuner_chan_levels calls made */
 };
 
 } // namespace wrhost
