@@ -52,6 +52,7 @@ extern "C" {
                                     Added to 6 later: wr_spectrum_create_real, wr_spectrum_channels, wr_spectrum_batch_db_rows.
                                     Added to 6 later: wr_tuner_chan_spectra.
                                     Added to 6 later: wr_tuner_chan_levels, wr_iq_levels.
+                                    Added to 6 later: wr_agc_design, wr_agc_rows, wr_chan_set_agc, wr_chan_get_agc, wr_tuner_agc_info.
                                     Nothing of an earlier version changed or removed */
 #define WR_FIR_LENGTH    64      /* dsp/lowpass.cxx:39  FIR_LENGTH */
 #define WR_TABLE_SIZE    65536   /* dsp/downconverter.cxx:35 LOOKUP_BITS 16 */
@@ -601,6 +602,73 @@ int wr_tuner_chan_spectra(wr_tuner *tuner, wr_spectrum *spec, size_t first_frame
  * block depends on.  WR_ERR_STATE: nothing submitted yet, several rate groups. */
 int wr_tuner_chan_levels(wr_tuner *tuner, float *mean_host, float *peak_host, unsigned int *muted_host, size_t *frames,
                          size_t *audio_frames, unsigned int *slots);
+
+/* AUTOMATIC GAIN CONTROL of a receiver's audio.  The reference has none: its demodulators hand on sqrt(i^2 + q^2), i + q
+ * and i - q at whatever level the antenna delivers (dsp/demodulator.cxx:88-104), and its only "AGC" is the RTL-SDR's RF
+ * gain mode, one setting for the whole band (io/tuner.h:56-62).  Here every receiver has a gain of its own.
+ *
+ * THE RULE is this library's own definition, as the ones of af_gain and squelch are.  v[m] is the receiver's audio-filter
+ * output after the squelch gate, m counts audio frames over the stream, and all state is ONE unsigned 32-bit word E:
+ *   L[m]   = min(bits(v[m]) & 0x7fffffff, 0x7f7fffff)      bits(): the float's own 32 bits; an inf or a NaN counts as FLT_MAX
+ *   E[m]   = max(L[m], E[m-1] - step, floor)               integers, the subtraction does not wrap; E[-1] = floor
+ *   env[m] = the float whose bits are E[m]                 (positive, finite, normal)
+ *   g[m]   = target / env[m]                               one IEEE float32 division, correctly rounded
+ *   out[m] = v[m] * g[m], then * af_gain if it is not 1, then * scale if it is not 1     (separate float32 products)
+ * The bit pattern of a positive float is a monotone, piecewise-linear log2: an octave (6.02 dB of amplitude) is 2^23
+ * units.  So this is a peak detector with
+ *   an instant attack: env[m] >= |v[m]|, i.e. |v * g| <= target up to the two roundings;
+ *   a release that is linear in (almost) dB: E falls `step` units per audio frame; inside an octave the bit pattern is
+ *     linear in the amplitude, not in its logarithm, so the rate in dB/s wobbles between 0.72 and 1.44 of its nominal value
+ *     (fastest at the octave's lower end);
+ *   exact integer arithmetic: E has ONE value whatever order it is computed in.  In closed form, with a carry C = E[-1]
+ *     and U[j] = L[j] + j * step in 64 bits:  E[m] = max(max_{j<=m} U[j] - m * step, C - (m + 1) * step, floor)  -- a prefix
+ *     maximum, which is how the GPU computes it; a restatement by the plain loop is bit-identical.
+ * The order in a tuner: audio filter -> squelch -> AGC -> af_gain -> scale (wr_tuner_set_audio_scale).  An AGC that is
+ * off leaves every bit as it was.
+ * Left out on purpose: attack smoothing and a hang time (a sliding maximum over a window longer than a block needs
+ * history rows); a host-side C++ block (af_gain and squelch have none either, and the reference has no class to mirror);
+ * AGC under time sharding (the state has unbounded memory: a shard that seeks starts from floor).
+ *
+ * wr_agc_design: the rule's three numbers, on the host in double; needs no device.
+ *   *target     = (float)10^(target_dbfs / 20)
+ *   *floor_bits = bits((float)(10^(target_dbfs / 20) / 10^(max_gain_db / 20))): the gain never exceeds max_gain_db, and
+ *                 silence is no special case
+ *   *step       = llround(decay_db_per_s / (20 log10 2) * 2^23 / audio_rate), at most 2^31 (20 dB/s at 10 kHz: 2787)
+ * WR_ERR_ARG: a NaN, target_dbfs outside [-100, 0], decay_db_per_s outside [0, 1e4], max_gain_db outside [0, 120], a
+ * floor that would be subnormal, audio_rate 0, a NULL result. */
+int wr_agc_design(float target_dbfs, float decay_db_per_s, float max_gain_db, unsigned int audio_rate, float *target,
+                  unsigned int *floor_bits, unsigned int *step);
+/* The rule on a plain block of audio in device memory, in place: `nrows` rows of `nframes` floats, `row_stride` floats
+ * apart, row r with target_host[r], floor_bits_host[r], step_host[r] and the state word state_host[r] -- E[-1] on entry
+ * (floor_bits to begin a stream with), the row's last E on return, so consecutive calls continue one stream whatever
+ * the lengths.  step_host[r] = 0xffffffff: row r has no AGC and is not touched.  af_gain and scale are 1.  Synchronous;
+ * counted by wr_block_kernel_calls.  WR_ERR_ARG: NULL arguments, no rows, row_stride < nframes with several rows, a step
+ * above 2^31, floor bits that are no positive normal float, a state above 0x7f7fffff, a target that is not positive and
+ * finite. */
+int wr_agc_rows(wr_dev *dev, float *audio_dev, size_t row_stride, size_t nrows, size_t nframes,
+                const float *target_host, const unsigned int *floor_bits_host, const unsigned int *step_host,
+                unsigned int *state_host /* [nrows], in and out */);
+/* A receiver's AGC inside the tuner.  Staged like every setter and applied at the next block boundary; `step` is derived
+ * for the receiver's audio rate, and again when a filter change alters that rate.  Coming on, wr_chan_reset_history and
+ * wr_tuner_seek set the state to floor; new settings while it is on keep the state.  enable = 0 turns it off (the other
+ * arguments are then ignored).  The AGC runs as one more kernel behind the post stage of a rate group that has one on,
+ * in place on the group's audio: wr_chan_fetch(WR_STAGE_AUDIO), wr_tuner_audio_dev, wr_tuner_fetch_audio_all, the audio
+ * ring and wr_spectrum_batch_db_rows on the audio rows see its output; WR_STAGE_DEMOD, WR_STAGE_CHAN_IQ and
+ * wr_tuner_chan_levels are what they were.  A receiver WITHOUT AGC in such a group goes through the same float products
+ * in the same order as before: its audio is bit-identical to the same tuner with no AGC anywhere.  While any receiver
+ * has its AGC on, the tuner's blocks are not held back (wr_tuner_set_blocks_per_launch) and do not go into the
+ * streaming launch (wr_tuner_set_streaming): an open launch is closed at the boundary where AGC comes on, and streaming
+ * resumes when the last one goes off.  With no AGC on, nothing new runs.
+ * WR_ERR_ARG: no such channel, wr_agc_design's limits. */
+int wr_chan_set_agc(wr_tuner *tuner, int chan, float target_dbfs, float decay_db_per_s, float max_gain_db, int enable);
+/* what the last submit used (*enabled, *target, *floor_bits, *step: the numbers uploaded for it; all 0 before the first
+ * block with AGC on) and left (*state: E behind the block's last audio frame).  Any result may be NULL.  Reading the state
+ * waits for the tuner's work. */
+int wr_chan_get_agc(wr_tuner *tuner, int chan, int *enabled, float *target, unsigned int *floor_bits,
+                    unsigned int *step, unsigned int *state);
+/* *channels_on: receivers whose AGC the last submit ran; *launches: AGC kernels launched for this tuner so far (one per
+ * block and rate group with an AGC on, none otherwise).  Either may be NULL. */
+int wr_tuner_agc_info(wr_tuner *tuner, unsigned int *channels_on, unsigned long long *launches);
 #ifdef __cplusplus
 }
 #endif

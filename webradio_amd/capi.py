@@ -125,6 +125,13 @@ SIGNATURES = {
     "wr_tuner_chan_spectra": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(C.c_uint)]),
     "wr_tuner_chan_levels": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(C.c_uint)]),
     "wr_iq_levels": (C.c_int, [_vp, _vp, _sz, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "wr_agc_design": (C.c_int, [C.c_float, C.c_float, C.c_float, _u32, C.POINTER(C.c_float), C.POINTER(_u32),
+                                C.POINTER(_u32)]),
+    "wr_agc_rows": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "wr_chan_set_agc": (C.c_int, [_vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int]),
+    "wr_chan_get_agc": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(_u32),
+                                  C.POINTER(_u32), C.POINTER(_u32)]),
+    "wr_tuner_agc_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_ulonglong)]),
 }
 
 

@@ -100,6 +100,13 @@ struct Chan {
 	bool prev_dirty;           /* prev_iq must be uploaded to the slot */
 	bool phase_dirty;
 	bool dem_hist_reset;       /* audio filter history must be zeroed */
+	/* wr_chan_set_agc: the settings as given, in dB -- wrc_group_upload derives the kernel's numbers from them for the
+	 * audio rate of the group the channel sits in, so a filter change re-derives the step */
+	bool agc_on;
+	float agc_dbfs, agc_decay, agc_max_gain;
+	bool agc_reset;            /* the AGC's state word must be set to floor */
+	bool agc_used_on;          /* what the last upload gave the device (wr_chan_get_agc): AGC on, and ... */
+	WrAgcPar agc_used;         /* ... these numbers */
 };
 
 struct Group {
@@ -110,6 +117,11 @@ struct Group {
 	unsigned int l1b = WR_FIR_LENGTH;  /* ... of its second channel stage (k_tuner_iq2) */
 	int p2 = 0;                /* which iq2_hist set the next block reads */
 	bool use_gain = false, use_squelch = false;
+	/* some channel has its AGC on: the post stage runs with a scale of 1 and a gain of 1 in those channels' slots, does not
+	 * wait for the next launch, and k_agc_rows follows it on `audio` (wr_tuner.hip: submit_post) */
+	bool use_agc = false;
+	WrAgcPar *agc_par = nullptr;         /* [slots] */
+	unsigned int *agc_state = nullptr;   /* [slots] the envelope E behind the last block */
 	unsigned int slots;
 	size_t k1max, k2max;
 	WrGroupDev dev;
@@ -169,6 +181,7 @@ struct wr_tuner {
 	int in_par;
 	bool submitted;
 	float audio_scale;
+	unsigned long long agc_launches = 0;   /* launches of k_agc_rows so far (wr_tuner_agc_info) */
 	bool profiling;
 	unsigned int prof_stride;  /* 1: every submit's launch stamps its own start/stop; n > 1: one event pair
 	                              around every n consecutive submits (see wr_tuner_profile) */

@@ -128,3 +128,23 @@ void wrd_twiddles(unsigned int n, float *tw)
 		tw[2 * k + 1] = (float)(-sin(a));
 	}
 }
+
+/* wr_agc_design (include/webradio_amd.h): the three numbers of a receiver's AGC from its settings in dB.  The envelope
+ * lives in the bit pattern of a float, where an octave -- 20 log10(2) = 6.02 dB of amplitude -- is 2^23 units. */
+int wrd_agc_design(float target_dbfs, float decay_db_per_s, float max_gain_db, unsigned int audio_rate, float *target,
+                   unsigned int *floor_bits, unsigned int *step)
+{
+	if (!(target_dbfs >= -100.0f && target_dbfs <= 0.0f) || !(decay_db_per_s >= 0.0f && decay_db_per_s <= 1.0e4f) ||
+	    !(max_gain_db >= 0.0f && max_gain_db <= 120.0f) || !audio_rate)
+		return 1;                                               /* (a NaN fails every comparison) */
+	const double level = pow(10.0, (double)target_dbfs / 20.0);
+	const float floor_f = (float)(level / pow(10.0, (double)max_gain_db / 20.0));
+	if (!(floor_f >= 1.17549435e-38f))
+		return 1;
+	const double per_frame = (double)decay_db_per_s / (20.0 * log10(2.0)) * 8388608.0 / (double)audio_rate;
+	const long long units = llround(per_frame);
+	*target = (float)level;
+	memcpy(floor_bits, &floor_f, sizeof(*floor_bits));
+	*step = units > 0x80000000ll ? 0x80000000u : (unsigned int)units;
+	return 0;
+}

@@ -150,6 +150,18 @@ extern "C" int wr_lowpass_design_n(unsigned int fir_length, unsigned int passban
 	return WR_OK;
 }
 
+extern "C" int wr_agc_design(float target_dbfs, float decay_db_per_s, float max_gain_db, unsigned int audio_rate,
+                             float *target, unsigned int *floor_bits, unsigned int *step)
+{
+	if (!target || !floor_bits || !step || !audio_rate)
+		return wrc_fail(WR_ERR_ARG, "wr_agc_design: bad argument (a NULL result, or an audio rate of 0)");
+	if (wrd_agc_design(target_dbfs, decay_db_per_s, max_gain_db, audio_rate, target, floor_bits, step))
+		return wrc_fail(WR_ERR_ARG, "wr_agc_design: target %g dBFS (-100 .. 0), decay %g dB/s (0 .. 1e4), largest gain %g dB "
+		                "(0 .. 120), and a floor that is a normal float", (double)target_dbfs, (double)decay_db_per_s,
+		                (double)max_gain_db);
+	return WR_OK;
+}
+
 extern "C" int wr_spectrum_window(unsigned int fft_size, float *window_host)
 {
 	if (!window_host || !fft_size)
@@ -539,6 +551,42 @@ extern "C" int wr_iq_levels(wr_dev *d, const float *iq_dev, size_t nframes, floa
 		*mean_host = got[0];
 	if (peak_host)
 		*peak_host = got[1];
+	return WR_OK;
+}
+
+/* the AGC of a plain audio block (or of several rows of one): the tuner's kernel, parameters and state through scratch */
+extern "C" int wr_agc_rows(wr_dev *d, float *audio_dev, size_t row_stride, size_t nrows, size_t nframes,
+                           const float *target_host, const unsigned int *floor_bits_host, const unsigned int *step_host,
+                           unsigned int *state_host)
+{
+	if (!d || !audio_dev || !target_host || !floor_bits_host || !step_host || !state_host || !nrows || nrows > 0x7fffffffu ||
+	    (nrows > 1 && row_stride < nframes))
+		return wrc_fail(WR_ERR_ARG, "wr_agc_rows: bad argument (a NULL pointer, no rows, or rows that overlap)");
+	std::vector<WrAgcPar> par(nrows);
+	for (size_t r = 0; r < nrows; ++r) {
+		par[r] = WrAgcPar{target_host[r], floor_bits_host[r], step_host[r], 1.0f};
+		if (step_host[r] == WR_AGC_OFF)
+			continue;
+		/* the envelope stays a positive, finite, normal float: floor is one, and the state is none above FLT_MAX */
+		if (step_host[r] > 0x80000000u || floor_bits_host[r] < 0x00800000u || floor_bits_host[r] > 0x7f7fffffu ||
+		    state_host[r] > 0x7f7fffffu || !(target_host[r] > 0.0f) || !(target_host[r] <= 3.40282347e+38f))
+			return wrc_fail(WR_ERR_ARG, "wr_agc_rows: row %zu: step %u, floor bits 0x%08x, state 0x%08x, target %g", r,
+			                step_host[r], floor_bits_host[r], state_host[r], (double)target_host[r]);
+	}
+	if (!nframes)
+		return WR_OK;
+	g_block_kernel_calls.fetch_add(1, std::memory_order_relaxed);
+	DEV_SETTLE(d);
+	SCRATCH_GUARD(d);
+	if (int rc = wrc_dev_scratch(d, nrows * 5u))
+		return rc;
+	WrAgcPar *par_dev = (WrAgcPar *)d->scratch;
+	unsigned int *state_dev = (unsigned int *)(d->scratch + nrows * 4u);
+	HIP_TRY(hipMemcpyAsync(par_dev, par.data(), nrows * sizeof(WrAgcPar), hipMemcpyHostToDevice, d->stream));
+	HIP_TRY(hipMemcpyAsync(state_dev, state_host, nrows * sizeof(unsigned int), hipMemcpyHostToDevice, d->stream));
+	HIP_TRY(wrk_agc_rows(d->stream, audio_dev, row_stride, nrows, nframes, par_dev, state_dev, 1.0f));
+	HIP_TRY(hipMemcpyAsync(state_host, state_dev, nrows * sizeof(unsigned int), hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(wrc_dev_stream_sync(d));
 	return WR_OK;
 }
 

@@ -1,6 +1,6 @@
 /*
  * wr_internal.h -- internal C++ interface between the C ABI (wr_dev.hip, wr_tuner*.hip, wr_spectrum.hip), the host
- * design math (wr_design.cpp) and the kernels (wr_kernels.hip, wr_fft.hip, wr_levels.hip).
+ * design math (wr_design.cpp) and the kernels (wr_kernels.hip, wr_fft.hip, wr_levels.hip, wr_agc.hip).
  * Not installed; the public boundary is include/webradio_amd.h.
  */
 #ifndef WR_INTERNAL_H_
@@ -36,6 +36,9 @@ void     wrd_lowpass_design(unsigned int fir_length, unsigned int passband, unsi
 void     wrd_spectrum_window(unsigned int n, float *window);
 void     wrd_split_tables(float *hi_cs /* [256][2] cos,sin */, float *lo_cs /* [256][2] */);
 void     wrd_twiddles(unsigned int n, float *tw /* [n/2][2] cos,-sin of 2*pi*k/n */);
+/* wr_agc_design's arithmetic (in double); non-zero: an argument is a NaN or out of range, or the floor would be subnormal */
+int      wrd_agc_design(float target_dbfs, float decay_db_per_s, float max_gain_db, unsigned int audio_rate, float *target,
+                        unsigned int *floor_bits, unsigned int *step);
 
 /* ---- per-slot parameter block of one rate group of a tuner, device SoA ---- */
 struct WrGroupDev {
@@ -337,6 +340,20 @@ hipError_t wrk_fft_cols(hipStream_t st, const WrFftPlan &P, const float *iq, uns
 size_t     wrk_chan_levels_work(unsigned int cols, size_t k1);
 hipError_t wrk_chan_levels(hipStream_t st, const float *iq, size_t S, unsigned int cols, size_t k1, unsigned int d2, size_t k2,
                            const float *squelch, float *work, const float **out);
+
+/* ---- audio AGC (wr_agc.hip) ---- */
+struct WrAgcPar {                          /* one row's parameters */
+	float        target;               /* the level the peak is brought to, linear */
+	unsigned int floor_bits;           /* the envelope's lower bound, as a float's bits: target / the largest gain */
+	unsigned int step;                 /* what the envelope falls per frame, in units of a float's bit pattern; or one of: */
+	float        af_gain;              /* the row's af_gain factor (applied behind the AGC) */
+};
+#define WR_AGC_OFF  0xffffffffu            /* step: a row without AGC -- it gets the call's scale and nothing else */
+#define WR_AGC_IDLE 0xfffffffeu            /* step: a row that is nobody's (a tuner slot without a channel) -- left alone */
+/* in place on `nrows` rows of `nframes` floats, `row_stride` floats apart: include/webradio_amd.h's rule (wr_agc_rows) with
+ * par[row] and state[row] (read, and left as the row's last E), then `scale`; a workgroup per row */
+hipError_t wrk_agc_rows(hipStream_t st, float *audio, size_t row_stride, size_t nrows, size_t nframes, const WrAgcPar *par,
+                        unsigned int *state, float scale);
 
 hipError_t wrk_bins_to_db(hipStream_t st, const float *bins, unsigned int n, float *db);
 hipError_t wrk_waterfall_row(hipStream_t st, const float *bins, unsigned int n, unsigned int width, int hold,

@@ -103,6 +103,8 @@ static std::vector<GroupArray> group_arrays(Group *g)
 	add(&g->z_hist, (size_t)WR_HIST * S * 2);
 	add(&g->z_prev, S * 2);
 	add(&g->z_dem, (size_t)(g->l2 - 1) * S);
+	add(&g->agc_par, S);
+	add(&g->agc_state, S);
 	add2(D.prev_iq, S * 2);
 	add2(D.chan_iq, (g->k1max ? g->k1max : 1) * S * 2);
 	add2(D.dem, ((size_t)g->l2 - 1 + g->k1max) * S);
@@ -391,6 +393,7 @@ static int chan_unseat(wr_tuner *t, Chan &c, bool keep_state)
 	c.cs_hist_reset = true;
 	c.prev_dirty = keep_state;
 	c.phase_dirty = true;
+	c.agc_used_on = false;         /* (its envelope stays behind with the slot) */
 	return WR_OK;
 }
 
@@ -474,6 +477,7 @@ static int chan_seat(wr_tuner *t, int idx)
 	c.slot = slot;
 	c.cs_hist_reset = true;        /* fresh LowPass::block: zero history (lowpass.cxx:138-139) */
 	c.dem_hist_reset = true;
+	c.agc_reset = true;
 	c.prev_dirty = true;
 	c.phase_dirty = true;
 	return WR_OK;
@@ -618,6 +622,76 @@ extern "C" int wr_chan_set_squelch(wr_tuner *t, int chan, float threshold_dbfs, 
 		return wrc_fail(WR_ERR_ARG, "wr_chan_set_squelch: %g dBFS", (double)threshold_dbfs);
 	c->squelch = enable ? (float)pow(10.0, (double)threshold_dbfs / 10.0) : 0.0f;
 	chan_mark_dirty(t, c);
+	return WR_OK;
+}
+
+/* The control every AM / SSB listener expects beside them: a gain of the receiver's own that follows its audio's
+ * level (include/webradio_amd.h: the rule).  Staged like the two above; the kernel's numbers are derived when the group
+ * is uploaded, for the audio rate the channel then has. */
+extern "C" int wr_chan_set_agc(wr_tuner *t, int chan, float target_dbfs, float decay_db_per_s, float max_gain_db, int enable)
+{
+	Chan *c = chan_get(t, chan);
+	if (!c)
+		return g_settle_rc ? g_settle_rc : wrc_fail(WR_ERR_ARG, "wr_chan_set_agc: no channel %d", chan);
+	if (enable) {
+		float target;
+		unsigned int floor_bits, step;
+		if (wrd_agc_design(target_dbfs, decay_db_per_s, max_gain_db, 1u, &target, &floor_bits, &step))
+			return wrc_fail(WR_ERR_ARG, "wr_chan_set_agc: target %g dBFS (-100 .. 0), decay %g dB/s (0 .. 1e4), largest gain "
+			                "%g dB (0 .. 120)", (double)target_dbfs, (double)decay_db_per_s, (double)max_gain_db);
+		if (!c->agc_on)
+			c->agc_reset = true;                    /* coming on: the envelope starts from floor; new settings keep it */
+		c->agc_dbfs = target_dbfs;
+		c->agc_decay = decay_db_per_s;
+		c->agc_max_gain = max_gain_db;
+	}
+	c->agc_on = enable != 0;
+	chan_mark_dirty(t, c);
+	return WR_OK;
+}
+
+extern "C" int wr_chan_get_agc(wr_tuner *t, int chan, int *enabled, float *target, unsigned int *floor_bits,
+                               unsigned int *step, unsigned int *state)
+{
+	Chan *c = chan_get(t, chan);
+	if (!c)
+		return g_settle_rc ? g_settle_rc : wrc_fail(WR_ERR_ARG, "wr_chan_get_agc: no channel %d", chan);
+	const bool on = c->agc_used_on && c->group >= 0;
+	if (enabled)
+		*enabled = on ? 1 : 0;
+	if (target)
+		*target = on ? c->agc_used.target : 0.0f;
+	if (floor_bits)
+		*floor_bits = on ? c->agc_used.floor_bits : 0u;
+	if (step)
+		*step = on ? c->agc_used.step : 0u;
+	if (state) {
+		*state = 0;
+		if (on) {
+			Group *g = t->groups[c->group];
+			if (wrc_dev_bind(t->dev))
+				return WR_ERR_HIP;
+			if (int rc = wrc_tuner_quiesce(t))
+				return rc;
+			HIP_TRY(hipMemcpy(state, g->agc_state + c->slot, sizeof(unsigned int), hipMemcpyDeviceToHost));
+		}
+	}
+	return WR_OK;
+}
+
+extern "C" int wr_tuner_agc_info(wr_tuner *t, unsigned int *channels_on, unsigned long long *launches)
+{
+	if (!t)
+		return wrc_fail(WR_ERR_ARG, "wr_tuner_agc_info: tuner is NULL");
+	if (int rc = wrc_settle_held(t))
+		return rc;
+	if (channels_on) {
+		*channels_on = 0;
+		for (const Chan &c : t->chans)
+			*channels_on += c.in_use && c.group >= 0 && c.agc_used_on ? 1u : 0u;
+	}
+	if (launches)
+		*launches = t->agc_launches;
 	return WR_OK;
 }
 
@@ -827,7 +901,9 @@ int wrc_group_upload(wr_tuner *t, Group *g)
 	std::vector<float> taps1(S * WR_FIR_LENGTH, 0.0f), taps2(S * g->l2, 0.0f);
 	std::vector<float> taps1b(g->d1b ? S * g->l1b : 0, 0.0f), gain(S, 1.0f), squelch(S, 0.0f);
 	std::vector<float> taps1L(g->l1 > WR_FIR_LENGTH ? S * g->l1 : 0, 0.0f);
-	g->use_gain = g->use_squelch = false;
+	std::vector<WrAgcPar> agc(S, WrAgcPar{0.0f, 0u, WR_AGC_IDLE, 1.0f});
+	const unsigned int audio_rate = t->input_rate / g->d1 / (g->d1b ? g->d1b : 1u) / g->d2;
+	g->use_gain = g->use_squelch = g->use_agc = false;
 	for (size_t s = 0; s < S; ++s) {
 		int ci = g->owner[s];
 		if (ci < 0)
@@ -846,9 +922,20 @@ int wrc_group_upload(wr_tuner *t, Group *g)
 		if (g->l1 > WR_FIR_LENGTH)
 			for (unsigned int j = 0; j < g->l1; ++j)
 				taps1L[(size_t)j * S + s] = c.taps_long[j];
-		gain[s] = c.gain;
+		/* a channel with AGC: its af_gain follows the AGC (k_agc_rows), the post stage sees a gain of 1 */
+		agc[s].step = WR_AGC_OFF;
+		if (c.agc_on) {
+			WrAgcPar &a = agc[s];
+			if (wrd_agc_design(c.agc_dbfs, c.agc_decay, c.agc_max_gain, audio_rate, &a.target, &a.floor_bits, &a.step))
+				return wrc_fail(WR_ERR_ARG, "AGC of channel %d: no step for an audio rate of %u Hz", ci, audio_rate);
+			a.af_gain = c.gain;
+			c.agc_used = a;
+			g->use_agc = true;
+		}
+		c.agc_used_on = c.agc_on;
+		gain[s] = c.agc_on ? 1.0f : c.gain;
 		squelch[s] = c.squelch;
-		g->use_gain = g->use_gain || c.gain != 1.0f;
+		g->use_gain = g->use_gain || gain[s] != 1.0f;
 		g->use_squelch = g->use_squelch || c.squelch > 0.0f;
 	}
 	GroupFilters F;
@@ -881,6 +968,8 @@ int wrc_group_upload(wr_tuner *t, Group *g)
 	HIP_TRY(hipMemcpyAsync(g->dev.squelch, squelch.data(), S * sizeof(float), hipMemcpyHostToDevice, st));
 	if (g->d1b)
 		HIP_TRY(hipMemcpyAsync(g->dev.taps1b, taps1b.data(), taps1b.size() * sizeof(float), hipMemcpyHostToDevice, st));
+	if (g->use_agc)
+		HIP_TRY(hipMemcpyAsync(g->agc_par, agc.data(), S * sizeof(WrAgcPar), hipMemcpyHostToDevice, st));
 	/* what the setters staged for the channels themselves: phase, Demodulator prev_i/q, histories to be emptied */
 	for (size_t s = 0; s < S; ++s) {
 		int ci = g->owner[s];
@@ -916,6 +1005,10 @@ int wrc_group_upload(wr_tuner *t, Group *g)
 			/* 63 history rows of this slot: one float per row, stride S */
 			HIP_TRY(hipMemset2DAsync(g->dev.dem[g->parity] + s, S * sizeof(float), 0, sizeof(float), g->l2 - 1, st));
 			c.dem_hist_reset = false;
+		}
+		if (c.agc_on && c.agc_reset) {
+			HIP_TRY(hipMemcpyAsync(g->agc_state + s, &c.agc_used.floor_bits, sizeof(unsigned int), hipMemcpyHostToDevice, st));
+			c.agc_reset = false;
 		}
 	}
 	HIP_TRY(hipStreamSynchronize(st));     /* host vectors go out of scope */
@@ -1008,6 +1101,10 @@ extern "C" int wr_tuner_profile_read(wr_tuner *t, unsigned int *launches, double
  * truncates per block), which a merged block would not */
 static bool block_can_be_held(const wr_tuner *t, size_t nframes)
 {
+	/* (nor a block of a tuner with an AGC on: its groups' post stages go out block by block) */
+	for (const Chan &c : t->chans)
+		if (c.in_use && c.agc_on)
+			return false;
 	for (const Group *g : t->groups) {
 		if (g->active <= 0)
 			continue;
@@ -1130,11 +1227,15 @@ static int submit_post(wr_tuner *t, Group *g, const Submit &S, const WrTunerLaun
 	 * workgroups that ride are compiled for 64 taps) */
 	/* (r05: a group with a second channel stage defers as well -- its post stage reads chan_iq2, which the NEXT block's
 	 * k_tuner_iq2 does not touch: that one writes the other buffer, behind the launch the post stage rides in) */
+	/* (a group with an AGC on does not defer: k_agc_rows follows the post stage on the group's audio, below) */
 	const bool defer = !two_kernels && (g->l1 <= WR_FIR_LENGTH || long_rides) && Lp.k1 && t->defer_post &&
-	                   t->nco_mode == WR_NCO_ROTATE && g->l2 == WR_FIR_LENGTH;
+	                   t->nco_mode == WR_NCO_ROTATE && g->l2 == WR_FIR_LENGTH && !g->use_agc;
+	WrTunerLaunch Lq = Lp;
+	if (g->use_agc)
+		Lq.audio_scale = 1.0f;                  /* the sink's scale comes behind the AGC: k_agc_rows applies it to every slot in use */
 	if (two_kernels) {
-		HIP_TRY(wrk_tuner_demod(st, Lp, Gp));
-		HIP_TRY(wrk_tuner_audio(st, Lp, Gp));
+		HIP_TRY(wrk_tuner_demod(st, Lq, Gp));
+		HIP_TRY(wrk_tuner_audio(st, Lq, Gp));
 	} else if (defer) {
 		g->post_pending = true;
 		g->post_args = wrk_post_args(Lp, Gp);
@@ -1145,7 +1246,12 @@ static int submit_post(wr_tuner *t, Group *g, const Submit &S, const WrTunerLaun
 		g->post_args.host_stride = Lp.k2;           /* the ring's rows lie back to back (RingSlot::stride = frames) */
 		g->pend_direct = g->post_args.audio_host != nullptr;
 	} else {
-		HIP_TRY(wrk_tuner_post(st, Lp, Gp));
+		HIP_TRY(wrk_tuner_post(st, Lq, Gp));
+	}
+	if (g->use_agc && Lp.k2) {
+		/* whichever way the audio was made: in place, before the ring's copy (and every getter) reads it */
+		HIP_TRY(wrk_agc_rows(st, g->dev.audio, g->k2max, L.slots_used, Lp.k2, g->agc_par, g->agc_state, t->audio_scale));
+		++t->agc_launches;
 	}
 	if (!defer)
 		return wrc_ring_push(t, g, S.seq, Lp.k2, L.slots_used, false);
@@ -1675,6 +1781,7 @@ extern "C" int wr_chan_reset_history(wr_tuner *t, int chan)
 		return g_settle_rc ? g_settle_rc : wrc_fail(WR_ERR_ARG, "wr_chan_reset_history: no channel %d", chan);
 	c->cs_hist_reset = true;
 	c->dem_hist_reset = true;
+	c->agc_reset = true;
 	chan_mark_dirty(t, c);
 	return WR_OK;
 }
@@ -1719,6 +1826,11 @@ extern "C" int wr_tuner_seek(wr_tuner *t, unsigned long long frame)
 			c.phaseL = (unsigned int)((unsigned long long)c.stepL * frame);     /* host mirror; mod 2^32, left-aligned */
 			c.phase_dirty = c.prev_dirty = c.cs_hist_reset = c.dem_hist_reset = false;
 			c.prev_iq[0] = c.prev_iq[1] = 0.0f;
+			if (c.agc_on) {
+				/* the envelope starts from floor again: with the next submit's upload (the one thing a seek leaves staged) */
+				c.agc_reset = true;
+				g->dirty = true;
+			}
 		}
 		if (lazy) {
 			g->seek_pending = true;

@@ -163,6 +163,8 @@ int wrc_stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, bool *
 	if (g->dirty)
 		if (int rc = wrc_group_upload(t, g))
 			return rc;
+	if (g->use_agc)                                         /* k_agc_rows follows every block's post stage: the ordinary way */
+		return WR_OK;
 	const unsigned int used = wrc_group_slots_used(g), groups = used / 64u;
 	if (!groups || groups > 16u)
 		return WR_OK;

@@ -10,6 +10,14 @@ from . import capi
 from .capi import check, ptr
 
 
+def agc_design(target_dbfs=-12.0, decay_db_per_s=20.0, max_gain_db=60.0, audio_rate=10_000):
+    """(target float32, floor_bits, step) of an AGC with these settings at this audio rate (wr_agc_design); needs no device."""
+    target, floor_bits, step = C.c_float(), C.c_uint(), C.c_uint()
+    check(capi.load().wr_agc_design(C.c_float(target_dbfs), C.c_float(decay_db_per_s), C.c_float(max_gain_db), audio_rate,
+                                    C.byref(target), C.byref(floor_bits), C.byref(step)))
+    return np.float32(target.value), floor_bits.value, step.value
+
+
 class Device:
     """wr_dev: a gfx950 device + the HIP stream all work is issued on."""
 
@@ -95,6 +103,18 @@ class Device:
         mean, peak = C.c_float(), C.c_float()
         check(self.lib.wr_iq_levels(self.h, C.c_void_p(p), nframes, C.byref(mean), C.byref(peak)))
         return np.float32(mean.value), np.float32(peak.value)
+
+    def agc_rows(self, p, row_stride, nrows, nframes, target, floor_bits, step, state):
+        """AGC in place on nrows rows of nframes floats at device pointer p, row_stride floats apart (wr_agc_rows): per row a
+        target (float32), floor_bits, step (0xffffffff: no AGC on that row) and the state word; returns the new states."""
+        target = np.ascontiguousarray(target, dtype=np.float32)
+        floor_bits = np.ascontiguousarray(floor_bits, dtype=np.uint32)
+        step = np.ascontiguousarray(step, dtype=np.uint32)
+        state = np.array(state, dtype=np.uint32)
+        assert target.size == floor_bits.size == step.size == state.size == nrows
+        check(self.lib.wr_agc_rows(self.h, C.c_void_p(p), row_stride, nrows, nframes, ptr(target), ptr(floor_bits),
+                                   ptr(step), ptr(state)))
+        return state
 
 
 class Tuner:
@@ -232,6 +252,26 @@ class Tuner:
 
     def set_squelch(self, ch, threshold_dbfs, enable=True):
         check(self.lib.wr_chan_set_squelch(self.h, ch, C.c_float(threshold_dbfs), 1 if enable else 0))
+
+    def set_agc(self, ch, target_dbfs=-12.0, decay_db_per_s=20.0, max_gain_db=60.0, enable=True):
+        """The receiver's AGC (wr_chan_set_agc): peaks are brought to target_dbfs, the gain recovers at decay_db_per_s and
+        never exceeds max_gain_db; from the next block on."""
+        check(self.lib.wr_chan_set_agc(self.h, ch, C.c_float(target_dbfs), C.c_float(decay_db_per_s),
+                                       C.c_float(max_gain_db), 1 if enable else 0))
+
+    def get_agc(self, ch):
+        """(enabled, target float32, floor_bits, step, state) as the last submit used and left them (wr_chan_get_agc)"""
+        on, target = C.c_int(), C.c_float()
+        floor_bits, step, state = C.c_uint(), C.c_uint(), C.c_uint()
+        check(self.lib.wr_chan_get_agc(self.h, ch, C.byref(on), C.byref(target), C.byref(floor_bits), C.byref(step),
+                                       C.byref(state)))
+        return bool(on.value), np.float32(target.value), floor_bits.value, step.value, state.value
+
+    def agc_info(self):
+        """(receivers whose AGC the last submit ran, AGC kernel launches so far) (wr_tuner_agc_info)"""
+        on, launches = C.c_uint(), C.c_ulonglong()
+        check(self.lib.wr_tuner_agc_info(self.h, C.byref(on), C.byref(launches)))
+        return on.value, launches.value
 
     def set_mode(self, ch, mode):
         check(self.lib.wr_chan_set_mode(self.h, ch, mode))
