@@ -53,6 +53,8 @@ extern "C" {
                                     Added to 6 later: wr_tuner_chan_spectra.
                                     Added to 6 later: wr_tuner_chan_levels, wr_iq_levels.
                                     Added to 6 later: wr_agc_design, wr_agc_rows, wr_chan_set_agc, wr_chan_get_agc, wr_tuner_agc_info.
+                                    Added to 6 later: wr_tone_step, wr_tones_create, wr_tones_destroy, wr_tones_reset,
+                                                      wr_tones_push_rows, wr_tuner_tones_push, wr_tones_read.
                                     Nothing of an earlier version changed or removed */
 #define WR_FIR_LENGTH    64      /* dsp/lowpass.cxx:39  FIR_LENGTH */
 #define WR_TABLE_SIZE    65536   /* dsp/downconverter.cxx:35 LOOKUP_BITS 16 */
@@ -98,6 +100,7 @@ typedef struct wr_dev      wr_dev;
 typedef struct wr_tuner    wr_tuner;
 typedef struct wr_spectrum wr_spectrum;
 typedef struct wr_ring     wr_ring;
+typedef struct wr_tones    wr_tones;
 
 /* ------------------------------------------------------------------ misc -- */
 int         wr_abi_version(void);
@@ -669,6 +672,67 @@ int wr_chan_get_agc(wr_tuner *tuner, int chan, int *enabled, float *target, unsi
 /* *channels_on: receivers whose AGC the last submit ran; *launches: AGC kernels launched for this tuner so far (one per
  * block and rate group with an AGC on, none otherwise).  Either may be NULL. */
 int wr_tuner_agc_info(wr_tuner *tuner, unsigned int *channels_on, unsigned long long *launches);
+
+/* TONE BANK: which sub-audible tone (CTCSS) rides on each receiver's audio -- the basis of tone squelch; the same
+ * mechanism answers "is there a 1750 Hz burst" and "which DTMF pair".  The reference has nothing of the kind.  A spectrum
+ * cannot stand in for it: neighbouring CTCSS tones are 2.3 Hz apart, which needs 0.25 - 0.5 s of audio -- many tuner
+ * blocks, and the spectrum calls look at one.  A bank is up to 64 tone correlators per row that integrate across blocks.
+ *
+ * THE RULE is this library's own definition, as the ones of af_gain, squelch and AGC are.  A bank has
+ *   `ntones` tones, 1 to 64, each an unsigned 32-bit phase step (wr_tone_step);
+ *   a window of W audio frames, 16 <= W <= 65536;
+ *   `max_rows` rows, 1 to 65535.
+ * Every row is an independent audio stream cut into consecutive windows of W frames; the count starts at the row's first
+ * pushed frame, or after a reset.  For frame j (0 ... W-1) of a window, with audio value v:
+ *   v'   = 0.0f if (bits(v) & 0x7fffffff) >= 0x7f800000 (inf, NaN), else v
+ *   w    = min(max(v', -64.0f), 64.0f) * 16777216.0f          exact; |w| <= 2^30
+ *   p    = (uint32)(j * step_t)                                wraps mod 2^32
+ *   i    = p >> 20                                             12 bits
+ *   s    = T12[i],  c = T12[(i + 1024) & 4095]                 T12[i] = wr_sin_table()[16 * i]
+ *   I_t += (int64) rint(w * c)      Q_t += (int64) rint(w * s)
+ *   qv   = (int64) rint(w)          E  += (qv * qv) >> 14      E is per row, not per tone
+ * Each of w * c and w * s is one float32 product rounded once; rint rounds to nearest even, and its result fits an int32.
+ * At a window's last frame (I_t, Q_t, E) are latched as the row's result and the row's window count goes up by one; the
+ * accumulators then start again from 0.  |I|, |Q| <= 2^46 and E <= 2^62: nothing wraps.
+ * Everything is integer sums of per-frame terms, so a window's result has ONE value for any grid, any cut of the stream
+ * into pushes and any order of summation (integer atomics would not change it); a restatement in numpy is bit-identical.
+ * The share of the window's audio power that sits in tone t, computed by the caller in double:
+ *   rho_t = 2 (I_t^2 + Q_t^2) / (W * E * 2^14)
+ * about 1 for a pure tone at f_t, about 2 / W per tone for white noise; the rectangular window leaks
+ * sinc^2(df * W / rate) of it into a tone df away.
+ * Left out on purpose: muting audio by tone (the detector reports, the caller decides); a host-side C++ class (the
+ * reference has none to mirror, and af_gain, squelch and AGC have none either); window functions other than the
+ * rectangular one; per-receiver tone lists (one list per bank); time sharding.
+ *
+ * wr_tone_step: *step = llround(hz / audio_rate * 2^32); needs no device.  WR_ERR_ARG unless 0 < hz < audio_rate / 2. */
+int wr_tone_step(double hz, unsigned int audio_rate, unsigned int *step);
+/* WR_ERR_ARG: ntones outside 1..64, window outside 16..65536, max_rows outside 1..65535, a step of 0 or >= 2^31. */
+int wr_tones_create(wr_tones **bank, wr_dev *dev, unsigned int max_rows, const unsigned int *steps_host,
+                    unsigned int ntones, unsigned int window);
+int wr_tones_destroy(wr_tones *bank);
+/* Sets the row's accumulators, fill, window count and latched result to 0: the row begins a new stream.  row < 0: every
+ * row.  This is what a caller does after wr_tuner_seek, wr_chan_reset_history or a retune of the receiver in that slot:
+ * the bank does not watch the tuner.  Asynchronous on the device's stream. */
+int wr_tones_reset(wr_tones *bank, int row);
+/* The rule on a plain block of rows in device memory: `nrows` rows of `nframes` floats, `row_stride` floats apart; row r of
+ * the call is row r of the bank.  Consecutive calls continue the streams whatever the lengths.  A block may hold no
+ * window end, one, or many: with many, only the last complete window is latched and the count rises by all of them.
+ * Asynchronous on the device's stream; counted by wr_block_kernel_calls.  WR_ERR_ARG: NULL arguments, nrows > max_rows,
+ * row_stride < nframes with several rows. */
+int wr_tones_push_rows(wr_tones *bank, const float *audio_dev, size_t row_stride, size_t nrows, size_t nframes);
+/* Pushes the last submit's audio rows of every channel slot: WR_STAGE_AUDIO as wr_tuner_audio_dev shows it -- after
+ * squelch, AGC, af_gain and scale; row = wr_chan_slot.  Rows are counted as wr_tuner_chan_levels counts them (*slots: whole
+ * lane groups of 64); rows of slots that hold no channel carry no meaning.  rho does not depend on af_gain and scale:
+ * they multiply I, Q and sqrt(E) alike.  Like every getter it sends held blocks out, launches a pending post stage and
+ * closes an open streaming launch; it changes nothing the next block depends on.  Asynchronous behind that.
+ * WR_ERR_STATE: nothing submitted yet, several rate groups, the same submit pushed twice (the bank remembers the tuner's
+ * submit count).  WR_ERR_ARG: max_rows below the slot count, a bank of another device. */
+int wr_tuner_tones_push(wr_tuner *tuner, wr_tones *bank, unsigned int *slots);
+/* The latched result (iq_host[rows][ntones][2]: I, Q; energy_host[rows]: E), the window count and the frames in the open
+ * window of every row; *rows = max_rows.  Any array may be NULL, all four NULL is WR_ERR_ARG.  Waits for the device's
+ * stream. */
+int wr_tones_read(wr_tones *bank, long long *iq_host /* [rows][ntones][2] */, long long *energy_host,
+                  unsigned long long *windows_host, unsigned int *fill_host, unsigned int *rows);
 #ifdef __cplusplus
 }
 #endif

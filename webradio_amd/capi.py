@@ -132,6 +132,13 @@ SIGNATURES = {
     "wr_chan_get_agc": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(_u32),
                                   C.POINTER(_u32), C.POINTER(_u32)]),
     "wr_tuner_agc_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_ulonglong)]),
+    "wr_tone_step": (C.c_int, [C.c_double, _u32, C.POINTER(_u32)]),
+    "wr_tones_create": (C.c_int, [C.POINTER(_vp), _vp, _u32, _vp, _u32, _u32]),
+    "wr_tones_destroy": (C.c_int, [_vp]),
+    "wr_tones_reset": (C.c_int, [_vp, C.c_int]),
+    "wr_tones_push_rows": (C.c_int, [_vp, _vp, _sz, _sz, _sz]),
+    "wr_tuner_tones_push": (C.c_int, [_vp, _vp, C.POINTER(_u32)]),
+    "wr_tones_read": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),
 }
 
 

@@ -285,6 +285,17 @@ struct wr_spectrum {
 	unsigned long long deferred_pushes = 0, resolves = 0;
 };
 
+struct wr_tones {
+	wr_dev *dev;
+	unsigned int max_rows, ntones, window;
+	WrTonesRow *rows;          /* device, [max_rows] */
+	float *t12;                /* device, [4096]: every 16th entry of the reference sine table */
+	unsigned int *steps;       /* device, [64]: the tones' phase steps, 0 beyond ntones */
+	/* wr_tuner_tones_push: whose submit, and which, the bank took last -- the same one is not pushed twice */
+	const wr_tuner *last_tuner = nullptr;
+	unsigned long long last_seq = 0;
+};
+
 /* ------------------------------------------------------------------ helpers that cross files -- */
 
 /* wr_dev.hip */

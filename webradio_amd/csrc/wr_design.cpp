@@ -148,3 +148,12 @@ int wrd_agc_design(float target_dbfs, float decay_db_per_s, float max_gain_db, u
 	*step = units > 0x80000000ll ? 0x80000000u : (unsigned int)units;
 	return 0;
 }
+
+/* wr_tone_step (include/webradio_amd.h): a tone's phase step per audio frame, in units of 2^-32 of a turn */
+int wrd_tone_step(double hz, unsigned int audio_rate, unsigned int *step)
+{
+	if (!audio_rate || !(hz > 0.0) || !(hz < (double)audio_rate / 2.0))       /* (a NaN fails every comparison) */
+		return 1;
+	*step = (unsigned int)llround(hz / (double)audio_rate * 4294967296.0);
+	return 0;
+}

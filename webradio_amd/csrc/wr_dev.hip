@@ -590,6 +590,150 @@ extern "C" int wr_agc_rows(wr_dev *d, float *audio_dev, size_t row_stride, size_
 	return WR_OK;
 }
 
+/* ------------------------------------------------------------------ tone bank -- */
+
+extern "C" int wr_tone_step(double hz, unsigned int audio_rate, unsigned int *step)
+{
+	if (!step)
+		return wrc_fail(WR_ERR_ARG, "wr_tone_step: step is NULL");
+	if (wrd_tone_step(hz, audio_rate, step))
+		return wrc_fail(WR_ERR_ARG, "wr_tone_step: %g Hz is not inside (0, %g), half the audio rate", hz, (double)audio_rate / 2.0);
+	return WR_OK;
+}
+
+extern "C" int wr_tones_create(wr_tones **bank, wr_dev *d, unsigned int max_rows, const unsigned int *steps_host,
+                               unsigned int ntones, unsigned int window)
+{
+	if (!bank || !d || !steps_host)
+		return wrc_fail(WR_ERR_ARG, "wr_tones_create: bad argument (NULL bank, dev or steps_host)");
+	if (!max_rows || max_rows > 65535u || !ntones || ntones > WR_LANES || window < 16u || window > 65536u)
+		return wrc_fail(WR_ERR_ARG, "wr_tones_create: %u rows (1 .. 65535), %u tones (1 .. 64), a window of %u frames "
+		                "(16 .. 65536)", max_rows, ntones, window);
+	unsigned int steps[WR_LANES] = {0};
+	for (unsigned int t = 0; t < ntones; ++t) {
+		if (!steps_host[t] || steps_host[t] >= 0x80000000u)
+			return wrc_fail(WR_ERR_ARG, "wr_tones_create: tone %u: a step of %u is not inside (0, 2^31)", t, steps_host[t]);
+		steps[t] = steps_host[t];
+	}
+	if (wrc_dev_bind(d))
+		return WR_ERR_HIP;
+	DEV_SETTLE(d);
+	std::vector<float> table(WR_TABLE_SIZE), t12(4096);
+	wrd_sin_table(table.data());
+	for (unsigned int i = 0; i < 4096u; ++i)
+		t12[i] = table[16u * i];
+	wr_tones *b = new (std::nothrow) wr_tones();
+	if (!b)
+		return wrc_fail(WR_ERR_ARG, "wr_tones_create: out of memory");
+	b->dev = d;
+	b->max_rows = max_rows;
+	b->ntones = ntones;
+	b->window = window;
+	b->rows = nullptr;
+	b->t12 = nullptr;
+	b->steps = nullptr;
+	hipError_t e = hipMalloc((void **)&b->rows, (size_t)max_rows * sizeof(WrTonesRow));
+	if (e == hipSuccess)
+		e = hipMalloc((void **)&b->t12, t12.size() * sizeof(float));
+	if (e == hipSuccess)
+		e = hipMalloc((void **)&b->steps, sizeof(steps));
+	if (e == hipSuccess)
+		e = hipMemsetAsync(b->rows, 0, (size_t)max_rows * sizeof(WrTonesRow), d->stream);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(b->t12, t12.data(), t12.size() * sizeof(float), hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(b->steps, steps, sizeof(steps), hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess)
+		e = wrc_dev_stream_sync(d);                             /* (the copies' sources are this call's own) */
+	if (e != hipSuccess) {
+		wr_tones_destroy(b);
+		return wrc_fail(WR_ERR_HIP, "wr_tones_create: %s", hipGetErrorString(e));
+	}
+	*bank = b;
+	return WR_OK;
+}
+
+extern "C" int wr_tones_destroy(wr_tones *b)
+{
+	if (!b)
+		return WR_OK;
+	(void)hipSetDevice(b->dev->device);
+	(void)wrc_dev_stream_sync(b->dev);
+	(void)hipFree(b->rows);
+	(void)hipFree(b->t12);
+	(void)hipFree(b->steps);
+	delete b;
+	return WR_OK;
+}
+
+extern "C" int wr_tones_reset(wr_tones *b, int row)
+{
+	if (!b)
+		return wrc_fail(WR_ERR_ARG, "wr_tones_reset: bank is NULL");
+	if (row >= 0 && (unsigned int)row >= b->max_rows)
+		return wrc_fail(WR_ERR_ARG, "wr_tones_reset: row %d of a bank of %u", row, b->max_rows);
+	wr_dev *d = b->dev;
+	if (wrc_dev_bind(d))
+		return WR_ERR_HIP;
+	DEV_SETTLE(d);
+	/* a row that begins its stream is all zero: accumulators, latched result, window count and fill */
+	if (row < 0)
+		HIP_TRY(hipMemsetAsync(b->rows, 0, (size_t)b->max_rows * sizeof(WrTonesRow), d->stream));
+	else
+		HIP_TRY(hipMemsetAsync(b->rows + row, 0, sizeof(WrTonesRow), d->stream));
+	return WR_OK;
+}
+
+extern "C" int wr_tones_push_rows(wr_tones *b, const float *audio_dev, size_t row_stride, size_t nrows, size_t nframes)
+{
+	if (!b || !audio_dev)
+		return wrc_fail(WR_ERR_ARG, "wr_tones_push_rows: bad argument (NULL bank or audio_dev)");
+	if (nrows > b->max_rows || (nrows > 1 && row_stride < nframes) || nframes > ((size_t)1 << 40))
+		return wrc_fail(WR_ERR_ARG, "wr_tones_push_rows: %zu rows for a bank of %u, or rows of %zu frames that overlap at a "
+		                "stride of %zu, or more than 2^40 frames", nrows, b->max_rows, nframes, row_stride);
+	if (!nrows || !nframes)
+		return WR_OK;
+	wr_dev *d = b->dev;
+	if (wrc_dev_bind(d))
+		return WR_ERR_HIP;
+	g_block_kernel_calls.fetch_add(1, std::memory_order_relaxed);
+	DEV_SETTLE(d);
+	HIP_TRY(wrk_tones_push(d->stream, audio_dev, row_stride, nrows, nframes, b->rows, b->t12, b->steps, b->ntones, b->window));
+	return WR_OK;
+}
+
+extern "C" int wr_tones_read(wr_tones *b, long long *iq_host, long long *energy_host, unsigned long long *windows_host,
+                             unsigned int *fill_host, unsigned int *rows)
+{
+	if (!b)
+		return wrc_fail(WR_ERR_ARG, "wr_tones_read: bank is NULL");
+	if (!iq_host && !energy_host && !windows_host && !fill_host)
+		return wrc_fail(WR_ERR_ARG, "wr_tones_read: no array to fill");
+	wr_dev *d = b->dev;
+	if (wrc_dev_bind(d))
+		return WR_ERR_HIP;
+	DEV_SETTLE(d);
+	const char *base = (const char *)b->rows;
+	const size_t pitch = sizeof(WrTonesRow), n = b->max_rows;
+	if (iq_host) {
+		const size_t width = (size_t)b->ntones * 2u * sizeof(long long);
+		HIP_TRY(hipMemcpy2DAsync(iq_host, width, base + offsetof(WrTonesRow, lat), pitch, width, n, hipMemcpyDeviceToHost, d->stream));
+	}
+	if (energy_host)
+		HIP_TRY(hipMemcpy2DAsync(energy_host, sizeof(long long), base + offsetof(WrTonesRow, lat_e), pitch, sizeof(long long), n,
+		                         hipMemcpyDeviceToHost, d->stream));
+	if (windows_host)
+		HIP_TRY(hipMemcpy2DAsync(windows_host, sizeof(unsigned long long), base + offsetof(WrTonesRow, windows), pitch,
+		                         sizeof(unsigned long long), n, hipMemcpyDeviceToHost, d->stream));
+	if (fill_host)
+		HIP_TRY(hipMemcpy2DAsync(fill_host, sizeof(unsigned int), base + offsetof(WrTonesRow, fill), pitch, sizeof(unsigned int), n,
+		                         hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(wrc_dev_stream_sync(d));
+	if (rows)
+		*rows = b->max_rows;
+	return WR_OK;
+}
+
 extern "C" int wr_u8_to_f32(wr_dev *d, const uint8_t *in_dev, float *out_dev, size_t count)
 {
 	if (!d || (count && (!in_dev || !out_dev)))

@@ -1,6 +1,6 @@
 /*
  * wr_internal.h -- internal C++ interface between the C ABI (wr_dev.hip, wr_tuner*.hip, wr_spectrum.hip), the host
- * design math (wr_design.cpp) and the kernels (wr_kernels.hip, wr_fft.hip, wr_levels.hip, wr_agc.hip).
+ * design math (wr_design.cpp) and the kernels (wr_kernels.hip, wr_fft.hip, wr_levels.hip, wr_agc.hip, wr_tones.hip).
  * Not installed; the public boundary is include/webradio_amd.h.
  */
 #ifndef WR_INTERNAL_H_
@@ -39,6 +39,8 @@ void     wrd_twiddles(unsigned int n, float *tw /* [n/2][2] cos,-sin of 2*pi*k/n
 /* wr_agc_design's arithmetic (in double); non-zero: an argument is a NaN or out of range, or the floor would be subnormal */
 int      wrd_agc_design(float target_dbfs, float decay_db_per_s, float max_gain_db, unsigned int audio_rate, float *target,
                         unsigned int *floor_bits, unsigned int *step);
+/* wr_tone_step's arithmetic (in double); non-zero unless 0 < hz < audio_rate / 2 */
+int      wrd_tone_step(double hz, unsigned int audio_rate, unsigned int *step);
 
 /* ---- per-slot parameter block of one rate group of a tuner, device SoA ---- */
 struct WrGroupDev {
@@ -354,6 +356,21 @@ struct WrAgcPar {                          /* one row's parameters */
  * par[row] and state[row] (read, and left as the row's last E), then `scale`; a workgroup per row */
 hipError_t wrk_agc_rows(hipStream_t st, float *audio, size_t row_stride, size_t nrows, size_t nframes, const WrAgcPar *par,
                         unsigned int *state, float scale);
+
+/* ---- tone bank (wr_tones.hip) ---- */
+struct WrTonesRow {                        /* everything a bank holds of one row; all zero: a row that begins its stream */
+	long long acc[WR_LANES][2];        /* I, Q of the open window, per tone */
+	long long lat[WR_LANES][2];        /* I, Q of the last complete window */
+	long long part[2][WR_LANES][2];    /* what a push's workgroups add up: [the last window that ends in it, the open one behind
+	                                      it][tone][I, Q]; zero between pushes */
+	long long acc_e, lat_e, part_e[2]; /* the same three for E */
+	unsigned long long windows;        /* complete windows so far */
+	unsigned int fill, pad;            /* frames in the open window, < window */
+};
+/* include/webradio_amd.h's rule (wr_tones_push_rows) on `nrows` rows of `nframes` floats, `row_stride` floats apart: row r
+ * goes into rows[r]; t12[4096] is every 16th entry of the sine table, steps[64] the tones' phase steps (0 beyond ntones) */
+hipError_t wrk_tones_push(hipStream_t st, const float *audio, size_t row_stride, size_t nrows, size_t nframes, WrTonesRow *rows,
+                          const float *t12, const unsigned int *steps, unsigned int ntones, unsigned int window);
 
 hipError_t wrk_bins_to_db(hipStream_t st, const float *bins, unsigned int n, float *db);
 hipError_t wrk_waterfall_row(hipStream_t st, const float *bins, unsigned int n, unsigned int width, int hold,

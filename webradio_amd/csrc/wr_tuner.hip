@@ -1720,6 +1720,43 @@ extern "C" int wr_tuner_chan_levels(wr_tuner *t, float *mean_host, float *peak_h
 	return WR_OK;
 }
 
+/* the last submit's audio rows of every channel slot into a tone bank (wr_tones.hip): the rows wr_tuner_audio_dev shows,
+ * counted as wr_tuner_chan_levels counts them, read where they lie */
+extern "C" int wr_tuner_tones_push(wr_tuner *t, wr_tones *bank, unsigned int *slots)
+{
+	if (!t || !bank)
+		return wrc_fail(WR_ERR_ARG, "wr_tuner_tones_push: bad argument (NULL tuner or bank)");
+	if (bank->dev != t->dev)
+		return wrc_fail(WR_ERR_ARG, "wr_tuner_tones_push: the bank belongs to another device than the tuner");
+	if (int rc = wrc_settle_held(t))
+		return rc;
+	bool several = false;
+	Group *g = wrc_single_group(t, &several);
+	if (several)
+		return wrc_fail(WR_ERR_STATE, "wr_tuner_tones_push: the tuner has several rate groups");
+	if (!g || !t->submitted)
+		return wrc_fail(WR_ERR_STATE, "wr_tuner_tones_push: nothing submitted yet");
+	const unsigned int used = wrc_group_slots_used(g);
+	if (used > bank->max_rows)
+		return wrc_fail(WR_ERR_ARG, "wr_tuner_tones_push: the tuner has %u channel slots, the bank %u rows", used, bank->max_rows);
+	if (bank->last_tuner == t && bank->last_seq == t->submit_seq)
+		return wrc_fail(WR_ERR_STATE, "wr_tuner_tones_push: submit %llu of this tuner is in the bank already", t->submit_seq);
+	wr_dev *d = t->dev;
+	if (wrc_dev_bind(d))
+		return WR_ERR_HIP;
+	if (int rc = wrc_tuner_flush(t))
+		return rc;
+	DEV_SETTLE(d);
+	if (used && g->last_k2)
+		HIP_TRY(wrk_tones_push(d->stream, g->dev.audio, g->k2max, used, g->last_k2, bank->rows, bank->t12, bank->steps,
+		                       bank->ntones, bank->window));
+	bank->last_tuner = t;
+	bank->last_seq = t->submit_seq;
+	if (slots)
+		*slots = used;
+	return WR_OK;
+}
+
 extern "C" int wr_tuner_fetch_audio_all(wr_tuner *t, float *out_host, size_t out_capacity,
                                         size_t *chan_stride, size_t *frames, unsigned int *slots_used)
 {

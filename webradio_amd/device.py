@@ -365,6 +365,78 @@ class Tuner:
         n = slots.value
         return mean[:n], peak[:n], muted[:n], frames.value, audio_frames.value
 
+    def tones_push(self, bank):
+        """The last submit's audio rows of every channel slot into a ToneBank (wr_tuner_tones_push); row = Tuner.slot.
+        Returns the rows pushed (whole lane groups of 64)."""
+        slots = C.c_uint()
+        check(self.lib.wr_tuner_tones_push(self.h, bank.h, C.byref(slots)))
+        return slots.value
+
+
+def tone_step(hz, audio_rate):
+    """a tone's phase step per audio frame, llround(hz / audio_rate * 2^32) (wr_tone_step); needs no device."""
+    step = C.c_uint()
+    check(capi.load().wr_tone_step(C.c_double(hz), audio_rate, C.byref(step)))
+    return step.value
+
+
+class ToneBank:
+    """wr_tones: up to 64 tone correlators per row, integrated over windows of `window` audio frames that run on from
+    push to push (include/webradio_amd.h: TONE BANK)."""
+
+    def __init__(self, dev, max_rows, tones_hz, audio_rate, window, steps=None):
+        """tones_hz at audio_rate -- or, with `steps`, the phase steps themselves (tones_hz and audio_rate are then ignored)"""
+        self.dev = dev
+        self.lib = dev.lib
+        self.max_rows = max_rows
+        self.window = window
+        if steps is None:
+            steps = [tone_step(hz, audio_rate) for hz in tones_hz]
+        self.steps = np.array(steps, dtype=np.uint32)
+        self.ntones = self.steps.size
+        h = C.c_void_p()
+        check(self.lib.wr_tones_create(C.byref(h), dev.h, max_rows, ptr(self.steps), self.ntones, window))
+        self.h = h
+
+    def destroy(self):
+        if self.h:
+            self.lib.wr_tones_destroy(self.h)
+            self.h = None
+
+    def reset(self, row=-1):
+        """a row (every row: row < 0) begins a new stream -- after Tuner.seek, a history reset or a retune"""
+        check(self.lib.wr_tones_reset(self.h, row))
+
+    def push_rows(self, p, row_stride, nrows, nframes):
+        """nrows rows of nframes floats at device pointer p, row_stride floats apart, continue rows 0 .. nrows-1"""
+        check(self.lib.wr_tones_push_rows(self.h, C.c_void_p(p), row_stride, nrows, nframes))
+
+    def read(self):
+        """(iq int64 [rows][ntones][2], energy int64 [rows], windows uint64 [rows], fill uint32 [rows]): the last complete
+        window's I, Q and E, the windows so far and the frames in the open one (wr_tones_read); waits for the device."""
+        iq = np.zeros((self.max_rows, self.ntones, 2), np.int64)
+        energy = np.zeros(self.max_rows, np.int64)
+        windows = np.zeros(self.max_rows, np.uint64)
+        fill = np.zeros(self.max_rows, np.uint32)
+        rows = C.c_uint()
+        check(self.lib.wr_tones_read(self.h, ptr(iq), ptr(energy), ptr(windows), ptr(fill), C.byref(rows)))
+        assert rows.value == self.max_rows
+        return iq, energy, windows, fill
+
+    def ratios(self):
+        """rho[rows][ntones] = 2 (I^2 + Q^2) / (W E 2^14) in float64: the share of the last complete window's audio power
+        that sits in each tone; 0 where E is 0"""
+        iq, energy, _, _ = self.read()
+        return ratios(iq, energy, self.window)
+
+
+def ratios(iq, energy, window):
+    i, q = iq[..., 0].astype(np.float64), iq[..., 1].astype(np.float64)
+    den = float(window) * energy.astype(np.float64) * 16384.0
+    out = np.zeros(i.shape, np.float64)
+    np.divide(2.0 * (i * i + q * q), den[..., None], out=out, where=den[..., None] > 0)
+    return out
+
 
 class Spectrum:
     """wr_spectrum: SpectrumSink (io/spectrumsink.h:44-68).  real=True: one float per frame (a receiver's audio),
