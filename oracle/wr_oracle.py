@@ -145,6 +145,24 @@ class Fir:
             pass
 
 
+def fir_keep_history(fir, in_floats):
+    """Prepare a FirState (Fir.s, ReceiverState.chan_fir / .audio_fir) for a block of in_floats floats where the block before
+    had another size: the reference's LowPass resizes its buffer BEFORE it saves the history (lowpass.cxx:138-141, quirk Q7),
+    so that history is lost; this gives the buffer the new length by a wro_fir_process call on zeros and puts the true last
+    L - 1 frames back at its end, which is what wro_fir_process takes as history when the size does not change.  For
+    yardsticks of streams whose block size varies (the product keeps the true history: tests/test_gpu_blocks.py)."""
+    hist = int(fir.channels) * (int(fir.length) - 1)
+    want = int(in_floats) + hist
+    if not fir.block or fir.block_len == want:
+        return
+    old = np.ctypeslib.as_array(fir.block, shape=(fir.block_len,))[fir.block_len - hist:].copy()
+    x = np.zeros(max(in_floats, 1), np.float32)
+    out = np.empty(in_floats + 1, np.float32)
+    lib().wro_fir_process(C.byref(fir), _p(x), C.c_size_t(in_floats), _p(out))
+    assert fir.block_len == want
+    np.ctypeslib.as_array(fir.block, shape=(want,))[want - hist:] = old
+
+
 def demod(mode, prev, iq):
     iq = _f32(iq)
     out = np.empty(iq.size // 2, np.float32)

@@ -16,22 +16,24 @@ MODE_NAMES = {capi.WR_AM: "AM", capi.WR_FM: "FM", capi.WR_USB: "USB", capi.WR_LS
 
 class OracleChain:
     """A Receiver chain assembled from the oracle's blocks with explicit filter lengths:
-    mixer -> LowPass(L1, D1) [-> LowPass(L1b, D1b)] -> demodulator -> LowPass(L2, D2)."""
+    mixer -> LowPass(L1, D1) [-> LowPass(L1b, D1b)] -> demodulator -> LowPass(L2, D2).
+    taps: {"channel" / "second" / "audio": coefficients} in place of that stage's LowPass design (wr_chan_set_taps_n)."""
 
-    def __init__(self, oracle, fs, if_hz, l1, pb1, d1, mode, l2, pb2, d2, stage2=None):
+    def __init__(self, oracle, fs, if_hz, l1, pb1, d1, mode, l2, pb2, d2, stage2=None, taps=None):
+        taps = taps or {}
         self.o, self.mode = oracle, mode
         self.table = oracle.sin_table()
         self.step = oracle.phase_step(if_hz, fs)
         self.phase = 0
         self.prev = (0.0, 0.0)
-        self.f1 = oracle.Fir(2, d1, oracle.lowpass_design(pb1, fs, l1))
+        self.f1 = oracle.Fir(2, d1, taps.get("channel", oracle.lowpass_design(pb1, fs, l1)))
         r = fs // d1
         self.f1b = None
         if stage2:
             l1b, pb1b, d1b = stage2
-            self.f1b = oracle.Fir(2, d1b, oracle.lowpass_design(pb1b, r, l1b))
+            self.f1b = oracle.Fir(2, d1b, taps.get("second", oracle.lowpass_design(pb1b, r, l1b)))
             r //= d1b
-        self.f2 = oracle.Fir(1, d2, oracle.lowpass_design(pb2, r, l2))
+        self.f2 = oracle.Fir(1, d2, taps.get("audio", oracle.lowpass_design(pb2, r, l2)))
 
     def run(self, iq):
         mixed, self.phase = self.o.mix(self.table, self.phase, self.step, iq)

@@ -1,0 +1,573 @@
+"""-m gpu: a tuner's getters and controls used together, the way a caller between blocks would -- random scripts of submits,
+setters, receivers coming and going, seeks and every getter (tests/tuner_model.py: make_script), played on a wr_tuner and on
+the CPU model of one (TunerModel: the oracle's receivers and the numpy restatements of squelch, AGC, levels and tone bank).
+
+  test_script_against_the_model      WR_NCO_EXACT, a launch per block: whatever an operation hands back is the model's
+  test_script_in_every_launch_mode   WR_NCO_ROTATE: a launch per block, held blocks and the streaming launch hand back the
+                                     same bits, and the first of them is the model's within the ROTATE tolerance
+  test_a_receiver_moves_to_another_rate_group_and_back
+  test_caller_designed_taps          wr_chan_set_taps(_n) with taps of full size at every position
+
+Tolerances are the suite's own: DB_ATOL on bins within 60 dB of a row's peak (test_gpu_spectrum_real._check_db), FM_ATOL
+and the ROTATE bound through the audio filter's absolute gain (test_gpu_fuzz.py), 1e-6 on ROTATE channel IQ (test_gpu_f4.py)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import agc_np
+import tuner_model as tm
+from test_gpu_f4 import OracleChain
+from test_gpu_spectrum import DB_ATOL
+from webradio_amd import capi
+from webradio_amd.device import Spectrum, ToneBank, Tuner
+
+pytestmark = pytest.mark.gpu
+
+CPB, APB = tm.CHAN_PASSBANDS[0], tm.AUDIO_PASSBAND
+WR_TUNE_DDC_NG2_MIN_PASSES = 1                                            # include/webradio_amd.h: enum wr_tunable
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _same_bits(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape:
+        return False
+    if a.dtype == np.float32 or b.dtype == np.float32:
+        return np.array_equal(_bits(a), _bits(b))
+    return np.array_equal(a, b)
+
+
+def _same(a, b):
+    """two results of an operation, bit for bit, whatever their shape"""
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, (tuple, list)):
+        return isinstance(b, (tuple, list)) and len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    if a is None or b is None:
+        return a is b
+    return _same_bits(a, b)
+
+
+def _db_close(got, want):
+    """test_gpu_spectrum_real._check_db: DB_ATOL on the bins within 60 dB of the row's peak"""
+    strong = want >= want.max() - 60.0
+    return float(np.abs(got[strong] - want[strong]).max()) <= DB_ATOL
+
+
+class GpuPlay:
+    """a script's operations on a wr_tuner; do(op) returns what ModelPlay.do returns for it, from the library"""
+
+    def __init__(self, dev, script, iq, x, nco, how="block"):
+        self.dev, self.s, self.iq, self.x = dev, script, iq, x
+        s = script
+        self.t = t = Tuner(dev, tm.FS, s["max_channels"], s["max_block"], nco)
+        for c, f in enumerate(s["ifs"]):
+            assert t.add_receiver(f, CPB, tm.CHAN_RATE, c % 4, APB, s["audio_rate"]) == c and t.slot(c) == c
+        capi.check(t.lib.wr_tuner_set_audio_scale(t.h, C.c_float(s["scale"])))
+        t.audio_ring(128)
+        if how == "hold":
+            t.blocks_per_launch(s["hold"])
+        if how == "stream":
+            t.streaming(True)
+        self.rows = tm.slot_rows(s["max_channels"])
+        steps = tm.bank_steps(s["audio_rate"])
+        self.banks = [ToneBank(dev, self.rows, None, None, w, steps=steps) for w in tm.BANK_WINDOWS]
+        self.chan_spec = Spectrum(dev, tm.CHAN_SPECTRUM_N)
+        self.audio_spec = Spectrum(dev, tm.AUDIO_SPECTRUM_N, real=True)
+        self.live = {c: c for c in range(s["nrx"])}                       # handle -> slot
+        self.pos = 0
+        self.cap = s["max_block"] // tm.D1
+
+    def close(self):
+        for b in self.banks:
+            b.destroy()
+        self.chan_spec.destroy()
+        self.audio_spec.destroy()
+        self.t.destroy()
+
+    def bank(self, b):
+        iq, energy, windows, fill = self.banks[b].read()
+        return {s: (iq[s].copy(), int(energy[s]), int(windows[s]), int(fill[s])) for s in self.live.values()}
+
+    def do(self, op):
+        t, k, lib = self.t, op[0], self.t.lib
+        if k == "submit":
+            if op[1] == "host":
+                t.submit_host(self.iq[2 * self.pos: 2 * (self.pos + op[2])])
+            else:
+                t.submit_device(self.x + 8 * self.pos, op[2])
+            self.pos += op[2]
+        elif k == "set_if":
+            t.set_if(op[1], op[2])
+        elif k == "set_mode":
+            t.set_mode(op[1], op[2])
+        elif k == "set_filter":
+            t.set_filter(op[1], 0, op[2], tm.CHAN_RATE)
+        elif k == "af_gain":
+            t.set_af_gain(op[1], op[2])
+        elif k in ("squelch_on", "squelch_thr"):
+            t.set_squelch(op[1], op[2], True)
+        elif k == "squelch_off":
+            t.set_squelch(op[1], 0.0, False)
+        elif k in ("agc_on", "agc_new"):
+            t.set_agc(op[1], *op[2])
+        elif k == "agc_off":
+            t.set_agc(op[1], enable=False)
+        elif k == "reset_history":
+            capi.check(lib.wr_chan_reset_history(t.h, op[1]))
+        elif k == "seek":
+            t.seek(op[1])
+        elif k == "remove":
+            t.remove_receiver(op[1])
+            del self.live[op[1]]
+        elif k == "add":
+            c = t.add_receiver(op[3], CPB, tm.CHAN_RATE, op[4], APB, self.s["audio_rate"])
+            assert (c, t.slot(c)) == (op[1], op[2]), (op, c, t.slot(c))   # the lowest free handle, the slot that was left
+            self.live[c] = op[2]
+        elif k == "bank_reset":
+            for b in self.banks:
+                b.reset(op[1])
+        elif k == "fetch_audio":
+            return t.fetch(op[1], capi.WR_STAGE_AUDIO, self.cap)
+        elif k == "fetch_chan":
+            return t.fetch(op[1], capi.WR_STAGE_CHAN_IQ, 2 * self.cap)
+        elif k == "fetch_all":
+            rows = t.fetch_audio_all()
+            return {s: rows[s].copy() for s in self.live.values()}
+        elif k == "levels":
+            mean, peak, muted, frames, audio_frames = t.chan_levels()
+            return {c: (mean[s], peak[s], int(muted[s])) for c, s in self.live.items()}, frames, audio_frames
+        elif k == "spectra":
+            rows = t.chan_spectra(self.chan_spec, op[1])
+            return {c: rows[s].copy() for c, s in self.live.items()}
+        elif k == "audio_spectrum":
+            a, stride, frames = t.audio_dev()
+            assert frames >= tm.AUDIO_SPECTRUM_N
+            n, used = tm.AUDIO_SPECTRUM_N, max(self.live.values()) + 1
+            out = self.dev.malloc(used * n * 4)
+            try:
+                self.audio_spec.batch_db_rows(a, stride, used, out)
+                self.dev.sync()
+                rows = self.dev.download(out, used * n).reshape(used, n)
+            finally:
+                self.dev.free(out)
+            return {c: rows[s].copy() for c, s in self.live.items()}
+        elif k == "tones":
+            assert t.tones_push(self.banks[op[1]]) >= max(self.live.values()) + 1
+            return self.bank(op[1])
+        elif k == "tones_again":
+            assert lib.wr_tuner_tones_push(t.h, self.banks[op[1]].h, None) == capi.WR_ERR_STATE     # ... and nothing is counted
+            assert b"already" in lib.wr_last_error()
+            return self.bank(op[1])
+        elif k == "get_agc":
+            return t.get_agc(op[1])
+        elif k == "state":
+            return t.state(op[1])[0]
+        elif k == "flush":
+            t.flush()
+        elif k == "drain":
+            out = []
+            while t.ring_stats()[0]:
+                rows, seq = t.ring_acquire()
+                whole = np.zeros((self.rows, rows.shape[1]), np.float32)  # (an entry holds the lane groups in use)
+                whole[: rows.shape[0]] = rows
+                out.append((seq, whole))
+                t.ring_release()
+            return out
+        return None
+
+
+@pytest.fixture(scope="module")
+def scripts(dev):
+    """scripts(seed) -> (script, the stream on the host, the stream in device memory); made once per seed"""
+    made = {}
+
+    def get(seed):
+        if seed not in made:
+            script = tm.make_script(seed)
+            iq = tm.signal(script["total"], script["carriers"], seed)
+            made[seed] = (script, iq, dev.upload(iq))
+        return made[seed]
+    yield get
+    dev.sync()
+    for _, _, x in made.values():
+        dev.free(x)
+
+
+# ---- 1: every operation's answer against the model --------------------------------------------------------------------------
+
+def _audio_is_the_models(m, c, got, want, what):
+    """bit for bit; a receiver that has run the FM detector since its histories were last empty: within the FM tolerance"""
+    r = m.rxs[c]
+    assert got.shape == want.shape, what
+    if not r.was_fm:
+        bad = np.flatnonzero(_bits(got) != _bits(want))
+        assert bad.size == 0, (what, c, bad[:4], got[bad[:4]], want[bad[:4]])
+        return 1
+    if not r.used_agc and want.size:
+        assert float(np.abs(got - want).max()) <= m.fm_tolerance(c), (what, c)
+    return 0
+
+
+def _check_exact(play, op, got, want, seen):
+    m, k = play.m, op[0]
+    by_slot = {r.slot: c for c, r in m.rxs.items()}
+    what = (play.s["seed"], k, op[1:] if k != "add" else op[1])
+    if k == "fetch_audio":
+        seen["exact"] += _audio_is_the_models(m, op[1], got, want, what)
+    elif k == "fetch_chan":
+        assert _same_bits(got, want), what
+    elif k == "fetch_all":
+        assert got.keys() == want.keys(), what
+        for s in got:
+            seen["exact"] += _audio_is_the_models(m, by_slot[s], got[s], want[s], what)
+    elif k == "drain":
+        assert [seq for seq, _ in got] == [e[0] for e in want], what
+        for (seq, rows), (_, audio, standing) in zip(got, want):
+            for s, w in audio.items():                                    # (the receiver's standing when the block was made)
+                exact, tol, _ = standing[s]
+                assert rows[s].shape == w.shape, (what, seq, s)
+                if exact:
+                    assert _same_bits(rows[s], w), (what, seq, s)
+                elif tol is not None and w.size:
+                    assert float(np.abs(rows[s] - w).max()) <= tol, (what, seq, s)
+                seen["exact"] += exact
+    elif k == "levels":
+        assert _same(got, want), (what, [c for c in want[0] if not _same(got[0][c], want[0][c])][:4], got[1:], want[1:])
+    elif k == "spectra":
+        assert got.keys() == want.keys()
+        for c in got:
+            assert _db_close(got[c], want[c]), (what, c)
+    elif k == "audio_spectrum":
+        for c in got:
+            if not m.rxs[c].was_fm and float(np.abs(m.audio(c)[: tm.AUDIO_SPECTRUM_N]).max()) > 0.0:
+                assert _db_close(got[c], want[c]), (what, c)
+    elif k in ("tones", "tones_again"):
+        for c, r in m.rxs.items():
+            if not r.was_fm:
+                assert _same(got[r.slot], want[r.slot]), (what, c, got[r.slot][1:], want[r.slot][1:])
+                seen["latched"] += want[r.slot][2] > 0
+    elif k == "get_agc":
+        assert _same(got, want), (what, got, want)
+        seen["agc"] += bool(want[0])
+    elif k == "state":
+        assert got == want, what
+
+
+@pytest.mark.parametrize("seed", tm.fuzz_seeds())
+def test_script_against_the_model(dev, scripts, seed):
+    script, iq, x = scripts(seed)
+    model, gpu = tm.ModelPlay(script, iq), GpuPlay(dev, script, iq, x, capi.WR_NCO_EXACT)
+    seen = {"exact": 0, "gated": 0, "latched": 0, "agc": 0}
+    try:
+        for op in script["ops"]:
+            got, want = gpu.do(op), model.do(op)
+            assert (got is None) == (want is None), op
+            if want is not None:
+                _check_exact(model, op, got, want, seen)
+            if op[0] == "submit":                                         # a squelch that closes and opens within the block
+                seen["gated"] += any(0 < r.gate()[0] < r.last[3] for r in model.m.rxs.values() if r.used_sq is not None)
+        for c in gpu.live:                                                # the NCO phases at the end
+            assert gpu.t.state(c)[0] == model.m.phase(c), c
+        assert gpu.live == {c: r.slot for c, r in model.m.rxs.items()}
+        assert gpu.t.agc_info()[0] == model.m.agc_on()
+    finally:
+        gpu.close()
+    print("seed %d: %s" % (seed, seen))
+    assert seen["exact"] > 0 and seen["latched"] > 0 and seen["gated"] > 0 and seen["agc"] > 0
+
+
+# ---- 2: a launch per block, held blocks, the streaming launch -------------------------------------------------------------------
+
+def _ring_mask(script, rows):
+    """[rows][audio frames of the whole script]: where a receiver sat in the slot when the frame was made"""
+    live = {c: c for c in range(script["nrx"])}
+    parts = []
+    for op in script["ops"]:
+        if op[0] == "remove":
+            del live[op[1]]
+        elif op[0] == "add":
+            live[op[1]] = op[2]
+        elif op[0] == "submit":
+            m = np.zeros((rows, op[2] // tm.D1 // script["d2"]), bool)
+            m[sorted(live.values())] = True
+            parts.append(m)
+    return np.concatenate(parts, axis=1)
+
+
+def _check_rotate(model, op, got, want, ring):
+    """the play with a launch per block against the model: audio of receivers that never ran the FM detector and have neither
+    AGC nor squelch in use, within the ROTATE tolerance through the audio filter (test_gpu_fuzz.py); `ring`: the model's
+    entries the library has not handed out yet (a block's entry may wait for the next submit: wr_tuner_flush)"""
+    m, k = model.m, op[0]
+    pairs = []
+    if k == "drain":
+        ring.update({seq: (audio, standing) for seq, audio, standing in want})
+        n = 0
+        for seq, rows in got:
+            audio, standing = ring.pop(seq)
+            for s, w in audio.items():
+                if standing[s][2] is not None and w.size:
+                    assert rows[s].shape == w.shape and float(np.abs(rows[s] - w).max()) <= standing[s][2], (op, seq, s)
+                    n += 1
+        return n
+    if k == "fetch_audio":
+        pairs = [(op[1], got, want)]
+    elif k == "fetch_all":
+        by_slot = {r.slot: c for c, r in m.rxs.items()}
+        pairs = [(by_slot[s], got[s], want[s]) for s in want]
+    elif k == "fetch_chan":
+        assert float(np.abs(got - want).max()) <= 1e-6, op                # (test_gpu_f4.py: ROTATE channel IQ)
+    n = 0
+    for c, g, w in pairs:
+        r = m.rxs[c]
+        if c % 4 != 1 and not r.used_agc and r.used_sq is None and w.size:
+            assert g.shape == w.shape and float(np.abs(g - w).max()) <= m.rotate_tolerance(c), (op, c)
+            n += 1
+    return n
+
+
+@pytest.mark.parametrize("seed", tm.fuzz_seeds())
+def test_script_in_every_launch_mode(dev, scripts, seed):
+    script, iq, x = scripts(seed)
+    lib = dev.lib
+    previous = C.c_long()
+    ng2 = script["nrx"] == 128                   # two full lane groups: the script runs under the two-lane-group kernel
+    if ng2:
+        assert lib.wr_tune(WR_TUNE_DDC_NG2_MIN_PASSES, C.c_long(0), C.byref(previous)) == 0
+    try:
+        plays, held_to_model, model_ring = {}, 0, {}
+        for how in ("block", "hold", "stream"):
+            gpu = GpuPlay(dev, script, iq, x, capi.WR_NCO_ROTATE, how)
+            model = tm.ModelPlay(script, iq) if how == "block" else None
+            results, ring = [], []
+            try:
+                for op in script["ops"]:
+                    got = gpu.do(op)
+                    if model is not None:
+                        held_to_model += _check_rotate(model, op, got, model.do(op), model_ring)
+                    if op[0] == "drain":
+                        ring += [rows for _, rows in got]
+                    else:
+                        results.append(got)
+                assert gpu.t.ring_stats() == (0, 0)
+                plays[how] = (results, np.concatenate(ring, axis=1), gpu.t.stream_info(), gpu.t.agc_info())
+            finally:
+                gpu.close()
+    finally:
+        if ng2:
+            assert lib.wr_tune(WR_TUNE_DDC_NG2_MIN_PASSES, C.c_long(previous.value), None) == 0
+    assert held_to_model > 0 and not model_ring                           # every block's ring entry was held to the model's
+    base, ring, _, agc = plays["block"]
+    mask = _ring_mask(script, ring.shape[0])
+    assert mask.shape == ring.shape and ring.shape[1] > 0
+    for how in ("hold", "stream"):
+        results, other_ring, info, other_agc = plays[how]
+        for i, (a, b) in enumerate(zip(base, results)):
+            assert _same(a, b), (how, i, [op for op in script["ops"] if op[0] != "drain"][i])
+        assert other_ring.shape == ring.shape, how
+        assert np.array_equal(_bits(ring)[mask], _bits(other_ring)[mask]), how
+        assert other_agc == agc, how
+    print("seed %d: stream_info %s, agc_info %s, %d audio rows held to the model" % (seed, plays["stream"][2], agc, held_to_model))
+    assert plays["stream"][2][2] >= 3                                     # blocks that did stream
+    assert plays["block"][2][2] == 0 and plays["hold"][2][2] == 0
+
+
+# ---- 3: a receiver moves to another rate group and back -------------------------------------------------------------------------
+
+def test_a_receiver_moves_to_another_rate_group_and_back(dev):
+    """wr_chan_set_filter on stage 1 with another audio rate seats the receiver in a rate group of its own; the same call with
+    the old rate brings it back into the slot it left.  Either way it arrives like a new receiver -- empty filter histories,
+    its AGC from floor with a step for the rate it now has -- except for the NCO phase and the detector's previous frame; the
+    other receivers never lose a bit.  While there are two rate groups the per-tuner getters answer WR_ERR_STATE."""
+    lib = dev.lib
+    nrx, n, mover = 6, 80 * tm.D1, 2
+    ifs = [(c - 3) * 25_000 + 321 for c in range(nrx)]
+    modes = [tm.AM, tm.FM, tm.USB, tm.LSB, tm.AM, tm.USB]
+    settings = (-12.0, 5.0, 60.0)
+    iq = tm.signal(7 * n, [ifs[0], ifs[mover]], seed=5)
+    t = Tuner(dev, tm.FS, nrx, n, capi.WR_NCO_EXACT)
+    m, twin = tm.TunerModel(tm.FS, 1.0), tm.TunerModel(tm.FS, 1.0)        # twin: the receiver never moves
+    for c in range(nrx):
+        assert t.add_receiver(ifs[c], CPB, tm.CHAN_RATE, modes[c], APB, 1_000) == c
+        for model in (m, twin):
+            model.add(c, t.slot(c), ifs[c], CPB, tm.CHAN_RATE, modes[c], APB, 1_000)
+    for c in (mover, 4):
+        t.set_agc(c, *settings)
+    t.set_squelch(0, -46.0, True)
+    t.set_af_gain(3, 6.0)
+    for model in (m, twin):
+        model.set_agc(mover, settings)
+        model.set_agc(4, settings)
+        model.set_squelch(0, -46.0)
+        model.set_af_gain(3, 6.0)
+    bank = ToneBank(dev, 64, None, None, 16, steps=tm.bank_steps(1_000))
+    want_bank = tm.tones_np.Bank(64, tm.bank_steps(1_000), 16)
+    spec = Spectrum(dev, tm.CHAN_SPECTRUM_N)
+    out = dev.malloc(64 * tm.CHAN_SPECTRUM_N * 4)
+    pos = [0]
+
+    def block(one_group):
+        b = iq[2 * pos[0]: 2 * (pos[0] + n)]
+        pos[0] += n
+        t.submit_host(b)
+        m.submit(b)
+        twin.submit(b)
+        for c in range(nrx):
+            k1 = n // tm.D1
+            assert _same_bits(t.fetch(c, capi.WR_STAGE_CHAN_IQ, 2 * k1), m.chan_iq(c)), (pos[0] // n, c)
+            ga, wa = t.fetch(c, capi.WR_STAGE_AUDIO, k1), m.audio(c)
+            if modes[c] == tm.FM:
+                assert ga.shape == wa.shape and float(np.abs(ga - wa).max()) <= m.fm_tolerance(c)
+            else:
+                assert _same_bits(ga, wa), (pos[0] // n, c)
+            got = t.get_agc(c)
+            assert _same(got, m.get_agc(c)), (pos[0] // n, c, got, m.get_agc(c))
+        if not one_group:
+            assert lib.wr_tuner_chan_levels(t.h, capi.ptr(np.zeros(64, np.float32)), None, None, None, None, None) == capi.WR_ERR_STATE
+            assert b"several rate groups" in lib.wr_last_error()
+            assert lib.wr_tuner_chan_spectra(t.h, spec.h, 0, C.c_void_p(out), None) == capi.WR_ERR_STATE
+            assert b"several rate groups" in lib.wr_last_error()
+            assert lib.wr_tuner_tones_push(t.h, bank.h, None) == capi.WR_ERR_STATE
+            assert b"several rate groups" in lib.wr_last_error()
+            return
+        mean, peak, muted, frames, audio_frames = t.chan_levels()
+        rows = t.chan_spectra(spec, 7)
+        assert t.tones_push(bank) == 64
+        want_bank.push(m.audio_rows(64))
+        got_bank, ref_bank = bank.read(), want_bank.read()
+        assert (frames, audio_frames) == (n // tm.D1, n // tm.D1 // 5)
+        for c in range(nrx):
+            s = t.slot(c)
+            assert _same((mean[s], peak[s], int(muted[s])), m.levels(c)), (pos[0] // n, c)
+            assert _db_close(rows[s], m.chan_spectrum(c, 7)), (pos[0] // n, c)
+            if modes[c] != tm.FM:
+                for g, w in zip(got_bank, ref_bank):
+                    assert np.array_equal(g[s], w[s]), (pos[0] // n, c)
+
+    try:
+        block(True)
+        block(True)
+        home = t.slot(mover)
+        carried = t.get_agc(mover)[4]
+        floor_bits = agc_np.design(*settings, 1_000)[1]
+        assert carried > floor_bits                                       # an envelope that a reset would be seen to lose
+        t.set_filter(mover, 1, APB, 2_500)                                # 5 kHz -> 2.5 kHz: a rate group of its own
+        m.set_audio_rate(mover, APB, 2_500, t.slot(mover))
+        block(False)
+        assert t.get_agc(mover)[3] == agc_np.design(*settings, 2_500)[2] != agc_np.design(*settings, 1_000)[2]
+        block(False)
+        assert t.fetch(mover, capi.WR_STAGE_AUDIO, n).size == n // tm.D1 // 2
+        t.set_filter(mover, 1, APB, 1_000)                                # ... and back
+        assert t.slot(mover) == home
+        m.set_audio_rate(mover, APB, 1_000, home)
+        bank.reset(home)
+        want_bank.reset(home)
+        block(True)
+        # it came back like a new receiver: not with the envelope it left behind in the slot, not with the histories it had
+        on, target, fb, step, state = t.get_agc(mover)
+        assert (on, fb, step) == (True, floor_bits, agc_np.design(*settings, 1_000)[2])
+        assert not _same_bits(m.audio(mover), twin.audio(mover))
+        assert not _same_bits(m.chan_iq(mover), twin.chan_iq(mover))
+        for c in range(nrx):
+            if c != mover and modes[c] != tm.FM:                          # the others: as if nothing had happened
+                assert _same_bits(t.fetch(c, capi.WR_STAGE_AUDIO, n), twin.audio(c)), c
+        block(True)
+        block(True)
+        assert int(want_bank.windows[home]) >= 2
+    finally:
+        dev.free(out)
+        spec.destroy()
+        bank.destroy()
+        t.destroy()
+
+
+# ---- 4: caller-designed taps ----------------------------------------------------------------------------------------------------
+
+class _Chain(OracleChain):
+    """OracleChain over blocks of several sizes: its filters keep their true histories (wr_oracle.fir_keep_history; quirk Q7)"""
+
+    def run(self, iq):
+        n = np.asarray(iq).size // 2
+        tm.oracle.fir_keep_history(self.f1.s, 2 * n)
+        k = n // self.f1.decimation
+        if self.f1b is not None:
+            tm.oracle.fir_keep_history(self.f1b.s, 2 * k)
+            k //= self.f1b.decimation
+        tm.oracle.fir_keep_history(self.f2.s, k)
+        return OracleChain.run(self, iq)
+
+
+STAGES = {"channel": 0, "audio": 1, "second": 2}                          # WR_FILTER_CHANNEL, WR_FILTER_AUDIO, WR_FILTER_CHANNEL2
+
+
+@pytest.mark.parametrize("nco", [capi.WR_NCO_EXACT, capi.WR_NCO_ROTATE], ids=["exact", "rotate"])
+@pytest.mark.parametrize("length", [8, 64, 256])
+@pytest.mark.parametrize("stage", ["channel", "audio", "second"])
+def test_caller_designed_taps(dev, oracle, stage, length, nco):
+    """wr_chan_set_taps_n with taps that no lowpass design would give: uniform(-1, 1) / length, asymmetric and of full size at
+    every position (wr_lowpass_design's are a thousand times smaller at the ends than in the middle, so that an error at an end
+    tap hides in the ROTATE tolerance).  One stage at a time on 70 receivers -- two receivers with a second tap set of their
+    own -- over three blocks of 100, 20 and 60 frames at the demodulator.  The second is shorter than the audio filter's history
+    at every length and than a 256-tap second stage's; a channel filter's history (up to 255 input frames) is shorter than
+    any block that gives a receiver a frame, so for that stage the blocks differ in size only."""
+    lib = dev.lib
+    two = stage == "second"
+    fs, d2, nrx = tm.FS, 5, 70
+    d1, d1b = (40, 10) if two else (400, 1)
+    r1 = fs // d1
+    r_dem = r1 // d1b
+    pb1, pb1b, pb2 = 128_000, r1 // 8, 160
+    rng = np.random.default_rng(1000 * length + 10 * STAGES[stage] + nco)
+    sets = [(rng.uniform(-1.0, 1.0, length) / length).astype(np.float32) for _ in range(2)]
+    own = (5, 66)
+    ifs = [(c - nrx // 2) * 25_000 + 321 for c in range(nrx)]
+    modes = [tm.AM, tm.USB, tm.LSB]
+    probe = [0, 1, 5, 33, 63, 64, 66, 69]
+    decim = {"channel": d1, "audio": d2, "second": d1b}[stage]
+    t = Tuner(dev, fs, nrx, 40_000, nco)
+    try:
+        for c, f in enumerate(ifs):
+            ch = t.add_receiver(f, pb1, r1, modes[c % 3], pb2, r_dem // d2, stage2=(64, pb1b, r_dem) if two else None)
+            taps = sets[c in own]
+            if (stage, length, nco) == ("channel", 64, capi.WR_NCO_EXACT):
+                capi.check(lib.wr_chan_set_taps(t.h, ch, STAGES[stage], capi.ptr(taps), decim))     # the 64-tap entry
+            else:
+                capi.check(lib.wr_chan_set_taps_n(t.h, ch, STAGES[stage], capi.ptr(taps), length, decim))
+        rxs = {c: _Chain(oracle, fs, ifs[c], 64, pb1, d1, modes[c % 3], 64, pb2, d2, stage2=(64, pb1b, d1b) if two else None,
+                         taps={stage: sets[c in own]}) for c in probe}
+        gain = {s: max(1.0, float(np.abs(sets[s]).sum())) for s in (0, 1)}
+        gain2 = max(1.0, float(np.abs(oracle.lowpass_design(pb2, r_dem)).sum()))
+        pos, live = 0, 0.0
+        iq = tm.signal(72_000, [ifs[c] for c in probe[::2]], seed=length)
+        for n in (40_000, 8_000, 24_000):                                 # 100, 20 and 60 frames at the demodulator
+            b = iq[2 * pos: 2 * (pos + n)]
+            pos += n
+            t.submit_host(b)
+            for c in probe:
+                wa, wc, _ = rxs[c].run(b)
+                gc = t.fetch(c, capi.WR_STAGE_CHAN_IQ, 2 * n)
+                ga = t.fetch(c, capi.WR_STAGE_AUDIO, n)
+                assert gc.size == wc.size == 2 * (n // d1 // d1b) and ga.size == wa.size == n // d1 // d1b // d2, (n, c)
+                if nco == capi.WR_NCO_EXACT:
+                    assert np.array_equal(_bits(gc), _bits(wc)), (n, c)
+                    assert np.array_equal(_bits(ga), _bits(wa)), (n, c)
+                else:
+                    g = gain[c in own]
+                    assert float(np.abs(gc - wc).max()) <= 1e-6, (n, c, float(np.abs(gc - wc).max()))      # (test_gpu_f4.py)
+                    # |.| and the sums of Re and Im are 2-Lipschitz, then the linear audio filter (test_gpu_f4.py)
+                    assert float(np.abs(ga - wa).max()) <= 2e-6 * (g if stage == "audio" else gain2), (n, c)
+                live = max(live, float(np.abs(ga).max()))
+        assert live > 1e-4                                                # a live channel, not zeros
+        count = C.c_int()
+        capi.check(lib.wr_chan_count(t.h, C.byref(count)))
+        assert count.value == nrx
+        t.remove_receiver(7)
+        capi.check(lib.wr_chan_count(t.h, C.byref(count)))
+        assert count.value == nrx - 1
+    finally:
+        t.destroy()
