@@ -1,8 +1,8 @@
 /*
  * wr_capi_internal.h -- what the translation units of the extern "C" boundary (wr_dev.hip, wr_tuner.hip,
- * wr_tuner_stream.hip, wr_tuner_ring.hip, wr_spectrum.hip) share: the objects behind the handles, the error
- * macros, and ONE declaration of every helper that crosses a file boundary (the wrc_ names, as in wr_internal.h).
- * Included by those files only.
+ * wr_tuner_submit.hip, wr_tuner_read.hip, wr_tuner_stream.hip, wr_tuner_ring.hip, wr_spectrum.hip) share: the objects
+ * behind the handles, the error macros, and ONE declaration of every helper that crosses a file boundary (the wrc_
+ * names, as in wr_internal.h).  Included by those files only.
  */
 #ifndef WR_CAPI_INTERNAL_H
 #define WR_CAPI_INTERNAL_H
@@ -118,7 +118,7 @@ struct Group {
 	int p2 = 0;                /* which iq2_hist set the next block reads */
 	bool use_gain = false, use_squelch = false;
 	/* some channel has its AGC on: the post stage runs with a scale of 1 and a gain of 1 in those channels' slots, does not
-	 * wait for the next launch, and k_agc_rows follows it on `audio` (wr_tuner.hip: submit_post) */
+	 * wait for the next launch, and k_agc_rows follows it on `audio` (wr_tuner_submit.hip: submit_post) */
 	bool use_agc = false;
 	WrAgcPar *agc_par = nullptr;         /* [slots] */
 	unsigned int *agc_state = nullptr;   /* [slots] the envelope E behind the last block */
@@ -312,15 +312,29 @@ int        wrc_dev_up_stream(wr_dev *d);
 unsigned int  wrc_group_slots_used(const Group *g);
 WrTunerLaunch wrc_group_launch(const wr_tuner *t, const Group *g, const float *cur, const uint8_t *cur_u8, size_t nframes);
 Group        *wrc_single_group(wr_tuner *t, bool *several = nullptr);
-int           wrc_group_upload(wr_tuner *t, Group *g);
+int           wrc_post_send_pending(wr_tuner *t, Group *g, bool rode);
+int           wrc_seek_materialize(wr_tuner *t, Group *g);
 int           wrc_settle_held(wr_tuner *t);
-int           wrc_tuner_launch_held(wr_tuner *t);
 int           wrc_tuner_flush(wr_tuner *t);
 int           wrc_tuner_quiesce(wr_tuner *t);
-int           wrc_tuner_submit_now(wr_tuner *t, const void *iq, size_t nframes, int where, bool u8);
-void          wrc_advance_phases(wr_tuner *t, unsigned long long frames);
-int           wrc_prof_pair_begin(wr_tuner *t, void **ev_start, void **ev_stop);
-void          wrc_prof_pair_stamped(wr_tuner *t);
+int           wrc_chan_get(wr_tuner *t, int chan, Chan **c, const char *what);
+
+/* wr_tuner_submit.hip */
+int  wrc_group_upload(wr_tuner *t, Group *g);
+int  wrc_tuner_launch_held(wr_tuner *t);
+int  wrc_tuner_submit_now(wr_tuner *t, const void *iq, size_t nframes, int where, bool u8);
+void wrc_advance_phases(wr_tuner *t, unsigned long long frames);
+int  wrc_prof_pair_begin(wr_tuner *t, void **ev_start, void **ev_stop);
+void wrc_prof_pair_stamped(wr_tuner *t);
+
+/* wr_tuner_read.hip: the last submit as its readers see it, in two steps (a reader's own refusals go between them) */
+struct WrLastSubmit {
+	Group *g;                  /* the rate group read from: the tuner's one active group, or the channel's */
+	unsigned int used;         /* wrc_group_slots_used(g) */
+	const float *chan_iq;      /* the last block's channel IQ at the demodulator's input, [frames][g->slots][2] */
+};
+int wrc_last_submit_group(wr_tuner *t, const char *who, bool submitted, WrLastSubmit *v);
+int wrc_last_submit_flush(wr_tuner *t, WrLastSubmit *v);
 
 /* wr_tuner_stream.hip */
 int  wrc_stream_close(wr_tuner *t);

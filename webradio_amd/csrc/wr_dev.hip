@@ -2,7 +2,8 @@
  * wr_dev.hip -- the device context of the extern "C" boundary declared in include/webradio_amd.h: the error string,
  * the design-helper wrappers, wr_dev_*, the upload streams, and the reference's blocks as one kernel each.  No DSP
  * arithmetic lives here (design math: wr_design.cpp; kernels: wr_kernels.hip, wr_fft.hip).  The tuner is in
- * wr_tuner.hip (its streaming launch: wr_tuner_stream.hip, its pinned audio ring: wr_tuner_ring.hip), the spectrum
+ * wr_tuner.hip (submit: wr_tuner_submit.hip, readers: wr_tuner_read.hip, streaming launch: wr_tuner_stream.hip, pinned
+ * audio ring: wr_tuner_ring.hip), the spectrum
  * sink in wr_spectrum.hip.
  *
  * There is deliberately no CPU code path: every data-path entry point needs a

@@ -20,7 +20,7 @@
                                               receivers of one tuner mostly share a passband (radio.cxx:78-79),
                                               the UI lets each choose its own (receiverhandler.cxx:130-137) */
 
-/* ---- what other translation units need of a wr_dev (wr_dev.hip, wr_tuner.hip) ---- */
+/* ---- what other translation units need of a wr_dev (wr_dev.hip, wr_tuner_submit.hip) ---- */
 int         wrc_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));   /* sets wr_last_error() */
 int         wrc_dev_index(const wr_dev *dev);
 hipStream_t wrc_dev_stream(const wr_dev *dev);
@@ -117,7 +117,7 @@ struct WrTunerLaunch {
 	int          one_filter;           /* every channel of the rate group uses ONE and the same channel filter */
 	void        *ev_start, *ev_stop;   /* hipEvent_t pair the DDC launch itself stamps (profiling), or NULL */
 	bool         seeking = false;      /* the first block after wr_tuner_seek: phase = frame * step in closed form, the state sets
-	                                      handed to the launch are all-zero ones (wr_tuner.hip: seek_pending) */
+	                                      handed to the launch are all-zero ones (wr_tuner_submit.hip: submit_group) */
 	unsigned int seek_lo = 0;          /* the frame's low 32 bits */
 };
 

@@ -1,6 +1,6 @@
 /*
  * wr_tuner_ring.hip -- the tuner's pinned audio ring (wr_tuner_audio_ring): blocks of audio queued in page-locked
- * host memory by the submit path (wr_tuner.hip) and by the streaming launch (wr_tuner_stream.hip), handed out in
+ * host memory by the submit path (wr_tuner_submit.hip) and by the streaming launch (wr_tuner_stream.hip), handed out in
  * order to a consumer thread.
  */
 #include "wr_capi_internal.h"

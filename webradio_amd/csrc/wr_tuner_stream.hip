@@ -1,7 +1,7 @@
 /*
  * wr_tuner_stream.hip -- the host half of the tuner's streaming launch (wr_tuner_set_streaming): open, doorbell,
  * blocks out of page-locked host memory, close.  The device half is k_tuner_stream (wr_stream_kernel.inc); the
- * tuner itself is in wr_tuner.hip.
+ * tuner itself is in wr_tuner.hip, the launch-per-block submit path in wr_tuner_submit.hip.
  */
 #include "wr_capi_internal.h"
 

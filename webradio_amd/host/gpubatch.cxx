@@ -792,22 +792,50 @@ unsigned long long TunerBatch::chanSpectraCalls()
 	return _tapCalls;
 }
 
+/* What both taps begin with: the batch below whose source `block` runs is locked with `lock`, and the channel that `owns`
+ * says `block` belongs to is looked up in the batch's own list under that lock (withdraw() may be taking the chain out on
+ * another thread).  Returns the channel, seated in a slot of the batch's tuner (Channel::batch) -- or NULL and the tap's
+ * `*answer`: TAP_NONE or TAP_NOTHING_YET. */
+const Channel *TunerBatch::tapChannel(const DspBlock *block, bool (*owns)(const Channel *, const DspBlock *),
+                                      std::unique_lock<std::mutex> &lock, Tap *answer)
+{
+	DspSource *src = rootSource(block);
+	TunerBatch *b = src ? src->batch() : NULL;
+	*answer = TAP_NONE;
+	if (!b)
+		return NULL;
+	lock = std::unique_lock<std::mutex>(b->_lock);
+	const Channel *ch = NULL;
+	for (size_t n = 0; n < b->_channels.size() && !ch; n++)
+		if (owns(b->_channels[n], block))
+			ch = b->_channels[n];
+	if (!ch || !b->_tuner)
+		return NULL;
+	*answer = TAP_NOTHING_YET;
+	return ch->slot < 0 ? NULL : ch;
+}
+
+/* rows of room for every slot in use: the lane groups up to the highest one */
+size_t TunerBatch::rowsInUse() const
+{
+	int top = 0;
+	for (size_t n = 0; n < _channels.size(); n++)
+		if (_channels[n]->slot > top)
+			top = _channels[n]->slot;
+	return ((size_t)top / 64 + 1) * 64;
+}
+
 TunerBatch::Tap TunerBatch::chanSpectrum(const DspBlock *filter, wr_spectrum *spec, unsigned int fftSize, unsigned int hop,
                                          float *magnitudes)
 {
-	DspSource *src = rootSource(filter);
-	TunerBatch *b = src ? src->batch() : NULL;
-	if (!b)
-		return TAP_NONE;
-	std::lock_guard<std::mutex> g(b->_lock);
-	/* (looked up in the batch's own list under its lock: withdraw() may be taking the chain out on another thread) */
-	const Channel *ch = NULL;
-	for (size_t n = 0; n < b->_channels.size() && !ch; n++)
-		if ((b->_channels[n]->chanFilter2 ? b->_channels[n]->chanFilter2 : b->_channels[n]->chanFilter) == filter)
-			ch = b->_channels[n];
-	if (!ch || !b->_tuner)
-		return TAP_NONE;
-	if (ch->slot < 0 || !ch->tapLast)
+	std::unique_lock<std::mutex> g;
+	Tap answer;
+	const Channel *ch = tapChannel(filter, [](const Channel *c, const DspBlock *f) {
+		return (c->chanFilter2 ? c->chanFilter2 : c->chanFilter) == f; }, g, &answer);
+	if (!ch)
+		return answer;
+	TunerBatch *b = ch->batch;
+	if (!ch->tapLast)
 		return TAP_NOTHING_YET;
 	unsigned long long first = 0;
 	switch (spectrumFrameStart(ch->tapTotal, fftSize, hop, ch->tapLast, &first)) {
@@ -830,11 +858,7 @@ TunerBatch::Tap TunerBatch::chanSpectrum(const DspBlock *filter, wr_spectrum *sp
 		if (b->_tapRows[n].n == fftSize && b->_tapRows[n].first == first)
 			rows = &b->_tapRows[n];
 	if (!rows) {
-		int top = 0;
-		for (size_t n = 0; n < b->_channels.size(); n++)
-			if (b->_channels[n]->slot > top)
-				top = b->_channels[n]->slot;
-		const size_t room = ((size_t)top / 64 + 1) * 64;             /* the lane groups in use */
+		const size_t room = b->rowsInUse();
 		TapRows fresh;
 		fresh.n = fftSize;
 		fresh.first = first;
@@ -868,26 +892,16 @@ unsigned long long TunerBatch::chanLevelCalls()
 
 TunerBatch::Tap TunerBatch::chanLevel(const Demodulator *demod, float *mean, float *peak, unsigned int *muted)
 {
-	DspSource *src = rootSource(demod);
-	TunerBatch *b = src ? src->batch() : NULL;
-	if (!b)
-		return TAP_NONE;
-	std::lock_guard<std::mutex> g(b->_lock);
-	/* (looked up in the batch's own list under its lock, as chanSpectrum does) */
-	const Channel *ch = NULL;
-	for (size_t n = 0; n < b->_channels.size() && !ch; n++)
-		if (b->_channels[n]->demod == demod)
-			ch = b->_channels[n];
-	if (!ch || !b->_tuner)
-		return TAP_NONE;
-	if (ch->slot < 0 || !b->_lateSeq)
+	std::unique_lock<std::mutex> g;
+	Tap answer;
+	const Channel *ch = tapChannel(demod, [](const Channel *c, const DspBlock *d) { return c->demod == d; }, g, &answer);
+	if (!ch)
+		return answer;
+	TunerBatch *b = ch->batch;
+	if (!b->_lateSeq)
 		return TAP_NOTHING_YET;
 	if (b->_lvSeq != b->_lateSeq) {
-		int top = 0;
-		for (size_t n = 0; n < b->_channels.size(); n++)
-			if (b->_channels[n]->slot > top)
-				top = b->_channels[n]->slot;
-		const size_t room = ((size_t)top / 64 + 1) * 64;             /* the lane groups in use */
+		const size_t room = b->rowsInUse();
 		b->_lvMean.assign(room, 0.0f);
 		b->_lvPeak.assign(room, 0.0f);
 		b->_lvMuted.assign(room, 0u);

@@ -167,6 +167,9 @@ private:
 	void drainRing();
 	void countTapFrames(unsigned int nframes, unsigned int parts);
 	bool sinkQualifies(const SpectrumSink *sink, const LowPass *f1, const LowPass *f1b) const;
+	static const Channel *tapChannel(const DspBlock *block, bool (*owns)(const Channel *, const DspBlock *),
+	                                 std::unique_lock<std::mutex> &lock, Tap *answer);
+	size_t rowsInUse() const;
 
 	DspSource *_source;
 	wr_dev *_dev;
