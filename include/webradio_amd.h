@@ -55,6 +55,9 @@ extern "C" {
                                     Added to 6 later: wr_agc_design, wr_agc_rows, wr_chan_set_agc, wr_chan_get_agc, wr_tuner_agc_info.
                                     Added to 6 later: wr_tone_step, wr_tones_create, wr_tones_destroy, wr_tones_reset,
                                                       wr_tones_push_rows, wr_tuner_tones_push, wr_tones_read.
+                                    Added to 6 later: wr_resamp_ratio, wr_resamp_design, wr_resamp_create, wr_resamp_destroy,
+                                                      wr_resamp_reset, wr_resamp_out_frames, wr_resamp_push_rows,
+                                                      wr_resamp_info, wr_tuner_resamp_push.
                                     Nothing of an earlier version changed or removed */
 #define WR_FIR_LENGTH    64      /* dsp/lowpass.cxx:39  FIR_LENGTH */
 #define WR_TABLE_SIZE    65536   /* dsp/downconverter.cxx:35 LOOKUP_BITS 16 */
@@ -101,6 +104,7 @@ typedef struct wr_tuner    wr_tuner;
 typedef struct wr_spectrum wr_spectrum;
 typedef struct wr_ring     wr_ring;
 typedef struct wr_tones    wr_tones;
+typedef struct wr_resamp   wr_resamp;
 
 /* ------------------------------------------------------------------ misc -- */
 int         wr_abi_version(void);
@@ -733,6 +737,79 @@ int wr_tuner_tones_push(wr_tuner *tuner, wr_tones *bank, unsigned int *slots);
  * stream. */
 int wr_tones_read(wr_tones *bank, long long *iq_host /* [rows][ntones][2] */, long long *energy_host,
                   unsigned long long *windows_host, unsigned int *fill_host, unsigned int *rows);
+
+/* RESAMPLER: every receiver's audio at a sound-card rate.  A tuner's audio rate is what its decimations leave (50 kHz off
+ * 100 Msps with 400 and 5; 32 kHz in BASELINE config 1); the reference avoids the question by choosing a tuner rate that
+ * divides down to 48 000 (radio.cxx:79-81), which a 100 Msps front end does not have.  A bank is `max_rows` rows with ONE
+ * rational ratio L / M and P taps per phase: a polyphase FIR run over plain rows of audio, or over the last submit's audio
+ * rows of every channel slot of a tuner, in one launch sequence.
+ *
+ * THE RULE is this library's own definition, as the ones of af_gain, squelch, AGC and the tones are.
+ * The bank has ONE clock: N, the input frames pushed since creation or since a reset of every row.  Every push advances
+ * all rows together, so all rows of a push yield the same number of output frames and the receivers stay aligned.
+ * A row holds the stream x[n]; x[n] = 0 for n < 0 and for frames before the row's last reset.  Each input is cleaned:
+ *   x'   = 0.0f if (bits(x) & 0x7fffffff) >= 0x7f800000 (inf, NaN), else min(max(x, -65536.0f), 65536.0f)
+ * (-0.0f stays -0.0f).  Output frame m = 0, 1, ... has t = m * M, n0 = t / L (floor), ph = t mod L and
+ *   acc  = +0.0f
+ *   for k = 0 ... P-1 in this order:  acc = acc + c[ph][k] * x'[n0 - k]
+ *   y[m] = acc
+ * Every product and every sum is rounded to float32 once; nothing is fused, and there is one accumulator.  Taps are finite
+ * and |c| <= 16 (wr_resamp_create refuses others), so |acc| <= 2^26: nothing overflows and no NaN arises.
+ * Frame m comes out with the push that holds input frame n0(m): a push that takes the clock from N0 to N1 yields
+ * ceil(N1 * L / M) - ceil(N0 * L / M) frames, which can be 0.  Only N mod M is needed and kept, so nothing ever wraps; two
+ * 64-bit counts of frames in and out are kept beside it (wr_resamp_info).  A row's state is its last P - 1 cleaned inputs.
+ * An output has ONE value whatever the grid and whatever the cut of the stream into pushes; a restatement in float32 numpy
+ * is bit-identical.  The group delay is (L * P - 1) / 2 samples at L times the input rate: about P / 2 input frames.
+ * Limits, each WR_ERR_ARG: 1 <= L <= 1024; 1 <= M <= 8 L and L <= 8 M (more decimation than that belongs to the tuner's
+ * own filters); P a multiple of 4 from 4 to 64; L * P <= 16384; max_rows from 1 to 65535; a push of at most 2^28 frames;
+ * input and output of a push may not overlap.
+ * Left out on purpose: an int16 output; a host-side C++ class (the reference has none to mirror); per-row ratios; arbitrary
+ * (non-rational) ratios and clock-drift tracking; resampling inside the streaming launch; time sharding.
+ *
+ * wr_resamp_ratio: *L = out_rate / g, *M = in_rate / g with g = gcd(in_rate, out_rate); needs no device.  WR_ERR_ARG: a
+ * rate of 0, a NULL pointer (the limits above are wr_resamp_design's and wr_resamp_create's to enforce). */
+int wr_resamp_ratio(unsigned int in_rate, unsigned int out_rate, unsigned int *L, unsigned int *M);
+/* A Kaiser-windowed sinc for in_rate -> out_rate with P taps per phase, computed in double; needs no device.  beta = 8,
+ * Nh = L * P taps at L * in_rate, transition width D = 5 * in_rate / P Hz centred at fc = min(in_rate, out_rate) / 2 - D / 2:
+ *   h[i] = sinc(2 fc / (L in_rate) * (i - (Nh - 1) / 2)) * kaiser(i),   sinc(x) = sin(pi x) / (pi x),
+ *   kaiser(i) = I0(beta * sqrt(1 - (2 i / (Nh - 1) - 1)^2)) / I0(beta)
+ * scaled so that sum h = L, rounded to float32 once and stored as c[ph][k] = h[k * L + ph].  The stopband (from min / 2
+ * up) lies below -65 dB, the passband (to min / 2 - D) within -60 dB of 1.  WR_ERR_ARG: a limit above, or unless
+ * min(in_rate, out_rate) > 10 * in_rate / P (the passband edge would not lie above 0).  L and M may be NULL. */
+int wr_resamp_design(unsigned int in_rate, unsigned int out_rate, unsigned int P, float *taps_host /* [L][P] */,
+                     unsigned int *L, unsigned int *M);
+/* taps_host[L][P] as wr_resamp_design stores them (or the caller's own).  WR_ERR_ARG: a limit above, a tap that is not
+ * finite or whose magnitude exceeds 16. */
+int wr_resamp_create(wr_resamp **rs, wr_dev *dev, unsigned int max_rows, unsigned int L, unsigned int M, unsigned int P,
+                     const float *taps_host);
+int wr_resamp_destroy(wr_resamp *rs);
+/* Clears the row's history: it holds silence before its next frame; the clock runs on.  row < 0: every history, and the
+ * clock returns to 0 (the frame counts too).  What a caller does after wr_tuner_seek, wr_chan_reset_history or a retune of
+ * the receiver in that slot: the bank does not watch the tuner.  Asynchronous on the device's stream. */
+int wr_resamp_reset(wr_resamp *rs, int row);
+/* *n_out: the output frames a push of `nframes` frames would yield now.  Host only. */
+int wr_resamp_out_frames(wr_resamp *rs, size_t nframes, size_t *n_out);
+/* The rule on a plain block of rows in device memory: `nrows` rows of `nframes` floats, `row_stride` floats apart; row r of
+ * the call is row r of the bank, and its *n_out output frames go to out_dev + r * out_stride.  Consecutive calls continue
+ * the streams whatever the lengths.  A push of nrows < max_rows clears the histories of the rows it leaves out: those rows
+ * saw nothing.  Asynchronous on the device's stream, *n_out is known without a wait; counted by wr_block_kernel_calls.
+ * WR_ERR_ARG: NULL arguments, nrows > max_rows, row_stride < nframes or out_stride < *n_out with several rows, more than
+ * 2^28 frames, input and output that overlap. */
+int wr_resamp_push_rows(wr_resamp *rs, const float *in_dev, size_t row_stride, size_t nrows, size_t nframes, float *out_dev,
+                        size_t out_stride, size_t *n_out);
+/* The ratio, the taps per phase and the frames pushed and yielded since creation or the last reset of every row.  Any
+ * pointer may be NULL.  Host only. */
+int wr_resamp_info(wr_resamp *rs, unsigned int *L, unsigned int *M, unsigned int *P, unsigned long long *frames_in,
+                   unsigned long long *frames_out);
+/* Pushes the last submit's audio rows of every channel slot: WR_STAGE_AUDIO as wr_tuner_audio_dev shows it -- after
+ * squelch, AGC, af_gain and scale; row = wr_chan_slot, rows counted as wr_tuner_tones_push counts them (*slots: whole
+ * lane groups of 64); rows of slots that hold no channel carry no meaning.  Row s yields *n_out frames at
+ * out_dev + s * out_stride.  Like every getter it sends held blocks out, launches a pending post stage and closes an
+ * open streaming launch; it writes nothing the next block reads.  Asynchronous behind that.
+ * WR_ERR_STATE: nothing submitted yet, several rate groups, the same submit pushed twice (the bank remembers the tuner's
+ * submit count).  WR_ERR_ARG: max_rows below the slot count, a bank of another device, out_stride < *n_out. */
+int wr_tuner_resamp_push(wr_tuner *tuner, wr_resamp *rs, float *out_dev, size_t out_stride, size_t *n_out,
+                         unsigned int *slots);
 #ifdef __cplusplus
 }
 #endif

@@ -6,10 +6,18 @@ the reference's DspBlock operator API.  The Python modules here are plumbing for
 and bench.py:
 
   capi    ctypes declarations of the C ABI (fails loudly if the library is not built)
-  device  Device / Tuner / Spectrum handles over the C ABI
+  device  Device / Tuner / Spectrum / ToneBank / Resampler handles over the C ABI
   synth   synthetic tuner streams (test and bench inputs)
 """
-__all__ = ["capi", "device", "synth", "CTCSS_HZ"]
+__all__ = ["capi", "device", "synth", "CTCSS_HZ", "Resampler", "resamp_design", "resamp_ratio"]
+
+
+def __getattr__(name):
+    # the resampler's names, from device (imported on first use: importing the package loads no library)
+    if name in ("Resampler", "resamp_design", "resamp_ratio"):
+        from . import device
+        return getattr(device, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 # the 50 standard CTCSS tones, Hz (device.ToneBank)
 CTCSS_HZ = (67.0, 69.3, 71.9, 74.4, 77.0, 79.7, 82.5, 85.4, 88.5, 91.5, 94.8, 97.4, 100.0, 103.5, 107.2, 110.9, 114.8, 118.8,

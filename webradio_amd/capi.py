@@ -139,6 +139,16 @@ SIGNATURES = {
     "wr_tones_push_rows": (C.c_int, [_vp, _vp, _sz, _sz, _sz]),
     "wr_tuner_tones_push": (C.c_int, [_vp, _vp, C.POINTER(_u32)]),
     "wr_tones_read": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "wr_resamp_ratio": (C.c_int, [_u32, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
+    "wr_resamp_design": (C.c_int, [_u32, _u32, _u32, _vp, C.POINTER(_u32), C.POINTER(_u32)]),
+    "wr_resamp_create": (C.c_int, [C.POINTER(_vp), _vp, _u32, _u32, _u32, _u32, _vp]),
+    "wr_resamp_destroy": (C.c_int, [_vp]),
+    "wr_resamp_reset": (C.c_int, [_vp, C.c_int]),
+    "wr_resamp_out_frames": (C.c_int, [_vp, _sz, C.POINTER(_sz)]),
+    "wr_resamp_push_rows": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "wr_resamp_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_ulonglong),
+                                 C.POINTER(C.c_ulonglong)]),
+    "wr_tuner_resamp_push": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_u32)]),
 }
 
 

@@ -296,9 +296,27 @@ struct wr_tones {
 	unsigned long long last_seq = 0;
 };
 
+struct wr_resamp {
+	wr_dev *dev;
+	unsigned int max_rows, L, M, P;
+	float *taps;               /* device, [L][P] */
+	float *hist[2];            /* device, [max_rows][P - 1] each: a push reads set `cur` and writes the other (wr_resamp.hip) */
+	unsigned int cur = 0;
+	unsigned int zero_from[2] = {0, 0};   /* rows of a set from this one on are known to hold silence */
+	unsigned int nmod = 0;     /* the clock: input frames so far, mod M */
+	unsigned long long frames_in = 0, frames_out = 0;
+	/* wr_tuner_resamp_push: whose submit, and which, the bank took last -- the same one is not pushed twice */
+	const wr_tuner *last_tuner = nullptr;
+	unsigned long long last_seq = 0;
+};
+
 /* ------------------------------------------------------------------ helpers that cross files -- */
 
 /* wr_dev.hip */
+int        wrc_resamp_check(const wr_resamp *rs, const char *who, const float *in_dev, size_t row_stride, size_t nrows,
+                            size_t nframes, const float *out_dev, size_t out_stride, size_t *n_out);
+int        wrc_resamp_push(wr_resamp *rs, const float *in_dev, size_t row_stride, size_t nrows, size_t nframes, float *out_dev,
+                           size_t out_stride);
 int        wrc_dev_bind(wr_dev *d);
 int        wrc_dev_settle_stream(wr_dev *d);        /* closes the streaming launch that is open on the device's stream, if any */
 hipError_t wrc_dev_stream_sync(wr_dev *d);          /* ... and waits for the stream */

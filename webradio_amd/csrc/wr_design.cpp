@@ -157,3 +157,76 @@ int wrd_tone_step(double hz, unsigned int audio_rate, unsigned int *step)
 	*step = (unsigned int)llround(hz / (double)audio_rate * 4294967296.0);
 	return 0;
 }
+
+/* wr_resamp_ratio (include/webradio_amd.h): both rates divided by their gcd */
+int wrd_resamp_ratio(unsigned int in_rate, unsigned int out_rate, unsigned int *L, unsigned int *M)
+{
+	if (!in_rate || !out_rate)
+		return 1;
+	unsigned int a = in_rate, b = out_rate;
+	while (b) {
+		const unsigned int r = a % b;
+		a = b;
+		b = r;
+	}
+	*L = out_rate / a;
+	*M = in_rate / a;
+	return 0;
+}
+
+/* the header's limits on a resampler's ratio and taps per phase */
+int wrd_resamp_limits(unsigned int L, unsigned int M, unsigned int P)
+{
+	return !L || L > 1024u || !M || M > 8u * L || L > 8u * M || P < 4u || P > 64u || (P & 3u) || L * P > 16384u;
+}
+
+namespace {
+/* the modified Bessel function I0 by its power series: sum ((x / 2)^k / k!)^2, terms falling from k > x / 2 on */
+double bessel_i0(double x)
+{
+	const double q = x * x / 4.0;
+	double term = 1.0, sum = 1.0;
+	for (unsigned int k = 1; k < 500u; ++k) {
+		term *= q / ((double)k * (double)k);
+		sum += term;
+		if (term < sum * 1e-18)
+			break;
+	}
+	return sum;
+}
+}
+
+/* wr_resamp_design (include/webradio_amd.h): the Kaiser-windowed sinc, in double, narrowed once; taps[L][P].  Non-zero: a
+ * limit, or no passband */
+int wrd_resamp_design(unsigned int in_rate, unsigned int out_rate, unsigned int P, float *taps, unsigned int *L_out,
+                      unsigned int *M_out)
+{
+	unsigned int L, M;
+	if (wrd_resamp_ratio(in_rate, out_rate, &L, &M) || wrd_resamp_limits(L, M, P))
+		return 1;
+	const unsigned int lo = in_rate < out_rate ? in_rate : out_rate;
+	if (!((unsigned long long)lo * P > 10ull * in_rate))
+		return 1;
+	const double beta = 8.0, width = 5.0 * (double)in_rate / (double)P;
+	const double fc = (double)lo / 2.0 - width / 2.0;
+	const double wn = 2.0 * fc / ((double)L * (double)in_rate);            /* cut-off in units of the Nyquist rate at L x in_rate */
+	const unsigned int nh = L * P;
+	const double mid = ((double)nh - 1.0) / 2.0, i0b = bessel_i0(beta);
+	double *h = new double[nh];
+	double sum = 0.0;
+	for (unsigned int i = 0; i < nh; ++i) {
+		const double x = wn * ((double)i - mid);
+		const double s = x == 0.0 ? 1.0 : sin(kPi * x) / (kPi * x);
+		const double u = ((double)i - mid) / mid;
+		const double w = bessel_i0(beta * sqrt(1.0 - u * u > 0.0 ? 1.0 - u * u : 0.0)) / i0b;
+		h[i] = s * w;
+		sum += h[i];
+	}
+	for (unsigned int k = 0; k < P; ++k)
+		for (unsigned int ph = 0; ph < L; ++ph)
+			taps[(size_t)ph * P + k] = (float)(h[(size_t)k * L + ph] * (double)L / sum);
+	delete[] h;
+	*L_out = L;
+	*M_out = M;
+	return 0;
+}

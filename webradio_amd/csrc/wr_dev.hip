@@ -735,6 +735,199 @@ extern "C" int wr_tones_read(wr_tones *b, long long *iq_host, long long *energy_
 	return WR_OK;
 }
 
+/* ------------------------------------------------------------------ resampler -- */
+
+extern "C" int wr_resamp_ratio(unsigned int in_rate, unsigned int out_rate, unsigned int *L, unsigned int *M)
+{
+	if (!L || !M || wrd_resamp_ratio(in_rate, out_rate, L, M))
+		return wrc_fail(WR_ERR_ARG, "wr_resamp_ratio: bad argument (NULL L or M, or a rate of 0: %u -> %u)", in_rate, out_rate);
+	return WR_OK;
+}
+
+extern "C" int wr_resamp_design(unsigned int in_rate, unsigned int out_rate, unsigned int P, float *taps_host, unsigned int *L,
+                                unsigned int *M)
+{
+	if (!taps_host)
+		return wrc_fail(WR_ERR_ARG, "wr_resamp_design: taps_host is NULL");
+	unsigned int l = 0, m = 0;
+	if (wrd_resamp_design(in_rate, out_rate, P, taps_host, &l, &m))
+		return wrc_fail(WR_ERR_ARG, "wr_resamp_design: %u -> %u Hz with %u taps per phase: a rate of 0, L / M outside 1 <= L <= 1024, "
+		                "M <= 8 L, L <= 8 M, P not a multiple of 4 in 4 .. 64, L * P above 16384, or no passband "
+		                "(min(in, out) <= 10 in / P)", in_rate, out_rate, P);
+	if (L)
+		*L = l;
+	if (M)
+		*M = m;
+	return WR_OK;
+}
+
+extern "C" int wr_resamp_create(wr_resamp **rs, wr_dev *d, unsigned int max_rows, unsigned int L, unsigned int M, unsigned int P,
+                                const float *taps_host)
+{
+	if (!rs || !d || !taps_host)
+		return wrc_fail(WR_ERR_ARG, "wr_resamp_create: bad argument (NULL rs, dev or taps_host)");
+	if (!max_rows || max_rows > 65535u || wrd_resamp_limits(L, M, P))
+		return wrc_fail(WR_ERR_ARG, "wr_resamp_create: %u rows (1 .. 65535), L / M = %u / %u (1 <= L <= 1024, M <= 8 L, L <= 8 M), "
+		                "%u taps per phase (a multiple of 4 in 4 .. 64, L * P <= 16384)", max_rows, L, M, P);
+	const size_t ntaps = (size_t)L * P, nhist = (size_t)max_rows * (P - 1u);
+	for (size_t i = 0; i < ntaps; ++i) {
+		uint32_t bits;
+		memcpy(&bits, taps_host + i, sizeof(bits));
+		if ((bits & 0x7fffffffu) >= 0x7f800000u || !(fabsf(taps_host[i]) <= 16.0f))
+			return wrc_fail(WR_ERR_ARG, "wr_resamp_create: tap [%zu][%zu] = %g is not finite or above 16 in magnitude", i / P, i % P,
+			                (double)taps_host[i]);
+	}
+	if (wrc_dev_bind(d))
+		return WR_ERR_HIP;
+	DEV_SETTLE(d);
+	wr_resamp *r = new (std::nothrow) wr_resamp();
+	if (!r)
+		return wrc_fail(WR_ERR_ARG, "wr_resamp_create: out of memory");
+	r->dev = d;
+	r->max_rows = max_rows;
+	r->L = L;
+	r->M = M;
+	r->P = P;
+	r->taps = r->hist[0] = r->hist[1] = nullptr;
+	hipError_t e = hipMalloc((void **)&r->taps, ntaps * sizeof(float));
+	for (unsigned int s = 0; s < 2u && e == hipSuccess; ++s) {
+		e = hipMalloc((void **)&r->hist[s], nhist * sizeof(float));
+		if (e == hipSuccess)
+			e = hipMemsetAsync(r->hist[s], 0, nhist * sizeof(float), d->stream);
+	}
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(r->taps, taps_host, ntaps * sizeof(float), hipMemcpyHostToDevice, d->stream);
+	if (e == hipSuccess)
+		e = wrc_dev_stream_sync(d);                             /* (the copy's source is the caller's) */
+	if (e != hipSuccess) {
+		wr_resamp_destroy(r);
+		return wrc_fail(WR_ERR_HIP, "wr_resamp_create: %s", hipGetErrorString(e));
+	}
+	*rs = r;
+	return WR_OK;
+}
+
+extern "C" int wr_resamp_destroy(wr_resamp *r)
+{
+	if (!r)
+		return WR_OK;
+	(void)hipSetDevice(r->dev->device);
+	(void)wrc_dev_stream_sync(r->dev);
+	(void)hipFree(r->taps);
+	(void)hipFree(r->hist[0]);
+	(void)hipFree(r->hist[1]);
+	delete r;
+	return WR_OK;
+}
+
+extern "C" int wr_resamp_reset(wr_resamp *r, int row)
+{
+	if (!r)
+		return wrc_fail(WR_ERR_ARG, "wr_resamp_reset: rs is NULL");
+	if (row >= 0 && (unsigned int)row >= r->max_rows)
+		return wrc_fail(WR_ERR_ARG, "wr_resamp_reset: row %d of a bank of %u", row, r->max_rows);
+	wr_dev *d = r->dev;
+	if (wrc_dev_bind(d))
+		return WR_ERR_HIP;
+	DEV_SETTLE(d);
+	/* only the set the next push reads matters: that push writes the other one */
+	const size_t H = r->P - 1u;
+	if (row < 0) {
+		HIP_TRY(hipMemsetAsync(r->hist[r->cur], 0, (size_t)r->max_rows * H * sizeof(float), d->stream));
+		r->zero_from[r->cur] = 0;
+		r->nmod = 0;
+		r->frames_in = r->frames_out = 0;
+	} else {
+		HIP_TRY(hipMemsetAsync(r->hist[r->cur] + (size_t)row * H, 0, H * sizeof(float), d->stream));
+	}
+	return WR_OK;
+}
+
+extern "C" int wr_resamp_out_frames(wr_resamp *r, size_t nframes, size_t *n_out)
+{
+	if (!r || !n_out || nframes > ((size_t)1 << 28))
+		return wrc_fail(WR_ERR_ARG, "wr_resamp_out_frames: bad argument (NULL rs or n_out, or more than 2^28 frames)");
+	*n_out = (size_t)wrk_resamp_out_frames(r->L, r->M, r->nmod, nframes);
+	return WR_OK;
+}
+
+/* what both pushes refuse, and the output frames of the push (`who` names the caller in the message) */
+int wrc_resamp_check(const wr_resamp *r, const char *who, const float *in_dev, size_t row_stride, size_t nrows, size_t nframes,
+                     const float *out_dev, size_t out_stride, size_t *n_out)
+{
+	if (nrows > r->max_rows || (nrows > 1 && row_stride < nframes) || nframes > ((size_t)1 << 28))
+		return wrc_fail(WR_ERR_ARG, "%s: %zu rows for a bank of %u, or rows of %zu frames that overlap at a stride of %zu, or more "
+		                "than 2^28 frames", who, nrows, r->max_rows, nframes, row_stride);
+	const size_t n = (size_t)wrk_resamp_out_frames(r->L, r->M, r->nmod, nframes);
+	*n_out = n;
+	if (!nrows || !n)
+		return WR_OK;
+	if (!out_dev || (nrows > 1 && out_stride < n))
+		return wrc_fail(WR_ERR_ARG, "%s: out_dev is NULL, or rows of %zu output frames overlap at a stride of %zu", who, n, out_stride);
+	const uintptr_t a0 = (uintptr_t)in_dev, a1 = a0 + ((nrows - 1u) * row_stride + nframes) * sizeof(float);
+	const uintptr_t b0 = (uintptr_t)out_dev, b1 = b0 + ((nrows - 1u) * out_stride + n) * sizeof(float);
+	if (a0 < b1 && b0 < a1)
+		return wrc_fail(WR_ERR_ARG, "%s: input and output overlap", who);
+	return WR_OK;
+}
+
+/* the push itself, behind wrc_resamp_check, on a bound and settled device: the rows it leaves out lose their histories,
+ * the clock and the counts advance, the history sets change places */
+int wrc_resamp_push(wr_resamp *r, const float *in_dev, size_t row_stride, size_t nrows, size_t nframes, float *out_dev,
+                    size_t out_stride)
+{
+	if (!nframes)
+		return WR_OK;
+	wr_dev *d = r->dev;
+	const unsigned int from = r->cur, to = from ^ 1u;
+	const size_t H = r->P - 1u;
+	if (nrows < r->zero_from[to])
+		HIP_TRY(hipMemsetAsync(r->hist[to] + nrows * H, 0, (r->zero_from[to] - nrows) * H * sizeof(float), d->stream));
+	const WrResampPush p = {r->taps, r->L, r->M, r->P, r->nmod, r->hist[from], r->hist[to]};
+	HIP_TRY(wrk_resamp_push(d->stream, in_dev, row_stride, nrows, nframes, p, out_dev, out_stride));
+	r->zero_from[to] = (unsigned int)nrows;
+	r->cur = to;
+	r->frames_in += nframes;
+	r->frames_out += wrk_resamp_out_frames(r->L, r->M, r->nmod, nframes);
+	r->nmod = (unsigned int)((r->nmod + nframes) % r->M);
+	return WR_OK;
+}
+
+extern "C" int wr_resamp_push_rows(wr_resamp *r, const float *in_dev, size_t row_stride, size_t nrows, size_t nframes,
+                                   float *out_dev, size_t out_stride, size_t *n_out)
+{
+	if (!r || !in_dev || !n_out)
+		return wrc_fail(WR_ERR_ARG, "wr_resamp_push_rows: bad argument (NULL rs, in_dev or n_out)");
+	if (int rc = wrc_resamp_check(r, "wr_resamp_push_rows", in_dev, row_stride, nrows, nframes, out_dev, out_stride, n_out))
+		return rc;
+	if (!nframes)
+		return WR_OK;
+	wr_dev *d = r->dev;
+	if (wrc_dev_bind(d))
+		return WR_ERR_HIP;
+	g_block_kernel_calls.fetch_add(1, std::memory_order_relaxed);
+	DEV_SETTLE(d);
+	return wrc_resamp_push(r, in_dev, row_stride, nrows, nframes, out_dev, out_stride);
+}
+
+extern "C" int wr_resamp_info(wr_resamp *r, unsigned int *L, unsigned int *M, unsigned int *P, unsigned long long *frames_in,
+                              unsigned long long *frames_out)
+{
+	if (!r)
+		return wrc_fail(WR_ERR_ARG, "wr_resamp_info: rs is NULL");
+	if (L)
+		*L = r->L;
+	if (M)
+		*M = r->M;
+	if (P)
+		*P = r->P;
+	if (frames_in)
+		*frames_in = r->frames_in;
+	if (frames_out)
+		*frames_out = r->frames_out;
+	return WR_OK;
+}
+
 extern "C" int wr_u8_to_f32(wr_dev *d, const uint8_t *in_dev, float *out_dev, size_t count)
 {
 	if (!d || (count && (!in_dev || !out_dev)))

@@ -1,6 +1,7 @@
 /*
  * wr_internal.h -- internal C++ interface between the C ABI (wr_dev.hip, wr_tuner*.hip, wr_spectrum.hip), the host
- * design math (wr_design.cpp) and the kernels (wr_kernels.hip, wr_fft.hip, wr_levels.hip, wr_agc.hip, wr_tones.hip).
+ * design math (wr_design.cpp) and the kernels (wr_kernels.hip, wr_fft.hip, wr_levels.hip, wr_agc.hip, wr_tones.hip,
+ * wr_resamp.hip).
  * Not installed; the public boundary is include/webradio_amd.h.
  */
 #ifndef WR_INTERNAL_H_
@@ -41,6 +42,11 @@ int      wrd_agc_design(float target_dbfs, float decay_db_per_s, float max_gain_
                         unsigned int *floor_bits, unsigned int *step);
 /* wr_tone_step's arithmetic (in double); non-zero unless 0 < hz < audio_rate / 2 */
 int      wrd_tone_step(double hz, unsigned int audio_rate, unsigned int *step);
+/* wr_resamp_ratio's and wr_resamp_design's arithmetic, and the header's limits on (L, M, P); non-zero: refused */
+int      wrd_resamp_ratio(unsigned int in_rate, unsigned int out_rate, unsigned int *L, unsigned int *M);
+int      wrd_resamp_limits(unsigned int L, unsigned int M, unsigned int P);
+int      wrd_resamp_design(unsigned int in_rate, unsigned int out_rate, unsigned int P, float *taps /* [L][P] */, unsigned int *L,
+                           unsigned int *M);
 
 /* ---- per-slot parameter block of one rate group of a tuner, device SoA ---- */
 struct WrGroupDev {
@@ -371,6 +377,22 @@ struct WrTonesRow {                        /* everything a bank holds of one row
  * goes into rows[r]; t12[4096] is every 16th entry of the sine table, steps[64] the tones' phase steps (0 beyond ntones) */
 hipError_t wrk_tones_push(hipStream_t st, const float *audio, size_t row_stride, size_t nrows, size_t nframes, WrTonesRow *rows,
                           const float *t12, const unsigned int *steps, unsigned int ntones, unsigned int window);
+
+/* ---- resampler (wr_resamp.hip) ---- */
+/* what a push is, besides its rows: the bank's ratio and taps, the clock before it (nmod = N mod M) and the two history
+ * sets [rows][P - 1] -- read from hist_old, written (for the `nrows` rows of the push) to hist_new */
+struct WrResampPush {
+	const float *taps;                 /* device, [L][P]; 16-byte aligned */
+	unsigned int L, M, P, nmod;
+	const float *hist_old;
+	float       *hist_new;
+};
+/* the output frames a push of `nframes` yields at clock `nmod`: ceil((nmod + nframes) L / M) - ceil(nmod L / M) */
+unsigned long long wrk_resamp_out_frames(unsigned int L, unsigned int M, unsigned int nmod, unsigned long long nframes);
+/* include/webradio_amd.h's rule (wr_resamp_push_rows) on `nrows` rows of `nframes` floats, `row_stride` floats apart: row r
+ * yields wrk_resamp_out_frames() frames at out + r * out_stride */
+hipError_t wrk_resamp_push(hipStream_t st, const float *in, size_t row_stride, size_t nrows, size_t nframes, const WrResampPush &p,
+                           float *out, size_t out_stride);
 
 hipError_t wrk_bins_to_db(hipStream_t st, const float *bins, unsigned int n, float *db);
 hipError_t wrk_waterfall_row(hipStream_t st, const float *bins, unsigned int n, unsigned int width, int hold,

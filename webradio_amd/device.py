@@ -372,6 +372,21 @@ class Tuner:
         check(self.lib.wr_tuner_tones_push(self.h, bank.h, C.byref(slots)))
         return slots.value
 
+    def resamp_push(self, rs):
+        """The last submit's audio rows of every channel slot through a Resampler (wr_tuner_resamp_push); row = Tuner.slot.
+        Returns the output frames as an array [slots][n_out] (slots: whole lane groups of 64), downloaded."""
+        rows = (self.max_channels + 63) // 64 * 64
+        _, _, frames = self.audio_dev()
+        stride = max(rs.out_frames(frames), 1)
+        p = self.dev.malloc(rows * stride * 4)
+        try:
+            n_out, slots = C.c_size_t(), C.c_uint()
+            check(self.lib.wr_tuner_resamp_push(self.h, rs.h, C.c_void_p(p), stride, C.byref(n_out), C.byref(slots)))
+            out = self.dev.download(p, slots.value * stride)
+        finally:
+            self.dev.free(p)
+        return out.reshape(slots.value, stride)[:, : n_out.value].copy()
+
 
 def tone_step(hz, audio_rate):
     """a tone's phase step per audio frame, llround(hz / audio_rate * 2^32) (wr_tone_step); needs no device."""
@@ -551,3 +566,69 @@ class Ring:
         if self.h:
             self.lib.wr_ring_destroy(self.h)
             self.h = None
+
+
+def resamp_ratio(in_rate, out_rate):
+    """(L, M): out_rate / in_rate in lowest terms (wr_resamp_ratio); needs no device."""
+    L, M = C.c_uint(), C.c_uint()
+    check(capi.load().wr_resamp_ratio(in_rate, out_rate, C.byref(L), C.byref(M)))
+    return L.value, M.value
+
+
+def resamp_design(in_rate, out_rate, taps_per_phase=32):
+    """(taps float32 [L][P], L, M): the Kaiser-windowed sinc of wr_resamp_design; needs no device."""
+    L, M = resamp_ratio(in_rate, out_rate)
+    taps = np.zeros((L, max(taps_per_phase, 1)), np.float32)
+    check(capi.load().wr_resamp_design(in_rate, out_rate, taps_per_phase, ptr(taps), None, None))
+    return taps, L, M
+
+
+class Resampler:
+    """wr_resamp: max_rows rows of audio resampled by one ratio L / M = out_rate / in_rate with a polyphase FIR of
+    taps_per_phase taps per phase, the streams running on from push to push (include/webradio_amd.h: RESAMPLER)."""
+
+    def __init__(self, dev, max_rows, in_rate, out_rate, taps_per_phase=32, taps=None):
+        """wr_resamp_design's taps -- or, with `taps` [L][P], the caller's own for the same ratio"""
+        self.dev = dev
+        self.lib = dev.lib
+        self.max_rows = max_rows
+        if taps is None:
+            taps, self.L, self.M = resamp_design(in_rate, out_rate, taps_per_phase)
+        else:
+            self.L, self.M = resamp_ratio(in_rate, out_rate)
+            taps = np.ascontiguousarray(taps, dtype=np.float32)
+            assert taps.ndim == 2 and taps.shape[0] == self.L
+        self.taps = taps
+        self.P = taps.shape[1]
+        h = C.c_void_p()
+        check(self.lib.wr_resamp_create(C.byref(h), dev.h, max_rows, self.L, self.M, self.P, ptr(self.taps)))
+        self.h = h
+
+    def destroy(self):
+        if self.h:
+            self.lib.wr_resamp_destroy(self.h)
+            self.h = None
+
+    def reset(self, row=-1):
+        """a row's history is cleared (row < 0: every row's, and the clock returns to 0)"""
+        check(self.lib.wr_resamp_reset(self.h, row))
+
+    def out_frames(self, nframes):
+        """the output frames a push of nframes would yield now"""
+        n = C.c_size_t()
+        check(self.lib.wr_resamp_out_frames(self.h, nframes, C.byref(n)))
+        return n.value
+
+    def push_rows(self, p, row_stride, nrows, nframes, out_p, out_stride):
+        """nrows rows of nframes floats at device pointer p, row_stride floats apart, continue rows 0 .. nrows-1; row r's
+        output frames go to device pointer out_p + 4 * r * out_stride.  Returns their number.  Asynchronous."""
+        n = C.c_size_t()
+        check(self.lib.wr_resamp_push_rows(self.h, C.c_void_p(p), row_stride, nrows, nframes, C.c_void_p(out_p), out_stride,
+                                           C.byref(n)))
+        return n.value
+
+    def info(self):
+        """(L, M, P, frames_in, frames_out)"""
+        L, M, P, fi, fo = C.c_uint(), C.c_uint(), C.c_uint(), C.c_ulonglong(), C.c_ulonglong()
+        check(self.lib.wr_resamp_info(self.h, C.byref(L), C.byref(M), C.byref(P), C.byref(fi), C.byref(fo)))
+        return L.value, M.value, P.value, fi.value, fo.value
