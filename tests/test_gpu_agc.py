@@ -12,6 +12,7 @@ import pytest
 
 import agc_np
 from agc_np import OFF, bits
+from rowcases import channel_ifs as _ifs, keyed_block as _block   # (at FS, the builder's default rate)
 from webradio_amd import capi
 from webradio_amd.device import Tuner, agc_design
 
@@ -147,22 +148,6 @@ def test_edge_steps(dev, n):
 
 
 # ---- 4, 5: the tuner -----------------------------------------------------------------------------------------------------------
-
-def _ifs(nrx):
-    return [(c - nrx // 2) * 25_000 + 321 for c in range(nrx)]
-
-
-def _block(nframes, ifs, seed, pos=0):
-    """noise in every channel, and a carrier keyed at 150 Hz on each of `ifs` (test_gpu_chan_levels._block)"""
-    tt = (np.arange(nframes) + pos) / FS
-    iq = (0.002 * np.random.default_rng(seed).standard_normal(2 * nframes)).astype(np.float32)
-    env = 0.02 * (1.0 + np.sign(np.sin(2 * np.pi * 150.0 * tt))) * 0.5
-    for f in ifs:
-        ph = 2 * np.pi * ((f * tt) % 1.0)
-        iq[0::2] += (env * np.cos(ph)).astype(np.float32)
-        iq[1::2] += (env * np.sin(ph)).astype(np.float32)
-    return iq
-
 
 def _agc_settings(c):
     return -12.0 - c % 5, 20.0 * (1 + c % 3), 60.0

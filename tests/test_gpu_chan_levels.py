@@ -13,6 +13,7 @@ import pytest
 
 import levels_np
 from levels_np import bits
+from rowcases import channel_ifs as _ifs, keyed_block as _block   # (at FS, the builder's default rate, unless told)
 from webradio_amd import capi, synth
 from webradio_amd.device import Tuner
 
@@ -20,22 +21,6 @@ pytestmark = pytest.mark.gpu
 
 FS, CHAN_RATE, AUDIO_RATE, D1, D2 = 2_000_000, 5_000, 1_000, 400, 5
 K1S = [1, 10, 15, 16, 17, 255, 256, 257, 600]
-
-
-def _ifs(nrx):
-    return [(c - nrx // 2) * 25_000 + 321 for c in range(nrx)]
-
-
-def _block(nframes, ifs, seed, pos=0, scale=1.0, fs=FS):
-    """noise in every channel, and a carrier keyed at 150 Hz on each of `ifs`"""
-    tt = (np.arange(nframes) + pos) / fs
-    iq = (0.002 * scale * np.random.default_rng(seed).standard_normal(2 * nframes)).astype(np.float32)
-    env = 0.02 * scale * (1.0 + np.sign(np.sin(2 * np.pi * 150.0 * tt))) * 0.5
-    for f in ifs:
-        ph = 2 * np.pi * ((f * tt) % 1.0)
-        iq[0::2] += (env * np.cos(ph)).astype(np.float32)
-        iq[1::2] += (env * np.sin(ph)).astype(np.float32)
-    return iq
 
 
 def _as_u8(iq):

@@ -14,9 +14,11 @@ import numpy as np
 import pytest
 
 import resamp_np
+import rowcases
 import tones_np
+from rowcases import BLOCK, K2, NBLOCKS
 from webradio_amd import capi
-from webradio_amd.device import Resampler, Tuner, resamp_design
+from webradio_amd.device import Resampler, resamp_design
 
 pytestmark = pytest.mark.gpu
 
@@ -44,13 +46,7 @@ def _bank(dev, max_rows, L, M, taps):
 def _rows(nrows, n, seed):
     """values from 1e-4 to beyond the clamp, both signs, and in every row the non-finite, saturating, signed-zero and
     subnormal values"""
-    rng = np.random.default_rng(seed)
-    v = (rng.standard_normal((nrows, n)) * 10.0 ** rng.integers(-4, 7, (nrows, n))).astype(np.float32)
-    for r in range(nrows):
-        where = rng.choice(n, size=min(n, len(SPECIAL)), replace=False)
-        for k, at in enumerate(where):
-            v[r, at] = np.float32(SPECIAL[k])
-    return v
+    return rowcases.special_rows(nrows, n, seed, 7, SPECIAL)
 
 
 def _frames_for(want, outputs):
@@ -201,41 +197,16 @@ def test_reset_and_rows_left_out(dev):
 
 # ---- 3: behind a tuner ----------------------------------------------------------------------------------------------------------
 
-NBLOCKS, BLOCK = 12, 100_000
-K2 = BLOCK // (tones_np.FS // tones_np.AUDIO_RATE)
 OUT_RATE, TAPS = 750, 32
-_plain_audio = {}
 
 
 @pytest.fixture(scope="module")
 def fm_stream(dev):
     """the twelve blocks in device memory, back to back; uploaded once"""
-    p = dev.upload(np.concatenate([tones_np.fm_block(BLOCK, b * BLOCK) for b in range(NBLOCKS)]))
+    p = rowcases.fm_upload(dev)
     yield p
-    _plain_audio.clear()
+    rowcases.forget_twins()
     dev.free(p)
-
-
-def _fm_tuner(dev, streaming, spare=0):
-    t = Tuner(dev, tones_np.FS, len(tones_np.IFS) + spare, BLOCK, capi.WR_NCO_ROTATE)
-    chans = [t.add_receiver(f, tones_np.CHAN_PASSBAND, tones_np.CHAN_RATE, capi.WR_FM, tones_np.AUDIO_PASSBAND,
-                            tones_np.AUDIO_RATE) for f in tones_np.IFS]
-    if streaming:
-        t.streaming(True)
-    return t, chans
-
-
-def _twin_audio(dev, x, streaming):
-    """[block][receiver] audio of the same tuner that never sees the call; run once per way of launching"""
-    if streaming not in _plain_audio:
-        t, chans = _fm_tuner(dev, streaming)
-        out = []
-        for b in range(NBLOCKS):
-            t.submit_device(x + 8 * BLOCK * b, BLOCK)
-            out.append([t.fetch(ch, capi.WR_STAGE_AUDIO, K2) for ch in chans])
-        t.destroy()
-        _plain_audio[streaming] = out
-    return _plain_audio[streaming]
 
 
 def _raw_push(dev, t, rs, stride):
@@ -253,8 +224,8 @@ def _raw_push(dev, t, rs, stride):
 @pytest.mark.parametrize("streaming", [False, True], ids=["per-block", "streaming"])
 def test_behind_a_tuner(dev, fm_stream, streaming):
     x = fm_stream
-    plain = _twin_audio(dev, x, streaming)
-    t, chans = _fm_tuner(dev, streaming)
+    plain = rowcases.twin_audio(dev, x, capi.WR_NCO_ROTATE, streaming)   # the same tuner that never sees the call
+    t, chans = rowcases.fm_tuner(dev, capi.WR_NCO_ROTATE, streaming)
     slots = [t.slot(ch) for ch in chans]
     rs = Resampler(dev, 64, tones_np.AUDIO_RATE, OUT_RATE, TAPS)
     want = resamp_np.Bank(64, rs.L, rs.M, rs.taps)
@@ -293,7 +264,7 @@ def test_behind_a_tuner(dev, fm_stream, streaming):
 
 def test_tuner_errors_and_a_new_slot(dev, fm_stream):
     lib = dev.lib
-    t, chans = _fm_tuner(dev, False, spare=2)
+    t, chans = rowcases.fm_tuner(dev, capi.WR_NCO_ROTATE, spare=2)
     rs = Resampler(dev, 64, tones_np.AUDIO_RATE, OUT_RATE, TAPS)
     small = Resampler(dev, 5, tones_np.AUDIO_RATE, OUT_RATE, TAPS)
     want = resamp_np.Bank(64, rs.L, rs.M, rs.taps)

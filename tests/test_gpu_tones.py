@@ -12,9 +12,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import rowcases
 import tones_np
+from rowcases import BLOCK, K2, NBLOCKS
 from webradio_amd import CTCSS_HZ, capi
-from webradio_amd.device import ToneBank, Tuner
+from webradio_amd.device import ToneBank
 
 pytestmark = pytest.mark.gpu
 
@@ -35,13 +37,7 @@ def _steps(ntones):
 
 def _rows(nrows, n, seed):
     """values from 1e-4 to beyond the clamp, both signs, and in every row the non-finite and saturating values"""
-    rng = np.random.default_rng(seed)
-    v = (rng.standard_normal((nrows, n)) * 10.0 ** rng.integers(-4, 3, (nrows, n))).astype(np.float32)
-    for r in range(nrows):
-        where = rng.choice(n, size=min(n, len(SPECIAL)), replace=False)
-        for k, at in enumerate(where):
-            v[r, at] = np.float32(SPECIAL[k])
-    return v
+    return rowcases.special_rows(nrows, n, seed, 3, SPECIAL)
 
 
 def _lengths(W):
@@ -171,46 +167,21 @@ def test_reset_clears_that_row_alone(dev):
 
 # ---- 3: behind a tuner ----------------------------------------------------------------------------------------------------------
 
-NBLOCKS, BLOCK = 12, 100_000
-_plain_audio = {}
-K2 = BLOCK // (tones_np.FS // tones_np.AUDIO_RATE)
-
-
 @pytest.fixture(scope="module")
 def fm_stream(dev):
     """the twelve blocks in device memory, back to back; uploaded once"""
-    p = dev.upload(np.concatenate([tones_np.fm_block(BLOCK, b * BLOCK) for b in range(NBLOCKS)]))
+    p = rowcases.fm_upload(dev)
     yield p
-    _plain_audio.clear()
+    rowcases.forget_twins()
     dev.free(p)
-
-
-def _fm_tuner(dev, nco, spare=0):
-    t = Tuner(dev, tones_np.FS, len(tones_np.IFS) + spare, BLOCK, nco)
-    chans = [t.add_receiver(f, tones_np.CHAN_PASSBAND, tones_np.CHAN_RATE, capi.WR_FM, tones_np.AUDIO_PASSBAND,
-                            tones_np.AUDIO_RATE) for f in tones_np.IFS]
-    return t, chans
-
-
-def _audio_without_a_bank(dev, x, nco):
-    """[block][receiver] audio of the same tuner with no bank, a launch per block; run once per NCO mode"""
-    if nco not in _plain_audio:
-        t, chans = _fm_tuner(dev, nco)
-        out = []
-        for b in range(NBLOCKS):
-            t.submit_device(x + 8 * BLOCK * b, BLOCK)
-            out.append([t.fetch(ch, capi.WR_STAGE_AUDIO, K2) for ch in chans])
-        t.destroy()
-        _plain_audio[nco] = out
-    return _plain_audio[nco]
 
 
 @pytest.mark.parametrize("how", ["per-block", "streaming", "two-per-launch"])
 @pytest.mark.parametrize("nco", [capi.WR_NCO_EXACT, capi.WR_NCO_ROTATE], ids=["exact", "rotate"])
 def test_behind_a_tuner(dev, fm_stream, nco, how):
     x = fm_stream
-    plain = _audio_without_a_bank(dev, x, nco)
-    t, chans = _fm_tuner(dev, nco)
+    plain = rowcases.twin_audio(dev, x, nco)             # the same tuner with no bank, a launch per block
+    t, chans = rowcases.fm_tuner(dev, nco)
     if how == "streaming":
         t.streaming(True)
     if how == "two-per-launch":
@@ -259,7 +230,7 @@ def test_behind_a_tuner(dev, fm_stream, nco, how):
 
 def test_tuner_errors(dev, fm_stream):
     lib = dev.lib
-    t, chans = _fm_tuner(dev, capi.WR_NCO_ROTATE, spare=1)
+    t, chans = rowcases.fm_tuner(dev, capi.WR_NCO_ROTATE, spare=1)
     bank = ToneBank(dev, 64, CTCSS_HZ, tones_np.AUDIO_RATE, 500)
     small = ToneBank(dev, 5, CTCSS_HZ, tones_np.AUDIO_RATE, 500)
     try:

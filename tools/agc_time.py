@@ -16,71 +16,28 @@ over repeated calls, ALTERNATING window by window:
   rows_64       the same on 64 x 2 000: a quarter of the workgroups, three quarters of the CUs idle;
   copy          a device-to-device copy of the same 2.05 MB: the price of touching those bytes once.
 Prints one JSON line."""
-import argparse
 import json
-import os
 import statistics
-import sys
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--windows", type=int, default=8)
-ap.add_argument("--seconds", type=float, default=0.2)
-ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-args = ap.parse_args()
-sys.path.insert(0, os.path.abspath(args.root))
+import timing
+
+args = timing.parse(timing.parser())
 
 import numpy as np                                        # noqa: E402
 import torch                                              # noqa: E402
-from webradio_amd import capi, synth                      # noqa: E402
-from webradio_amd.device import Device, Tuner, agc_design  # noqa: E402
+from webradio_amd import synth                            # noqa: E402
+from webradio_amd.device import agc_design                # noqa: E402
 
 C2 = synth.C2
 NRX, NFRAMES = C2["channels"], C2["block_frames"]
 K2 = NFRAMES // (C2["input_rate"] // C2["audio_rate"])
 BYTES = K2 * NRX * 4
 
-dev = Device(0, torch.cuda.current_stream().cuda_stream)
-ifs = synth.c2_ifs()
-block = synth.fm_stream_torch(NFRAMES, C2["input_rate"], ifs[::8], "cuda", noise_dbfs=-50.0)
-
-
-def make(agc):
-    t = Tuner(dev, C2["input_rate"], NRX, NFRAMES)
-    chans = [t.add_receiver(f, C2["chan_passband"], C2["chan_rate"], capi.WR_FM, C2["audio_passband"], C2["audio_rate"])
-             for f in ifs]
-    if agc:
-        for ch in chans:
-            t.set_agc(ch)
-    return t
-
-
-with_agc, plain = make(True), make(False)
+dev, ifs, block = timing.c2_case()
+with_agc, plain = timing.c2_tuner(dev, ifs, agc=True)[0], timing.c2_tuner(dev, ifs)[0]
 rows = torch.randn(NRX * K2, device="cuda")
 target, floor_bits, step = agc_design(audio_rate=C2["audio_rate"])
 par = {n: (np.full(n, target, np.float32), np.full(n, floor_bits, np.uint32), np.full(n, step, np.uint32)) for n in (NRX, 64)}
-src = torch.randn(BYTES // 4, device="cuda")
-dst = torch.empty_like(src)
-
-
-def us_per_call(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / reps
-
-
-def reps_for(fn):
-    for _ in range(3):                                    # warm-up: code objects, uploads, the scratch buffer
-        fn()
-    torch.cuda.synchronize()
-    return max(8, int(args.seconds * 1e6 / us_per_call(fn, 20)) + 1)
-
-
-def summary(us):
-    return {"median": round(statistics.median(us), 2), "min": round(min(us), 2), "max": round(max(us), 2)}
 
 
 def submit_agc():
@@ -96,17 +53,9 @@ def rows_n(n):
     return lambda: dev.agc_rows(rows.data_ptr(), K2, n, K2, t, f, s, f)
 
 
-def copy():
-    dst.copy_(src)
-
-
 fns = {"submit_agc": submit_agc, "submit_plain": submit_plain, "submit_plain_b": submit_plain, "rows_256": rows_n(NRX),
-       "rows_64": rows_n(64), "copy": copy}
-reps = {k: reps_for(fn) for k, fn in fns.items()}
-got = {k: [] for k in fns}
-for _ in range(args.windows):
-    for k, fn in fns.items():
-        got[k].append(us_per_call(fn, reps[k]))
+       "rows_64": rows_n(64), "copy": timing.copier(BYTES)}
+got, reps = timing.measure(fns, args)
 with_agc.flush()
 plain.flush()
 torch.cuda.synchronize()
@@ -114,8 +63,8 @@ on, launches = with_agc.agc_info()
 assert on == NRX and launches > 0 and plain.agc_info() == (0, 0)
 med = {k: statistics.median(v) for k, v in got.items()}
 print(json.dumps({"receivers": NRX, "k2": K2, "bytes": BYTES, "step": step, "windows": args.windows, "reps_per_window": reps,
-                  **{k + "_us": summary(v) for k, v in got.items()},
-                  "spread_same_code": round(max(abs(u / v - 1.0) for u, v in zip(got["submit_plain"], got["submit_plain_b"])), 4),
+                  **{k + "_us": timing.summary(v) for k, v in got.items()},
+                  "spread_same_code": timing.spread(got["submit_plain"], got["submit_plain_b"]),
                   "agc_in_a_submit_us": round(med["submit_agc"] - 0.5 * (med["submit_plain"] + med["submit_plain_b"]), 2),
                   "rows_64_over_rows_256": round(med["rows_64"] / med["rows_256"], 3),
                   "rows_256_over_copy": round(med["rows_256"] / med["copy"], 3)}), flush=True)

@@ -17,62 +17,31 @@ calls, the four ALTERNATING window by window:
 and with a host clock:
   per_chan   256 x wr_chan_fetch(WR_STAGE_CHAN_IQ) plus the sum in numpy: what there was.
 Prints one JSON line per case."""
-import argparse
 import json
-import os
 import statistics
-import sys
 import time
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--windows", type=int, default=8)
-ap.add_argument("--seconds", type=float, default=0.2)
+import timing
+
+ap = timing.parser()
 ap.add_argument("--per-chan-rounds", type=int, default=2)
-ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-args = ap.parse_args()
-sys.path.insert(0, os.path.abspath(args.root))
+args = timing.parse(ap)
 
 import numpy as np                                        # noqa: E402
 import torch                                              # noqa: E402
 from webradio_amd import capi, synth                      # noqa: E402
-from webradio_amd.device import Device, Spectrum, Tuner   # noqa: E402
+from webradio_amd.device import Spectrum                  # noqa: E402
 
 C2 = synth.C2
 NRX, NFRAMES = C2["channels"], C2["block_frames"]
 K1 = NFRAMES // (C2["input_rate"] // C2["chan_rate"])
 BYTES = K1 * NRX * 8
 
-dev = Device(0, torch.cuda.current_stream().cuda_stream)
-ifs = synth.c2_ifs()
-block = synth.fm_stream_torch(NFRAMES, C2["input_rate"], ifs[::8], "cuda", noise_dbfs=-50.0)
-tuner = Tuner(dev, C2["input_rate"], NRX, NFRAMES)
-chans = [tuner.add_receiver(f, C2["chan_passband"], C2["chan_rate"], capi.WR_FM, C2["audio_passband"], C2["audio_rate"])
-         for f in ifs]
+dev, ifs, block = timing.c2_case()
+tuner, chans = timing.c2_tuner(dev, ifs)
 spec = Spectrum(dev, 512)
 db = torch.empty(NRX * 512, device="cuda")
-src = torch.randn(BYTES // 4, device="cuda")
-dst = torch.empty_like(src)
-
-
-def us_per_call(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / reps
-
-
-def reps_for(fn):
-    for _ in range(3):                                    # warm-up: code objects, the LDS attribute, the scratch buffer
-        fn()
-    torch.cuda.synchronize()
-    return max(8, int(args.seconds * 1e6 / us_per_call(fn, 20)) + 1)
-
-
-def summary(us):
-    return {"median": round(statistics.median(us), 2), "min": round(min(us), 2), "max": round(max(us), 2)}
+copy = timing.copier(BYTES)
 
 
 def levels():
@@ -83,10 +52,6 @@ def spectra():
     tuner.chan_spectra(spec, K1 - 512, db_dev=db)
 
 
-def copy():
-    dst.copy_(src)
-
-
 for squelch in (False, True):
     for ch in chans:
         tuner.set_squelch(ch, -30.0, squelch)
@@ -95,13 +60,9 @@ for squelch in (False, True):
     torch.cuda.synchronize()
     mean, peak, muted, frames, audio_frames = tuner.chan_levels()
     assert frames == K1 and mean.size == NRX
-    rl, rs, rc = reps_for(levels), reps_for(spectra), reps_for(copy)
-    a, b, s, c = [], [], [], []
-    for _ in range(args.windows):
-        a.append(us_per_call(levels, rl))
-        s.append(us_per_call(spectra, rs))
-        b.append(us_per_call(levels, rl))
-        c.append(us_per_call(copy, rc))
+    rl, rs, rc = (timing.reps_for(fn, args.seconds) for fn in (levels, spectra, copy))
+    got = timing.alternate({"a": levels, "s": spectra, "b": levels, "c": copy}, {"a": rl, "s": rs, "b": rl, "c": rc}, args.windows)
+    a, b, s, c = got["a"], got["b"], got["s"], got["c"]
     per, worst = [], 0.0
     for rnd in range(args.per_chan_rounds + 1):
         t0 = time.perf_counter()
@@ -116,13 +77,13 @@ for squelch in (False, True):
     print(json.dumps({"squelch_on_every_receiver": squelch, "receivers": NRX, "k1": K1, "bytes": BYTES,
                       "muted_frames_min_max": [int(muted.min()), int(muted.max())], "audio_frames": audio_frames,
                       "windows": args.windows, "reps_per_window": {"levels": rl, "spectra": rs, "copy": rc},
-                      "levels_us_per_call": summary(a), "levels_b_us_per_call": summary(b),
-                      "spread_same_code": round(max(abs(u / v - 1.0) for u, v in zip(a, b)), 4),
-                      "spectra_512_us_per_call": summary(s), "copy_us": summary(c),
+                      "levels_us_per_call": timing.summary(a), "levels_b_us_per_call": timing.summary(b),
+                      "spread_same_code": timing.spread(a, b),
+                      "spectra_512_us_per_call": timing.summary(s), "copy_us": timing.summary(c),
                       "levels_GB_per_s_whole_call": round(BYTES / med / 1e3, 1),
                       "copy_GB_per_s_read_plus_write": round(2 * BYTES / statistics.median(c) / 1e3, 1),
                       "levels_over_copy": round(med / statistics.median(c), 3),
-                      "per_chan_route_us_for_all": summary(per),
+                      "per_chan_route_us_for_all": timing.summary(per),
                       "per_chan_route_over_levels": round(statistics.median(per) / med, 1),
                       "max_relative_difference_of_the_means": float("%.3g" % worst)}), flush=True)
 spec.destroy()

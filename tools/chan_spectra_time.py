@@ -13,60 +13,34 @@ channel-rate frames per receiver.  Per size three figures:
   per_chan   256 x (wr_chan_fetch(WR_STAGE_CHAN_IQ) + wr_spectrum_push from the host + wr_spectrum_get_db), a host clock
              around calls that each end in a synchronise.
 Prints one JSON line per size."""
-import argparse
 import json
-import os
 import statistics
-import sys
 import time
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--windows", type=int, default=8)
-ap.add_argument("--seconds", type=float, default=0.2)
+import timing
+
+ap = timing.parser()
 ap.add_argument("--sizes", default="512,2048,8192")
 ap.add_argument("--per-chan-rounds", type=int, default=3)
-ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-args = ap.parse_args()
-sys.path.insert(0, os.path.abspath(args.root))
+args = timing.parse(ap)
 
 import torch                                              # noqa: E402
 from webradio_amd import capi, synth                      # noqa: E402
-from webradio_amd.device import Device, Spectrum, Tuner   # noqa: E402
+from webradio_amd.device import Spectrum                  # noqa: E402
 
 C2 = synth.C2
 NRX, NFRAMES = C2["channels"], C2["block_frames"]
 K1 = NFRAMES // (C2["input_rate"] // C2["chan_rate"])
 
-dev = Device(0, torch.cuda.current_stream().cuda_stream)
-ifs = synth.c2_ifs()
-block = synth.fm_stream_torch(NFRAMES, C2["input_rate"], ifs[::8], "cuda", noise_dbfs=-50.0)
-tuner = Tuner(dev, C2["input_rate"], NRX, NFRAMES)
-chans = [tuner.add_receiver(f, C2["chan_passband"], C2["chan_rate"], capi.WR_FM, C2["audio_passband"], C2["audio_rate"])
-         for f in ifs]
+dev, ifs, block = timing.c2_case()
+tuner, chans = timing.c2_tuner(dev, ifs)
 tuner.submit_device(block, NFRAMES)
 tuner.flush()
 torch.cuda.synchronize()
 
 
-def ms_per_call(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def reps_for(fn):
-    for _ in range(3):                                    # warm-up of this shape: code objects, the LDS attribute
-        fn()
-    torch.cuda.synchronize()
-    return max(8, int(args.seconds * 1e3 / ms_per_call(fn, 20)) + 1)
-
-
 def summary(ms):
-    return {"median": round(statistics.median(ms), 5), "min": round(min(ms), 5), "max": round(max(ms), 5)}
+    return timing.summary(ms, 5)
 
 
 for n in (int(s) for s in args.sizes.split(",")):
@@ -86,16 +60,12 @@ for n in (int(s) for s in args.sizes.split(",")):
     def rows2():
         spec2.batch_db_rows(rows_iq, n, NRX, out[1])
 
-    rc, rr = reps_for(columns), reps_for(rows)
-    reps_for(rows2)
-    a, b, c, r = [], [], [], []
-    for _ in range(args.windows):                         # the same code against itself
-        a.append(ms_per_call(rows, rr))
-        b.append(ms_per_call(rows2, rr))
-    for _ in range(args.windows):                         # columns against rows
-        c.append(ms_per_call(columns, rc))
-        r.append(ms_per_call(rows, rr))
-    spread = max(abs(u / v - 1.0) for u, v in zip(a, b))
+    rc, rr = timing.reps_for(columns, args.seconds), timing.reps_for(rows, args.seconds)
+    timing.reps_for(rows2, args.seconds)
+    reps = {"a": rr, "b": rr, "c": rc, "r": rr}
+    same = timing.alternate({"a": rows, "b": rows2}, reps, args.windows, timing.MS)          # the same code against itself
+    got = timing.alternate({"c": columns, "r": rows}, reps, args.windows, timing.MS)          # columns against rows
+    a, b, c, r = same["a"], same["b"], got["c"], got["r"]
 
     # the route there was: per receiver one gather kernel, one copy to the host, one synchronise -- and the frame back up
     want = tuner.chan_spectra(spec, first)
@@ -114,7 +84,7 @@ for n in (int(s) for s in args.sizes.split(",")):
             per.append((time.perf_counter() - t0) * 1e3)
     print(json.dumps({"fft_size": n, "receivers": NRX, "k1": K1, "first_frame": first, "windows": args.windows,
                       "reps_per_window": {"columns": rc, "rows": rr},
-                      "rows_ms_a": summary(a), "rows_ms_b": summary(b), "spread_same_code": round(spread, 4),
+                      "rows_ms_a": summary(a), "rows_ms_b": summary(b), "spread_same_code": timing.spread(a, b),
                       "columns_ms_per_call": summary(c), "rows_ms_per_call": summary(r),
                       "columns_over_rows": round(statistics.median(c) / statistics.median(r), 4),
                       "per_chan_route_ms_for_all": summary(per),

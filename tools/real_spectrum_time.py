@@ -9,47 +9,24 @@ receivers, else as many as --mbytes of real input hold), wr_spectrum_batch_db on
 the two ALTERNATING window by window; a window repeats the batch until it fills --seconds, between two device events.
 The first pair of figures per size is the IQ path against itself (two spectra of the same kind, alternating): the spread
 below which a difference means nothing.  Prints one JSON line per size."""
-import argparse
 import json
-import os
 import statistics
-import sys
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--windows", type=int, default=8)
-ap.add_argument("--seconds", type=float, default=0.2)
+import timing
+
+ap = timing.parser()
 ap.add_argument("--sizes", default="1024,4096,65536,1048576")
 ap.add_argument("--mbytes", type=int, default=64, help="real input per batch of the large sizes")
-ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-args = ap.parse_args()
-sys.path.insert(0, os.path.abspath(args.root))
+args = timing.parse(ap)
 
 import torch                                              # noqa: E402
-from webradio_amd.device import Device, Spectrum          # noqa: E402
+from webradio_amd.device import Spectrum                  # noqa: E402
 
-dev = Device(0, torch.cuda.current_stream().cuda_stream)
-
-
-def ms_per_batch(spec, x, rows, out, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        spec.batch_db(x, rows, out)
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def reps_for(spec, x, rows, out):
-    for _ in range(3):                                    # warm-up of this shape: code objects, the work area's growth
-        spec.batch_db(x, rows, out)
-    torch.cuda.synchronize()
-    ms = ms_per_batch(spec, x, rows, out, 20)
-    return max(8, int(args.seconds * 1e3 / ms) + 1)
+dev = timing.open_device()
 
 
 def summary(ms):
-    return {"median": round(statistics.median(ms), 5), "min": round(min(ms), 5), "max": round(max(ms), 5)}
+    return timing.summary(ms, 5)
 
 
 for n in (int(s) for s in args.sizes.split(",")):
@@ -63,25 +40,27 @@ for n in (int(s) for s in args.sizes.split(",")):
     iq[0::2] = x                                          # what a caller did before: zeros for Q, twice the bytes
     out = [torch.empty(rows * n, device="cuda") for _ in range(2)]
     real, cplx, cplx2 = Spectrum(dev, n, real=True), Spectrum(dev, n), Spectrum(dev, n)
-    rr, rc = reps_for(real, x, rows, out[0]), reps_for(cplx, iq, rows, out[1])
-    reps_for(cplx2, iq, rows, out[1])
+
+    def batch(spec, samples, db):
+        return lambda: spec.batch_db(samples, rows, db)
+
+    fns = {"r": batch(real, x, out[0]), "c": batch(cplx, iq, out[1]), "b": batch(cplx2, iq, out[1])}
+    rr, rc = timing.reps_for(fns["r"], args.seconds), timing.reps_for(fns["c"], args.seconds)
+    timing.reps_for(fns["b"], args.seconds)
     same = float((out[0] - out[1]).abs().max())           # (dB rows of the two paths, everywhere: noise-floor bins included)
-    a, b, r, c = [], [], [], []
-    for _ in range(args.windows):                         # the same code against itself
-        a.append(ms_per_batch(cplx, iq, rows, out[1], rc))
-        b.append(ms_per_batch(cplx2, iq, rows, out[1], rc))
-    for _ in range(args.windows):                         # real against IQ with zeros
-        r.append(ms_per_batch(real, x, rows, out[0], rr))
-        c.append(ms_per_batch(cplx, iq, rows, out[1], rc))
-    spread = max(abs(u / v - 1.0) for u, v in zip(a, b))
+    reps = {"r": rr, "c": rc, "b": rc}
+    got = timing.alternate({"c": fns["c"], "b": fns["b"]}, reps, args.windows, timing.MS)   # the same code against itself
+    a, b = got["c"], got["b"]
+    got = timing.alternate({"r": fns["r"], "c": fns["c"]}, reps, args.windows, timing.MS)   # real against IQ with zeros
+    r, c = got["r"], got["c"]
     print(json.dumps({"fft_size": n, "rows": rows, "windows": args.windows, "reps_per_window": {"real": rr, "iq": rc},
                       "iq_ms_per_batch_a": summary(a), "iq_ms_per_batch_b": summary(b),
-                      "spread_same_code": round(spread, 4),
+                      "spread_same_code": timing.spread(a, b),
                       "real_ms_per_batch": summary(r), "iq_zero_q_ms_per_batch": summary(c),
                       "real_over_iq": round(statistics.median(r) / statistics.median(c), 4),
                       "max_db_difference_real_vs_iq": round(same, 5)}), flush=True)
     for s in (real, cplx, cplx2):
         s.destroy()
-    del x, iq, out, t
+    del x, iq, out, t, fns
     torch.cuda.empty_cache()
 dev.close()

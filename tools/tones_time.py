@@ -16,115 +16,31 @@ streaming off in both tuners.  Figures, all between two device events over repea
   submit_plain_b the same again: the spread below which a difference means nothing;
   copy           a device-to-device copy of the same 2.05 MB: the price of touching those bytes once.
 Prints one JSON line."""
-import argparse
 import json
-import os
-import statistics
-import sys
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--windows", type=int, default=8)
-ap.add_argument("--seconds", type=float, default=0.2)
-ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-args = ap.parse_args()
-sys.path.insert(0, os.path.abspath(args.root))
+import timing
+
+args = timing.parse(timing.parser())
 
 import torch                                              # noqa: E402
-from webradio_amd import CTCSS_HZ, capi, synth            # noqa: E402
-from webradio_amd.device import Device, ToneBank, Tuner   # noqa: E402
+from webradio_amd import CTCSS_HZ, synth                  # noqa: E402
+from webradio_amd.device import ToneBank                  # noqa: E402
 
 C2 = synth.C2
 NRX, NFRAMES = C2["channels"], C2["block_frames"]
 K2 = NFRAMES // (C2["input_rate"] // C2["audio_rate"])
-BYTES = K2 * NRX * 4
 WINDOW = 12_500
 
-dev = Device(0, torch.cuda.current_stream().cuda_stream)
-ifs = synth.c2_ifs()
-block = synth.fm_stream_torch(NFRAMES, C2["input_rate"], ifs[::8], "cuda", noise_dbfs=-50.0)
-
-
-def make():
-    t = Tuner(dev, C2["input_rate"], NRX, NFRAMES)
-    for f in ifs:
-        t.add_receiver(f, C2["chan_passband"], C2["chan_rate"], capi.WR_FM, C2["audio_passband"], C2["audio_rate"])
-    return t
-
-
-pushed, flushed, plain = make(), make(), make()
+dev, ifs, block = timing.c2_case()
 bank = ToneBank(dev, NRX, CTCSS_HZ, C2["audio_rate"], WINDOW)
 rows_bank = ToneBank(dev, NRX, CTCSS_HZ, C2["audio_rate"], WINDOW)
 rows = 0.05 * torch.randn(NRX * K2, device="cuda")
-src = torch.randn(BYTES // 4, device="cuda")
-dst = torch.empty_like(src)
 
-
-def us_per_call(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / reps
-
-
-def reps_for(fn):
-    for _ in range(3):                                    # warm-up: code objects, uploads
-        fn()
-    torch.cuda.synchronize()
-    return max(8, int(args.seconds * 1e6 / us_per_call(fn, 20)) + 1)
-
-
-def summary(us):
-    return {"median": round(statistics.median(us), 2), "min": round(min(us), 2), "max": round(max(us), 2)}
-
-
-def submit_push():
-    pushed.submit_device(block, NFRAMES)
-    pushed.tones_push(bank)
-
-
-def submit_flush():
-    flushed.submit_device(block, NFRAMES)
-    flushed.flush()
-
-
-def submit_plain():
-    plain.submit_device(block, NFRAMES)
-
-
-def rows_n(n):
-    return lambda: rows_bank.push_rows(rows.data_ptr(), K2, n, K2)
-
-
-def copy():
-    dst.copy_(src)
-
-
-fns = {"rows_256": rows_n(NRX), "rows_64": rows_n(64), "submit_push": submit_push, "submit_flush": submit_flush,
-       "submit_plain": submit_plain, "submit_plain_b": submit_plain, "copy": copy}
-reps = {k: reps_for(fn) for k, fn in fns.items()}
-got = {k: [] for k in fns}
-for _ in range(args.windows):
-    for k, fn in fns.items():
-        got[k].append(us_per_call(fn, reps[k]))
-for t in (pushed, flushed, plain):
-    t.flush()
-torch.cuda.synchronize()
+figures = timing.row_bank_figures(args, dev, ifs, block, lambda tuner: tuner.tones_push(bank),
+                                  lambda n: lambda: rows_bank.push_rows(rows.data_ptr(), K2, n, K2), K2 * NRX * 4)
 iq, energy, windows, fill = bank.read()
 assert int(windows[0]) > 0 and int(energy[0]) > 0 and int(windows[0]) == int(windows[NRX - 1])
-med = {k: statistics.median(v) for k, v in got.items()}
-plain_us = 0.5 * (med["submit_plain"] + med["submit_plain_b"])
-print(json.dumps({"receivers": NRX, "k2": K2, "tones": len(CTCSS_HZ), "window": WINDOW, "bytes": BYTES, "windows": args.windows,
-                  "reps_per_window": reps, **{k + "_us": summary(v) for k, v in got.items()},
-                  "spread_same_code": round(max(abs(u / v - 1.0) for u, v in zip(got["submit_plain"], got["submit_plain_b"])), 4),
-                  "push_in_a_submit_us": round(med["submit_push"] - plain_us, 2),
-                  "push_over_a_flush_us": round(med["submit_push"] - med["submit_flush"], 2),
-                  "rows_64_over_rows_256": round(med["rows_64"] / med["rows_256"], 3),
-                  "rows_256_over_copy": round(med["rows_256"] / med["copy"], 3)}), flush=True)
+print(json.dumps({"receivers": NRX, "k2": K2, "tones": len(CTCSS_HZ), "window": WINDOW, **figures}), flush=True)
 bank.destroy()
 rows_bank.destroy()
-for t in (pushed, flushed, plain):
-    t.destroy()
 dev.close()

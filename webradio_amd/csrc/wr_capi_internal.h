@@ -1,7 +1,7 @@
 /*
  * wr_capi_internal.h -- what the translation units of the extern "C" boundary (wr_dev.hip, wr_tuner.hip,
- * wr_tuner_submit.hip, wr_tuner_read.hip, wr_tuner_stream.hip, wr_tuner_ring.hip, wr_spectrum.hip) share: the objects
- * behind the handles, the error macros, and ONE declaration of every helper that crosses a file boundary (the wrc_
+ * wr_tuner_submit.hip, wr_tuner_read.hip, wr_tuner_stream.hip, wr_tuner_ring.hip, wr_spectrum.hip, wr_banks.hip) share: the
+ * objects behind the handles, the error macros, and ONE declaration of every helper that crosses a file boundary (the wrc_
  * names, as in wr_internal.h).  Included by those files only.
  */
 #ifndef WR_CAPI_INTERNAL_H
@@ -285,38 +285,35 @@ struct wr_spectrum {
 	unsigned long long deferred_pushes = 0, resolves = 0;
 };
 
-struct wr_tones {
+/* what the two objects of wr_banks.hip, which keep something per audio row of every receiver, begin with */
+struct WrRowBank {
 	wr_dev *dev;
-	unsigned int max_rows, ntones, window;
-	WrTonesRow *rows;          /* device, [max_rows] */
-	float *t12;                /* device, [4096]: every 16th entry of the reference sine table */
-	unsigned int *steps;       /* device, [64]: the tones' phase steps, 0 beyond ntones */
-	/* wr_tuner_tones_push: whose submit, and which, the bank took last -- the same one is not pushed twice */
+	unsigned int max_rows;
+	/* wr_tuner_tones_push, wr_tuner_resamp_push: whose submit, and which, the bank took last -- the same one is not pushed twice */
 	const wr_tuner *last_tuner = nullptr;
 	unsigned long long last_seq = 0;
 };
 
-struct wr_resamp {
-	wr_dev *dev;
-	unsigned int max_rows, L, M, P;
+struct wr_tones : WrRowBank {
+	unsigned int ntones, window;
+	WrTonesRow *rows;          /* device, [max_rows] */
+	float *t12;                /* device, [4096]: every 16th entry of the reference sine table */
+	unsigned int *steps;       /* device, [64]: the tones' phase steps, 0 beyond ntones */
+};
+
+struct wr_resamp : WrRowBank {
+	unsigned int L, M, P;
 	float *taps;               /* device, [L][P] */
 	float *hist[2];            /* device, [max_rows][P - 1] each: a push reads set `cur` and writes the other (wr_resamp.hip) */
 	unsigned int cur = 0;
 	unsigned int zero_from[2] = {0, 0};   /* rows of a set from this one on are known to hold silence */
 	unsigned int nmod = 0;     /* the clock: input frames so far, mod M */
 	unsigned long long frames_in = 0, frames_out = 0;
-	/* wr_tuner_resamp_push: whose submit, and which, the bank took last -- the same one is not pushed twice */
-	const wr_tuner *last_tuner = nullptr;
-	unsigned long long last_seq = 0;
 };
 
 /* ------------------------------------------------------------------ helpers that cross files -- */
 
 /* wr_dev.hip */
-int        wrc_resamp_check(const wr_resamp *rs, const char *who, const float *in_dev, size_t row_stride, size_t nrows,
-                            size_t nframes, const float *out_dev, size_t out_stride, size_t *n_out);
-int        wrc_resamp_push(wr_resamp *rs, const float *in_dev, size_t row_stride, size_t nrows, size_t nframes, float *out_dev,
-                           size_t out_stride);
 int        wrc_dev_bind(wr_dev *d);
 int        wrc_dev_settle_stream(wr_dev *d);        /* closes the streaming launch that is open on the device's stream, if any */
 hipError_t wrc_dev_stream_sync(wr_dev *d);          /* ... and waits for the stream */
@@ -325,6 +322,7 @@ void      *wrc_host_mapped(const void *host, hipError_t *why = nullptr);
 int        wrc_upload_mark_locked(wr_dev *d, hipStream_t st);
 int        wrc_upload_mark(wr_dev *d, hipStream_t st);
 int        wrc_dev_up_stream(wr_dev *d);
+void       wrc_block_kernel_called(void);           /* one more call for wr_block_kernel_calls() to report */
 
 /* wr_tuner.hip */
 unsigned int  wrc_group_slots_used(const Group *g);
@@ -345,7 +343,8 @@ void wrc_advance_phases(wr_tuner *t, unsigned long long frames);
 int  wrc_prof_pair_begin(wr_tuner *t, void **ev_start, void **ev_stop);
 void wrc_prof_pair_stamped(wr_tuner *t);
 
-/* wr_tuner_read.hip: the last submit as its readers see it, in two steps (a reader's own refusals go between them) */
+/* wr_tuner_read.hip: the last submit as its readers (and the tuner pushes of wr_banks.hip) see it, in two steps (a reader's
+ * own refusals go between them) */
 struct WrLastSubmit {
 	Group *g;                  /* the rate group read from: the tuner's one active group, or the channel's */
 	unsigned int used;         /* wrc_group_slots_used(g) */

@@ -3,8 +3,7 @@
  * the design-helper wrappers, wr_dev_*, the upload streams, and the reference's blocks as one kernel each.  No DSP
  * arithmetic lives here (design math: wr_design.cpp; kernels: wr_kernels.hip, wr_fft.hip).  The tuner is in
  * wr_tuner.hip (submit: wr_tuner_submit.hip, readers: wr_tuner_read.hip, streaming launch: wr_tuner_stream.hip, pinned
- * audio ring: wr_tuner_ring.hip), the spectrum
- * sink in wr_spectrum.hip.
+ * audio ring: wr_tuner_ring.hip), the spectrum sink in wr_spectrum.hip, the tone bank and the resampler in wr_banks.hip.
  *
  * There is deliberately no CPU code path: every data-path entry point needs a
  * wr_dev, and wr_dev_open fails with WR_ERR_NODEV when HIP reports no device.
@@ -468,6 +467,10 @@ extern "C" unsigned long long wr_block_kernel_calls(void)
 {
 	return g_block_kernel_calls.load(std::memory_order_relaxed);
 }
+void wrc_block_kernel_called(void)                       /* (the plain-rows pushes of wr_banks.hip count here too) */
+{
+	g_block_kernel_calls.fetch_add(1, std::memory_order_relaxed);
+}
 
 extern "C" int wr_mix(wr_dev *d, const float *in_dev, float *out_dev, size_t nframes,
                       unsigned int *phase_io, int phase_step)
@@ -588,343 +591,6 @@ extern "C" int wr_agc_rows(wr_dev *d, float *audio_dev, size_t row_stride, size_
 	HIP_TRY(wrk_agc_rows(d->stream, audio_dev, row_stride, nrows, nframes, par_dev, state_dev, 1.0f));
 	HIP_TRY(hipMemcpyAsync(state_host, state_dev, nrows * sizeof(unsigned int), hipMemcpyDeviceToHost, d->stream));
 	HIP_TRY(wrc_dev_stream_sync(d));
-	return WR_OK;
-}
-
-/* ------------------------------------------------------------------ tone bank -- */
-
-extern "C" int wr_tone_step(double hz, unsigned int audio_rate, unsigned int *step)
-{
-	if (!step)
-		return wrc_fail(WR_ERR_ARG, "wr_tone_step: step is NULL");
-	if (wrd_tone_step(hz, audio_rate, step))
-		return wrc_fail(WR_ERR_ARG, "wr_tone_step: %g Hz is not inside (0, %g), half the audio rate", hz, (double)audio_rate / 2.0);
-	return WR_OK;
-}
-
-extern "C" int wr_tones_create(wr_tones **bank, wr_dev *d, unsigned int max_rows, const unsigned int *steps_host,
-                               unsigned int ntones, unsigned int window)
-{
-	if (!bank || !d || !steps_host)
-		return wrc_fail(WR_ERR_ARG, "wr_tones_create: bad argument (NULL bank, dev or steps_host)");
-	if (!max_rows || max_rows > 65535u || !ntones || ntones > WR_LANES || window < 16u || window > 65536u)
-		return wrc_fail(WR_ERR_ARG, "wr_tones_create: %u rows (1 .. 65535), %u tones (1 .. 64), a window of %u frames "
-		                "(16 .. 65536)", max_rows, ntones, window);
-	unsigned int steps[WR_LANES] = {0};
-	for (unsigned int t = 0; t < ntones; ++t) {
-		if (!steps_host[t] || steps_host[t] >= 0x80000000u)
-			return wrc_fail(WR_ERR_ARG, "wr_tones_create: tone %u: a step of %u is not inside (0, 2^31)", t, steps_host[t]);
-		steps[t] = steps_host[t];
-	}
-	if (wrc_dev_bind(d))
-		return WR_ERR_HIP;
-	DEV_SETTLE(d);
-	std::vector<float> table(WR_TABLE_SIZE), t12(4096);
-	wrd_sin_table(table.data());
-	for (unsigned int i = 0; i < 4096u; ++i)
-		t12[i] = table[16u * i];
-	wr_tones *b = new (std::nothrow) wr_tones();
-	if (!b)
-		return wrc_fail(WR_ERR_ARG, "wr_tones_create: out of memory");
-	b->dev = d;
-	b->max_rows = max_rows;
-	b->ntones = ntones;
-	b->window = window;
-	b->rows = nullptr;
-	b->t12 = nullptr;
-	b->steps = nullptr;
-	hipError_t e = hipMalloc((void **)&b->rows, (size_t)max_rows * sizeof(WrTonesRow));
-	if (e == hipSuccess)
-		e = hipMalloc((void **)&b->t12, t12.size() * sizeof(float));
-	if (e == hipSuccess)
-		e = hipMalloc((void **)&b->steps, sizeof(steps));
-	if (e == hipSuccess)
-		e = hipMemsetAsync(b->rows, 0, (size_t)max_rows * sizeof(WrTonesRow), d->stream);
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(b->t12, t12.data(), t12.size() * sizeof(float), hipMemcpyHostToDevice, d->stream);
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(b->steps, steps, sizeof(steps), hipMemcpyHostToDevice, d->stream);
-	if (e == hipSuccess)
-		e = wrc_dev_stream_sync(d);                             /* (the copies' sources are this call's own) */
-	if (e != hipSuccess) {
-		wr_tones_destroy(b);
-		return wrc_fail(WR_ERR_HIP, "wr_tones_create: %s", hipGetErrorString(e));
-	}
-	*bank = b;
-	return WR_OK;
-}
-
-extern "C" int wr_tones_destroy(wr_tones *b)
-{
-	if (!b)
-		return WR_OK;
-	(void)hipSetDevice(b->dev->device);
-	(void)wrc_dev_stream_sync(b->dev);
-	(void)hipFree(b->rows);
-	(void)hipFree(b->t12);
-	(void)hipFree(b->steps);
-	delete b;
-	return WR_OK;
-}
-
-extern "C" int wr_tones_reset(wr_tones *b, int row)
-{
-	if (!b)
-		return wrc_fail(WR_ERR_ARG, "wr_tones_reset: bank is NULL");
-	if (row >= 0 && (unsigned int)row >= b->max_rows)
-		return wrc_fail(WR_ERR_ARG, "wr_tones_reset: row %d of a bank of %u", row, b->max_rows);
-	wr_dev *d = b->dev;
-	if (wrc_dev_bind(d))
-		return WR_ERR_HIP;
-	DEV_SETTLE(d);
-	/* a row that begins its stream is all zero: accumulators, latched result, window count and fill */
-	if (row < 0)
-		HIP_TRY(hipMemsetAsync(b->rows, 0, (size_t)b->max_rows * sizeof(WrTonesRow), d->stream));
-	else
-		HIP_TRY(hipMemsetAsync(b->rows + row, 0, sizeof(WrTonesRow), d->stream));
-	return WR_OK;
-}
-
-extern "C" int wr_tones_push_rows(wr_tones *b, const float *audio_dev, size_t row_stride, size_t nrows, size_t nframes)
-{
-	if (!b || !audio_dev)
-		return wrc_fail(WR_ERR_ARG, "wr_tones_push_rows: bad argument (NULL bank or audio_dev)");
-	if (nrows > b->max_rows || (nrows > 1 && row_stride < nframes) || nframes > ((size_t)1 << 40))
-		return wrc_fail(WR_ERR_ARG, "wr_tones_push_rows: %zu rows for a bank of %u, or rows of %zu frames that overlap at a "
-		                "stride of %zu, or more than 2^40 frames", nrows, b->max_rows, nframes, row_stride);
-	if (!nrows || !nframes)
-		return WR_OK;
-	wr_dev *d = b->dev;
-	if (wrc_dev_bind(d))
-		return WR_ERR_HIP;
-	g_block_kernel_calls.fetch_add(1, std::memory_order_relaxed);
-	DEV_SETTLE(d);
-	HIP_TRY(wrk_tones_push(d->stream, audio_dev, row_stride, nrows, nframes, b->rows, b->t12, b->steps, b->ntones, b->window));
-	return WR_OK;
-}
-
-extern "C" int wr_tones_read(wr_tones *b, long long *iq_host, long long *energy_host, unsigned long long *windows_host,
-                             unsigned int *fill_host, unsigned int *rows)
-{
-	if (!b)
-		return wrc_fail(WR_ERR_ARG, "wr_tones_read: bank is NULL");
-	if (!iq_host && !energy_host && !windows_host && !fill_host)
-		return wrc_fail(WR_ERR_ARG, "wr_tones_read: no array to fill");
-	wr_dev *d = b->dev;
-	if (wrc_dev_bind(d))
-		return WR_ERR_HIP;
-	DEV_SETTLE(d);
-	const char *base = (const char *)b->rows;
-	const size_t pitch = sizeof(WrTonesRow), n = b->max_rows;
-	if (iq_host) {
-		const size_t width = (size_t)b->ntones * 2u * sizeof(long long);
-		HIP_TRY(hipMemcpy2DAsync(iq_host, width, base + offsetof(WrTonesRow, lat), pitch, width, n, hipMemcpyDeviceToHost, d->stream));
-	}
-	if (energy_host)
-		HIP_TRY(hipMemcpy2DAsync(energy_host, sizeof(long long), base + offsetof(WrTonesRow, lat_e), pitch, sizeof(long long), n,
-		                         hipMemcpyDeviceToHost, d->stream));
-	if (windows_host)
-		HIP_TRY(hipMemcpy2DAsync(windows_host, sizeof(unsigned long long), base + offsetof(WrTonesRow, windows), pitch,
-		                         sizeof(unsigned long long), n, hipMemcpyDeviceToHost, d->stream));
-	if (fill_host)
-		HIP_TRY(hipMemcpy2DAsync(fill_host, sizeof(unsigned int), base + offsetof(WrTonesRow, fill), pitch, sizeof(unsigned int), n,
-		                         hipMemcpyDeviceToHost, d->stream));
-	HIP_TRY(wrc_dev_stream_sync(d));
-	if (rows)
-		*rows = b->max_rows;
-	return WR_OK;
-}
-
-/* ------------------------------------------------------------------ resampler -- */
-
-extern "C" int wr_resamp_ratio(unsigned int in_rate, unsigned int out_rate, unsigned int *L, unsigned int *M)
-{
-	if (!L || !M || wrd_resamp_ratio(in_rate, out_rate, L, M))
-		return wrc_fail(WR_ERR_ARG, "wr_resamp_ratio: bad argument (NULL L or M, or a rate of 0: %u -> %u)", in_rate, out_rate);
-	return WR_OK;
-}
-
-extern "C" int wr_resamp_design(unsigned int in_rate, unsigned int out_rate, unsigned int P, float *taps_host, unsigned int *L,
-                                unsigned int *M)
-{
-	if (!taps_host)
-		return wrc_fail(WR_ERR_ARG, "wr_resamp_design: taps_host is NULL");
-	unsigned int l = 0, m = 0;
-	if (wrd_resamp_design(in_rate, out_rate, P, taps_host, &l, &m))
-		return wrc_fail(WR_ERR_ARG, "wr_resamp_design: %u -> %u Hz with %u taps per phase: a rate of 0, L / M outside 1 <= L <= 1024, "
-		                "M <= 8 L, L <= 8 M, P not a multiple of 4 in 4 .. 64, L * P above 16384, or no passband "
-		                "(min(in, out) <= 10 in / P)", in_rate, out_rate, P);
-	if (L)
-		*L = l;
-	if (M)
-		*M = m;
-	return WR_OK;
-}
-
-extern "C" int wr_resamp_create(wr_resamp **rs, wr_dev *d, unsigned int max_rows, unsigned int L, unsigned int M, unsigned int P,
-                                const float *taps_host)
-{
-	if (!rs || !d || !taps_host)
-		return wrc_fail(WR_ERR_ARG, "wr_resamp_create: bad argument (NULL rs, dev or taps_host)");
-	if (!max_rows || max_rows > 65535u || wrd_resamp_limits(L, M, P))
-		return wrc_fail(WR_ERR_ARG, "wr_resamp_create: %u rows (1 .. 65535), L / M = %u / %u (1 <= L <= 1024, M <= 8 L, L <= 8 M), "
-		                "%u taps per phase (a multiple of 4 in 4 .. 64, L * P <= 16384)", max_rows, L, M, P);
-	const size_t ntaps = (size_t)L * P, nhist = (size_t)max_rows * (P - 1u);
-	for (size_t i = 0; i < ntaps; ++i) {
-		uint32_t bits;
-		memcpy(&bits, taps_host + i, sizeof(bits));
-		if ((bits & 0x7fffffffu) >= 0x7f800000u || !(fabsf(taps_host[i]) <= 16.0f))
-			return wrc_fail(WR_ERR_ARG, "wr_resamp_create: tap [%zu][%zu] = %g is not finite or above 16 in magnitude", i / P, i % P,
-			                (double)taps_host[i]);
-	}
-	if (wrc_dev_bind(d))
-		return WR_ERR_HIP;
-	DEV_SETTLE(d);
-	wr_resamp *r = new (std::nothrow) wr_resamp();
-	if (!r)
-		return wrc_fail(WR_ERR_ARG, "wr_resamp_create: out of memory");
-	r->dev = d;
-	r->max_rows = max_rows;
-	r->L = L;
-	r->M = M;
-	r->P = P;
-	r->taps = r->hist[0] = r->hist[1] = nullptr;
-	hipError_t e = hipMalloc((void **)&r->taps, ntaps * sizeof(float));
-	for (unsigned int s = 0; s < 2u && e == hipSuccess; ++s) {
-		e = hipMalloc((void **)&r->hist[s], nhist * sizeof(float));
-		if (e == hipSuccess)
-			e = hipMemsetAsync(r->hist[s], 0, nhist * sizeof(float), d->stream);
-	}
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(r->taps, taps_host, ntaps * sizeof(float), hipMemcpyHostToDevice, d->stream);
-	if (e == hipSuccess)
-		e = wrc_dev_stream_sync(d);                             /* (the copy's source is the caller's) */
-	if (e != hipSuccess) {
-		wr_resamp_destroy(r);
-		return wrc_fail(WR_ERR_HIP, "wr_resamp_create: %s", hipGetErrorString(e));
-	}
-	*rs = r;
-	return WR_OK;
-}
-
-extern "C" int wr_resamp_destroy(wr_resamp *r)
-{
-	if (!r)
-		return WR_OK;
-	(void)hipSetDevice(r->dev->device);
-	(void)wrc_dev_stream_sync(r->dev);
-	(void)hipFree(r->taps);
-	(void)hipFree(r->hist[0]);
-	(void)hipFree(r->hist[1]);
-	delete r;
-	return WR_OK;
-}
-
-extern "C" int wr_resamp_reset(wr_resamp *r, int row)
-{
-	if (!r)
-		return wrc_fail(WR_ERR_ARG, "wr_resamp_reset: rs is NULL");
-	if (row >= 0 && (unsigned int)row >= r->max_rows)
-		return wrc_fail(WR_ERR_ARG, "wr_resamp_reset: row %d of a bank of %u", row, r->max_rows);
-	wr_dev *d = r->dev;
-	if (wrc_dev_bind(d))
-		return WR_ERR_HIP;
-	DEV_SETTLE(d);
-	/* only the set the next push reads matters: that push writes the other one */
-	const size_t H = r->P - 1u;
-	if (row < 0) {
-		HIP_TRY(hipMemsetAsync(r->hist[r->cur], 0, (size_t)r->max_rows * H * sizeof(float), d->stream));
-		r->zero_from[r->cur] = 0;
-		r->nmod = 0;
-		r->frames_in = r->frames_out = 0;
-	} else {
-		HIP_TRY(hipMemsetAsync(r->hist[r->cur] + (size_t)row * H, 0, H * sizeof(float), d->stream));
-	}
-	return WR_OK;
-}
-
-extern "C" int wr_resamp_out_frames(wr_resamp *r, size_t nframes, size_t *n_out)
-{
-	if (!r || !n_out || nframes > ((size_t)1 << 28))
-		return wrc_fail(WR_ERR_ARG, "wr_resamp_out_frames: bad argument (NULL rs or n_out, or more than 2^28 frames)");
-	*n_out = (size_t)wrk_resamp_out_frames(r->L, r->M, r->nmod, nframes);
-	return WR_OK;
-}
-
-/* what both pushes refuse, and the output frames of the push (`who` names the caller in the message) */
-int wrc_resamp_check(const wr_resamp *r, const char *who, const float *in_dev, size_t row_stride, size_t nrows, size_t nframes,
-                     const float *out_dev, size_t out_stride, size_t *n_out)
-{
-	if (nrows > r->max_rows || (nrows > 1 && row_stride < nframes) || nframes > ((size_t)1 << 28))
-		return wrc_fail(WR_ERR_ARG, "%s: %zu rows for a bank of %u, or rows of %zu frames that overlap at a stride of %zu, or more "
-		                "than 2^28 frames", who, nrows, r->max_rows, nframes, row_stride);
-	const size_t n = (size_t)wrk_resamp_out_frames(r->L, r->M, r->nmod, nframes);
-	*n_out = n;
-	if (!nrows || !n)
-		return WR_OK;
-	if (!out_dev || (nrows > 1 && out_stride < n))
-		return wrc_fail(WR_ERR_ARG, "%s: out_dev is NULL, or rows of %zu output frames overlap at a stride of %zu", who, n, out_stride);
-	const uintptr_t a0 = (uintptr_t)in_dev, a1 = a0 + ((nrows - 1u) * row_stride + nframes) * sizeof(float);
-	const uintptr_t b0 = (uintptr_t)out_dev, b1 = b0 + ((nrows - 1u) * out_stride + n) * sizeof(float);
-	if (a0 < b1 && b0 < a1)
-		return wrc_fail(WR_ERR_ARG, "%s: input and output overlap", who);
-	return WR_OK;
-}
-
-/* the push itself, behind wrc_resamp_check, on a bound and settled device: the rows it leaves out lose their histories,
- * the clock and the counts advance, the history sets change places */
-int wrc_resamp_push(wr_resamp *r, const float *in_dev, size_t row_stride, size_t nrows, size_t nframes, float *out_dev,
-                    size_t out_stride)
-{
-	if (!nframes)
-		return WR_OK;
-	wr_dev *d = r->dev;
-	const unsigned int from = r->cur, to = from ^ 1u;
-	const size_t H = r->P - 1u;
-	if (nrows < r->zero_from[to])
-		HIP_TRY(hipMemsetAsync(r->hist[to] + nrows * H, 0, (r->zero_from[to] - nrows) * H * sizeof(float), d->stream));
-	const WrResampPush p = {r->taps, r->L, r->M, r->P, r->nmod, r->hist[from], r->hist[to]};
-	HIP_TRY(wrk_resamp_push(d->stream, in_dev, row_stride, nrows, nframes, p, out_dev, out_stride));
-	r->zero_from[to] = (unsigned int)nrows;
-	r->cur = to;
-	r->frames_in += nframes;
-	r->frames_out += wrk_resamp_out_frames(r->L, r->M, r->nmod, nframes);
-	r->nmod = (unsigned int)((r->nmod + nframes) % r->M);
-	return WR_OK;
-}
-
-extern "C" int wr_resamp_push_rows(wr_resamp *r, const float *in_dev, size_t row_stride, size_t nrows, size_t nframes,
-                                   float *out_dev, size_t out_stride, size_t *n_out)
-{
-	if (!r || !in_dev || !n_out)
-		return wrc_fail(WR_ERR_ARG, "wr_resamp_push_rows: bad argument (NULL rs, in_dev or n_out)");
-	if (int rc = wrc_resamp_check(r, "wr_resamp_push_rows", in_dev, row_stride, nrows, nframes, out_dev, out_stride, n_out))
-		return rc;
-	if (!nframes)
-		return WR_OK;
-	wr_dev *d = r->dev;
-	if (wrc_dev_bind(d))
-		return WR_ERR_HIP;
-	g_block_kernel_calls.fetch_add(1, std::memory_order_relaxed);
-	DEV_SETTLE(d);
-	return wrc_resamp_push(r, in_dev, row_stride, nrows, nframes, out_dev, out_stride);
-}
-
-extern "C" int wr_resamp_info(wr_resamp *r, unsigned int *L, unsigned int *M, unsigned int *P, unsigned long long *frames_in,
-                              unsigned long long *frames_out)
-{
-	if (!r)
-		return wrc_fail(WR_ERR_ARG, "wr_resamp_info: rs is NULL");
-	if (L)
-		*L = r->L;
-	if (M)
-		*M = r->M;
-	if (P)
-		*P = r->P;
-	if (frames_in)
-		*frames_in = r->frames_in;
-	if (frames_out)
-		*frames_out = r->frames_out;
 	return WR_OK;
 }
 

@@ -1,5 +1,5 @@
 /*
- * wr_internal.h -- internal C++ interface between the C ABI (wr_dev.hip, wr_tuner*.hip, wr_spectrum.hip), the host
+ * wr_internal.h -- internal C++ interface between the C ABI (wr_dev.hip, wr_tuner*.hip, wr_spectrum.hip, wr_banks.hip), the host
  * design math (wr_design.cpp) and the kernels (wr_kernels.hip, wr_fft.hip, wr_levels.hip, wr_agc.hip, wr_tones.hip,
  * wr_resamp.hip).
  * Not installed; the public boundary is include/webradio_amd.h.

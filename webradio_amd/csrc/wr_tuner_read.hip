@@ -1,7 +1,8 @@
 /*
  * wr_tuner_read.hip -- what reads the results of a tuner's last submit back: wr_chan_fetch and the whole-tuner readers
- * (audio, channel spectra, signal levels, tone bank, resampler).  All of them see that submit through wrc_last_submit_group and
- * wrc_last_submit_flush.  The tuner itself is in wr_tuner.hip, the submit path in wr_tuner_submit.hip.
+ * (audio, channel spectra, signal levels).  All of them see that submit through wrc_last_submit_group and
+ * wrc_last_submit_flush, and so do the tone bank and the resampler when they take its audio rows (wr_tuner_tones_push,
+ * wr_tuner_resamp_push: wr_banks.hip).  The tuner itself is in wr_tuner.hip, the submit path in wr_tuner_submit.hip.
  */
 #include "wr_capi_internal.h"
 
@@ -173,68 +174,6 @@ extern "C" int wr_tuner_chan_levels(wr_tuner *t, float *mean_host, float *peak_h
 		memcpy(peak_host, got.data() + used, used * sizeof(float));
 	if (muted_host)
 		memcpy(muted_host, got.data() + 2u * used, used * sizeof(unsigned int));
-	return WR_OK;
-}
-
-/* the last submit's audio rows of every channel slot into a tone bank (wr_tones.hip): the rows wr_tuner_audio_dev shows,
- * counted as wr_tuner_chan_levels counts them, read where they lie */
-extern "C" int wr_tuner_tones_push(wr_tuner *t, wr_tones *bank, unsigned int *slots)
-{
-	if (!t || !bank)
-		return wrc_fail(WR_ERR_ARG, "wr_tuner_tones_push: bad argument (NULL tuner or bank)");
-	if (bank->dev != t->dev)
-		return wrc_fail(WR_ERR_ARG, "wr_tuner_tones_push: the bank belongs to another device than the tuner");
-	WrLastSubmit v;
-	if (int rc = wrc_last_submit_group(t, "wr_tuner_tones_push", true, &v))
-		return rc;
-	const Group *g = v.g;
-	const unsigned int used = wrc_group_slots_used(g);
-	if (used > bank->max_rows)
-		return wrc_fail(WR_ERR_ARG, "wr_tuner_tones_push: the tuner has %u channel slots, the bank %u rows", used, bank->max_rows);
-	if (bank->last_tuner == t && bank->last_seq == t->submit_seq)
-		return wrc_fail(WR_ERR_STATE, "wr_tuner_tones_push: submit %llu of this tuner is in the bank already", t->submit_seq);
-	if (int rc = wrc_last_submit_flush(t, &v))
-		return rc;
-	wr_dev *d = t->dev;
-	DEV_SETTLE(d);
-	if (used && g->last_k2)
-		HIP_TRY(wrk_tones_push(d->stream, g->dev.audio, g->k2max, used, g->last_k2, bank->rows, bank->t12, bank->steps,
-		                       bank->ntones, bank->window));
-	bank->last_tuner = t;
-	bank->last_seq = t->submit_seq;
-	if (slots)
-		*slots = used;
-	return WR_OK;
-}
-
-/* the same rows through a resampler (wr_resamp.hip): row s yields *n_out frames at out_dev + s * out_stride */
-extern "C" int wr_tuner_resamp_push(wr_tuner *t, wr_resamp *rs, float *out_dev, size_t out_stride, size_t *n_out,
-                                    unsigned int *slots)
-{
-	if (!t || !rs || !n_out)
-		return wrc_fail(WR_ERR_ARG, "wr_tuner_resamp_push: bad argument (NULL tuner, rs or n_out)");
-	if (rs->dev != t->dev)
-		return wrc_fail(WR_ERR_ARG, "wr_tuner_resamp_push: the resampler belongs to another device than the tuner");
-	WrLastSubmit v;
-	if (int rc = wrc_last_submit_group(t, "wr_tuner_resamp_push", true, &v))
-		return rc;
-	const Group *g = v.g;
-	const unsigned int used = wrc_group_slots_used(g);
-	if (used > rs->max_rows)
-		return wrc_fail(WR_ERR_ARG, "wr_tuner_resamp_push: the tuner has %u channel slots, the resampler %u rows", used, rs->max_rows);
-	if (rs->last_tuner == t && rs->last_seq == t->submit_seq)
-		return wrc_fail(WR_ERR_STATE, "wr_tuner_resamp_push: submit %llu of this tuner is in the resampler already", t->submit_seq);
-	if (int rc = wrc_resamp_check(rs, "wr_tuner_resamp_push", g->dev.audio, g->k2max, used, g->last_k2, out_dev, out_stride, n_out))
-		return rc;
-	if (int rc = wrc_last_submit_flush(t, &v))
-		return rc;
-	DEV_SETTLE(t->dev);
-	if (int rc = wrc_resamp_push(rs, g->dev.audio, g->k2max, used, g->last_k2, out_dev, out_stride))
-		return rc;
-	rs->last_tuner = t;
-	rs->last_seq = t->submit_seq;
-	if (slots)
-		*slots = used;
 	return WR_OK;
 }
 
