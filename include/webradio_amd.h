@@ -58,6 +58,8 @@ extern "C" {
                                     Added to 6 later: wr_resamp_ratio, wr_resamp_design, wr_resamp_create, wr_resamp_destroy,
                                                       wr_resamp_reset, wr_resamp_out_frames, wr_resamp_push_rows,
                                                       wr_resamp_info, wr_tuner_resamp_push.
+                                    Added to 6 later: wr_dcs_word, wr_dcs_step, wr_dcs_create, wr_dcs_destroy, wr_dcs_reset,
+                                                      wr_dcs_seek, wr_dcs_push_rows, wr_tuner_dcs_push, wr_dcs_read, wr_dcs_info.
                                     Nothing of an earlier version changed or removed */
 #define WR_FIR_LENGTH    64      /* dsp/lowpass.cxx:39  FIR_LENGTH */
 #define WR_TABLE_SIZE    65536   /* dsp/downconverter.cxx:35 LOOKUP_BITS 16 */
@@ -105,6 +107,7 @@ typedef struct wr_spectrum wr_spectrum;
 typedef struct wr_ring     wr_ring;
 typedef struct wr_tones    wr_tones;
 typedef struct wr_resamp   wr_resamp;
+typedef struct wr_dcs      wr_dcs;
 
 /* ------------------------------------------------------------------ misc -- */
 int         wr_abi_version(void);
@@ -737,6 +740,92 @@ int wr_tuner_tones_push(wr_tuner *tuner, wr_tones *bank, unsigned int *slots);
  * stream. */
 int wr_tones_read(wr_tones *bank, long long *iq_host /* [rows][ntones][2] */, long long *energy_host,
                   unsigned long long *windows_host, unsigned int *fill_host, unsigned int *rows);
+
+/* DCS BANK: which digital-coded squelch code rides on each receiver's audio -- the other half of tone squelch.  DCS is a
+ * 23-bit Golay word sent over and over at 134.4 bit/s as sub-audible NRZ under the voice, bit 0 first.  The reference has
+ * nothing of the kind.  A bank is up to 128 code words tried on every row, in both polarities, at every evaluation: a bit
+ * slicer and a correlator over words, on the audio rows the tone bank takes.
+ *
+ * THE RULE is this library's own definition, as the ones of af_gain, squelch, AGC, the tones and the resampler are.
+ * Everything is an integer after the first line of CHIP SUMS, so a stream has ONE result whatever the grid, the cut into
+ * pushes and the order of additions; a restatement in numpy is bit-identical.
+ *
+ * CODE WORD.  wr_dcs_word(code, &word) takes `code` in 0 ... 511, the three octal digits.
+ *   d = code | 0x800                                            the fixed bits 100 sit above the nine code bits
+ *   p = d;  twelve times:  if (p & 1) p ^= 0xC75;  p >>= 1      the parity
+ *   word = (p << 12) | d                                        bit 0 is sent first
+ * 023 -> 0x763813, 754 -> 0x20f9ec, 412 -> 0x79c90a.  The complement of 023's word is a rotation of 047's (an inverted 023
+ * IS a 047); all 512 words have weight 7, 8, 11, 12, 15 or 16.  The bank itself takes any 23-bit words.
+ *
+ * BIT CLOCK.  wr_dcs_step(audio_rate, &step):
+ *   step = (672 * 2^32 + (5 * rate) / 2) / (5 * rate)           integer division: 134.4 Hz in units of 2^-32 bit per frame
+ * WR_ERR_ARG for any rate whose step is not in [2^19, 2^28]: between 2 and 1024 frames per chip (an eighth of a bit).
+ * A bank has ONE clock, as the resampler has: N, the frames pushed since it was created, reset as a whole or sought; 64-bit,
+ * kept on the host.  Frame n of the stream belongs to chip
+ *   g(n) = floor(n * step / 2^29)                               eight chips per bit
+ * The product can pass 2^64: the host reduces the push's first frame (N0 * step mod 2^29, and its chip index), the kernel
+ * adds k * step for frame k < 2^28 of the push.
+ *
+ * CHIP SUMS.  For audio value v:
+ *   v'   = 0.0f if (bits(v) & 0x7fffffff) >= 0x7f800000 (inf, NaN), else v
+ *   q    = (int64) rint(min(max(v', -64.0f), 64.0f) * 16777216.0f)          the tone bank's cleaning
+ *   C[g(n)] += q
+ * A chip whose frames were never pushed is 0; after a reset the same goes for the chips in front of the stream.
+ *
+ * EVALUATION.  Evaluation e = 1, 2, ... happens once all frames of chip 8 e - 1 are in: after N frames floor(g(N) / 8)
+ * evaluations have happened, whatever the pushes were; a push may hold none or several.  Each tries eight timing phases
+ * f = 0 ... 7:
+ *   B_b  = sum_{c < 8} C[8 e - 184 - f + 8 b + c]               b = 0 ... 22
+ *   w_f  = sum_b 2^b * [2 * B_b > max_b B + min_b B]            the midpoint of the extremes is the slicer's threshold: it
+ *                                                               removes the discriminator's DC whatever the word's weight
+ * For code word k of the bank and its 23 rotations rot_r, agreeing bits in both polarities:
+ *   agree[k][0] = max_{f, r} (23 - popcount(w_f ^ rot_r(word_k)))
+ *   agree[k][1] = max_{f, r} popcount(w_f ^ rot_r(word_k))                  the inverted polarity
+ * A polarity matches when agree >= 23 - max_errors.  A match does hits[k][pol] += 1 and run[k][pol] += 1; a miss sets
+ * run[k][pol] = 0.  After all of it evals += 1.  agree keeps the last evaluation's values.
+ * A single exact match is not a detection: noise alone yields one now and then (of the order of 8 * 23 / 2^23 per code,
+ * polarity and evaluation).  The library reports, the caller decides; run >= 3 is a sensible "open".
+ *
+ * ROWS.  wr_dcs_reset(bank, row) zeroes row `row`: its chips, the open chip, agree, run, hits and evals; the clock goes
+ * on.  A negative row resets all rows and sets the clock to 0.  wr_dcs_seek(bank, frame) is the same with the clock at
+ * `frame`: for a bank that joins a running stream.  A row that a push leaves out (nrows < max_rows) is reset: the
+ * resampler's convention.
+ * Limits, each WR_ERR_ARG: max_rows from 1 to 65535; ncodes from 1 to 128; words below 2^23; step in [2^19, 2^28];
+ * max_errors from 0 to 3; a push of at most 2^28 frames.
+ * Left out on purpose: muting audio by code (the detector reports, the caller decides); a host-side C++ class (the
+ * reference has none to mirror); per-receiver code lists (one list per bank); clock recovery beyond the eight phases;
+ * time sharding. */
+int wr_dcs_word(unsigned int code, unsigned int *word);
+int wr_dcs_step(unsigned int audio_rate, unsigned int *step);
+/* words_host[ncodes]: 23-bit words (wr_dcs_word, or the caller's own); step: wr_dcs_step's. */
+int wr_dcs_create(wr_dcs **bank, wr_dev *dev, unsigned int max_rows, const unsigned int *words_host, unsigned int ncodes,
+                  unsigned int step, unsigned int max_errors);
+int wr_dcs_destroy(wr_dcs *bank);
+/* What a caller does for the row after wr_chan_reset_history or a retune of the receiver in that slot (and for all rows,
+ * with wr_dcs_seek where the stream runs on, after wr_tuner_seek): the bank does not watch the tuner.  Asynchronous on the
+ * device's stream. */
+int wr_dcs_reset(wr_dcs *bank, int row);
+int wr_dcs_seek(wr_dcs *bank, unsigned long long frame);
+/* THE RULE on a plain block of rows in device memory: `nrows` rows of `nframes` floats, `row_stride` floats apart; row r of
+ * the call is row r of the bank, and N advances by nframes.  Consecutive calls continue the streams whatever the lengths.
+ * Asynchronous on the device's stream (as many launches as the rows' rings of chip sums ask for: one, unless the push
+ * holds more than 255 chips); counted by wr_block_kernel_calls.  WR_ERR_ARG: NULL arguments, nrows > max_rows,
+ * row_stride < nframes with several rows, more than 2^28 frames. */
+int wr_dcs_push_rows(wr_dcs *bank, const float *audio_dev, size_t row_stride, size_t nrows, size_t nframes);
+/* Pushes the last submit's audio rows of every channel slot, the rows wr_tuner_tones_push takes and counted as it counts
+ * them (*slots: whole lane groups of 64); rows of slots that hold no channel carry no meaning.  The slicer's threshold
+ * makes the result independent of af_gain, scale and the demodulator's DC.  Like every getter it sends held blocks out,
+ * launches a pending post stage and closes an open streaming launch; it changes nothing the next block depends on.
+ * WR_ERR_STATE: nothing submitted yet, several rate groups, the same submit pushed twice.  WR_ERR_ARG: max_rows below the
+ * slot count, a bank of another device. */
+int wr_tuner_dcs_push(wr_tuner *tuner, wr_dcs *bank, unsigned int *slots);
+/* agree_host: uint8 [rows][ncodes][2]; run_host: uint32 [rows][ncodes][2]; hits_host: uint64 [rows][ncodes][2];
+ * evals_host: uint64 [rows]; *rows = max_rows.  Any array may be NULL, all four NULL is WR_ERR_ARG.  Waits for the
+ * device's stream. */
+int wr_dcs_read(wr_dcs *bank, unsigned char *agree_host, unsigned int *run_host, unsigned long long *hits_host,
+                unsigned long long *evals_host, unsigned int *rows);
+/* What the bank was created with, and N.  Any pointer may be NULL.  Host only. */
+int wr_dcs_info(wr_dcs *bank, unsigned int *ncodes, unsigned int *step, unsigned int *max_errors, unsigned long long *frames);
 
 /* RESAMPLER: every receiver's audio at a sound-card rate.  A tuner's audio rate is what its decimations leave (50 kHz off
  * 100 Msps with 400 and 5; 32 kHz in BASELINE config 1); the reference avoids the question by choosing a tuner rate that

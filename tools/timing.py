@@ -111,10 +111,11 @@ def c2_tuner(dev, ifs, agc=False):
     return t, chans
 
 
-def row_bank_figures(args, dev, ifs, block, push, rows_n, nbytes):
-    """The figures tones_time.py and resamp_time.py share, as the fields of their JSON line behind the shape's own:
-    rows_256 / rows_64 (`rows_n(n)`: the plain-rows call on n rows), submit_push (`push(tuner)` behind a submit),
-    submit_flush and submit_plain(_b) on twin tuners, copy (`nbytes`), and what is derived from their medians."""
+def row_bank_figures(args, dev, ifs, block, push, rows_n, nbytes, beside=None):
+    """The figures tones_time.py, dcs_time.py and resamp_time.py share, as the fields of their JSON line behind the shape's
+    own: rows_256 / rows_64 (`rows_n(n)`: the plain-rows call on n rows), submit_push (`push(tuner)` behind a submit),
+    submit_flush and submit_plain(_b) on twin tuners, copy (`nbytes`), and what is derived from their medians.
+    `beside`: {name: call} timed in the same windows, to set the figures beside."""
     import torch
     nframes = block.numel() // 2
     pushed, flushed, plain = (c2_tuner(dev, ifs)[0] for _ in range(3))
@@ -131,7 +132,7 @@ def row_bank_figures(args, dev, ifs, block, push, rows_n, nbytes):
         plain.submit_device(block, nframes)
 
     fns = {"rows_256": rows_n(256), "rows_64": rows_n(64), "submit_push": submit_push, "submit_flush": submit_flush,
-           "submit_plain": submit_plain, "submit_plain_b": submit_plain, "copy": copier(nbytes)}
+           "submit_plain": submit_plain, "submit_plain_b": submit_plain, "copy": copier(nbytes), **(beside or {})}
     got, reps = measure(fns, args)
     for t in (pushed, flushed, plain):
         t.flush()

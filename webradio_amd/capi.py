@@ -149,6 +149,16 @@ SIGNATURES = {
     "wr_resamp_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_ulonglong),
                                  C.POINTER(C.c_ulonglong)]),
     "wr_tuner_resamp_push": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_u32)]),
+    "wr_dcs_word": (C.c_int, [_u32, C.POINTER(_u32)]),
+    "wr_dcs_step": (C.c_int, [_u32, C.POINTER(_u32)]),
+    "wr_dcs_create": (C.c_int, [C.POINTER(_vp), _vp, _u32, _vp, _u32, _u32, _u32]),
+    "wr_dcs_destroy": (C.c_int, [_vp]),
+    "wr_dcs_reset": (C.c_int, [_vp, C.c_int]),
+    "wr_dcs_seek": (C.c_int, [_vp, C.c_ulonglong]),
+    "wr_dcs_push_rows": (C.c_int, [_vp, _vp, _sz, _sz, _sz]),
+    "wr_tuner_dcs_push": (C.c_int, [_vp, _vp, C.POINTER(_u32)]),
+    "wr_dcs_read": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "wr_dcs_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_ulonglong)]),
 }
 
 

@@ -1,7 +1,8 @@
 /*
- * wr_banks.hip -- the two objects that keep something per audio row of every receiver: the tone bank (wr_tones_*, kernels
- * in wr_tones.hip) and the resampler (wr_resamp_*, kernels in wr_resamp.hip).  Each takes plain rows (wr_*_push_rows) or the
- * audio rows of a tuner's last submit where they lie (wr_tuner_*_push); what the two share has one copy, up front.
+ * wr_banks.hip -- the three objects that keep something per audio row of every receiver: the tone bank (wr_tones_*, kernels
+ * in wr_tones.hip), the DCS bank (wr_dcs_*, kernel in wr_dcs.hip) and the resampler (wr_resamp_*, kernels in wr_resamp.hip).
+ * Each takes plain rows (wr_*_push_rows) or the audio rows of a tuner's last submit where they lie (wr_tuner_*_push); what
+ * the three share has one copy, up front.
  */
 #include "wr_capi_internal.h"
 
@@ -224,6 +225,205 @@ extern "C" int wr_tones_read(wr_tones *b, long long *iq_host, long long *energy_
 	HIP_TRY(wrc_dev_stream_sync(d));
 	if (rows)
 		*rows = b->max_rows;
+	return WR_OK;
+}
+
+/* ------------------------------------------------------------------ DCS bank -- */
+
+extern "C" int wr_dcs_word(unsigned int code, unsigned int *word)
+{
+	if (!word || code > 511u)
+		return wrc_fail(WR_ERR_ARG, "wr_dcs_word: word is NULL, or code %u (octal %o) is not inside 0 .. 511 (octal 777)", code, code);
+	const unsigned int d = code | 0x800u;
+	unsigned int p = d;
+	for (unsigned int i = 0; i < 12u; ++i) {
+		if (p & 1u)
+			p ^= 0xC75u;
+		p >>= 1;
+	}
+	*word = (p << 12) | d;
+	return WR_OK;
+}
+
+static bool dcs_step_ok(unsigned long long step)
+{
+	return step >= (1ull << 19) && step <= (1ull << 28);
+}
+
+extern "C" int wr_dcs_step(unsigned int audio_rate, unsigned int *step)
+{
+	if (!step)
+		return wrc_fail(WR_ERR_ARG, "wr_dcs_step: step is NULL");
+	const unsigned long long den = 5ull * audio_rate;
+	const unsigned long long s = den ? ((672ull << 32) + den / 2u) / den : 0;
+	if (!dcs_step_ok(s))
+		return wrc_fail(WR_ERR_ARG, "wr_dcs_step: at %u Hz a chip (an eighth of a bit at 134.4 bit/s) is not 2 .. 1024 frames: the "
+		                "step would be %llu, outside 2^19 .. 2^28", audio_rate, s);
+	*step = (unsigned int)s;
+	return WR_OK;
+}
+
+extern "C" int wr_dcs_create(wr_dcs **bank, wr_dev *d, unsigned int max_rows, const unsigned int *words_host, unsigned int ncodes,
+                             unsigned int step, unsigned int max_errors)
+{
+	if (!bank || !words_host)
+		return wrc_fail(WR_ERR_ARG, "wr_dcs_create: bad argument (NULL bank or words_host)");
+	if (!max_rows || max_rows > 65535u || !ncodes || ncodes > WR_DCS_CODES || !dcs_step_ok(step) || max_errors > 3u)
+		return wrc_fail(WR_ERR_ARG, "wr_dcs_create: %u rows (1 .. 65535), %u codes (1 .. 128), a step of %u (2^19 .. 2^28), "
+		                "max_errors %u (0 .. 3)", max_rows, ncodes, step, max_errors);
+	for (unsigned int k = 0; k < ncodes; ++k)
+		if (words_host[k] >= (1u << 23))
+			return wrc_fail(WR_ERR_ARG, "wr_dcs_create: code %u: the word 0x%x is not below 2^23", k, words_host[k]);
+	if (!d)                                                     /* (behind the limits: those are refused without a device too) */
+		return wrc_fail(WR_ERR_ARG, "wr_dcs_create: bad argument (NULL dev)");
+	wr_dcs *b;
+	if (int rc = bank_new(&b, "wr_dcs_create", d, max_rows))
+		return rc;
+	b->ncodes = ncodes;
+	b->step = step;
+	b->max_errors = max_errors;
+	hipError_t e = hipMalloc((void **)&b->rows, (size_t)max_rows * sizeof(WrDcsRow));
+	if (e == hipSuccess)
+		e = hipMalloc((void **)&b->words, ncodes * sizeof(unsigned int));
+	if (e == hipSuccess)
+		e = hipMemsetAsync(b->rows, 0, (size_t)max_rows * sizeof(WrDcsRow), d->stream);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(b->words, words_host, ncodes * sizeof(unsigned int), hipMemcpyHostToDevice, d->stream);
+	return bank_created(bank, b, e, "wr_dcs_create", wr_dcs_destroy);
+}
+
+extern "C" int wr_dcs_destroy(wr_dcs *b)
+{
+	if (!b)
+		return WR_OK;
+	(void)hipSetDevice(b->dev->device);
+	(void)wrc_dev_stream_sync(b->dev);
+	(void)hipFree(b->rows);
+	(void)hipFree(b->words);
+	delete b;
+	return WR_OK;
+}
+
+/* a reset of every row with the clock at `frame` */
+static int dcs_restart(wr_dcs *b, const char *who, unsigned long long frame)
+{
+	size_t first, n;
+	if (int rc = bank_reset_begin(b, who, -1, &first, &n))
+		return rc;
+	HIP_TRY(hipMemsetAsync(b->rows, 0, n * sizeof(WrDcsRow), b->dev->stream));
+	b->zero_from = 0;
+	b->frames = frame;
+	return WR_OK;
+}
+
+extern "C" int wr_dcs_reset(wr_dcs *b, int row)
+{
+	if (!b)
+		return wrc_fail(WR_ERR_ARG, "wr_dcs_reset: bank is NULL");
+	if (row < 0)
+		return dcs_restart(b, "wr_dcs_reset", 0);
+	size_t first, n;
+	if (int rc = bank_reset_begin(b, "wr_dcs_reset", row, &first, &n))
+		return rc;
+	/* a row that begins its stream is all zero: chips, the open one among them, agree, run, hits and evals; the clock runs on */
+	HIP_TRY(hipMemsetAsync(b->rows + first, 0, n * sizeof(WrDcsRow), b->dev->stream));
+	return WR_OK;
+}
+
+extern "C" int wr_dcs_seek(wr_dcs *b, unsigned long long frame)
+{
+	if (!b)
+		return wrc_fail(WR_ERR_ARG, "wr_dcs_seek: bank is NULL");
+	return dcs_restart(b, "wr_dcs_seek", frame);
+}
+
+/* the push itself, on a device made ready: the rows it leaves out are reset, the clock advances */
+static int dcs_push(wr_dcs *b, const float *audio_dev, size_t row_stride, size_t nrows, size_t nframes)
+{
+	if (!nframes)
+		return WR_OK;
+	wr_dev *d = b->dev;
+	if (nrows < b->zero_from)
+		HIP_TRY(hipMemsetAsync(b->rows + nrows, 0, (b->zero_from - nrows) * sizeof(WrDcsRow), d->stream));
+	HIP_TRY(wrk_dcs_push(d->stream, audio_dev, row_stride, nrows, nframes, b->rows, b->words, b->ncodes, b->step, b->frames,
+	                     b->max_errors));
+	b->zero_from = (unsigned int)nrows;
+	b->frames += nframes;
+	return WR_OK;
+}
+
+extern "C" int wr_dcs_push_rows(wr_dcs *b, const float *audio_dev, size_t row_stride, size_t nrows, size_t nframes)
+{
+	if (!b || !audio_dev)
+		return wrc_fail(WR_ERR_ARG, "wr_dcs_push_rows: bad argument (NULL bank or audio_dev)");
+	if (int rc = bank_rows_refused(b, "wr_dcs_push_rows", row_stride, nrows, nframes, 28))
+		return rc;
+	if (!nframes)
+		return WR_OK;
+	if (int rc = bank_dev_ready(b->dev, true))
+		return rc;
+	return dcs_push(b, audio_dev, row_stride, nrows, nframes);
+}
+
+/* the rows wr_tuner_tones_push takes, into the DCS bank */
+extern "C" int wr_tuner_dcs_push(wr_tuner *t, wr_dcs *bank, unsigned int *slots)
+{
+	if (!t || !bank)
+		return wrc_fail(WR_ERR_ARG, "wr_tuner_dcs_push: bad argument (NULL tuner or bank)");
+	WrLastSubmit v;
+	if (int rc = bank_take_submit(bank, "wr_tuner_dcs_push", "bank", t, &v))
+		return rc;
+	if (int rc = wrc_last_submit_flush(t, &v))
+		return rc;
+	DEV_SETTLE(t->dev);
+	const Group *g = v.g;
+	if (int rc = dcs_push(bank, g->dev.audio, g->k2max, v.used, g->last_k2))
+		return rc;
+	return bank_took_submit(bank, t, v, slots);
+}
+
+extern "C" int wr_dcs_read(wr_dcs *b, unsigned char *agree_host, unsigned int *run_host, unsigned long long *hits_host,
+                           unsigned long long *evals_host, unsigned int *rows)
+{
+	if (!b)
+		return wrc_fail(WR_ERR_ARG, "wr_dcs_read: bank is NULL");
+	if (!agree_host && !run_host && !hits_host && !evals_host)
+		return wrc_fail(WR_ERR_ARG, "wr_dcs_read: no array to fill");
+	wr_dev *d = b->dev;
+	if (int rc = bank_dev_ready(d, false))
+		return rc;
+	const char *base = (const char *)b->rows;
+	const size_t pitch = sizeof(WrDcsRow), n = b->max_rows, pairs = (size_t)b->ncodes * 2u;
+	if (agree_host)
+		HIP_TRY(hipMemcpy2DAsync(agree_host, pairs, base + offsetof(WrDcsRow, agree), pitch, pairs, n, hipMemcpyDeviceToHost,
+		                         d->stream));
+	if (run_host)
+		HIP_TRY(hipMemcpy2DAsync(run_host, pairs * sizeof(unsigned int), base + offsetof(WrDcsRow, run), pitch,
+		                         pairs * sizeof(unsigned int), n, hipMemcpyDeviceToHost, d->stream));
+	if (hits_host)
+		HIP_TRY(hipMemcpy2DAsync(hits_host, pairs * sizeof(unsigned long long), base + offsetof(WrDcsRow, hits), pitch,
+		                         pairs * sizeof(unsigned long long), n, hipMemcpyDeviceToHost, d->stream));
+	if (evals_host)
+		HIP_TRY(hipMemcpy2DAsync(evals_host, sizeof(unsigned long long), base + offsetof(WrDcsRow, evals), pitch,
+		                         sizeof(unsigned long long), n, hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(wrc_dev_stream_sync(d));
+	if (rows)
+		*rows = b->max_rows;
+	return WR_OK;
+}
+
+extern "C" int wr_dcs_info(wr_dcs *b, unsigned int *ncodes, unsigned int *step, unsigned int *max_errors, unsigned long long *frames)
+{
+	if (!b)
+		return wrc_fail(WR_ERR_ARG, "wr_dcs_info: bank is NULL");
+	if (ncodes)
+		*ncodes = b->ncodes;
+	if (step)
+		*step = b->step;
+	if (max_errors)
+		*max_errors = b->max_errors;
+	if (frames)
+		*frames = b->frames;
 	return WR_OK;
 }
 

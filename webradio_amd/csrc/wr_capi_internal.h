@@ -285,11 +285,11 @@ struct wr_spectrum {
 	unsigned long long deferred_pushes = 0, resolves = 0;
 };
 
-/* what the two objects of wr_banks.hip, which keep something per audio row of every receiver, begin with */
+/* what the three objects of wr_banks.hip, which keep something per audio row of every receiver, begin with */
 struct WrRowBank {
 	wr_dev *dev;
 	unsigned int max_rows;
-	/* wr_tuner_tones_push, wr_tuner_resamp_push: whose submit, and which, the bank took last -- the same one is not pushed twice */
+	/* wr_tuner_tones_push, wr_tuner_dcs_push, wr_tuner_resamp_push: whose submit, and which, the bank took last -- the same one is not pushed twice */
 	const wr_tuner *last_tuner = nullptr;
 	unsigned long long last_seq = 0;
 };
@@ -299,6 +299,14 @@ struct wr_tones : WrRowBank {
 	WrTonesRow *rows;          /* device, [max_rows] */
 	float *t12;                /* device, [4096]: every 16th entry of the reference sine table */
 	unsigned int *steps;       /* device, [64]: the tones' phase steps, 0 beyond ntones */
+};
+
+struct wr_dcs : WrRowBank {
+	unsigned int ncodes, step, max_errors;
+	WrDcsRow *rows;            /* device, [max_rows] */
+	unsigned int *words;       /* device, [ncodes]: the 23-bit code words */
+	unsigned int zero_from = 0;        /* rows from this one on are known to be all zero */
+	unsigned long long frames = 0;     /* the clock: frames since creation, a reset of every row or a seek */
 };
 
 struct wr_resamp : WrRowBank {

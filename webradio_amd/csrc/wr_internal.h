@@ -1,7 +1,7 @@
 /*
  * wr_internal.h -- internal C++ interface between the C ABI (wr_dev.hip, wr_tuner*.hip, wr_spectrum.hip, wr_banks.hip), the host
  * design math (wr_design.cpp) and the kernels (wr_kernels.hip, wr_fft.hip, wr_levels.hip, wr_agc.hip, wr_tones.hip,
- * wr_resamp.hip).
+ * wr_dcs.hip, wr_resamp.hip).
  * Not installed; the public boundary is include/webradio_amd.h.
  */
 #ifndef WR_INTERNAL_H_
@@ -377,6 +377,23 @@ struct WrTonesRow {                        /* everything a bank holds of one row
  * goes into rows[r]; t12[4096] is every 16th entry of the sine table, steps[64] the tones' phase steps (0 beyond ntones) */
 hipError_t wrk_tones_push(hipStream_t st, const float *audio, size_t row_stride, size_t nrows, size_t nframes, WrTonesRow *rows,
                           const float *t12, const unsigned int *steps, unsigned int ntones, unsigned int window);
+
+/* ---- DCS bank (wr_dcs.hip) ---- */
+#define WR_DCS_CODES 128                   /* code words a bank holds at most: a lane each, two waves */
+#define WR_DCS_RING  512                   /* chip sums a row keeps, indexed by chip mod 512 (wr_dcs.hip: why that many) */
+struct WrDcsRow {                          /* everything a bank holds of one row; all zero: a row that begins its stream */
+	long long ring[WR_DCS_RING];       /* chip sums; the open chip among them */
+	unsigned long long hits[WR_DCS_CODES][2];
+	unsigned long long evals;
+	unsigned int run[WR_DCS_CODES][2];
+	unsigned char agree[WR_DCS_CODES][2];   /* of the last evaluation; [][0]: as sent, [][1]: inverted */
+};
+/* include/webradio_amd.h's rule (wr_dcs_push_rows) on `nrows` rows of `nframes` <= 2^28 floats, `row_stride` floats apart: row r
+ * goes into rows[r]; words[ncodes] are the bank's 23-bit code words, `first_frame` is the clock in front of the push.  As
+ * many launches as the rows' rings ask for */
+hipError_t wrk_dcs_push(hipStream_t st, const float *audio, size_t row_stride, size_t nrows, size_t nframes, WrDcsRow *rows,
+                        const unsigned int *words, unsigned int ncodes, unsigned int step, unsigned long long first_frame,
+                        unsigned int max_errors);
 
 /* ---- resampler (wr_resamp.hip) ---- */
 /* what a push is, besides its rows: the bank's ratio and taps, the clock before it (nmod = N mod M) and the two history

@@ -372,6 +372,13 @@ class Tuner:
         check(self.lib.wr_tuner_tones_push(self.h, bank.h, C.byref(slots)))
         return slots.value
 
+    def dcs_push(self, bank):
+        """The last submit's audio rows of every channel slot into a DcsBank (wr_tuner_dcs_push); row = Tuner.slot.
+        Returns the rows pushed (whole lane groups of 64)."""
+        slots = C.c_uint()
+        check(self.lib.wr_tuner_dcs_push(self.h, bank.h, C.byref(slots)))
+        return slots.value
+
     def resamp_push(self, rs):
         """The last submit's audio rows of every channel slot through a Resampler (wr_tuner_resamp_push); row = Tuner.slot.
         Returns the output frames as an array [slots][n_out] (slots: whole lane groups of 64), downloaded."""
@@ -451,6 +458,76 @@ def ratios(iq, energy, window):
     out = np.zeros(i.shape, np.float64)
     np.divide(2.0 * (i * i + q * q), den[..., None], out=out, where=den[..., None] > 0)
     return out
+
+
+def dcs_word(code):
+    """the 23-bit Golay word of a DCS code (0o023: dcs_word(0o023)), bit 0 sent first (wr_dcs_word); needs no device."""
+    word = C.c_uint()
+    check(capi.load().wr_dcs_word(code, C.byref(word)))
+    return word.value
+
+
+def dcs_step(audio_rate):
+    """134.4 bit/s in units of 2^-32 bit per audio frame (wr_dcs_step); needs no device."""
+    step = C.c_uint()
+    check(capi.load().wr_dcs_step(audio_rate, C.byref(step)))
+    return step.value
+
+
+class DcsBank:
+    """wr_dcs: up to 128 DCS code words tried on every row at every bit, in both polarities, the streams running on from
+    push to push on one clock (include/webradio_amd.h: DCS BANK)."""
+
+    def __init__(self, dev, max_rows, codes, audio_rate, max_errors=0, words=None):
+        """codes (ints: 0o023 ...) at audio_rate -- or, with `words`, the 23-bit words themselves (codes is then ignored)"""
+        self.dev = dev
+        self.lib = dev.lib
+        self.max_rows = max_rows
+        if words is None:
+            words = [dcs_word(code) for code in codes]
+        self.words = np.array(words, dtype=np.uint32)
+        self.ncodes = self.words.size
+        self.step = dcs_step(audio_rate)
+        self.max_errors = max_errors
+        h = C.c_void_p()
+        check(self.lib.wr_dcs_create(C.byref(h), dev.h, max_rows, ptr(self.words), self.ncodes, self.step, max_errors))
+        self.h = h
+
+    def destroy(self):
+        if self.h:
+            self.lib.wr_dcs_destroy(self.h)
+            self.h = None
+
+    def reset(self, row=-1):
+        """a row begins a new stream, the clock runs on (row < 0: every row, and the clock returns to 0)"""
+        check(self.lib.wr_dcs_reset(self.h, row))
+
+    def seek(self, frame):
+        """every row begins a new stream with the clock at `frame`"""
+        check(self.lib.wr_dcs_seek(self.h, frame))
+
+    def push_rows(self, p, row_stride, nrows, nframes):
+        """nrows rows of nframes floats at device pointer p, row_stride floats apart, continue rows 0 .. nrows-1"""
+        check(self.lib.wr_dcs_push_rows(self.h, C.c_void_p(p), row_stride, nrows, nframes))
+
+    def read(self):
+        """(agree uint8 [rows][ncodes][2], run uint32 [rows][ncodes][2], hits uint64 [rows][ncodes][2], evals uint64 [rows]):
+        the last evaluation's agreeing bits per code as sent ([..., 0]) and inverted ([..., 1]), the matches in a row up
+        to it, all matches and the evaluations so far (wr_dcs_read); waits for the device."""
+        agree = np.zeros((self.max_rows, self.ncodes, 2), np.uint8)
+        run = np.zeros((self.max_rows, self.ncodes, 2), np.uint32)
+        hits = np.zeros((self.max_rows, self.ncodes, 2), np.uint64)
+        evals = np.zeros(self.max_rows, np.uint64)
+        rows = C.c_uint()
+        check(self.lib.wr_dcs_read(self.h, ptr(agree), ptr(run), ptr(hits), ptr(evals), C.byref(rows)))
+        assert rows.value == self.max_rows
+        return agree, run, hits, evals
+
+    def info(self):
+        """(ncodes, step, max_errors, frames)"""
+        n, step, me, frames = C.c_uint(), C.c_uint(), C.c_uint(), C.c_ulonglong()
+        check(self.lib.wr_dcs_info(self.h, C.byref(n), C.byref(step), C.byref(me), C.byref(frames)))
+        return n.value, step.value, me.value, frames.value
 
 
 class Spectrum:
