@@ -1,12 +1,14 @@
 /*
  * cpu_host_checks.cxx -- host-only logic of the runtime that needs no GPU: FileTuner
  * (read, (u8-128)/128 conversion, loop, end of file, raw byte access) driven through
- * DspSource::run() into a capture sink.  Built from dspblock.cxx + filetuner.cxx only.
+ * DspSource::run() into a capture sink; the part arithmetic of the tuner batch.  Built from
+ * dspblock.cxx + filetuner.cxx only.
  */
 #include <string.h>
 
 #include <vector>
 
+#include "blockparts.h"
 #include "filetuner.h"
 
 namespace {
@@ -92,6 +94,17 @@ extern "C" int wr_filetuner_two_buffers(const char *path, unsigned int block_fra
 	}
 	t.stop();
 	return rc;
+}
+
+/* ---- in how many parts a block goes through the tuner batch (blockparts.h): the arithmetic of TunerBatch::piecesFor ---- */
+extern "C" unsigned int wr_block_parts(unsigned int nframes, unsigned int pieces, unsigned long q, unsigned int min_frames)
+{
+	return wrhost::partsOf(nframes, pieces, q, min_frames);
+}
+
+extern "C" unsigned long wr_lcm_capped(unsigned long a, unsigned long b)
+{
+	return wrhost::lcmCapped(a, b);
 }
 
 /* ---- device hand-over bookkeeping of DspBlock (no GPU involved: pointers are just tokens) ---- */

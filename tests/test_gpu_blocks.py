@@ -150,7 +150,7 @@ def test_u8_ingest(dev, oracle):
 def test_u8_ingest_from_page_locked_host_memory(dev, oracle, page_locked):
     """wr_u8_to_f32_from_host: the bytes cross PCIe on the library's own stream (DMA + conversion kernel) and the
     device's stream waits for them.  Blocks alternate between two device buffers and two host buffers the way the host
-    runtime stages a RawU8Block source (gpubatch.cxx), one size that is not a multiple of 16, the same buffer twice in a
+    runtime stages a RawU8Block source (sourcestage.cxx), one size that is not a multiple of 16, the same buffer twice in a
     row; wr_dev_wait_uploads_but(1) lets the host refill one buffer while the other is in flight.  Every block is the
     reference's (u8 - 128) / 128 bit for bit (rtlsdrtuner.cxx:106)."""
     import ctypes as C

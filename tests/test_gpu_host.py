@@ -117,6 +117,9 @@ def test_sparse_staging_and_parts_give_the_same_bits(tmp_path, block):
                       ("sparse-1", {"WEBRADIO_SPARSE": "1", "WEBRADIO_PIECES": "1"}),
                       ("sparse-4", {"WEBRADIO_SPARSE": "1", "WEBRADIO_PIECES": "4", "WEBRADIO_PIECE_MIN_FRAMES": "1000"}),
                       ("whole-4", {"WEBRADIO_SPARSE": "0", "WEBRADIO_PIECES": "4", "WEBRADIO_PIECE_MIN_FRAMES": "1000"}),
+                      # (memory that cannot be page-locked: sparse staging and staging in parts both decline at their first
+                      # step, and the block goes over in one piece by a plain copy)
+                      ("unpinned-4", {"WEBRADIO_NO_PINNING": "1", "WEBRADIO_PIECES": "4", "WEBRADIO_PIECE_MIN_FRAMES": "1000"}),
                       ("sparse-default", {})):
         runs[name] = _run("libwr_host_pipeline.so", tmp_path, iq, CFG["rate"], block, ifs, modes, CFG["cpb"],
                           CFG["crate"], CFG["apb"], CFG["arate"], fft=512, env=env)
@@ -499,8 +502,11 @@ def test_c1_recorded_rtlsdr_file(tmp_path, oracle, with_frontend):
             c1["audio_rate"], with_frontend]
     # (default: the recording's BYTES are staged and converted on the device, the float vector stays unfilled;
     #  WEBRADIO_NO_U8_STAGING=1: FileTuner converts on the host and the float block is staged, as r02 did)
+    # (WEBRADIO_PIECES=2: config 1 decimates 8 x 8 through 64 taps, too densely for sparse staging; the block's 16 384 frames
+    #  go through in two parts of 8 192, each part's BYTES brought over and converted on their own)
     for env, tol in (({"WEBRADIO_NCO_EXACT": "1"}, 4.8e-7), ({}, 1e-5),
-                     ({"WEBRADIO_NCO_EXACT": "1", "WEBRADIO_NO_U8_STAGING": "1"}, 4.8e-7)):
+                     ({"WEBRADIO_NCO_EXACT": "1", "WEBRADIO_NO_U8_STAGING": "1"}, 4.8e-7),
+                     ({"WEBRADIO_NCO_EXACT": "1", "WEBRADIO_PIECES": "2", "WEBRADIO_PIECE_MIN_FRAMES": "1000"}, 4.8e-7)):
         _proc.run([sys.executable, "-c", FILE_RUNNER, lib, path, out] + [str(a) for a in args],
                               env=dict(os.environ, WEBRADIO_QUIET="1", WEBRADIO_PIN_MIN_BYTES="0", **env))
         r = np.load(out)

@@ -32,13 +32,15 @@ using namespace std;	// reference headers do this and its sources rely on it (ra
 
 typedef float sample_t;
 
+class DspBlock;
 class DspSource;
-namespace wrhost { class TunerBatch; struct Channel; }
+namespace wrhost { class TunerBatch; struct Channel; DspSource *rootSource(const DspBlock *block); }
 
 class DspBlock
 {
 	friend class DspSource;
 	friend class wrhost::TunerBatch;
+	friend DspSource *wrhost::rootSource(const DspBlock *block);
 public:
 	DspBlock(const string &name = "<undefined>", const string &type = "DspBlock");
 	virtual ~DspBlock();
@@ -148,7 +150,7 @@ public:
 
 	/* number of run() calls so far: the "epoch" the tuner batch keys its launches on */
 	unsigned long epoch() const { return _epoch; }
-	/* per-source GPU resources, owned by the GPU glue (gpubatch.cxx) and released through
+	/* per-source GPU resources, owned by the GPU glue (sourcestage.cxx, gpubatch.cxx) and released through
 	 * `_gpuCleanup` when the source dies: the tuner batch (created on demand by the first
 	 * DownConverter), the device copy of the current block shared by every GPU consumer of
 	 * this source, and the GPU the source's blocks run on (-1: not chosen yet) */

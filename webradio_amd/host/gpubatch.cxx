@@ -12,6 +12,7 @@
 #include <time.h>
 #include <stdio.h>
 
+#include "blockparts.h"
 #include "debug.h"
 #include "demodulator.h"
 #include "downconverter.h"
@@ -22,516 +23,38 @@
 
 namespace wrhost {
 
-namespace {
-std::mutex g_devLock;
-std::vector<wr_dev *> g_devs;
-int g_batches = 0;
-
-unsigned int envUnsigned(const char *name, unsigned int fallback)
+/* the tuner batch of `block`'s root source, or NULL */
+static TunerBatch *batchOf(const DspBlock *block)
 {
-	const char *v = getenv(name);
-	return (v && *v) ? (unsigned int)strtoul(v, NULL, 0) : fallback;
-}
-}
-
-namespace {
-std::vector<TraceEvent> g_trace;
-std::mutex g_traceLock;
-bool traceOn()
-{
-	static const bool on = envUnsigned("WEBRADIO_TRACE", 0) != 0;
-	return on;
-}
-void traceAdd(const void *src, char kind)
-{
-	if (!traceOn())
-		return;
-	std::lock_guard<std::mutex> g(g_traceLock);
-	TraceEvent e = { src, kind };
-	g_trace.push_back(e);
-}
-}
-
-const std::vector<TraceEvent> &trace() { return g_trace; }
-void traceClear()
-{
-	std::lock_guard<std::mutex> g(g_traceLock);
-	g_trace.clear();
-}
-
-int deviceCount()
-{
-	int n = 0;
-	if (wr_device_count(&n) != WR_OK)
-		return 0;
-	return n;
-}
-
-wr_dev *device(int index)
-{
-	std::lock_guard<std::mutex> g(g_devLock);
-	if (index < 0)
-		return NULL;
-	if ((size_t)index >= g_devs.size())
-		g_devs.resize(index + 1, NULL);
-	if (!g_devs[index]) {
-		wr_dev *d = NULL;
-		if (wr_dev_open(&d, index, NULL) != WR_OK) {
-			/* no CPU path: the caller's init()/process() reports failure */
-			LOG_ERROR("GPU device %d unavailable: %s\n", index, wr_last_error());
-			return NULL;
-		}
-		g_devs[index] = d;
-	}
-	return g_devs[index];
-}
-
-/* the device copy of a source's current block, and the host buffers it has been uploaded from:
- * sources hand out the same one or two vectors block after block (RtlSdrTuner swaps two,
- * rtlsdrtuner.cxx:280), so they are page-locked once and the copy is a DMA nobody waits for */
-struct SourceStage {
-	DevBuf buf;
-	DevBuf buf2;                /* a float source's blocks alternate between `buf` and `buf2`: block b + 1 crosses PCIe on the
-	                               upload stream while block b is being worked on (wr_dev_upload_ahead) */
-	bool second;
-	DevBuf raw;                 /* the block as the source holds it in the RTL-SDR byte format (RawU8Block), on the device */
-	unsigned long epoch;
-	const void *host;
-	size_t floats;
-	wr_dev *dev;
-	struct Pinned { void *ptr; size_t bytes; };
-	std::vector<Pinned> pinned;
-	const float *cur;           /* the staged block: in `buf`, or `buf2` */
-	bool rawStaged;             /* the block now staged came from the source's raw bytes: its float vector was not read */
-	/* sparse staging (stagedWindows / stagedTail): of the source's block of `sparseEpoch` only the windows
-	 * [k * sparsePeriod - (sparseLen - 1), k * sparsePeriod] and the last `sparseTail` frames lie in `buf` */
-	unsigned long sparseEpoch;
-	unsigned int sparsePeriod, sparseLen;
-	size_t sparseTail;
-	size_t tailWanted;          /* the longest tail a consumer has asked for so far (a SpectrumSink: its frame + hop) */
-	SourceStage() : second(false), epoch(0), host(NULL), floats(0), dev(NULL), cur(NULL), rawStaged(false), sparseEpoch(0),
-	                sparsePeriod(0), sparseLen(0), sparseTail(0), tailWanted(0) {}
-	~SourceStage() { unpin(); }
-	/* the page locks must go before the memory does: freed but still registered, it is handed out
-	 * again by the allocator and a later copy out of it fails ("invalid argument") */
-	void unpin() {
-		if (dev)
-			wr_dev_wait_uploads(dev);
-		for (size_t n = 0; n < pinned.size(); n++)
-			wr_dev_host_unregister(dev, pinned[n].ptr);
-		pinned.clear();
-		epoch = 0;
-		host = NULL;
-	}
-	bool pin(wr_dev *d, const void *p, size_t bytes) {
-		for (size_t n = 0; n < pinned.size(); n++)
-			if (pinned[n].ptr == p && pinned[n].bytes >= bytes)
-				return true;
-		if (envUnsigned("WEBRADIO_NO_PINNING", 0))
-			return false;
-		/* Small blocks are not page-locked: the allocator serves them from the heap, where a registered range shares
-		 * its first and last page with its neighbours and its address is soon handed out again -- and on this ROCm a
-		 * registered range that overlaps memory the runtime page-locks on the fly (the destination of any copy into
-		 * pageable memory) can abort the process (r04: profiles/r04_abort_hunt.txt).  Large vectors get a mapping of
-		 * their own from the allocator; small ones are copied through the runtime's staging buffers, which at their
-		 * size costs nothing that matters. */
-		static const size_t minBytes = envUnsigned("WEBRADIO_PIN_MIN_BYTES", 1u << 20);
-		if (bytes < minBytes)
-			return false;
-		/* ... and of the large ones only those that start where a mapping of their own starts: glibc hands out a
-		 * request above its mmap threshold as a private mapping with the user pointer 16 bytes into its first page
-		 * (an aligned_alloc / mmap / hipHostMalloc'ed buffer starts ON a page); once the threshold has grown -- it
-		 * follows the largest mapped block freed so far, up to 32 MB -- even megabytes come from the heap, in the
-		 * middle of a page somebody else also lives on.  WEBRADIO_PIN_ANY=1 lifts the check. */
-		static const bool pinAny = envUnsigned("WEBRADIO_PIN_ANY", 0) != 0 || minBytes == 0;
-		if (!pinAny && ((uintptr_t)p & 4095u) > 64u)
-			return false;
-		for (size_t n = 0; n < pinned.size(); n++)
-			if (pinned[n].ptr == p) {                      /* same address, grown: register afresh */
-				wr_dev_wait_uploads(d);                    /* (a copy out of it may still be in flight) */
-				wr_dev_host_unregister(d, pinned[n].ptr);
-				pinned.erase(pinned.begin() + n);
-				break;
-			}
-		if (pinned.size() >= 8) {                          /* (RtlSdrTuner rotates five vectors: its ring of N_BUFFERS = 4,
-		                                                      rtlsdrtuner.cxx:33-34, and the one handed out)
-		                                                      a source that allocates per block: give up on the oldest */
-			wr_dev_wait_uploads(d);
-			wr_dev_host_unregister(d, pinned[0].ptr);
-			pinned.erase(pinned.begin());
-		}
-		if (wr_dev_host_register(d, const_cast<void *>(p), bytes) != WR_OK)
-			return false;
-		Pinned e = { const_cast<void *>(p), bytes };
-		pinned.push_back(e);
-		dev = d;
-		return true;
-	}
-};
-
-static void releaseSource(DspSource *src)
-{
-	delete static_cast<SourceStage *>(src->gpuStage());
-	src->setGpuStage(NULL);
-	TunerBatch::destroyFor(src);
-}
-
-/* top of DspSource::stop(): the block vector is about to be released (dspblock.cxx:153-167) */
-static void beforeSourceStop(DspSource *src)
-{
-	SourceStage *st = static_cast<SourceStage *>(src->gpuStage());
-	if (st)
-		st->unpin();
-}
-
-/* top of DspSource::run(): the source is about to refill its block vector */
-static void beforeSourceRun(DspSource *src)
-{
-	SourceStage *st = static_cast<SourceStage *>(src->gpuStage());
-	if (!st || !st->dev)
-		return;
-	/* a source that alternates between raw buffers (RawU8Block::rawU8Buffers) may refill one while the transfer out
-	 * of the other is still in flight: the host then runs a block ahead of the GPU instead of in step with it */
-	unsigned int inflight = 0;
-	if (st->rawStaged) {
-		const RawU8Block *raw = dynamic_cast<const RawU8Block *>(src);
-		const unsigned int nbuf = raw ? raw->rawU8Buffers() : 1u;
-		inflight = nbuf > 1u ? (nbuf - 1u > 3u ? 3u : nbuf - 1u) : 0u;
-	}
-	wr_dev_wait_uploads_but(st->dev, inflight);
-}
-
-wr_dev *deviceFor(const DspBlock *block)
-{
-	DspSource *src = TunerBatch::rootSource(block);
-	if (!src)
-		return device((int)envUnsigned("WEBRADIO_DEVICE", 0));
-	if (src->gpuIndex() < 0) {
-		int count = deviceCount();
-		if (count <= 0) {
-			LOG_ERROR("no GPU: %s\n", wr_last_error());
-			return NULL;
-		}
-		std::lock_guard<std::mutex> g(g_devLock);
-		int index = getenv("WEBRADIO_DEVICE") ? (int)envUnsigned("WEBRADIO_DEVICE", 0) : (g_batches % count);
-		g_batches++;
-		src->setGpuIndex(index);
-		src->setGpuCleanup(releaseSource);
-	}
-	return device(src->gpuIndex());
-}
-
-static std::mutex g_stageLock;
-
-/* a source whose block already lies on `dev` (DeviceBlock): where */
-static const float *residentBlock(const DspSource *src, wr_dev *dev, size_t floats)
-{
-	const DeviceBlock *db = dynamic_cast<const DeviceBlock *>(src);
-	if (!db)
-		return NULL;
-	wr_dev *bd = NULL;
-	size_t frames = 0;
-	const float *p = db->deviceBlock(&bd, &frames);
-	return (p && bd == dev && frames * 2 == floats) ? p : NULL;
-}
-
-/* The source's current block staged in `pieces` equal parts, part `p` (0, 1, ... in order) now: part p crosses PCIe on the
- * upload stream -- as bytes where the source still holds them (RawU8Block), converted on the device -- while the caller has
- * the parts before it worked on.  Returns the device address of the part inside the staged block, which after the last
- * part is the same staged block stagedBlock() makes in one piece (the SpectrumSink then finds it there).  NULL: this block
- * cannot be staged in parts (host memory that cannot be page-locked, no memory): before part 0 nothing has happened and the
- * caller takes the one-piece path. */
-static const float *stagePiece(DspSource *src, wr_dev *dev, const vector<sample_t> &host, unsigned int pieces, unsigned int p)
-{
-	std::lock_guard<std::mutex> g(g_stageLock);
-	SourceStage *st = static_cast<SourceStage *>(src->gpuStage());
-	if (!st) {
-		st = new SourceStage();
-		src->setGpuStage(st);
-		src->setGpuCleanup(releaseSource);
-		src->setGpuBeforeRun(beforeSourceRun);
-		src->setGpuBeforeStop(beforeSourceStop);
-	}
-	const size_t bytes = host.size() * sizeof(float);
-	const RawU8Block *rawsrc = dynamic_cast<const RawU8Block *>(src);
-	size_t rawFrames = 0;
-	const uint8_t *rawBytes = rawsrc ? rawsrc->rawU8(&rawFrames) : NULL;
-	const bool raw = rawBytes && rawFrames * 2 == host.size() && !envUnsigned("WEBRADIO_NO_U8_STAGING", 0);
-	if (p == 0) {
-		if (st->epoch == src->epoch() && st->host == host.data() && st->floats == host.size())
-			return NULL;                                /* somebody staged the whole block already */
-		if (!raw && !src->hostBlockValid())
-			return NULL;
-		if (!(raw ? st->pin(dev, rawBytes, host.size()) : st->pin(dev, host.data(), bytes)))
-			return NULL;
-		st->dev = dev;
-		if (!raw)
-			st->second = !st->second;                   /* float blocks alternate between two device copies (see stagedBlock) */
-		DevBuf &dst = (!raw && st->second) ? st->buf2 : st->buf;
-		if (!dst.reserve(dev, bytes))
-			return NULL;
-		st->cur = (const float *)dst.ptr;
-		st->rawStaged = raw;
-		st->epoch = 0;                                  /* not complete until the last part is on its way */
-	}
-	const size_t part = host.size() / pieces, off = part * p;      /* floats */
-	float *dstp = const_cast<float *>(st->cur) + off;
-	const int rc = raw ? wr_u8_to_f32_from_host(dev, rawBytes + off, dstp, part)
-	                   : wr_dev_upload_ahead(dev, dstp, host.data() + off, part * sizeof(float));
-	if (rc != WR_OK) {
-		LOG_ERROR("staging part %u of %u of the source block failed: %s\n", p, pieces, wr_last_error());
-		return NULL;
-	}
-	if (p + 1 == pieces) {
-		st->epoch = src->epoch();
-		st->host = host.data();
-		st->floats = host.size();
-	}
-	return dstp;
-}
-
-static bool sparseEnabled()
-{
-	static const bool on = envUnsigned("WEBRADIO_SPARSE", 1) != 0;
-	return on;
-}
-
-/* Sparse staging of the source's current block (wr_stage_windows_from_host): of a block whose every receiver decimates by
- * `period` through a channel filter of `length` taps only the frames under the taps -- 64 of every 400 at BASELINE config 2 --
- * and the tail cross PCIe, read by a kernel on the device's own stream, in order with the tuner's launches behind it; there
- * is no transfer to wait for and no second stream to hand over from.  period = 0: the tail alone (a SpectrumSink's frame).
- * Returns the address the WHOLE block would have on the device (the frames not staged keep what the buffer held), or NULL when
- * this block cannot be staged that way (host memory that cannot be page-locked, windows too long for the kernel): the caller
- * stages the whole block. */
-static const float *stagedSparse(const DspBlock *consumer, const vector<sample_t> &host, wr_dev **dev_out, unsigned int period,
-                                 unsigned int length, size_t tail)
-{
-	DspSource *src = TunerBatch::rootSource(consumer);
-	if (!sparseEnabled() || !src || host.empty() || host.data() != src->currentBlock().data())
-		return NULL;
-	wr_dev *dev = deviceFor(consumer);
-	if (!dev)
-		return NULL;
-	if (const float *there = residentBlock(src, dev, host.size())) {
-		if (dev_out)
-			*dev_out = dev;
-		return there;                                   /* nothing to stage: the source produced it in device memory */
-	}
-	std::lock_guard<std::mutex> g(g_stageLock);
-	SourceStage *st = static_cast<SourceStage *>(src->gpuStage());
-	if (!st) {
-		st = new SourceStage();
-		src->setGpuStage(st);
-		src->setGpuCleanup(releaseSource);
-		src->setGpuBeforeRun(beforeSourceRun);
-		src->setGpuBeforeStop(beforeSourceStop);
-	}
-	const size_t nframes = host.size() / 2;
-	if (tail > nframes)
-		tail = nframes;
-	if (!period && tail > st->tailWanted)
-		st->tailWanted = tail;                          /* the next block's window pass brings it along */
-	if (st->epoch == src->epoch() && st->host == host.data() && st->floats == host.size() && st->dev == dev) {
-		if (dev_out)
-			*dev_out = dev;
-		return st->cur;                                 /* the whole block is there already */
-	}
-	const bool have = st->sparseEpoch == src->epoch() && st->host == host.data() && st->floats == host.size() && st->dev == dev;
-	if (have && (!period || (st->sparsePeriod == period && st->sparseLen == length)) && st->sparseTail >= tail) {
-		if (dev_out)
-			*dev_out = dev;
-		return st->cur;
-	}
-	if (have && period && st->sparsePeriod)
-		return NULL;                                    /* two consumers with different windows: the whole block then */
-	const RawU8Block *rawsrc = dynamic_cast<const RawU8Block *>(src);
-	size_t rawFrames = 0;
-	const uint8_t *rawBytes = rawsrc ? rawsrc->rawU8(&rawFrames) : NULL;
-	const bool raw = rawBytes && rawFrames == nframes && !envUnsigned("WEBRADIO_NO_U8_STAGING", 0);
-	if (!raw && !src->hostBlockValid())
-		return NULL;
-	const void *from = raw ? (const void *)rawBytes : (const void *)host.data();
-	const size_t bytes = host.size() * sizeof(float);
-	if ((uintptr_t)from & 15u)
-		return NULL;
-	if (!st->pin(dev, from, raw ? host.size() : bytes) || !st->buf.reserve(dev, bytes))
-		return NULL;
-	if (period && st->tailWanted > tail)
-		tail = st->tailWanted > nframes ? nframes : st->tailWanted;
-	if (wr_stage_windows_from_host(dev, from, raw ? 1 : 0, (float *)st->buf.ptr, nframes, period ? period : (unsigned int)nframes + 1u,
-	                               period ? length : 1u, tail) != WR_OK) {
-		LOG_ERROR("sparse staging of the source block failed: %s\n", wr_last_error());
-		return NULL;
-	}
-	st->dev = dev;
-	st->host = host.data();
-	st->floats = host.size();
-	st->cur = (const float *)st->buf.ptr;
-	st->rawStaged = raw;
-	st->epoch = 0;                                      /* (not the whole block) */
-	if (!have || period) {
-		st->sparsePeriod = period;
-		st->sparseLen = period ? length : 0;
-	}
-	st->sparseTail = (have && st->sparseTail > tail) ? st->sparseTail : tail;
-	st->sparseEpoch = src->epoch();
-	if (dev_out)
-		*dev_out = dev;
-	return st->cur;
-}
-
-const float *stagedTail(const DspBlock *consumer, const vector<sample_t> &host, wr_dev **dev_out, size_t tail_frames)
-{
-	return stagedSparse(consumer, host, dev_out, 0, 0, tail_frames);
-}
-
-const float *stagedBlock(const DspBlock *consumer, const vector<sample_t> &host, wr_dev **dev_out,
-                         bool only_if_present)
-{
-	DspSource *src = TunerBatch::rootSource(consumer);
-	if (!src || host.empty() || host.data() != src->currentBlock().data())
-		return NULL;                    /* not fed straight from the source: caller uploads itself */
-	wr_dev *dev = deviceFor(consumer);
-	if (!dev)
-		return NULL;
-	if (const float *there = residentBlock(src, dev, host.size())) {
-		if (dev_out)
-			*dev_out = dev;
-		return there;
-	}
-	std::lock_guard<std::mutex> g(g_stageLock);
-	SourceStage *st = static_cast<SourceStage *>(src->gpuStage());
-	if (!st && only_if_present)
-		return NULL;
-	if (!st) {
-		st = new SourceStage();
-		src->setGpuStage(st);
-		src->setGpuCleanup(releaseSource);
-		src->setGpuBeforeRun(beforeSourceRun);
-		src->setGpuBeforeStop(beforeSourceStop);
-	}
-	if (st->epoch != src->epoch() || st->host != host.data() || st->floats != host.size()) {
-		if (only_if_present)
-			return NULL;
-		const size_t bytes = host.size() * sizeof(float);
-		st->dev = dev;
-		/* A source that still holds the block in the RTL-SDR byte format (FileTuner; what RtlSdrTuner::dataReady
-		 * receives, rtlsdrtuner.cxx:86-117): ship the BYTES -- a quarter of the float block over PCIe -- and
-		 * convert on the device with the reference's rule (u8 - 128) / 128 (rtlsdrtuner.cxx:106: exact in
-		 * float, so the staged block is the float block bit for bit).  Such a source need not even fill its
-		 * float vector when every consumer reads the block on the device (DspBlock::readsSourceOnDevice). */
-		const RawU8Block *rawsrc = dynamic_cast<const RawU8Block *>(src);
-		size_t rawFrames = 0;
-		const uint8_t *rawBytes = rawsrc ? rawsrc->rawU8(&rawFrames) : NULL;
-		if (rawBytes && rawFrames * 2 == host.size() && !envUnsigned("WEBRADIO_NO_U8_STAGING", 0)) {
-			const bool pinned = st->pin(dev, rawBytes, host.size());
-			/* page-locked: the bytes cross PCIe as a DMA copy on the library's upload stream, beside the kernels of
-			 * the block before, and are converted on the device (wr_u8_to_f32_from_host: nothing the host waits
-			 * for); else a staged copy and the kernel on the device copy */
-			DevBuf &dst = st->buf;
-			if (!dst.reserve(dev, bytes) ||
-			    (pinned ? wr_u8_to_f32_from_host(dev, rawBytes, (float *)dst.ptr, host.size())
-			            : (!st->raw.reserve(dev, host.size()) ||
-			               wr_dev_upload(dev, st->raw.ptr, rawBytes, host.size()) != WR_OK)
-			                  ? WR_ERR_HIP
-			                  : wr_u8_to_f32(dev, (const uint8_t *)st->raw.ptr, (float *)dst.ptr, host.size())) != WR_OK) {
-				LOG_ERROR("staging the source block (byte format) failed: %s\n", wr_last_error());
-				return NULL;
-			}
-			st->epoch = src->epoch();
-			st->host = host.data();
-			st->floats = host.size();
-			st->rawStaged = pinned;
-			st->cur = (const float *)dst.ptr;
-			if (dev_out)
-				*dev_out = dev;
-			return st->cur;
-		}
-		st->rawStaged = false;
-		st->cur = NULL;
-		/* out of page-locked memory the copy is enqueued and the graph walk goes on beside it; the
-		 * source's next run() waits for it before it touches the vector again (beforeSourceRun) */
-		const bool pinned = st->pin(dev, host.data(), bytes);
-		/* page-locked: on the upload stream, into the device copy the LAST block was not staged in -- the 32 MB of block
-		 * b + 1 cross PCIe while the kernels of block b run (the source's next run() still waits for the copy before it
-		 * touches the vector again: a float source refills the vector it swapped out at once, rtlsdrtuner.cxx:265-285) */
-		if (pinned)
-			st->second = !st->second;
-		DevBuf &dst = (pinned && st->second) ? st->buf2 : st->buf;
-		if (!dst.reserve(dev, bytes) ||
-		    (pinned ? wr_dev_upload_ahead(dev, dst.ptr, host.data(), bytes)
-		            : wr_dev_upload(dev, dst.ptr, host.data(), bytes)) != WR_OK) {
-			LOG_ERROR("staging the source block failed: %s\n", wr_last_error());
-			return NULL;
-		}
-		st->epoch = src->epoch();
-		st->host = host.data();
-		st->floats = host.size();
-		st->cur = (const float *)dst.ptr;
-	}
-	if (dev_out)
-		*dev_out = dev;
-	return st->cur;
+	DspSource *src = rootSource(block);
+	return src ? src->batch() : NULL;
 }
 
 void submitBatchFirst(const DspBlock *consumer, const vector<sample_t> &host)
 {
-	DspSource *src = TunerBatch::rootSource(consumer);
-	if (!src || host.empty() || host.data() != src->currentBlock().data())
+	TunerBatch *batch = batchOf(consumer);
+	if (!batch || host.empty() || host.data() != batch->source()->currentBlock().data())
 		return;
-	TunerBatch *batch = src->batch();
-	if (batch && batch->channels())
+	if (batch->channels())
 		(void)batch->submitOnce(host, (unsigned int)(host.size() / 2));      /* (the receivers see its verdict when they ask) */
 }
 
 bool streamInfo(const DspBlock *block, bool *live, unsigned long long *launches, unsigned long long *blocks)
 {
-	DspSource *src = TunerBatch::rootSource(block);
-	TunerBatch *batch = src ? src->batch() : NULL;
+	TunerBatch *batch = batchOf(block);
 	return batch && batch->streamInfo(live, launches, blocks);
 }
 
 unsigned long long chanSpectraCalls(const DspBlock *block)
 {
-	DspSource *src = TunerBatch::rootSource(block);
-	TunerBatch *batch = src ? src->batch() : NULL;
+	TunerBatch *batch = batchOf(block);
 	return batch ? batch->chanSpectraCalls() : 0;
 }
 
 unsigned long long chanLevelCalls(const DspBlock *block)
 {
-	DspSource *src = TunerBatch::rootSource(block);
-	TunerBatch *batch = src ? src->batch() : NULL;
+	TunerBatch *batch = batchOf(block);
 	return batch ? batch->chanLevelCalls() : 0;
-}
-
-bool hostBlockValid(const DspBlock *block)
-{
-	DspSource *src = TunerBatch::rootSource(block);
-	return !src || src->hostBlockValid();
-}
-
-bool DevBuf::reserve(wr_dev *d, size_t nbytes)
-{
-	if (dev == d && bytes >= nbytes && ptr)
-		return true;
-	release();
-	if (!d || wr_dev_malloc(d, nbytes ? nbytes : 4, &ptr) != WR_OK) {
-		ptr = NULL;
-		return false;
-	}
-	dev = d;
-	bytes = nbytes;
-	return true;
-}
-
-void DevBuf::release()
-{
-	if (ptr && dev)
-		wr_dev_free(dev, ptr);
-	ptr = NULL;
-	bytes = 0;
-	dev = NULL;
 }
 
 /* ------------------------------------------------------------------ TunerBatch -- */
@@ -539,9 +62,6 @@ void DevBuf::release()
 /* WEBRADIO_TIMES=1 (measurement only): where the wall time of an on-time block goes inside the batch -- averaged and printed
  * when the batch goes (profiles/r05_host_times.txt) */
 static const bool g_times = getenv("WEBRADIO_TIMES") && atoi(getenv("WEBRADIO_TIMES")) != 0;
-static double g_tacc[8];
-static unsigned long g_tn;
-static double g_tlast;
 static inline double nowUs()
 {
 	struct timespec ts;
@@ -554,7 +74,8 @@ TunerBatch::TunerBatch(DspSource *source, wr_dev *dev)
 	  _submitOk(false), _audioPtr(NULL), _ringHeld(false), _audioStride(0), _audioFrames(0), _audioSlots(0),
 	  _late(envUnsigned("WEBRADIO_AUDIO_LATE", 0) != 0), _lateDepth(envUnsigned("WEBRADIO_AUDIO_LATE", 0) >= 2 ? 2u : 1u),
 	  _lateQueued(false), _silence(false), _lateSeq(0), _pieces(envUnsigned("WEBRADIO_PIECES", 2)), _delivered(false), _partSeq0(0),
-	  _streaming(false), _tapSeq(0), _tapCalls(0), _lvSlots(0), _lvSeq(0), _lvCalls(0)
+	  _streaming(false), _tapSeq(0), _tapCalls(0), _lvSlots(0), _lvSeq(0), _lvCalls(0), _timeSums(), _submitStart(0.0),
+	  _lastCollected(0.0), _timedBlocks(0)
 {
 	if (_pieces < 1 || _late)
 		_pieces = 1;
@@ -564,26 +85,14 @@ TunerBatch::TunerBatch(DspSource *source, wr_dev *dev)
 
 TunerBatch::~TunerBatch()
 {
-	if (g_times && g_tn)
+	const double *s = _timeSums;
+	const unsigned long n = _timedBlocks;
+	if (g_times && n)
 		fprintf(stderr, "WEBRADIO_TIMES, us per block over %lu blocks: walk+source %.1f | stage enqueued %.1f | submits+flush %.1f (from the submit's start) | "
-		        "wait part 0 %.1f copy %.1f | wait part 1 %.1f copy %.1f\n", g_tn, g_tacc[0] / g_tn, g_tacc[1] / g_tn, g_tacc[2] / g_tn,
-		        g_tacc[3] / g_tn, g_tacc[4] / g_tn, g_tacc[5] / g_tn, g_tacc[6] / g_tn);
+		        "wait part 0 %.1f copy %.1f | wait part 1 %.1f copy %.1f\n", n, s[0] / n, s[1] / n, s[2] / n,
+		        s[3] / n, s[4] / n, s[5] / n, s[6] / n);
 	if (_tuner)
 		wr_tuner_destroy(_tuner);
-}
-
-DspSource *TunerBatch::rootSource(const DspBlock *block)
-{
-	const DspBlock *b = block;
-	while (b && b->_producer)
-		b = b->_producer;
-	return const_cast<DspSource *>(dynamic_cast<const DspSource *>(b));
-}
-
-wr_dev *TunerBatch::batchDeviceOf(const DspBlock *block)
-{
-	DspSource *src = rootSource(block);
-	return (src && src->batch()) ? src->batch()->dev() : NULL;
 }
 
 void TunerBatch::destroyFor(DspSource *src)
@@ -799,8 +308,7 @@ unsigned long long TunerBatch::chanSpectraCalls()
 const Channel *TunerBatch::tapChannel(const DspBlock *block, bool (*owns)(const Channel *, const DspBlock *),
                                       std::unique_lock<std::mutex> &lock, Tap *answer)
 {
-	DspSource *src = rootSource(block);
-	TunerBatch *b = src ? src->batch() : NULL;
+	TunerBatch *b = batchOf(block);
 	*answer = TAP_NONE;
 	if (!b)
 		return NULL;
@@ -1008,6 +516,7 @@ bool TunerBatch::submitOnce(const vector<sample_t> &tunerBuffer, unsigned int nf
 		return _submitOk;
 	_submittedEpoch = _source->epoch();
 	_submitOk = false;
+	/* 1. what the setters changed since the last block */
 	bool pushed = false;
 	for (size_t n = 0; n < _channels.size(); n++)
 		if (_channels[n]->dirty || _channels[n]->slot < 0) {
@@ -1027,89 +536,89 @@ bool TunerBatch::submitOnce(const vector<sample_t> &tunerBuffer, unsigned int nf
 		_audioSlots = 0;
 	}
 	_delivered = false;
-	/* On time (the default: a block's audio is handed on within the run() that brought the block) the block goes through
-	 * in P equal parts: part p + 1 crosses PCIe while part p's kernels run, part p's audio comes back -- and is put where
-	 * the audio filters' consumers will read it -- while part p + 1 computes.  What run() then waits for after the link
+	/* 2. how the block goes.  On time (the default: a block's audio is handed on within the run() that brought the block) it
+	 * goes through in P equal parts: part p + 1 crosses PCIe while part p's kernels run, part p's audio comes back -- and is put
+	 * where the audio filters' consumers will read it -- while part p + 1 computes.  What run() then waits for after the link
 	 * has delivered the block is one part's kernels and transfer, not the block's (r03: transfer, kernels, audio copy
 	 * and hand-out in series, 0.43 ms a C2 block of bytes; the bits do not depend on how a stream is cut into blocks:
 	 * tests/test_gpu_tuner.py::test_block_split_invariance). */
 	/* (r04) Where every receiver decimates alike and by at least twice its channel filter's length, only the frames under
 	 * the taps are brought over (stagedSparse): a sixth of the block at BASELINE config 2 -- and no transfer to wait for. */
+	const unsigned int parts = pushed ? 1u : piecesFor(nframes);
+	Sent sent = NOT_IN_PARTS;
 	unsigned int sp = 0, sl = 0;
-	const double tt0 = g_times ? nowUs() : 0.0;
-	if (g_times && g_tlast > 0.0)
-		g_tacc[0] += tt0 - g_tlast;                 /* from the end of the last collectParts to this submit: the walk + the source */
+	_submitStart = g_times ? nowUs() : 0.0;
+	if (g_times && _lastCollected > 0.0)
+		_timeSums[0] += _submitStart - _lastCollected;      /* from the end of the last collectParts to this submit: the walk + the source */
 	if (!pushed && sparseWindows(&sp, &sl)) {
 		wr_dev *sdev = NULL;
 		const float *staged = stagedSparse(_channels[0]->mixer, tunerBuffer, &sdev, sp, sl, sl - 1u);
 		if (g_times)
-			g_tacc[1] += nowUs() - tt0;             /* staging enqueued */
-		if (staged && sdev == _dev) {
-			/* on time, the staged block goes through in P parts all the same: a part's audio is put where the audio
-			 * filters' consumers will read it while the parts behind it compute (collectParts) */
-			const unsigned int parts = piecesFor(nframes);
-			wr_tuner_submit_count(_tuner, &_partSeq0);      /* part p's ring entry will be numbered _partSeq0 + p: the library's count */
-			for (unsigned int p = 0; p < parts; p++)
-				if (wr_tuner_submit(_tuner, staged + (size_t)2 * (nframes / parts) * p, nframes / parts, WR_DEVICE) != WR_OK) {
-					LOG_ERROR("wr_tuner_submit: %s\n", wr_last_error());
-					if (p)
-						drainRing();                /* the parts that did go out must not be taken for the next block's */
-					return false;
-				}
-			if (parts == 1)
-				return afterSubmit(false, nframes);
-			countTapFrames(nframes, parts);
-			++_lateSeq;
-			if (!_streaming)
-				wr_tuner_flush(_tuner);                     /* (a streaming launch's post stage starts by itself) */
-			traceAdd(_source, 'S');
-			if (g_times)
-				g_tacc[2] += nowUs() - tt0;         /* ... parts submitted and flushed */
-			return collectParts(parts);
+			_timeSums[1] += nowUs() - _submitStart;             /* staging enqueued */
+		/* on time, the staged block goes through in P parts all the same: a part's audio is put where the audio
+		 * filters' consumers will read it while the parts behind it compute (collectParts) */
+		if (staged && sdev == _dev)
+			sent = submitParts(parts, nframes, staged, tunerBuffer);
+	}
+	/* 3. submit and collect: the sparse-staged block above, else in parts staged one by one, else in one piece */
+	if (sent == NOT_IN_PARTS && parts > 1)
+		sent = submitParts(parts, nframes, NULL, tunerBuffer);
+	return sent == NOT_IN_PARTS ? submitOnePiece(tunerBuffer, nframes, pushed) : sent == SENT;
+}
+
+/* The block in `parts` equal parts, one submit each, and their audio collected.  `onDevice`: the block lies there already
+ * (sparse-staged, or a DeviceBlock source's), part p a stride behind part p - 1; NULL: it is in host memory and part p is
+ * staged just before it is submitted (stagePiece).  NOT_IN_PARTS: the block cannot be staged in parts and nothing has been
+ * submitted -- the caller takes the one-piece path. */
+TunerBatch::Sent TunerBatch::submitParts(unsigned int parts, unsigned int nframes, const float *onDevice, const vector<sample_t> &host)
+{
+	const unsigned int each = nframes / parts;
+	wr_tuner_submit_count(_tuner, &_partSeq0);      /* part p's ring entry will be numbered _partSeq0 + p: the library's count */
+	for (unsigned int p = 0; p < parts; p++) {
+		const float *part = onDevice ? onDevice + (size_t)2 * each * p : stagePiece(_source, _dev, host, parts, p);
+		if (!part)
+			return p ? FAILED : NOT_IN_PARTS;
+		if (wr_tuner_submit(_tuner, part, each, WR_DEVICE) != WR_OK) {
+			if (onDevice)
+				LOG_ERROR("wr_tuner_submit: %s\n", wr_last_error());
+			else
+				LOG_ERROR("wr_tuner_submit (part %u of %u): %s\n", p, parts, wr_last_error());
+			if (p)
+				drainRing();                /* the parts that did go out must not be taken for the next block's */
+			return FAILED;
 		}
 	}
-	unsigned int P = pushed ? 1u : piecesFor(nframes);
-	if (P > 1) {
-		wr_tuner_submit_count(_tuner, &_partSeq0);
-		for (unsigned int p = 0; p < P; p++) {
-			const float *part = stagePiece(_source, _dev, tunerBuffer, P, p);
-			if (!part) {
-				if (p == 0) {
-					P = 1;                      /* cannot be staged in parts: the one-piece path below */
-					break;
-				}
-				return false;
-			}
-			if (wr_tuner_submit(_tuner, part, nframes / P, WR_DEVICE) != WR_OK) {
-				LOG_ERROR("wr_tuner_submit (part %u of %u): %s\n", p, P, wr_last_error());
-				if (p)
-					drainRing();
-				return false;
-			}
-		}
-	}
-	if (P > 1) {
-		countTapFrames(nframes, P);
-		++_lateSeq;
-		wr_tuner_flush(_tuner);                 /* the last part's demodulator + audio filter: nothing rides behind it */
-		traceAdd(_source, 'S');
-		return collectParts(P);
-	}
-	/* cheapest way to get the block to the GPU: (1) a device copy some other consumer of the
-	 * source already made this block, (2) the source's raw bytes (2 per frame, converted in
-	 * the kernel's load stage), (3) stage the float block once for everybody */
+	if (parts == 1)
+		return afterSubmit(false, nframes) ? SENT : FAILED;
+	countTapFrames(nframes, parts);
+	++_lateSeq;
+	/* the last part's demodulator + audio filter: nothing rides behind it.  Only a streaming launch's post stage starts by
+	 * itself, and only a block that lies on the device is streamed: one out of host memory is always flushed */
+	if (!(onDevice && _streaming))
+		wr_tuner_flush(_tuner);
+	traceAdd(_source, 'S');
+	if (g_times && onDevice)
+		_timeSums[2] += nowUs() - _submitStart;     /* ... parts submitted and flushed */
+	return collectParts(parts) ? SENT : FAILED;
+}
+
+/* the block in one submit, by the cheapest way to get it to the GPU: (1) a device copy some other consumer of the
+ * source already made this block, (2) the source's raw bytes (2 per frame, converted in
+ * the kernel's load stage), (3) stage the float block once for everybody */
+bool TunerBatch::submitOnePiece(const vector<sample_t> &tunerBuffer, unsigned int nframes, bool pushed)
+{
 	wr_dev *sdev = NULL;
 	int rc;
-	const float *staged = _channels.empty() ? NULL : stagedBlock(_channels[0]->mixer, tunerBuffer, &sdev, true);
-	const RawU8Block *raw = dynamic_cast<const RawU8Block *>(_source);
-	size_t rawFrames = 0;
-	const uint8_t *bytes = (raw && !staged) ? raw->rawU8(&rawFrames) : NULL;
+	const float *staged = _channels.empty() ? NULL : stagedBlockIfPresent(_channels[0]->mixer, tunerBuffer, &sdev);
+	const uint8_t *bytes = staged ? NULL : rawBytesOf(_source, (size_t)2 * nframes);
 	if (staged && sdev == _dev) {
 		rc = wr_tuner_submit(_tuner, staged, nframes, WR_DEVICE);
-	} else if (bytes && rawFrames == nframes && envUnsigned("WEBRADIO_NO_U8_STAGING", 0)) {
+	} else if (bytes && envUnsigned("WEBRADIO_NO_U8_STAGING", 0)) {
+		/* (the other way round than in sourcestage.cxx, on purpose: with the switch UNSET the bytes are staged and converted
+		 * for every consumer, (3); with it set nothing stages them, and the tuner takes them from the host itself) */
 		rc = wr_tuner_submit_u8(_tuner, bytes, nframes, WR_HOST);
 	} else {
-		staged = _channels.empty() ? NULL : stagedBlock(_channels[0]->mixer, tunerBuffer, &sdev, false);
+		staged = _channels.empty() ? NULL : stagedBlock(_channels[0]->mixer, tunerBuffer, &sdev);
 		if (!(staged && sdev == _dev) && !_source->hostBlockValid()) {
 			LOG_ERROR("the source left its block on the device and the device copy is not there\n");
 			return false;
@@ -1202,41 +711,21 @@ bool TunerBatch::afterSubmit(bool pushed, unsigned int nframes)
 		_silence = _lateSeq <= _lateDepth;          /* (blocks submitted so far, this one included) */
 		_lateQueued = true;
 		_audioSlots = 0;
-		if (!_silence) {
-			const float *p = NULL;
-			size_t stride = 0, frames = 0;
-			unsigned int slots = 0;
-			unsigned long long seq = 0;
-			if (wr_tuner_audio_ring_acquire(_tuner, &p, &stride, &frames, &slots, &seq) == WR_OK) {
-				_ringHeld = true;
-				_audioPtr = p;
-				_audioStride = stride;
-				_audioFrames = frames;
-				_audioSlots = slots;
-			}
-			/* else: nothing queued -- receivers in several rate groups are not ringed (see the C ABI);
-			 * audio() then fetches per channel, which is this block's audio, on time */
-		}
+		if (!_silence)
+			(void)holdRingSlot();
+			/* (not held: nothing queued -- receivers in several rate groups are not ringed (see the C ABI);
+			 * audio() then fetches per channel, which is this block's audio, on time) */
 		_submitOk = true;
 		return true;
 	}
 	/* one transfer brings back the audio of every channel: through the tuner's pinned ring
 	 * (queued behind the kernels by the submit itself), read in place until the next block */
+	if (holdRingSlot()) {
+		_submitOk = true;
+		return true;
+	}
 	size_t stride = 0, frames = 0;
 	unsigned int slots = 0;
-	{
-		const float *p = NULL;
-		unsigned long long seq = 0;
-		if (wr_tuner_audio_ring_acquire(_tuner, &p, &stride, &frames, &slots, &seq) == WR_OK) {
-			_ringHeld = true;
-			_audioPtr = p;
-			_audioStride = stride;
-			_audioFrames = frames;
-			_audioSlots = slots;
-			_submitOk = true;
-			return true;
-		}
-	}
 	if (wr_tuner_fetch_audio_all(_tuner, NULL, 0, &stride, &frames, &slots) != WR_OK && frames * slots == 0) {
 		/* several rate groups: fall back to per-channel fetches in audio() */
 		_audioSlots = 0;
@@ -1257,19 +746,22 @@ bool TunerBatch::afterSubmit(bool pushed, unsigned int nframes)
 	return true;
 }
 
-/* lcm with a ceiling: anything this large stands for "do not split" */
-static unsigned long lcmCapped(unsigned long a, unsigned long b)
+/* take the oldest entry of the tuner's pinned audio ring (waiting for it to land) and remember where audio() reads it;
+ * false: there is none */
+bool TunerBatch::holdRingSlot()
 {
-	if (!a || !b)
-		return 0;
-	unsigned long x = a, y = b;
-	while (y) {
-		const unsigned long t = x % y;
-		x = y;
-		y = t;
-	}
-	const unsigned long long l = (unsigned long long)(a / x) * b;
-	return l > (1ull << 40) ? 0 : (unsigned long)l;
+	const float *p = NULL;
+	size_t stride = 0, frames = 0;
+	unsigned int slots = 0;
+	unsigned long long seq = 0;
+	if (wr_tuner_audio_ring_acquire(_tuner, &p, &stride, &frames, &slots, &seq) != WR_OK)
+		return false;
+	_ringHeld = true;
+	_audioPtr = p;
+	_audioStride = stride;
+	_audioFrames = frames;
+	_audioSlots = slots;
+	return true;
 }
 
 /* in how many equal parts a block of `nframes` goes through (submitOnce): as many as WEBRADIO_PIECES allows (default 2: each further part costs a launch and a transfer of
@@ -1298,10 +790,7 @@ unsigned int TunerBatch::piecesFor(unsigned int nframes)
 			return 1;
 	}
 	static const unsigned int minFrames = envUnsigned("WEBRADIO_PIECE_MIN_FRAMES", 500000);
-	for (unsigned int p = _pieces; p > 1; p--)
-		if (nframes % (p * q) == 0 && nframes / p >= minFrames)
-			return p;
-	return 1;
+	return partsOf(nframes, _pieces, q, minFrames);
 }
 
 /* the audio of the P parts just submitted, in order: each part's rows are copied out of the tuner's pinned ring as soon as
@@ -1328,7 +817,7 @@ bool TunerBatch::collectParts(unsigned int P)
 		}
 		const double tb = g_times ? nowUs() : 0.0;
 		if (g_times)
-			g_tacc[p ? 5 : 3] += tb - ta;           /* waiting for the part's audio */
+			_timeSums[p ? 5 : 3] += tb - ta;           /* waiting for the part's audio */
 		if (p == 0) {
 			total = frames * P;
 			for (size_t n = 0; n < _channels.size() && direct; n++)
@@ -1357,11 +846,11 @@ bool TunerBatch::collectParts(unsigned int P)
 		wr_tuner_audio_ring_release(_tuner);
 		off += frames;
 		if (g_times)
-			g_tacc[p ? 6 : 4] += nowUs() - tb;      /* copying it out */
+			_timeSums[p ? 6 : 4] += nowUs() - tb;      /* copying it out */
 	}
 	if (g_times) {
-		g_tlast = nowUs();
-		++g_tn;
+		_lastCollected = nowUs();
+		++_timedBlocks;
 	}
 	_ringHeld = false;
 	_audioFrames = total;

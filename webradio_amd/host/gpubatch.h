@@ -11,8 +11,8 @@
  *     (DownConverter -> LowPass -> Demodulator -> LowPass), the four blocks are enrolled
  *     as one CHANNEL of the source's TunerBatch (a wr_tuner on one GPU); so is the same chain
  *     with a second LowPass in front of the demodulator (narrow channels off a fast stream);
- *   - the first enrolled DownConverter::process() of a source block ("epoch") uploads the
- *     tuner buffer once and submits every channel; later process() calls of enrolled
+ *   - the first enrolled DownConverter::process() of a source block ("epoch") has the tuner
+ *     buffer brought to the GPU once (sourcestage.h) and submits every channel; later process() calls of enrolled
  *     blocks in the same epoch are no-ops, except the audio LowPass, which copies its
  *     channel's audio out of the batch's single device-to-host transfer;
  *   - SpectrumSinks on the last channel filter of such a chain (a panadapter per listener) do not end the fusion:
@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "dspblock.h"
+#include "sourcestage.h"
 #include "webradio_amd.h"
 
 class DownConverter;
@@ -41,22 +42,8 @@ class SpectrumSink;
 
 namespace wrhost {
 
-/* process-wide device contexts, one per GPU, opened on first use */
-wr_dev *device(int index);
-int deviceCount();
-/* the device a block should use.  Every block below one DspSource shares that source's GPU:
- * the n-th source of the process that asks takes GPU n mod count (tuners shard one per GPU),
- * unless WEBRADIO_DEVICE pins all of them.  Blocks not below a source use WEBRADIO_DEVICE / 0. */
-wr_dev *deviceFor(const DspBlock *block);
-/* Device copy of the source's current block, uploaded once per source block and shared by
- * every GPU consumer of that source (the SpectrumSink and the tuner batch would otherwise
- * each push the same 32 MB over PCIe).  Returns NULL if `host` is not that source's current
- * output vector or the upload failed. */
-const float *stagedBlock(const DspBlock *consumer, const vector<sample_t> &host, wr_dev **dev_out,
-                         bool only_if_present = false);
-/* false while the root source of `block` left its host vector unfilled for the current block (a byte-format
- * source all of whose consumers read on the device): a device path that fails must then fail loudly */
-bool hostBlockValid(const DspBlock *block);
+/* ---- questions to the tuner batch of a block's root source ---- */
+
 /* r06: did the tuner batch of `block`'s root source stream (a DeviceBlock source: wr_tuner_set_streaming)?  `live`: a launch is
  * open right now; `launches` / `blocks`: opened / taken so far.  false: no batch */
 bool streamInfo(const DspBlock *block, bool *live, unsigned long long *launches, unsigned long long *blocks);
@@ -69,32 +56,6 @@ unsigned long long chanLevelCalls(const DspBlock *block);
  * come first on the device's stream and the audio does not wait behind the spectrum's copy and transform (the batch
  * submits once per block whoever asks first).  No batch, or not the source's current block: nothing happens. */
 void submitBatchFirst(const DspBlock *consumer, const vector<sample_t> &host);
-/* For a consumer that reads only the END of the source's block (the SpectrumSink: the most recent complete frame and what
- * follows it): the block's device address with at least its last `tail_frames` frames staged -- the whole staged block
- * where somebody staged it, else just that tail, brought over by the sparse staging kernel (a block whose receivers all
- * read it through sparse windows never crosses PCIe whole).  NULL: not fed straight from a source, or it cannot be done
- * (the caller falls back to stagedBlock). */
-const float *stagedTail(const DspBlock *consumer, const vector<sample_t> &host, wr_dev **dev_out, size_t tail_frames);
-
-
-/* WEBRADIO_TRACE=1: what the tuner batches did, in order -- 'S' a block submitted (enqueued, nothing
- * waited for), 'A' audio taken from the pinned ring that was already there, 'W' audio that had to
- * be waited for.  (source, kind) pairs; tests read it to see that the front ends of a Radio have
- * their blocks in flight at the same time. */
-struct TraceEvent { const void *source; char kind; };
-const std::vector<TraceEvent> &trace();
-void traceClear();
-
-/* a resizable device buffer */
-struct DevBuf {
-	DevBuf() : dev(NULL), ptr(NULL), bytes(0) {}
-	~DevBuf() { release(); }
-	bool reserve(wr_dev *d, size_t nbytes);
-	void release();
-	wr_dev *dev;
-	void *ptr;
-	size_t bytes;
-};
 
 class TunerBatch;
 
@@ -122,9 +83,7 @@ public:
 	static Channel *enrol(DownConverter *mixer);
 	static void withdraw(Channel *ch);
 	static void unfuseChainOf(DspBlock *block);
-	/* the root source's batch device, or NULL if the block is not below a batched source */
-	static wr_dev *batchDeviceOf(const DspBlock *block);
-	static DspSource *rootSource(const DspBlock *block);
+	/* the source is going (sourcestage.cxx: releaseSource): its batch and the batch's channels with it */
 	static void destroyFor(DspSource *src);
 
 	/* called from DownConverter::process of an enrolled block */
@@ -158,11 +117,14 @@ public:
 private:
 	TunerBatch(DspSource *source, wr_dev *dev);
 	~TunerBatch();
-	bool ensureTuner(unsigned int nframes);
 	bool pushParams(Channel *ch);
 	unsigned int piecesFor(unsigned int nframes);
 	bool sparseWindows(unsigned int *period, unsigned int *length);
+	enum Sent { SENT, FAILED, NOT_IN_PARTS };
+	Sent submitParts(unsigned int parts, unsigned int nframes, const float *onDevice, const vector<sample_t> &host);
+	bool submitOnePiece(const vector<sample_t> &tunerBuffer, unsigned int nframes, bool pushed);
 	bool afterSubmit(bool pushed, unsigned int nframes);
+	bool holdRingSlot();
 	bool collectParts(unsigned int parts);
 	void drainRing();
 	void countTapFrames(unsigned int nframes, unsigned int parts);
@@ -212,6 +174,11 @@ private:
 	unsigned int _lvSlots;
 	unsigned long long _lvSeq;        /* the block (_lateSeq) they belong to; 0: none */
 	unsigned long long _lvCalls;      /* wr_tuner_chan_levels calls made */
+	/* WEBRADIO_TIMES=1 (measurement only): microseconds summed over `_timedBlocks` on-time blocks that went through in parts,
+	 * by where they went (the destructor's line names the fields); `_submitStart`: when this block's submit began,
+	 * `_lastCollected`: when the last block's parts had been collected */
+	double _timeSums[7], _submitStart, _lastCollected;
+	unsigned long _timedBlocks;
 };
 
 } // namespace wrhost

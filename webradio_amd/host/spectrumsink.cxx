@@ -89,7 +89,7 @@ bool SpectrumSink::process(const vector<sample_t> &inBuffer, vector<sample_t> &o
 	/* two channels: IQ, as upstream assumes (spectrumsink.cxx:93) */
 	if (inBuffer.empty() && wrhost::TunerBatch::tapped(upstream()))
 		return true;                    /* on a channel filter inside the tuner batch: no samples, the batch counts the frames */
-	if (upstream() != wrhost::TunerBatch::rootSource(this)) {
+	if (upstream() != wrhost::rootSource(this)) {
 		/* behind a block that runs on its own (a channel filter outside the batch): its host output, nothing staged --
 		 * and what the SOURCE did with its host vector is no concern of this sink's */
 		if (wr_spectrum_push(_spec, inBuffer.data(), inBuffer.size() / 2, WR_HOST) != WR_OK) {
