@@ -1,8 +1,8 @@
 /*
  * cpu_host_checks.cxx -- host-only logic of the runtime that needs no GPU: FileTuner
  * (read, (u8-128)/128 conversion, loop, end of file, raw byte access) driven through
- * DspSource::run() into a capture sink; the part arithmetic of the tuner batch.  Built from
- * dspblock.cxx + filetuner.cxx only.
+ * DspSource::run() into a capture sink; the part arithmetic of the tuner batch; the launch plans of the
+ * tuner's kernels.  Built from dspblock.cxx + filetuner.cxx and two headers only.
  */
 #include <string.h>
 
@@ -10,6 +10,7 @@
 
 #include "blockparts.h"
 #include "filetuner.h"
+#include "wr_plan.h"
 
 namespace {
 class Capture : public DspBlock {
@@ -105,6 +106,147 @@ extern "C" unsigned int wr_block_parts(unsigned int nframes, unsigned int pieces
 extern "C" unsigned long wr_lcm_capped(unsigned long a, unsigned long b)
 {
 	return wrhost::lcmCapped(a, b);
+}
+
+/* ---- the launch geometry of the tuner's kernels (csrc/wr_plan.h): the plans as flat arrays of unsigned long long, in the
+ *      order of the comment at each ---- */
+extern "C" unsigned int wr_plan_post_tk(void)
+{
+	return POST_TK;
+}
+
+/* out[5]: gmap[0], gmap[1], ngroups, rest, kmax over `nsets`; order[ngroups]: the map read back, entry by entry */
+extern "C" void wr_plan_group_map(unsigned int slots_used, unsigned long long gsel, const unsigned char *nsets,
+                                  unsigned long long *out, unsigned int *order)
+{
+	const WrGroupMap m = wrp_group_map(slots_used, gsel);
+	out[0] = m.gmap[0];
+	out[1] = m.gmap[1];
+	out[2] = m.ngroups;
+	out[3] = m.rest;
+	out[4] = wrp_kmax(m, nsets);
+	for (unsigned int i = 0; i < m.ngroups; i++)
+		order[i] = wrp_group_at(m, i);
+}
+
+extern "C" unsigned int wr_plan_kslow(unsigned int d1, unsigned long k1)
+{
+	return wrp_kslow(d1, k1);
+}
+
+extern "C" int wr_plan_post_d2_supported(unsigned int d2)
+{
+	return wrp_post_d2_supported(d2) ? 1 : 0;
+}
+
+extern "C" unsigned long wr_plan_post_lds_bytes(unsigned int d2, unsigned int nseg)
+{
+	return post_lds_bytes(d2, nseg);
+}
+
+extern "C" unsigned long wr_plan_stream_lds_bytes(unsigned int d2, unsigned int nset, unsigned int nseg)
+{
+	return stream_lds_bytes(d2, nset, nseg);
+}
+
+extern "C" int wr_plan_stream_nseg_supported(unsigned int d2, unsigned int nseg)
+{
+	return stream_nseg_supported(d2, nseg) ? 1 : 0;
+}
+
+/* out[4]: ok, ng, ts, lds */
+extern "C" void wr_plan_stream(unsigned int d2, unsigned int groups, unsigned int kmax, int one_filter, unsigned int nseg,
+                               unsigned long long *out)
+{
+	const WrStreamPlan p = wrp_stream_plan(d2, groups, kmax, one_filter != 0, nseg);
+	out[0] = p.ok;
+	out[1] = p.ng;
+	out[2] = p.ts;
+	out[3] = p.lds;
+}
+
+/* rule 0: riding in a DDC launch, 1: on its own (`arg` = nseg); out[2]: run, ntiles */
+extern "C" void wr_plan_post_tiling(int rule, unsigned int tiles, unsigned int groups, unsigned int arg, unsigned int *out)
+{
+	const WrPostTiling t = rule ? wrp_post_tiling_alone(tiles, groups, arg) : wrp_post_tiling_riding(tiles, groups);
+	out[0] = t.run;
+	out[1] = t.ntiles;
+}
+
+/* a block of k2 audio frames; out[8]: tiles, min_run, run, ntiles, drain_run, drain_ntiles, long_runs, widened */
+extern "C" void wr_plan_stream_tiling(unsigned long k2, unsigned int groups, unsigned int n_post, unsigned int *out)
+{
+	const unsigned int tiles = wrp_post_tiles(k2);
+	const WrStreamTiling t = wrp_post_tiling_stream(tiles, groups, n_post);
+	out[0] = tiles;
+	out[1] = t.min_run;
+	out[2] = t.run;
+	out[3] = t.ntiles;
+	out[4] = t.drain_run;
+	out[5] = t.drain_ntiles;
+	out[6] = t.long_runs;
+	out[7] = t.widened;
+}
+
+/* out[2]: n_ddc, n_post */
+extern "C" void wr_plan_stream_roles(int per_cu, int num_cus, unsigned int *out)
+{
+	const WrStreamRoles r = wrp_stream_roles(per_cu, num_cus);
+	out[0] = r.n_ddc;
+	out[1] = r.n_post;
+}
+
+/* out[12]: ngroups, rest, ng, waves, kmax, lds, wgs_per_cu, post_wgs, kslow, n_bnd, units, wgs */
+extern "C" void wr_plan_ddc(int nco, int utaps, unsigned int pd2, unsigned int slots_used, unsigned long long gsel,
+                            const unsigned char *nsets, int one_filter, unsigned long k1, unsigned int d1, int num_cus,
+                            unsigned long min_passes, unsigned int post_ntiles, unsigned int post_groups, unsigned long long *out)
+{
+	const WrDdcPlan p = wrp_ddc_plan(nco, utaps != 0, pd2, slots_used, gsel, nsets, one_filter != 0, k1, d1, num_cus, min_passes,
+	                                 post_ntiles, post_groups);
+	out[0] = p.map.ngroups;
+	out[1] = p.map.rest;
+	out[2] = p.ng;
+	out[3] = p.waves;
+	out[4] = p.kmax;
+	out[5] = p.lds;
+	out[6] = p.wgs_per_cu;
+	out[7] = p.post_wgs;
+	out[8] = p.kslow;
+	out[9] = p.n_bnd;
+	out[10] = p.units;
+	out[11] = p.wgs;
+}
+
+/* out[8]: rot, two, wgs_r, post_wgs, roll_wgs, lds, wgs, rwgs */
+extern "C" void wr_plan_long(int rotate, int one_filter, unsigned long k1, unsigned int groups, unsigned int len, unsigned int slots,
+                             int num_cus, unsigned int ride_d2, unsigned int post_ntiles, unsigned int post_groups,
+                             unsigned long long *out)
+{
+	const WrLongPlan p = wrp_long_plan(rotate != 0, one_filter != 0, k1, groups, len, slots, num_cus, ride_d2, post_ntiles, post_groups);
+	out[0] = p.rot;
+	out[1] = p.two;
+	out[2] = p.wgs_r;
+	out[3] = p.post_wgs;
+	out[4] = p.roll_wgs;
+	out[5] = p.lds;
+	out[6] = p.wgs;
+	out[7] = p.rwgs;
+}
+
+/* out[5]: tk, need, lds, lds_max, grid_x */
+extern "C" void wr_plan_audio(unsigned long k2, unsigned int d2, unsigned int len, unsigned long long *out)
+{
+	const WrAudioPlan p = wrp_audio_plan(k2, d2, len);
+	out[0] = p.tk;
+	out[1] = p.need;
+	out[2] = p.lds;
+	out[3] = p.lds_max;
+	out[4] = p.grid_x;
+}
+
+extern "C" unsigned int wr_plan_grid_for(unsigned long n, unsigned int block, unsigned int cap)
+{
+	return grid_for(n, block, cap);
 }
 
 /* ---- device hand-over bookkeeping of DspBlock (no GPU involved: pointers are just tokens) ---- */

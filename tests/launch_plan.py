@@ -1,0 +1,117 @@
+"""The launch plans of the tuner's kernels (webradio_amd/csrc/wr_plan.h) through tests/cxx/libwr_cpu_host_checks.so: plain
+arithmetic, no GPU.  What tests/test_launch_plan.py holds to hand-worked figures, and where a GPU test that has to know which
+branch of a rule a case reaches asks the rule itself."""
+import ctypes as C
+import os
+import subprocess
+from collections import namedtuple
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CXXT = os.path.join(ROOT, "tests", "cxx")
+
+WR_NCO_SPLIT, WR_NCO_EXACT, WR_NCO_ROTATE = 0, 1, 2     # include/webradio_amd.h
+
+GroupMap = namedtuple("GroupMap", "gmap0 gmap1 ngroups rest kmax order")
+StreamPlan = namedtuple("StreamPlan", "ok ng ts lds")
+StreamTiling = namedtuple("StreamTiling", "tiles min_run run ntiles drain_run drain_ntiles long_runs widened")
+DdcPlan = namedtuple("DdcPlan", "ngroups rest ng waves kmax lds wgs_per_cu post_wgs kslow n_bnd units wgs")
+LongPlan = namedtuple("LongPlan", "rot two wgs_r post_wgs roll_wgs lds wgs rwgs")
+AudioPlan = namedtuple("AudioPlan", "tk need lds lds_max grid_x")
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        path = os.path.join(CXXT, "libwr_cpu_host_checks.so")
+        if not os.path.exists(path):
+            subprocess.check_call(["make", "-s", "-C", CXXT, "libwr_cpu_host_checks.so"])
+        L = C.CDLL(path)
+        u, ul, ull, i = C.c_uint, C.c_ulong, C.c_ulonglong, C.c_int
+        pu, pull, pb = C.POINTER(u), C.POINTER(ull), C.POINTER(C.c_ubyte)
+        for name, res, args in [
+            ("wr_plan_post_tk", u, []),
+            ("wr_plan_group_map", None, [u, ull, pb, pull, pu]),
+            ("wr_plan_kslow", u, [u, ul]),
+            ("wr_plan_post_d2_supported", i, [u]),
+            ("wr_plan_post_lds_bytes", ul, [u, u]),
+            ("wr_plan_stream_lds_bytes", ul, [u, u, u]),
+            ("wr_plan_stream_nseg_supported", i, [u, u]),
+            ("wr_plan_stream", None, [u, u, u, i, u, pull]),
+            ("wr_plan_post_tiling", None, [i, u, u, u, pu]),
+            ("wr_plan_stream_tiling", None, [ul, u, u, pu]),
+            ("wr_plan_stream_roles", None, [i, i, pu]),
+            ("wr_plan_ddc", None, [i, i, u, u, ull, pb, i, ul, u, i, ul, u, u, pull]),
+            ("wr_plan_long", None, [i, i, ul, u, u, u, i, u, u, u, pull]),
+            ("wr_plan_audio", None, [ul, u, u, pull]),
+            ("wr_plan_grid_for", u, [ul, u, u]),
+        ]:
+            f = getattr(L, name)
+            f.restype, f.argtypes = res, args
+        _lib = L
+    return _lib
+
+
+def _nsets(nsets):
+    return (C.c_ubyte * 64)(*(list(nsets) + [1] * (64 - len(nsets))))
+
+
+def post_tk():
+    return lib().wr_plan_post_tk()
+
+
+def group_map(groups, gsel=0, nsets=()):
+    out, order = (C.c_ulonglong * 5)(), (C.c_uint * 16)()
+    lib().wr_plan_group_map(64 * groups, gsel, _nsets(nsets), out, order)
+    return GroupMap(out[0], out[1], out[2], out[3], out[4], list(order[:out[2]]))
+
+
+def stream_plan(d2, groups, kmax, one_filter, nseg):
+    out = (C.c_ulonglong * 4)()
+    lib().wr_plan_stream(d2, groups, kmax, int(one_filter), nseg, out)
+    return StreamPlan(bool(out[0]), *out[1:])
+
+
+def post_tiling_riding(tiles, groups):
+    out = (C.c_uint * 2)()
+    lib().wr_plan_post_tiling(0, tiles, groups, 0, out)
+    return tuple(out)
+
+
+def post_tiling_alone(tiles, groups, nseg=1):
+    out = (C.c_uint * 2)()
+    lib().wr_plan_post_tiling(1, tiles, groups, nseg, out)
+    return tuple(out)
+
+
+def stream_tiling(k2, groups, n_post):
+    out = (C.c_uint * 8)()
+    lib().wr_plan_stream_tiling(k2, groups, n_post, out)
+    return StreamTiling(*out[:6], bool(out[6]), out[7])
+
+
+def stream_roles(per_cu, num_cus):
+    out = (C.c_uint * 2)()
+    lib().wr_plan_stream_roles(per_cu, num_cus, out)
+    return tuple(out)
+
+
+def ddc_plan(nco, utaps, pd2, groups, k1, d1, num_cus, one_filter=True, min_passes=4, gsel=0, nsets=(), post_ntiles=0,
+             post_groups=0):
+    out = (C.c_ulonglong * 12)()
+    lib().wr_plan_ddc(nco, int(utaps), pd2, 64 * groups, gsel, _nsets(nsets), int(one_filter), k1, d1, num_cus, min_passes,
+                      post_ntiles, post_groups, out)
+    return DdcPlan(*out)
+
+
+def long_plan(rotate, one_filter, k1, groups, length, slots, num_cus, ride_d2=0, post_ntiles=0, post_groups=0):
+    out = (C.c_ulonglong * 8)()
+    lib().wr_plan_long(int(rotate), int(one_filter), k1, groups, length, slots, num_cus, ride_d2, post_ntiles, post_groups, out)
+    return LongPlan(bool(out[0]), bool(out[1]), *out[2:])
+
+
+def audio_plan(k2, d2, length):
+    out = (C.c_ulonglong * 5)()
+    lib().wr_plan_audio(k2, d2, length, out)
+    return AudioPlan(*out)

@@ -11,6 +11,7 @@ import time
 import numpy as np
 import pytest
 
+import launch_plan
 from webradio_amd import capi, synth
 from webradio_amd.device import Tuner
 
@@ -702,7 +703,6 @@ def test_a_front_ends_spectrum_sink_beside_the_stream(dev, nfft, hop):
 
 IQ_ATOL, AUDIO_ATOL = 1e-6, 1e-5              # test_c2_full_size_stream_against_the_oracle's
 MODES = (capi.WR_FM, capi.WR_USB, capi.WR_AM, capi.WR_LSB)     # receiver c demodulates MODES[c % 4]
-POST_TK = 16                                  # audio frames per post-stage tile (wr_kernels.hip)
 
 
 def _lane_groups(nch):
@@ -714,31 +714,18 @@ def _ng(groups):
     return 1 if groups & 1 else 2
 
 
-def _post_run(tiles, groups, max_post):
-    """stream_post_run (wr_stream_kernel.inc)"""
-    run = 1
-    while run < tiles and -(-tiles // run) * groups > max_post:
-        run += 1
-    return run
-
-
 def _post_tiling(k2, groups, n_post):
-    """wrk_tuner_stream's cut of one block's post stage, restated: (min_run, run, drain_run, how run was chosen)"""
-    tiles = -(-k2 // POST_TK)
-    min_run = run = _post_run(tiles, groups, n_post)
-    how = "min"
-    if min_run >= 2 and n_post >= 8:
-        run, how = _post_run(tiles, groups, n_post // 2), "long"
-    while run < 4 and run < tiles and n_post // 4 < -(-tiles // run) * groups <= n_post // 2:
-        run += 1
-        how += "+loop"
-    return min_run, run, min(min_run, run), how
+    """wrk_tuner_stream's cut of one block's post stage, from the rule itself (wr_plan.h: wrp_post_tiling_stream, which says
+    which of its branches it took): (min_run, run, drain_run, how run was chosen)"""
+    t = launch_plan.stream_tiling(k2, groups, n_post)
+    return t.min_run, t.run, t.drain_run, ("long" if t.long_runs else "min") + "+loop" * t.widened
 
 
 def _n_post():
-    """post workgroups of a streaming launch: one slot per CU, less four (wrk_stream_geometry)"""
+    """post workgroups of a streaming launch on this device (wr_plan.h: wrp_stream_roles: one slot per CU, less four, whether
+    the launch has two or three workgroups per CU -- two, the fewest a launch exists with, is what is asked here)"""
     import torch
-    return torch.cuda.get_device_properties(0).multi_processor_count - 4
+    return launch_plan.stream_roles(2, torch.cuda.get_device_properties(0).multi_processor_count)[1]
 
 
 def _passbands(fs, crate, arate):

@@ -16,10 +16,11 @@ as the stream tests have it."""
 import numpy as np
 import pytest
 
+import launch_plan
 from webradio_amd import capi, synth
 from webradio_amd.device import Tuner
 from test_gpu_f4 import OracleChain
-from test_gpu_stream import (AUDIO_ATOL, DECIMATION_RATES, IQ_ATOL, MODES, POST_TK, _carriers, _drain, _lane_groups,
+from test_gpu_stream import (AUDIO_ATOL, DECIMATION_RATES, IQ_ATOL, MODES, _carriers, _drain, _lane_groups,
                              _passbands, _probes, _same_bits, _spread_ifs)
 
 pytestmark = pytest.mark.gpu
@@ -198,9 +199,9 @@ def test_long_audio_filter_block_edges(dev, oracle, case):
     if "below" in case or "one-short" in case:
         assert k1 < l2 <= k1 + pd2
     if "ragged" in case:
-        assert k2 > POST_TK and k2 % POST_TK
+        assert k2 > launch_plan.post_tk() and k2 % launch_plan.post_tk()
     if "one-tile" in case:
-        assert k2 == POST_TK
+        assert k2 == launch_plan.post_tk()
     nblk = 4
     _stream_vs_blocks(dev, oracle, l2, fs, crate, crate // pd2, 70, k1 * (fs // crate), nblk,
                       (True, 1, nblk) if streams else (False, 0, 0))

@@ -1,0 +1,269 @@
+"""The launch geometry of the tuner's kernels (webradio_amd/csrc/wr_plan.h): the arithmetic alone, no GPU.  Every expected
+figure is worked by hand from the rule as the launch functions had it before the plans were split out of them (the working
+stands beside each), never taken from a run of the code under test."""
+import pytest
+
+import launch_plan as lp
+from launch_plan import WR_NCO_EXACT, WR_NCO_ROTATE, WR_NCO_SPLIT
+
+D2S = [1, 2, 3, 4, 5, 6, 8, 10]             # the audio decimations the post stage is built for
+CU_LDS = 160 * 1024
+
+
+def test_supported_audio_decimations():
+    assert [d for d in range(0, 40) if lp.lib().wr_plan_post_d2_supported(d)] == D2S
+    assert lp.post_tk() == 16
+
+
+# ---- the streaming launch's post tiling --------------------------------------------------------------------------------
+# tiles = ceil(k2 / 16); tasks(run) = ceil(tiles / run) * groups.
+#   min_run : the least run with tasks <= n_post
+#   run     : min_run -- or, if min_run >= 2 and n_post >= 8, the least run with tasks <= n_post / 2 ("long") --
+#             then + 1 while run < 4, run < tiles and n_post / 4 < tasks(run) <= n_post / 2 ("loop")
+#   drain   : min(min_run, run)
+# n_post = 252: n_post / 2 = 126, n_post / 4 = 63.
+@pytest.mark.parametrize("k2,groups,n_post,want", [
+    # run-1-ragged: 4 tiles x 1 group = 4 tasks <= 252; 4 is not above 63: no loop
+    (60, 1, 252, dict(tiles=4, min_run=1, run=1, ntiles=4, drain_run=1, drain_ntiles=4, long_runs=False, widened=0)),
+    # run-2: 50 tiles x 2 = 100 <= 252; 63 < 100 <= 126 -> run 2: 25 x 2 = 50, not above 63
+    (790, 2, 252, dict(tiles=50, min_run=1, run=2, ntiles=25, drain_run=1, drain_ntiles=50, long_runs=False, widened=1)),
+    # run-3: 25 tiles x 5 = 125 <= 252; 63 < 125 <= 126 -> run 2: 13 x 5 = 65, still -> run 3: 9 x 5 = 45
+    (393, 5, 252, dict(tiles=25, min_run=1, run=3, ntiles=9, drain_run=1, drain_ntiles=25, long_runs=False, widened=2)),
+    # run-4: 300 tiles x 1: 300 > 252, 150 <= 252 -> min_run 2; long: 150 > 126, 100 <= 126 -> 3; 63 < 100 <= 126 -> 4 (the cap)
+    (4790, 1, 252, dict(tiles=300, min_run=2, run=4, ntiles=75, drain_run=2, drain_ntiles=150, long_runs=True, widened=1)),
+    # long-runs: 225 tiles x 2: 450, 226 <= 252 -> min_run 2; long: 226, 150 > 126, 57 x 2 = 114 <= 126 -> 4; no loop at 4
+    (3595, 2, 252, dict(tiles=225, min_run=2, run=4, ntiles=57, drain_run=2, drain_ntiles=113, long_runs=True, widened=0)),
+    # one tile: run < tiles never holds
+    (9, 3, 252, dict(tiles=1, min_run=1, run=1, ntiles=1, drain_run=1, drain_ntiles=1, long_runs=False, widened=0)),
+    (16, 16, 12, dict(tiles=1, min_run=1, run=1, ntiles=1, drain_run=1, drain_ntiles=1, long_runs=False, widened=0)),
+    # n_post < 8: the long-run rule must not apply.  20 tiles, n_post = 6: 20, 10, 7 > 6, 5 <= 6 -> min_run 4 (tasks for
+    # n_post / 2 = 3 would have been run 7); 10 tiles, n_post = 7: 10 > 7, 5 <= 7 -> 2 (for 3: run 4); 5 is not <= 7 / 2
+    (320, 1, 6, dict(tiles=20, min_run=4, run=4, ntiles=5, drain_run=4, drain_ntiles=5, long_runs=False, widened=0)),
+    (160, 1, 7, dict(tiles=10, min_run=2, run=2, ntiles=5, drain_run=2, drain_ntiles=5, long_runs=False, widened=0)),
+])
+def test_stream_post_tiling(k2, groups, n_post, want):
+    assert lp.stream_tiling(k2, groups, n_post)._asdict() == want
+
+
+# ---- the streaming launch's roles: per_cu capped at 3, fewer than 2 none; n_ddc = (per_cu - 1) * CUs, n_post = CUs - 4 ----
+@pytest.mark.parametrize("per_cu,num_cus,want", [
+    (3, 256, (512, 252)),
+    (5, 256, (512, 252)),                   # the cap at three
+    (2, 256, (256, 252)),
+    (1, 256, (0, 0)),
+    (3, 4, (0, 0)), (3, 1, (0, 0)), (3, 0, (0, 0)),     # no post workgroup to give: no launch, and no wrap
+    (3, 5, (10, 1)),
+])
+def test_stream_roles(per_cu, num_cus, want):
+    assert lp.stream_roles(per_cu, num_cus) == want
+
+
+def test_lds_sizes():
+    L = lp.lib()
+    # post stage at D2 = 5: ((15 * 5 + 64 nseg) rows * 64 + the tile 16 * 65 + 64 modes) floats
+    #   nseg 1: (139 * 64 + 1040 + 64) * 4 = 10 000 * 4 = 40 000; the streaming launch adds 16 words: 40 064
+    #   nseg 2: (203 * 64 + 1104) * 4 + 64 = 56 448;  nseg 4: (331 * 64 + 1104) * 4 + 64 = 89 216
+    assert L.wr_plan_post_lds_bytes(5, 1) == 40_000
+    assert [L.wr_plan_stream_lds_bytes(5, 1, nseg) for nseg in (1, 2, 4)] == [40_064, 56_448, 89_216]
+    # the DDC's side wins only where the post stage is small: D2 = 1, four window copies: 8 * 2 * 512 * 4 + 2 * 256 * 8 = 36 864
+    # against (15 + 64) * 64 + 1104 = 6 160 floats = 24 640 + 64
+    assert L.wr_plan_stream_lds_bytes(1, 4, 1) == 36_864
+    assert not L.wr_plan_stream_nseg_supported(4, 4) and L.wr_plan_stream_nseg_supported(3, 4)
+    assert L.wr_plan_stream_nseg_supported(10, 1) and L.wr_plan_stream_nseg_supported(10, 2)
+    assert not L.wr_plan_stream_nseg_supported(1, 3)
+
+
+def test_stream_plan():
+    # one filter, an even number of lane groups: NG = 2; several filters in a lane group: TS = 4 and kmax window copies
+    assert lp.stream_plan(5, 4, 1, True, 1) == (True, 2, 1, 40_064)
+    assert lp.stream_plan(5, 3, 1, True, 1) == (True, 1, 1, 40_064)
+    assert lp.stream_plan(5, 4, 1, False, 2) == (True, 1, 1, 56_448)
+    assert lp.stream_plan(1, 4, 3, False, 1) == (True, 1, 4, 8 * 2 * 512 * 3 + 4096)
+    for d2, groups, kmax, nseg in [(7, 4, 1, 1), (5, 0, 1, 1), (5, 17, 1, 1), (5, 4, 0, 1), (5, 4, 5, 1), (4, 4, 1, 4), (5, 4, 1, 3)]:
+        assert not lp.stream_plan(d2, groups, kmax, True, nseg).ok, (d2, groups, kmax, nseg)
+
+
+# ---- the group map: entry i (eight bits each, sixteen entries) = the i-th selected lane group ----
+def test_group_map():
+    assert lp.group_map(4) == (0x03020100, 0, 4, 0, 1, [0, 1, 2, 3])
+    assert lp.group_map(4, gsel=0b1010) == (0x0301, 0, 2, 0, 1, [1, 3])
+    m = lp.group_map(17)
+    assert (m.gmap0, m.gmap1, m.ngroups, m.rest) == (0x0706050403020100, 0x0F0E0D0C0B0A0908, 16, 1 << 16)
+    assert m.order == list(range(16))
+    m = lp.group_map(64)
+    assert (m.gmap0, m.gmap1, m.ngroups, m.rest) == (0x0706050403020100, 0x0F0E0D0C0B0A0908, 16, 0xFFFF_FFFF_FFFF_0000)
+    # the groups a launch leaves for the next come out of `rest` in ascending order too
+    m = lp.group_map(20, gsel=m.rest)
+    assert (m.ngroups, m.rest, m.order) == (4, 0, [16, 17, 18, 19])
+    assert lp.group_map(0).ngroups == 0 and lp.group_map(3, gsel=1 << 5).ngroups == 0
+    # kmax: over the mapped groups only
+    nsets = [1, 3, 2, 4]
+    assert lp.group_map(4, nsets=nsets).kmax == 4
+    assert lp.group_map(4, gsel=0b0101, nsets=nsets).kmax == 2
+    assert lp.group_map(4, gsel=0b0011, nsets=nsets).kmax == 3
+    assert lp.group_map(18, gsel=0, nsets=[1] * 16 + [4, 4]).kmax == 1       # groups 16, 17 are not in this launch
+
+
+@pytest.mark.parametrize("d1,k1,want", [(400, 10_000, 1), (1, 65, 63), (3, 10, 10), (64, 0, 0), (63, 5, 1), (62, 5, 2), (0, 0, 0)])
+def test_kslow(d1, k1, want):
+    """ceil(63 / d1), k1 at most; a block without an output frame has none (the launch never worked the quotient out for it)"""
+    assert lp.lib().wr_plan_kslow(d1, k1) == want
+
+
+def test_post_tilings_of_a_block():
+    # riding: tiles x groups >= 1536: runs of 4, >= 384: 2, else 1
+    assert lp.post_tiling_riding(125, 4) == (2, 63)          # C2: 500
+    assert lp.post_tiling_riding(125, 3) == (1, 125)         # 375
+    assert lp.post_tiling_riding(96, 16) == (4, 24)          # 1536
+    assert lp.post_tiling_riding(383, 1) == (1, 383) and lp.post_tiling_riding(384, 1) == (2, 192)
+    # on its own: one tile per workgroup up to 4096 tiles x groups; 256 taps: runs of 2 from 384 on
+    assert lp.post_tiling_alone(125, 4) == (1, 125)
+    assert lp.post_tiling_alone(500, 8) == (1, 500) and lp.post_tiling_alone(513, 8) == (2, 257)     # 4000, 4104
+    assert lp.post_tiling_alone(125, 4, nseg=4) == (2, 63) and lp.post_tiling_alone(125, 4, nseg=2) == (1, 125)
+    assert lp.post_tiling_alone(95, 4, nseg=4) == (1, 95)    # 380
+
+
+# ---- the per-block DDC --------------------------------------------------------------------------------------------------
+def _headline(**kw):
+    """ROTATE, folded taps, the post stage (D2 = 5, k2 = 2 000: 125 tiles) riding, 256 channels on one filter, 256 CUs"""
+    groups = kw.pop("groups", 4)
+    run, ntiles = lp.post_tiling_riding(125, groups)
+    a = dict(nco=WR_NCO_ROTATE, utaps=True, pd2=5, groups=groups, k1=10_000, d1=400, num_cus=256, one_filter=True, min_passes=4,
+             post_ntiles=ntiles, post_groups=groups)
+    a.update(kw)
+    return lp.ddc_plan(**a)
+
+
+def test_ddc_plan_headline():
+    # waves2 = 256 CUs * (6 * 4 / 8 - 1) * 8 = 4 096; 10 000 * (4 / 2) = 20 000 >= 4 * 4 096: NG = 2
+    # lds = max(8 * 2 * 512 + 2 * 256 * 8 = 12 288, 40 000); wgs_per_cu = min(6 * 4 / 8 = 3, 163 840 / 40 000 = 4) - 1 = 2
+    # riding tiling: 125 x 4 = 500 >= 384: run 2, 63 workgroups + the state one, x 4 groups = 256
+    # kslow = ceil(63 / 400) = 1, n_bnd = ceil(1 * 4 / 8) = 1, units = 9 999 * 2; wgs = min(ceil(19 998 / 8) = 2 500, 256 * 2)
+    p = _headline()
+    assert p == (4, 0, 2, 8, 1, 40_000, 2, 256, 1, 1, 19_998, 512)
+    assert p.wgs + p.n_bnd + p.post_wgs == 769
+
+
+def test_ddc_plan_ng2_threshold():
+    # the threshold: k1 * 2 >= 4 * 4 096, k1 >= 8 192
+    # 8 191: NG = 1: wgs_per_cu = min(4, 4) - 1 = 3; units = 8 190 * 4 = 32 760, 4 095 workgroups -> 256 * 3
+    assert _headline(k1=8_191) == (4, 0, 1, 8, 1, 40_000, 3, 256, 1, 1, 32_760, 768)
+    # 8 192: NG = 2: units = 8 191 * 2 = 16 382 -> 2 048 -> 512
+    assert _headline(k1=8_192) == (4, 0, 2, 8, 1, 40_000, 2, 256, 1, 1, 16_382, 512)
+    # min_passes = 0: always, down to one frame: kslow = 1 = k1, no units; two lane-group pairs still need a wave each: one workgroup
+    assert _headline(k1=1, min_passes=0) == (4, 0, 2, 8, 1, 40_000, 2, 256, 1, 1, 0, 1)
+    # no post stage riding: waves2 = 256 * 3 * 8 = 6 144, the threshold is 12 288; lds 12 288; three workgroups per CU
+    assert _headline(pd2=0, k1=12_287, post_ntiles=0, post_groups=0) == (4, 0, 1, 8, 1, 12_288, 4, 0, 1, 1, 12_286 * 4, 1024)
+    assert _headline(pd2=0, k1=12_288, post_ntiles=0, post_groups=0) == (4, 0, 2, 8, 1, 12_288, 3, 0, 1, 1, 12_287 * 2, 768)
+    # several channel filters: never
+    assert _headline(one_filter=False).ng == 1
+
+
+def test_ddc_plan_odd_group_count():
+    # 3 lane groups: NG = 1; 125 x 3 = 375 < 384: run 1, (125 + 1) x 3 = 378 post workgroups; n_bnd = ceil(3 / 8) = 1
+    # units = 9 999 * 3 = 29 997 -> 3 750 workgroups -> 256 * 3
+    assert _headline(groups=3) == (3, 0, 1, 8, 1, 40_000, 3, 378, 1, 1, 29_997, 768)
+
+
+def test_ddc_plan_tap_sets():
+    # a lane group that mixes three channel filters: three window copies per buffer: 8 * 2 * 512 * 3 + 4 096 = 28 672
+    p = lp.ddc_plan(WR_NCO_ROTATE, True, 0, 4, 1000, 8, 256, one_filter=False, nsets=[1, 3, 1, 2])
+    # kslow = ceil(63 / 8) = 8, n_bnd = ceil(8 * 4 / 8) = 4, units = 992 * 4 -> 496 workgroups
+    assert p == (4, 0, 1, 8, 3, 28_672, 4, 0, 8, 4, 3_968, 496)
+
+
+def test_ddc_plan_per_lane_taps():
+    # ROTATE, per-lane taps: 8 waves, windows + tables + one lane group's taps: 8 192 + 4 096 + 64 * 64 * 4 = 28 672; no roles
+    # 7 lane groups, k1 = 100: 700 units -> 88 workgroups -> a whole number per lane group: 84
+    assert lp.ddc_plan(WR_NCO_ROTATE, False, 0, 7, 100, 8, 256) == (7, 0, 1, 8, 1, 28_672, 4, 0, 0, 0, 700, 84)
+    # ... and one per lane group at the least
+    assert lp.ddc_plan(WR_NCO_ROTATE, False, 0, 7, 1, 8, 256) == (7, 0, 1, 8, 1, 28_672, 4, 0, 0, 0, 7, 7)
+    # the cap first: 256 CUs * 4 = 1 024 -> 1 022
+    assert lp.ddc_plan(WR_NCO_ROTATE, False, 0, 7, 10_000, 8, 256).wgs == 1_022
+
+
+def test_ddc_plan_exact_and_split():
+    # EXACT: 16 waves, two workgroups per CU, windows only: 16 * 2 * 512 = 16 384; no roles: 40 000 units -> 2 500 -> 512
+    assert lp.ddc_plan(WR_NCO_EXACT, False, 0, 4, 10_000, 400, 256) == (4, 0, 1, 16, 1, 16_384, 2, 0, 0, 0, 40_000, 512)
+    # SPLIT: the replicated tables: 2 * 256 * 32 * 8 = 131 072, + 16 384; one workgroup per CU
+    assert lp.ddc_plan(WR_NCO_SPLIT, True, 0, 4, 10_000, 400, 256) == (4, 0, 1, 16, 1, 147_456, 1, 0, 0, 0, 40_000, 256)
+
+
+def test_ddc_plan_beyond_sixteen_groups():
+    # 18 lane groups: 16 in this launch (never NG = 2: the rest goes out in a launch of its own), two left
+    p = lp.ddc_plan(WR_NCO_ROTATE, True, 0, 18, 10_000, 400, 256)
+    assert (p.ngroups, p.rest, p.ng) == (16, 0b11 << 16, 1)
+    p = lp.ddc_plan(WR_NCO_ROTATE, True, 0, 18, 10_000, 400, 256, gsel=p.rest)
+    assert (p.ngroups, p.rest, p.ng) == (2, 0, 1)           # 10 000 * 1 < 4 * 6 144
+    assert lp.ddc_plan(WR_NCO_ROTATE, True, 0, 18, 10_000, 400, 256, gsel=1 << 20).ngroups == 0
+
+
+def test_long_filter_plan():
+    # ROTATE, one filter, 4 groups, 128 taps, the post stage riding: two lane groups per wave: 20 000 units -> 2 500 -> 256 * 3
+    # roll: 127 * 256 = 32 512 entries / 512 -> 64; LDS: (512 + 8 * 128) * 8 + 8 * 64 * 4 = 14 336 against the post stage's 40 000
+    assert lp.long_plan(True, True, 10_000, 4, 128, 256, 256, 5, 63, 4) == (True, True, 768, 256, 64, 40_000, 0, 0)
+    # ... nothing riding, an odd group count: 30 000 units -> 3 750 -> 256 * 4
+    assert lp.long_plan(True, True, 10_000, 3, 128, 192, 256) == (True, False, 1024, 0, 48, 14_336, 0, 0)
+    assert lp.long_plan(True, False, 10, 4, 256, 2048, 256) == (True, False, 5, 0, 256, 14_336, 0, 0)    # 255 * 2 048 / 512 = 1 020
+    # the reference's arithmetic: 300 units in fours; the roll: 255 * 192 = 48 960 / 256 -> 192
+    assert lp.long_plan(False, False, 100, 3, 256, 192, 256) == (False, False, 0, 0, 0, 0, 75, 192)
+    assert lp.long_plan(False, False, 100_000, 16, 256, 1024, 256) == (False, False, 0, 0, 0, 0, 2048, 1020)
+    # a block without an output frame: the roll is all there is, in either mode
+    assert lp.long_plan(True, True, 0, 4, 128, 256, 256) == (False, False, 0, 0, 0, 0, 0, 127)
+
+
+def test_audio_filter_plan():
+    # D2 = 5, 64 taps: (352 - 64) / 5 + 1 = 58 frames would fit: 16; 15 * 5 + 64 = 139 rows; (139 + 64) * 64 + 16 * 65 floats
+    assert lp.audio_plan(2000, 5, 64) == (16, 139, 56_128, 159_808, 125)
+    # D2 = 10, 256 taps: (352 - 256) / 10 + 1 = 10 frames; 9 * 10 + 256 = 346 rows; (346 + 256) * 64 + 1 040 floats
+    assert lp.audio_plan(95, 10, 256) == (10, 346, 158_272, 159_808, 10)
+    assert lp.audio_plan(17, 1, 64) == (16, 79, 40_768, 159_808, 2)
+    assert lp.lib().wr_plan_grid_for(0, 256, 2048) == 1 and lp.lib().wr_plan_grid_for(257, 256, 2048) == 2
+    assert lp.lib().wr_plan_grid_for(1 << 40, 256, 2048) == 2048
+
+
+# ---- what holds whatever the shape ---------------------------------------------------------------------------------------
+KERNELS = [(WR_NCO_ROTATE, True), (WR_NCO_ROTATE, False), (WR_NCO_SPLIT, True), (WR_NCO_EXACT, False)]
+
+
+@pytest.mark.parametrize("num_cus", [8, 32, 256])
+def test_ddc_plan_invariants(num_cus):
+    for nco, utaps in KERNELS:
+        for pd2 in ([0] + D2S if nco == WR_NCO_ROTATE else [0]):
+            for groups in range(1, 17):
+                for k1 in (0, 1, 63, 64, 65, 1000, 10_000):
+                    for d1, one_filter in ((1, True), (8, False), (400, True)):
+                        p = lp.ddc_plan(nco, utaps, pd2, groups, k1, d1, num_cus, one_filter=one_filter, post_ntiles=7,
+                                        post_groups=groups)
+                        at = (nco, utaps, pd2, groups, k1, d1, one_filter, p)
+                        w = p.waves
+                        assert p.ngroups == groups and p.ng in (1, 2), at
+                        lowest = groups if (nco == WR_NCO_ROTATE and not utaps) else -(-(groups // p.ng) // w)
+                        assert p.wgs >= -(-(groups // p.ng) // w), at
+                        assert p.wgs <= max(num_cus * p.wgs_per_cu, lowest), at
+                        assert p.wgs_per_cu >= 1, at
+                        if p.ng == 2:
+                            assert groups % 2 == 0 and one_filter and nco == WR_NCO_ROTATE and utaps, at
+                        assert p.kslow <= k1 and p.n_bnd * w >= p.kslow * groups, at
+                        assert p.units == (k1 - p.kslow) * (groups // p.ng), at
+                        assert p.lds <= CU_LDS and p.lds * p.wgs_per_cu <= CU_LDS, at
+                        assert p.post_wgs == (8 * groups if pd2 else 0), at
+
+
+def test_tilings_cover_every_tile_once():
+    """ntiles x run >= tiles > (ntiles - 1) x run, for the three rules"""
+    def covers(tiles, run, ntiles):
+        return run >= 1 and ntiles * run >= tiles > (ntiles - 1) * run
+
+    for tiles in list(range(1, 70)) + [125, 255, 256, 257, 500, 1023, 4096, 5000]:
+        for groups in range(1, 17):
+            assert covers(tiles, *lp.post_tiling_riding(tiles, groups)), (tiles, groups)
+            for nseg in (1, 2, 4):
+                assert covers(tiles, *lp.post_tiling_alone(tiles, groups, nseg)), (tiles, groups, nseg)
+            for n_post in (1, 4, 7, 8, 28, 252):
+                t = lp.stream_tiling(16 * tiles, groups, n_post)
+                at = (tiles, groups, n_post, t)
+                assert t.tiles == tiles and covers(tiles, t.run, t.ntiles) and covers(tiles, t.drain_run, t.drain_ntiles), at
+                assert t.drain_run == t.min_run <= t.run <= tiles, at
+                # every task of the short runs has a post workgroup of its own, unless a lane group's tiles are one task already
+                assert t.drain_ntiles * groups <= n_post or t.min_run == tiles, at

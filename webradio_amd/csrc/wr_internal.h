@@ -12,14 +12,10 @@
 #include <stdint.h>
 
 #include "webradio_amd.h"
+#include "wr_plan.h"                       /* launch geometry and the constants it depends on (WR_HIST, WR_SPLIT_N, WR_TAPSETS, ...) */
 
-#define WR_HIST      (WR_FIR_LENGTH - 1)   /* 63 frames of FIR history, lowpass.cxx:133 */
 #define WR_LANES     64                    /* wavefront width on gfx950 */
-#define WR_SPLIT_N   256                   /* entries of the coarse and of the fine NCO table */
 #define WR_MAX_DEVICES 64                  /* device indices the per-device tables of this library hold */
-#define WR_TAPSETS   4                     /* distinct channel filters a lane group may mix in the fast DDC kernel:
-                                              receivers of one tuner mostly share a passband (radio.cxx:78-79),
-                                              the UI lets each choose its own (receiverhandler.cxx:130-137) */
 
 /* ---- what other translation units need of a wr_dev (wr_dev.hip, wr_tuner_submit.hip) ---- */
 int         wrc_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));   /* sets wr_last_error() */

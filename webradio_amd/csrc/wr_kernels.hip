@@ -441,7 +441,7 @@ __device__ __forceinline__ void gather_split(unsigned int P, unsigned int &ah, u
  *
  *   work unit  = (k, g): channel-rate output frame k for the 64 channel slots of
  *                lane group g.  One wave per unit; a wave of the persistent grid keeps one
- *                lane group and walks k with a fixed stride (launch geometry: DdcGeom).
+ *                lane group and walks k with a fixed stride (launch geometry: wrp_ddc_plan).
  *   per unit   : 64 taps.  Tap j touches input frame n = k*D1 - 63 + j, whose
  *                sample is wave-uniform.  Each lane advances its own left-aligned
  *                32-bit phase P (= reference phase << 1, so the 31-bit wrap of
@@ -492,13 +492,12 @@ __device__ __forceinline__ float2 input_frame(const float2 *__restrict__ cur, co
  *                 the last 63 demod outputs (audio filter history) and the last channel
  *                 frame (Demodulator::prev_i/q), into the other ping-pong set.
  */
-#define POST_TK 16u
+/* (POST_TK, POST_THREADS: wr_plan.h) */
 #define POST_B 4u
 #define POST_LB 5u                       /* rows whose loads a wave of the stage phase has in flight together (measured
                                             at C2, us per block at 1 / 4 blocks per launch: 3 rows 34.7 / 30.5, 5 rows
                                             34.0 / 29.7, 6 rows 35.0 / 31.3, 9 rows 35.7 / 31.0 -- more rows, more
                                             registers: spills) */
-#define POST_THREADS 512u
 /* What leaves the audio filter for the sink: af_gain and squelch (the reference has the two fields
  * and no code behind them, receiverhandler.cxx:112,118-119,127), then the sink's scale.
  *   af_gain : a factor applied in float;
@@ -797,13 +796,7 @@ k_tuner_post(WrPostArgs A)
 	}
 }
 
-/* LDS plan of k_tuner_ddc: [0, 128 KiB) the two replicated NCO tables (SPLIT only),
- * then one private 2 x 512 B sample window per wave (double buffered across units). */
-#define DDC_TABLE_BYTES   (2u * WR_SPLIT_N * 32u * 8u)
-#define DDC_WAVES         16u
-#define DDC_ROTATE_WAVES      8u          /* every ROTATE variant (folded or per-lane taps): 8-wave workgroups, */
-#define DDC_ROTATE_WGS_PER_CU 4u          /* four per CU */
-#define DDC_LDS_BYTES     (DDC_TABLE_BYTES + DDC_WAVES * 2u * 512u)
+/* (the LDS plan of k_tuner_ddc and its workgroup sizes, DDC_*: wr_plan.h) */
 #define DDC_DEAL_WAYS 2u                   /* measured at C2, us per block at 1 / 4 blocks per launch: in order (and as
                                               many workgroups as make the units come out even) 37.6 / 32.8, 2 ways
                                               36.8 / 32.0, 4 ways 37.0 / 32.0, 8 ways 38.5 / 32.0 */
@@ -1328,8 +1321,7 @@ ddc_body(DDC_PARAMS, v2f *lds, const int role)
  * two waves per SIMD (tools/ubench_tap.hip, profiles/r03_ubench_tap.txt).  The two recurrences are two lane
  * groups at the same output frame: they share the window and every one of its LDS reads.  NG = 2 takes an even
  * number of lane groups that all use ONE and the same channel filter (the host says: WrTunerLaunch::one_filter)
- * and 80 registers (6 waves per SIMD); otherwise NG = 1, as before. */
-#define DDC_NG2_WAVES_PER_EU 6u
+ * and 80 registers (6 waves per SIMD: DDC_NG2_WAVES_PER_EU); otherwise NG = 1, as before. */
 template <int NCO, bool UTAPS, unsigned int NG> struct DdcOcc {
 	static constexpr unsigned int per_eu = (NG == 2u) ? DDC_NG2_WAVES_PER_EU
 	                                       : (NCO == WR_NCO_ROTATE) ? DDC_ROTATE_WGS_PER_CU * DDC_ROTATE_WAVES / 4u
@@ -1781,9 +1773,7 @@ long_roll_body(const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u8
 /* r04: workgroups of LONG_ROT_WAVES waves, and -- PD2 != 0 -- the post stage of the PREVIOUS block in extra workgroups
  * [n_ddc, gridDim.x) of the same launch, as k_tuner_ddc carries it (post_role: demodulator + audio filter with audio
  * decimation PD2; the two share nothing but the kernel boundary before the launch).  LDS is dynamic: the tables, windows and
- * tap segments of the DDC waves, or the post role's stage and tile, whichever a workgroup is. */
-#define LONG_ROT_WAVES 8u
-#define LONG_ROT_LDS   ((2u * WR_SPLIT_N + LONG_ROT_WAVES * 2u * 64u) * 8u + LONG_ROT_WAVES * 64u * 4u)
+ * tap segments of the DDC waves (LONG_ROT_LDS), or the post role's stage and tile, whichever a workgroup is. */
 template <unsigned int NG, unsigned int PD2>
 __global__ void __launch_bounds__(LONG_ROT_WAVES * 64u)
 k_tuner_ddc_long_rot(const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u8, size_t k1,
@@ -1931,34 +1921,26 @@ k_ddc_long_roll(const float2 *__restrict__ cur, const uchar2 *__restrict__ cur_u
 	               (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
 }
 
-/* The audio decimations the post stage is built for (anything else takes the two-kernel path): 1..6, and 8 and 10 --
- * 256 k -> 32 k (BASELINE config 1), 240 k -> 24 k, 480 k -> 48 k.  Calls f with the run-time d2 as a compile-time
- * constant (std::integral_constant<unsigned int, D2>); any other d2: hipErrorInvalidValue. */
+/* Calls f with the run-time d2 as a compile-time constant (std::integral_constant<unsigned int, D2>), for the audio
+ * decimations the post stage is built for: a case per entry of WR_POST_D2_LIST (wr_plan.h), which is where the values
+ * stand; any other d2: hipErrorInvalidValue. */
+static constexpr unsigned int POST_D2[] = {WR_POST_D2_LIST};
+static_assert(sizeof(POST_D2) / sizeof(POST_D2[0]) == 8, "with_post_d2 needs a case for every entry of WR_POST_D2_LIST");
 template <class F>
 static hipError_t with_post_d2(unsigned int d2, F &&f)
 {
+#define POST_D2_CASE(i) case POST_D2[i]: return f(std::integral_constant<unsigned int, POST_D2[i]>());
 	switch (d2) {
-	case 1: return f(std::integral_constant<unsigned int, 1u>());
-	case 2: return f(std::integral_constant<unsigned int, 2u>());
-	case 3: return f(std::integral_constant<unsigned int, 3u>());
-	case 4: return f(std::integral_constant<unsigned int, 4u>());
-	case 5: return f(std::integral_constant<unsigned int, 5u>());
-	case 6: return f(std::integral_constant<unsigned int, 6u>());
-	case 8: return f(std::integral_constant<unsigned int, 8u>());
-	case 10: return f(std::integral_constant<unsigned int, 10u>());
+	POST_D2_CASE(0) POST_D2_CASE(1) POST_D2_CASE(2) POST_D2_CASE(3)
+	POST_D2_CASE(4) POST_D2_CASE(5) POST_D2_CASE(6) POST_D2_CASE(7)
 	default: return hipErrorInvalidValue;
 	}
+#undef POST_D2_CASE
 }
 
 bool wrk_tuner_post_supported(unsigned int d2)
 {
-	return with_post_d2(d2, [](auto) { return hipSuccess; }) == hipSuccess;
-}
-
-/* LDS of a post-stage workgroup (post_role): the staged rows of (POST_TK - 1) d2 + 64 nseg frames, the tile, the modes */
-static size_t post_lds_bytes(unsigned int d2, unsigned int nseg)
-{
-	return (((size_t)(POST_TK - 1u) * d2 + WR_FIR_LENGTH * nseg) * 64u + POST_TK * 65u + 64u) * sizeof(float);
+	return wrp_post_d2_supported(d2);
 }
 
 /* Launch `kernel`, stamping the launch's own start / stop events where the caller gave any.  Profiling (both events; with
@@ -1987,77 +1969,45 @@ hipError_t wrk_tuner_ddc_long(hipStream_t st, const WrTunerLaunch &L, const WrGr
 		return hipSuccess;
 	const unsigned int groups = L.slots_used / 64u;
 	/* `rotate` (a tolerance nco mode, one filter per lane group): only the frames whose window reaches into the previous
-	 * block take the reference's arithmetic, the others k_tuner_ddc_long_rot */
-	size_t k_exact = L.k1;
-	bool exact_done = false, rolled = false;
-	if (rotate && L.k1) {
-		const size_t units_r = L.k1 * groups;
-		exact_done = true;
-		k_exact = 0;
-		const bool two = rotate_one_filter && groups % 2u == 0;
-		const hipEvent_t e0 = (L.ev_start && L.ev_stop) ? (hipEvent_t)L.ev_start : nullptr;
-		const hipEvent_t e1 = (L.ev_start && L.ev_stop) ? (hipEvent_t)L.ev_stop : nullptr;
-		/* the previous block's post stage rides in this launch where the kernel is built for its audio decimation */
-		const bool ride = post && post->k1 && post->groups && wrk_tuner_post_supported(post->d2);
-		unsigned int wgs_r = (unsigned int)(((two ? units_r / 2 : units_r) + LONG_ROT_WAVES - 1u) / LONG_ROT_WAVES);
-		/* persistent: 32 waves per CU as before -- or 24 and one workgroup slot per CU left to the post workgroups, which
-		 * come and go beside the DDC ones (as in k_tuner_ddc) instead of queueing up behind them */
-		const unsigned int cap8 = (unsigned int)num_cus * (ride ? 3u : 4u);
-		if (wgs_r > cap8)
-			wgs_r = cap8;
-		const unsigned int d2r = ride ? post->d2 : 0u;
-		const unsigned int post_wgs = ride ? (post->ntiles + 1u) * post->groups : 0u;
+	 * block take the reference's arithmetic, the others k_tuner_ddc_long_rot.  The previous block's post stage rides in
+	 * that launch where the kernel is built for its audio decimation */
+	const bool ride = post && post->k1 && post->groups && wrk_tuner_post_supported(post->d2);
+	const unsigned int d2r = ride ? post->d2 : 0u;
+	const WrLongPlan P = wrp_long_plan(rotate, rotate_one_filter, L.k1, groups, len, L.slots, num_cus, d2r, ride ? post->ntiles : 0u,
+	                                   ride ? post->groups : 0u);
+	const bool prof = L.ev_start && L.ev_stop;
+	if (P.rot) {
+		const hipEvent_t e0 = prof ? (hipEvent_t)L.ev_start : nullptr;
+		const hipEvent_t e1 = prof ? (hipEvent_t)L.ev_stop : nullptr;
 		const WrPostArgs pa = ride ? *post : WrPostArgs();
-		const size_t roll_total = (size_t)(len - 1u) * L.slots;
-		const unsigned int roll_wgs = (unsigned int)((roll_total + LONG_ROT_WAVES * 64u - 1u) / (LONG_ROT_WAVES * 64u) > 256u
-		                                             ? 256u : (roll_total + LONG_ROT_WAVES * 64u - 1u) / (LONG_ROT_WAVES * 64u));
-		rolled = true;
-		size_t lds = LONG_ROT_LDS;
-		if (ride) {
-			const size_t need = post_lds_bytes(d2r, 1u);
-			if (need > lds)
-				lds = need;
-			if (post_taken)
-				*post_taken = true;
-		}
+		if (ride && post_taken)
+			*post_taken = true;
 		auto launch = [&](auto NG_) {
 			auto go = [&](auto PD2_) {
 				hipExtLaunchKernelGGL((k_tuner_ddc_long_rot<decltype(NG_)::value, decltype(PD2_)::value>),
-				                      dim3(wgs_r + post_wgs + roll_wgs), dim3(LONG_ROT_WAVES * 64u), (uint32_t)lds, st, e0, e1, 0u,
+				                      dim3(P.wgs_r + P.post_wgs + P.roll_wgs), dim3(LONG_ROT_WAVES * 64u), (uint32_t)P.lds, st, e0, e1, 0u,
 				                      (const float2 *)L.cur, (const uchar2 *)L.cur_u8, L.k1, L.d1, len, L.slots, groups,
 				                      (const unsigned int *)G.phase[L.sp], (const unsigned int *)G.step, (const int *)G.flags,
 				                      (const float4 *)G.rot, (const float *)G.taps1L, (const float2 *)hi_dev, (const float2 *)lo_dev,
-				                      (float2 *)G.chan_iq[L.cb], (const float2 *)G.mixhist[L.sp], wgs_r, pa, post_wgs, L.nframes,
+				                      (float2 *)G.chan_iq[L.cb], (const float2 *)G.mixhist[L.sp], P.wgs_r, pa, P.post_wgs, L.nframes,
 				                      G.phase[L.sp ^ 1], (float2 *)G.mixhist[L.sp ^ 1], table_dev);
 				return hipSuccess;
 			};
 			return d2r ? with_post_d2(d2r, go) : go(std::integral_constant<unsigned int, 0u>());
 		};
-		const hipError_t e = two ? launch(std::integral_constant<unsigned int, 2u>())
-		                         : launch(std::integral_constant<unsigned int, 1u>());
-		if (e != hipSuccess)
-			return e;
+		const hipError_t e = P.two ? launch(std::integral_constant<unsigned int, 2u>())
+		                           : launch(std::integral_constant<unsigned int, 1u>());
+		return e != hipSuccess ? e : hipGetLastError();     /* the ROTATE launch rolled the state itself */
 	}
-	const bool prof_exact = L.ev_start && L.ev_stop && !exact_done;
-	const size_t units = exact_done ? 0 : k_exact * groups;
-	if (units) {
-		unsigned int wgs = (unsigned int)((units + 3) / 4);
-		const unsigned int cap = (unsigned int)num_cus * 8u;
-		if (wgs > cap)
-			wgs = cap;
+	if (P.wgs) {
 		/* profiling: the filter kernel's own start and end (the roll behind it is not in the bracket) */
-		launch_stamped(k_tuner_ddc_long, dim3(wgs), dim3(256), 0, st, prof_exact ? L.ev_start : nullptr,
-		               prof_exact ? L.ev_stop : nullptr, (const float2 *)L.cur, (const uchar2 *)L.cur_u8, L.nframes, k_exact, L.d1,
-		               len, L.slots, groups, G.phase[L.sp], G.step, G.flags, G.taps1L, (const float2 *)G.mixhist[L.sp], table_dev,
-		               (float2 *)G.chan_iq[L.cb]);
+		launch_stamped(k_tuner_ddc_long, dim3(P.wgs), dim3(256), 0, st, prof ? L.ev_start : nullptr, prof ? L.ev_stop : nullptr,
+		               (const float2 *)L.cur, (const uchar2 *)L.cur_u8, L.nframes, L.k1, L.d1, len, L.slots, groups, G.phase[L.sp],
+		               G.step, G.flags, G.taps1L, (const float2 *)G.mixhist[L.sp], table_dev, (float2 *)G.chan_iq[L.cb]);
 	}
-	if (rolled)
-		return hipGetLastError();                           /* the ROTATE launch rolled the state itself */
-	const size_t total = (size_t)(len - 1u) * L.slots;
-	const unsigned int rwgs = (unsigned int)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256);
 	/* profiling a block too short for an output frame: the roll is all there is */
-	const bool prof_roll = L.ev_start && L.ev_stop && !L.k1;
-	launch_stamped(k_ddc_long_roll, dim3(rwgs), dim3(256), 0, st, prof_roll ? L.ev_start : nullptr,
+	const bool prof_roll = prof && !L.k1;
+	launch_stamped(k_ddc_long_roll, dim3(P.rwgs), dim3(256), 0, st, prof_roll ? L.ev_start : nullptr,
 	               prof_roll ? L.ev_stop : nullptr, (const float2 *)L.cur, (const uchar2 *)L.cur_u8, L.nframes, len, L.slots,
 	               G.phase[L.sp], G.step, G.flags, G.phase[L.sp ^ 1], (const float2 *)G.mixhist[L.sp],
 	               (float2 *)G.mixhist[L.sp ^ 1], table_dev);
@@ -2121,10 +2071,7 @@ k_tuner_demod(const float2 *__restrict__ chan_iq, unsigned int k1, unsigned int 
  * tile needs are staged in LDS once (each row is read by up to 64/D2 outputs), lanes
  * run over slots so both the global rows and the LDS rows are contiguous per wave, and
  * the finished 64 x tk tile is transposed through LDS so that audio[s][k2] (channel
- * major, what each audio sink consumes) is written in runs. */
-#define AUD_ROWS 352u          /* staged demod rows: 352 x 64 x 4 B = 88 KiB */
-#define AUD_TMAX 16u
-#define AUD_THREADS 1024u
+ * major, what each audio sink consumes) is written in runs.  (AUD_ROWS, AUD_TMAX, AUD_THREADS: wr_plan.h) */
 __global__ void __launch_bounds__(AUD_THREADS)
 k_tuner_audio(const float *__restrict__ dem, size_t rows_valid, size_t k2, unsigned int d2,
               unsigned int tk, unsigned int slots, const float *__restrict__ taps2,
@@ -2335,16 +2282,6 @@ static hipError_t allow_lds(const void *fn, size_t bytes, bool (&done)[WR_MAX_DE
 	return e;
 }
 
-static inline unsigned int grid_for(size_t n, unsigned int block, unsigned int cap)
-{
-	size_t g = (n + block - 1) / block;
-	if (g < 1)
-		g = 1;
-	if (g > cap)
-		g = cap;
-	return (unsigned int)g;
-}
-
 hipError_t wrk_mix(hipStream_t st, const float *in, float *out, size_t nframes,
                    unsigned int phase, int step, const float *table_dev)
 {
@@ -2496,12 +2433,7 @@ hipError_t wrk_u8_to_f32(hipStream_t st, const uint8_t *in, float *out, size_t c
 	return hipGetLastError();
 }
 
-/* launch geometry of k_tuner_ddc<NCO, UTAPS> (waves per workgroup, persistent workgroups per CU):
- *   ROTATE, uniform taps : 8 x 4 -- 64 VGPRs, 20 KiB of LDS: 8 waves per SIMD hide the recurrence's
- *                                  dependent FMAs better than 4 (measured 35.6 -> 34.7 us)
- *   ROTATE, per-lane taps: 16 x 1 -- one lane group's taps (16 KiB) per workgroup
- *   SPLIT                : 16 x 1 -- the replicated tables take 128 KiB
- *   EXACT                : 16 x 2 -- small LDS footprint, two workgroups hide the gather latency */
+/* (launch geometry of k_tuner_ddc<NCO, UTAPS>: wrp_ddc_plan, wr_plan.h) */
 /* include/webradio_amd.h: WR_TUNE_DDC_NG2_MIN_PASSES */
 static std::atomic<long> g_ng2_min_passes{-1};
 long wrk_tune_ng2_min_passes(long value, bool set)
@@ -2517,134 +2449,54 @@ long wrk_tune_ng2_min_passes(long value, bool set)
 	return before;
 }
 
-template <int NCO, bool UTAPS> struct DdcGeom {
-	static constexpr unsigned int waves = (NCO == WR_NCO_ROTATE) ? DDC_ROTATE_WAVES : DDC_WAVES;
-	static constexpr unsigned int wgs_per_cu = (NCO == WR_NCO_ROTATE) ? DDC_ROTATE_WGS_PER_CU
-	                                           : (NCO == WR_NCO_EXACT) ? 2u : 1u;
-};
-
-/* `gsel`: bit g set = lane group g takes part in this launch (0 = all of them); `whole`: the launch
- * also rolls the per-channel state of every group (exactly one launch per block does) */
-template <int NCO, bool UTAPS, unsigned int PD2, unsigned int NG = 1u>
-static hipError_t launch_ddc(hipStream_t st, const WrTunerLaunch &L, const WrGroupDev &G,
-                             const float *table_dev, const float *hi_dev, const float *lo_dev, int num_cus,
-                             const WrPostArgs *post, unsigned long long gsel = 0, bool whole = true)
+/* the launch itself: what only the runtime can give (allow_lds), then the plan's numbers */
+template <int NCO, bool UTAPS, unsigned int PD2, unsigned int NG>
+static hipError_t launch_ddc_planned(hipStream_t st, const WrTunerLaunch &L, const WrGroupDev &G, const float *table_dev,
+                                     const float *hi_dev, const float *lo_dev, const WrPostArgs *post, bool whole,
+                                     const WrDdcPlan &P)
 {
-	constexpr unsigned int W = DdcGeom<NCO, UTAPS>::waves;
-	if constexpr (NG == 1u && NCO == WR_NCO_ROTATE && UTAPS) {
-		/* two lane groups per wave (see k_tuner_ddc: NG) where the launch allows: an even number of lane groups, at
-		 * most 16, all on one and the same channel filter */
-		unsigned int n = 0;
-		for (unsigned int g = 0; g < L.slots_used / 64; ++g)
-			n += (!gsel || ((gsel >> g) & 1ull)) ? 1u : 0u;
-		/* ... and enough output frames: a wave of the NG = 2 kernel does twice the work per pass of its loop, so
-		 * with few passes per wave the grid ends ragged (BASELINE config 5: 5 065 frames per chunk, 2.5 passes per
-		 * wave -- 48 us against 43 with one lane group per wave); from four passes on the shared reads win */
-		const size_t waves2 = (size_t)num_cus * (DDC_NG2_WAVES_PER_EU * 4u / W - (PD2 ? 1u : 0u)) * W;
-		const size_t min_passes = (size_t)wrk_tune_ng2_min_passes(0, false);      /* wr_tune: 0 = always */
-		if (L.one_filter && n >= 2u && n <= 16u && (n & 1u) == 0u && L.k1 * (n / 2u) >= min_passes * waves2)
-			return launch_ddc<NCO, UTAPS, PD2, 2u>(st, L, G, table_dev, hi_dev, lo_dev, num_cus, post, gsel, whole);
-	}
-	const unsigned int allgroups = L.slots_used / 64;        /* <= 64: wr_tuner_create caps max_channels */
-	unsigned long long gmap[2] = {0, 0};
-	unsigned int ngroups = 0;
-	unsigned long long rest = 0;                             /* selected groups beyond the 16 one launch maps */
-	for (unsigned int g = 0; g < allgroups; ++g)
-		if (!gsel || ((gsel >> g) & 1ull)) {
-			if (ngroups < 16u) {
-				gmap[ngroups >> 3] |= (unsigned long long)g << ((ngroups & 7u) * 8u);
-				++ngroups;
-			} else {
-				rest |= 1ull << g;
-			}
-		}
-	if (!ngroups)
-		return hipSuccess;
-	if (rest) {
-		/* more than 1024 channels: the groups beyond the first 16 go out in launches of their own,
-		 * which neither roll the state again nor carry the post stage or the profiling events */
-		WrTunerLaunch L2 = L;
-		L2.ev_start = L2.ev_stop = nullptr;
-		hipError_t e = launch_ddc<NCO, UTAPS, 0>(st, L2, G, table_dev, hi_dev, lo_dev, num_cus, nullptr, rest, false);
-		if (e != hipSuccess)
-			return e;
-	}
-	/* tap sets in this launch: the largest count among the groups it covers (SPLIT: one, its
-	 * replicated tables leave no room for more windows) */
-	unsigned int kmax = 1;
-	if (UTAPS && NCO == WR_NCO_ROTATE)
-		for (unsigned int i = 0; i < ngroups; ++i) {
-			const unsigned int g = (unsigned int)((gmap[i >> 3] >> ((i & 7u) * 8u)) & 255u);
-			if (g < 64u && L.nsets[g] > kmax)
-				kmax = L.nsets[g];
-		}
-	size_t lds = (NCO == WR_NCO_SPLIT) ? DDC_LDS_BYTES
-	             : (W * 2u * 512u * kmax) + (NCO == WR_NCO_ROTATE ? 2u * WR_SPLIT_N * 8u : 0u)
-	               + (NCO == WR_NCO_ROTATE && !UTAPS ? WR_FIR_LENGTH * 64u * 4u : 0u);
-	/* NG = 2: 80 registers, 6 waves per SIMD: three 8-wave workgroups per CU */
-	unsigned int wgs_per_cu = (NG == 2u) ? DDC_NG2_WAVES_PER_EU * 4u / W : DdcGeom<NCO, UTAPS>::wgs_per_cu;
-	unsigned int post_wgs = 0;
-	if (PD2 != 0u) {
-		/* the post workgroups' stage + tile set the LDS size of every workgroup of the launch;
-		 * POST_RESERVE workgroup slots per CU are left to them (they come and go, the DDC ones
-		 * persist).  Measured at C2, kernel duration (r02: per-slot turns, priorities by progress,
-		 * post workgroups at priority 3): 1 slot 38.2 us, 2 slots 39.7, 3 slots 49.8 (the DDC
-		 * starves); DDC + post as two launches: 31.3 + 15.2 + gap. */
-		const size_t post_lds = post_lds_bytes(PD2, 1u);
-		if (post_lds > lds)
-			lds = post_lds;
-		unsigned int fit = (unsigned int)((160u * 1024u) / lds);
-		if (fit < wgs_per_cu)
-			wgs_per_cu = fit;
-		constexpr unsigned int POST_RESERVE = 1u;
-		wgs_per_cu = (wgs_per_cu > POST_RESERVE) ? wgs_per_cu - POST_RESERVE : 1u;
-		post_wgs = (post->ntiles + 1u) * post->groups;
-	}
-	/* launched even for a block too short to yield a channel-rate frame: workgroup 0 still
-	 * advances the NCO (downconverter.cxx:103 runs per input frame) and rolls the histories */
-	/* (ROLES) the first ceil(63 / D1) output frames of the block reach into the previous one: they go to
-	 * n_bnd workgroups of their own, one wave per (lane group, frame), and the persistent waves share the rest */
-	constexpr bool ROLES = NCO == WR_NCO_ROTATE && UTAPS;
-	unsigned int kslow = 0, n_bnd = 0;
-	if (ROLES && L.k1) {
-		kslow = (WR_HIST + L.d1 - 1u) / L.d1;
-		if (kslow > L.k1)
-			kslow = (unsigned int)L.k1;
-		n_bnd = (kslow * ngroups + W - 1u) / W;
-	}
-	const size_t units = (L.k1 - kslow) * (ngroups / NG);        /* per wave and pass of its loop: NG lane groups */
-	unsigned int wgs = (unsigned int)((units + W - 1) / W);
-	const unsigned int cap = (unsigned int)num_cus * wgs_per_cu;
-	if (wgs > cap) {
-		wgs = cap;                                     /* every slot: the kernel evens the units out (DDC_DEAL_WAYS) */
-	}
-	if (NCO == WR_NCO_ROTATE && !UTAPS) {
-		/* per-lane taps live in LDS, one lane group per WORKGROUP: a whole number of
-		 * workgroups per group, at least one */
-		wgs = (wgs / ngroups) * ngroups;
-		if (wgs < ngroups)
-			wgs = ngroups;
-	} else {
-		/* every lane group needs at least one wave of its own (the kernel deals waves to groups) */
-		const unsigned int min_wgs = (ngroups / NG + W - 1) / W;
-		if (wgs < min_wgs)
-			wgs = min_wgs;
-	}
 	static bool attr_done[WR_MAX_DEVICES];
-	if (lds > 64 * 1024) {
-		hipError_t e = allow_lds((const void *)k_tuner_ddc<NCO, UTAPS, PD2, NG>, lds, attr_done);
+	if (P.lds > 64 * 1024) {
+		hipError_t e = allow_lds((const void *)k_tuner_ddc<NCO, UTAPS, PD2, NG>, P.lds, attr_done);
 		if (e != hipSuccess)
 			return e;
 	}
 	const WrPostArgs pa = post ? *post : WrPostArgs();
-	launch_stamped(k_tuner_ddc<NCO, UTAPS, PD2, NG>, dim3(wgs + n_bnd + post_wgs), dim3(W * 64u), lds, st, L.ev_start, L.ev_stop,
-	               (const float2 *)L.cur, (const uchar2 *)L.cur_u8, (const float2 *)L.hist, (float2 *)L.hist_next, L.nframes,
-	               L.k1, L.d1, L.slots, ngroups, G.phase[L.sp], G.step, (const float2 *)G.hist_cs[L.sp], G.flags,
+	launch_stamped(k_tuner_ddc<NCO, UTAPS, PD2, NG>, dim3(P.wgs + P.n_bnd + P.post_wgs), dim3(P.waves * 64u), P.lds, st, L.ev_start,
+	               L.ev_stop, (const float2 *)L.cur, (const uchar2 *)L.cur_u8, (const float2 *)L.hist, (float2 *)L.hist_next, L.nframes,
+	               L.k1, L.d1, L.slots, P.map.ngroups, G.phase[L.sp], G.step, (const float2 *)G.hist_cs[L.sp], G.flags,
 	               G.phase[L.sp ^ 1], (float2 *)G.hist_cs[L.sp ^ 1], (const float2 *)G.hist_lo[L.sp],
-	               (float2 *)G.hist_lo[L.sp ^ 1], G.taps1, (const float4 *)G.rot, G.taps1u, G.tapsel, kmax,
-	               (float2 *)G.chan_iq[L.cb], table_dev, (const float2 *)hi_dev, (const float2 *)lo_dev, wgs, pa, gmap[0], gmap[1],
-	               whole ? 1 : 0, kslow, n_bnd, L.seeking ? 1u : 0u, L.seek_lo);
+	               (float2 *)G.hist_lo[L.sp ^ 1], G.taps1, (const float4 *)G.rot, G.taps1u, G.tapsel, P.kmax,
+	               (float2 *)G.chan_iq[L.cb], table_dev, (const float2 *)hi_dev, (const float2 *)lo_dev, P.wgs, pa, P.map.gmap[0],
+	               P.map.gmap[1], whole ? 1 : 0, P.kslow, P.n_bnd, L.seeking ? 1u : 0u, L.seek_lo);
 	return hipGetLastError();
+}
+
+/* `gsel`: bit g set = lane group g takes part in this launch (0 = all of them); `whole`: the launch
+ * also rolls the per-channel state of every group (exactly one launch per block does) */
+template <int NCO, bool UTAPS, unsigned int PD2>
+static hipError_t launch_ddc(hipStream_t st, const WrTunerLaunch &L, const WrGroupDev &G,
+                             const float *table_dev, const float *hi_dev, const float *lo_dev, int num_cus,
+                             const WrPostArgs *post, unsigned long long gsel = 0, bool whole = true)
+{
+	const WrDdcPlan P = wrp_ddc_plan(NCO, UTAPS, PD2, L.slots_used, gsel, L.nsets, L.one_filter != 0, L.k1, L.d1, num_cus,
+	                                 (size_t)wrk_tune_ng2_min_passes(0, false) /* wr_tune: 0 = always */,
+	                                 PD2 ? post->ntiles : 0u, PD2 ? post->groups : 0u);
+	if (!P.map.ngroups)
+		return hipSuccess;
+	if (P.map.rest) {
+		/* more than 1024 channels: the groups beyond the first 16 go out in launches of their own,
+		 * which neither roll the state again nor carry the post stage or the profiling events */
+		WrTunerLaunch L2 = L;
+		L2.ev_start = L2.ev_stop = nullptr;
+		hipError_t e = launch_ddc<NCO, UTAPS, 0>(st, L2, G, table_dev, hi_dev, lo_dev, num_cus, nullptr, P.map.rest, false);
+		if (e != hipSuccess)
+			return e;
+	}
+	if constexpr (NCO == WR_NCO_ROTATE && UTAPS)
+		if (P.ng == 2u)
+			return launch_ddc_planned<NCO, UTAPS, PD2, 2u>(st, L, G, table_dev, hi_dev, lo_dev, post, whole, P);
+	return launch_ddc_planned<NCO, UTAPS, PD2, 1u>(st, L, G, table_dev, hi_dev, lo_dev, post, whole, P);
 }
 
 /* the launch with the previous block's post stage riding: the audio decimation is a template parameter of the
@@ -2753,15 +2605,10 @@ WrPostArgs wrk_post_args(const WrTunerLaunch &L, const WrGroupDev &G)
 	A.dem_hist = G.dem[p];
 	A.dem_hist_next = G.dem[p ^ 1];
 	A.k2 = L.k2;
-	A.tiles = (unsigned int)((L.k2 + POST_TK - 1) / POST_TK);
-	/* tiles per workgroup: as long a run as still leaves every CU a few workgroups */
-	{
-		const unsigned int all = A.tiles * (L.slots_used / 64u);
-		/* measured at C2 (500 tiles a block), us per block: 1 block per launch, run 1 / 2 / 4:
-		 * 38.3 / 37.1 / 38.0; 4 blocks per launch: 33.6 / 32.3 / 32.2 */
-		A.run = all >= 1536u ? 4u : all >= 384u ? 2u : 1u;
-	}
-	A.ntiles = (A.tiles + A.run - 1u) / A.run;
+	A.tiles = wrp_post_tiles(L.k2);
+	const WrPostTiling T = wrp_post_tiling_riding(A.tiles, L.slots_used / 64u);
+	A.run = T.run;
+	A.ntiles = T.ntiles;
 	A.taps2 = G.taps2;
 	A.taps2u = G.taps2u;
 	A.uni2 = L.uniform2_mask;
@@ -2806,22 +2653,11 @@ hipError_t wrk_tuner_post_args(hipStream_t st, const WrPostArgs &A0)
 {
 	if (!A0.k1 || !A0.groups)
 		return hipSuccess;
-	/* on its own the post stage has the chip to itself and is a chain of latencies: one tile per
-	 * workgroup, all of them in flight at once (runs of tiles are for the workgroups that ride in a
-	 * DDC launch, where instructions are what is short); 15.4 against 18.2 us for a C2 block */
+	/* (on its own the post stage is cut otherwise than where it rides in a DDC launch) */
 	WrPostArgs A = A0;
-	{
-		/* ... unless there are tiles enough to fill the chip several times over anyway (the flush behind a launch of
-		 * several blocks): runs of tiles then save the rows two neighbouring tiles share from being loaded and
-		 * demodulated twice (59 of 139 at D2 = 5) */
-		const unsigned int all = A.tiles * A.groups;
-		A.run = all >= 4096u ? 2u : 1u;   /* C2, four blocks: 43.6 / 33.6 / 36.0 us at runs of 1 / 2 / 4 */
-		if (A.nseg == 4u && all >= 384u)
-			A.run = 2u;     /* 256 taps: a tile stages 331 rows for its 80 new ones (D2 = 5) and one workgroup fits a CU --
-			                   C2 (500 tiles), us per block all in at runs of 1 / 2 / 4: 93 / 83 / 104 (128 taps: 62 / 69 / 79),
-			                   profiles/r05_long_filter.txt */
-	}
-	A.ntiles = (A.tiles + A.run - 1u) / A.run;
+	const WrPostTiling T = wrp_post_tiling_alone(A.tiles, A.groups, A.nseg);
+	A.run = T.run;
+	A.ntiles = T.ntiles;
 	return with_post_d2(A.d2, [&](auto D2) { return launch_post<decltype(D2)::value>(st, A); });
 }
 
@@ -2836,23 +2672,14 @@ hipError_t wrk_tuner_audio(hipStream_t st, const WrTunerLaunch &L, const WrGroup
 {
 	if (!L.k2 || !L.slots_used)
 		return hipSuccess;
-	/* as many output frames per tile as the staged rows allow */
 	const unsigned int len = G.l2;                      /* 64, or 128 / 256 taps (LowPass::_firLength) */
-	unsigned int tk = AUD_TMAX;
-	if (L.d2 > 1 && (AUD_ROWS - len) / L.d2 + 1u < tk)
-		tk = (AUD_ROWS - len) / L.d2 + 1u;
-	/* LDS sized to what this decimation needs, so that two workgroups fit a CU when D2 is small */
-	const unsigned int need = (tk - 1u) * L.d2 + len;
-	const size_t lds = ((size_t)need * 64u + (size_t)len * 64u + AUD_TMAX * 65u) * sizeof(float);
+	const WrAudioPlan P = wrp_audio_plan(L.k2, L.d2, len);
 	static bool attr_done[WR_MAX_DEVICES];
-	{
-		const size_t lds_max = ((size_t)AUD_ROWS * 64u + (size_t)WR_FIR_FUSED_MAX * 64u + AUD_TMAX * 65u) * sizeof(float);   /* 156 KiB of 160 */
-		hipError_t e = allow_lds((const void *)k_tuner_audio, lds_max, attr_done);
-		if (e != hipSuccess)
-			return e;
-	}
-	dim3 grid((unsigned int)((L.k2 + tk - 1) / tk), L.slots_used / 64);
-	k_tuner_audio<<<grid, AUD_THREADS, lds, st>>>(G.dem[L.parity], (size_t)(len - 1u) + L.k1, L.k2, L.d2, tk, L.slots,
+	hipError_t e = allow_lds((const void *)k_tuner_audio, P.lds_max, attr_done);
+	if (e != hipSuccess)
+		return e;
+	dim3 grid(P.grid_x, L.slots_used / 64);
+	k_tuner_audio<<<grid, AUD_THREADS, P.lds, st>>>(G.dem[L.parity], (size_t)(len - 1u) + L.k1, L.k2, L.d2, P.tk, L.slots,
 	                                      G.taps2, G.mode, G.audio, L.k2max, L.audio_scale,
 	                                      L.use_gain ? G.gain : nullptr, L.use_squelch ? G.squelch : nullptr,
 	                                      (const float2 *)G.chan_iq[L.cb], len);

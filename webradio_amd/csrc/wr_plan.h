@@ -1,0 +1,458 @@
+/*
+ * wr_plan.h -- the launch geometry of every tuner launch (the per-block DDC, the long-filter DDC, the post stage, the audio
+ * filter, the streaming launch): which kernel instance, how many workgroups per role, how much LDS, the group map, kslow,
+ * kmax, the post stage's runs of tiles.  The arithmetic alone, with no HIP call and no environment read, so that a CPU test
+ * can hold it to the rule (tests/test_launch_plan.py through tests/cxx/cpu_host_checks.cxx).  The launch functions
+ * (wr_kernels.hip, wr_stream_kernel.inc) obtain a plan, ask the runtime for what only it can give (allow_lds, the occupancy
+ * query), and launch with the plan's numbers.  The only home of the constants geometry depends on: the kernels use the
+ * same names.  Plain C++11.
+ */
+#ifndef WR_PLAN_H_
+#define WR_PLAN_H_
+
+#include <stddef.h>
+
+#include "webradio_amd.h"
+
+#define WR_HIST      (WR_FIR_LENGTH - 1)   /* 63 frames of FIR history, lowpass.cxx:133 */
+#define WR_SPLIT_N   256                   /* entries of the coarse and of the fine NCO table */
+#define WR_TAPSETS   4                     /* distinct channel filters a lane group may mix in the fast DDC kernel:
+                                              receivers of one tuner mostly share a passband (radio.cxx:78-79),
+                                              the UI lets each choose its own (receiverhandler.cxx:130-137) */
+#define WR_CU_LDS_BYTES (160u * 1024u)     /* LDS of one CU (gfx950) */
+
+/* ---- the post stage (post_role, k_tuner_post) ---- */
+#define POST_TK 16u                        /* audio frames per tile */
+#define POST_THREADS 512u
+
+/* ---- k_tuner_ddc.  LDS plan: [0, 128 KiB) the two replicated NCO tables (SPLIT only),
+ * then one private 2 x 512 B sample window per wave (double buffered across units). ---- */
+#define DDC_TABLE_BYTES   (2u * WR_SPLIT_N * 32u * 8u)
+#define DDC_WAVES         16u
+#define DDC_ROTATE_WAVES      8u          /* every ROTATE variant (folded or per-lane taps): 8-wave workgroups, */
+#define DDC_ROTATE_WGS_PER_CU 4u          /* four per CU */
+#define DDC_LDS_BYTES     (DDC_TABLE_BYTES + DDC_WAVES * 2u * 512u)
+#define DDC_NG2_WAVES_PER_EU 6u           /* NG = 2 (two lane groups per wave, k_tuner_ddc): 80 registers, 6 waves per SIMD */
+
+/* ---- k_tuner_ddc_long_rot ---- */
+#define LONG_ROT_WAVES 8u
+#define LONG_ROT_LDS   ((2u * WR_SPLIT_N + LONG_ROT_WAVES * 2u * 64u) * 8u + LONG_ROT_WAVES * 64u * 4u)
+
+/* ---- k_tuner_audio ---- */
+#define AUD_ROWS 352u          /* staged demod rows: 352 x 64 x 4 B = 88 KiB */
+#define AUD_TMAX 16u
+#define AUD_THREADS 1024u
+
+/* ---- k_tuner_stream: the audio filter lengths a launch is built for, by audio decimation: 64 and 128 taps at every one,
+ * 256 taps up to D2 = 3 -- from D2 = 4 on a 256-tap window is 85 KB and more, ONE workgroup per CU, and a launch needs two (a
+ * DDC and a post workgroup: wrp_stream_roles): those tuners keep their launch per block, and no kernel is built for them. */
+#define STREAM_NSEG4_MAX_D2 3u
+
+static inline unsigned int grid_for(size_t n, unsigned int block, unsigned int cap)
+{
+	size_t g = (n + block - 1) / block;
+	if (g < 1)
+		g = 1;
+	if (g > cap)
+		g = cap;
+	return (unsigned int)g;
+}
+
+/* ---- the group map: which lane groups a DDC launch works on, eight bits per entry, sixteen entries ---- */
+struct WrGroupMap {
+	unsigned long long gmap[2];
+	unsigned int ngroups;                  /* entries in use, 16 at most */
+	unsigned long long rest;               /* bit g: selected group g is beyond the 16 one launch maps */
+};
+
+/* `gsel`: bit g set = lane group g takes part (0 = all `slots_used / 64` of them, <= 64: wr_tuner_create caps max_channels) */
+static inline WrGroupMap wrp_group_map(unsigned int slots_used, unsigned long long gsel)
+{
+	WrGroupMap m = {{0, 0}, 0, 0};
+	const unsigned int allgroups = slots_used / 64u;
+	for (unsigned int g = 0; g < allgroups; ++g)
+		if (!gsel || ((gsel >> g) & 1ull)) {
+			if (m.ngroups < 16u) {
+				m.gmap[m.ngroups >> 3] |= (unsigned long long)g << ((m.ngroups & 7u) * 8u);
+				++m.ngroups;
+			} else {
+				m.rest |= 1ull << g;
+			}
+		}
+	return m;
+}
+
+/* the lane group of entry i < ngroups */
+static inline unsigned int wrp_group_at(const WrGroupMap &m, unsigned int i)
+{
+	return (unsigned int)((m.gmap[i >> 3] >> ((i & 7u) * 8u)) & 255u);
+}
+
+/* output frames of a block whose window reaches into the block before: the first ceil(63 / D1), k1 at most (a block
+ * without an output frame has none, whatever d1) */
+static inline unsigned int wrp_kslow(unsigned int d1, size_t k1)
+{
+	if (!k1 || !d1)
+		return 0;
+	const unsigned int kslow = (WR_HIST + d1 - 1u) / d1;
+	return kslow > k1 ? (unsigned int)k1 : kslow;
+}
+
+/* tap sets in a launch: the largest count among the lane groups it maps (`nsets`: WrTunerLaunch::nsets) */
+static inline unsigned int wrp_kmax(const WrGroupMap &m, const unsigned char *nsets)
+{
+	unsigned int kmax = 1;
+	for (unsigned int i = 0; i < m.ngroups; ++i) {
+		const unsigned int g = wrp_group_at(m, i);
+		if (g < 64u && nsets[g] > kmax)
+			kmax = nsets[g];
+	}
+	return kmax;
+}
+
+/* ---- The audio decimations the post stage is built for (anything else takes the two-kernel path): 1..6, and 8 and 10 --
+ * 256 k -> 32 k (BASELINE config 1), 240 k -> 24 k, 480 k -> 48 k.  with_post_d2 (wr_kernels.hip) instantiates these. ---- */
+#define WR_POST_D2_LIST 1, 2, 3, 4, 5, 6, 8, 10
+
+static inline bool wrp_post_d2_supported(unsigned int d2)
+{
+	static const unsigned int list[] = {WR_POST_D2_LIST};
+	for (size_t i = 0; i < sizeof(list) / sizeof(list[0]); ++i)
+		if (list[i] == d2)
+			return true;
+	return false;
+}
+
+/* LDS of a post-stage workgroup (post_role): the staged rows of (POST_TK - 1) d2 + 64 nseg frames, the tile, the modes */
+static inline size_t post_lds_bytes(unsigned int d2, unsigned int nseg)
+{
+	return (((size_t)(POST_TK - 1u) * d2 + WR_FIR_LENGTH * nseg) * 64u + POST_TK * 65u + 64u) * sizeof(float);
+}
+
+/* ---- post tiling: a lane group's `tiles` tiles of POST_TK audio frames go to workgroups in runs of `run` consecutive
+ * tiles, `ntiles` = ceil(tiles / run) workgroups per lane group.  Three rules. ---- */
+struct WrPostTiling {
+	unsigned int run, ntiles;
+};
+
+static inline unsigned int wrp_post_tiles(size_t k2)
+{
+	return (unsigned int)((k2 + POST_TK - 1) / POST_TK);
+}
+
+static inline WrPostTiling wrp_post_tiling(unsigned int tiles, unsigned int run)
+{
+	const WrPostTiling t = {run, (tiles + run - 1u) / run};
+	return t;
+}
+
+/* riding in a DDC launch (wrk_post_args): as long a run as still leaves every CU a few workgroups */
+static inline WrPostTiling wrp_post_tiling_riding(unsigned int tiles, unsigned int groups)
+{
+	const unsigned int all = tiles * groups;
+	/* measured at C2 (500 tiles a block), us per block: 1 block per launch, run 1 / 2 / 4:
+	 * 38.3 / 37.1 / 38.0; 4 blocks per launch: 33.6 / 32.3 / 32.2 */
+	return wrp_post_tiling(tiles, all >= 1536u ? 4u : all >= 384u ? 2u : 1u);
+}
+
+/* on its own (wrk_tuner_post_args) the post stage has the chip to itself and is a chain of latencies: one tile per
+ * workgroup, all of them in flight at once (runs of tiles are for the workgroups that ride in a
+ * DDC launch, where instructions are what is short); 15.4 against 18.2 us for a C2 block */
+static inline WrPostTiling wrp_post_tiling_alone(unsigned int tiles, unsigned int groups, unsigned int nseg)
+{
+	/* ... unless there are tiles enough to fill the chip several times over anyway (the flush behind a launch of
+	 * several blocks): runs of tiles then save the rows two neighbouring tiles share from being loaded and
+	 * demodulated twice (59 of 139 at D2 = 5) */
+	const unsigned int all = tiles * groups;
+	unsigned int run = all >= 4096u ? 2u : 1u;   /* C2, four blocks: 43.6 / 33.6 / 36.0 us at runs of 1 / 2 / 4 */
+	if (nseg == 4u && all >= 384u)
+		run = 2u;       /* 256 taps: a tile stages 331 rows for its 80 new ones (D2 = 5) and one workgroup fits a CU --
+		                   C2 (500 tiles), us per block all in at runs of 1 / 2 / 4: 93 / 83 / 104 (128 taps: 62 / 69 / 79),
+		                   profiles/r05_long_filter.txt */
+	return wrp_post_tiling(tiles, run);
+}
+
+/* post-stage tiles per workgroup for a launch that may keep `max_post` post workgroups resident */
+static inline unsigned int stream_post_run(unsigned int tiles, unsigned int groups, unsigned int max_post)
+{
+	unsigned int run = 1;
+	while (run < tiles && ((tiles + run - 1u) / run) * groups > max_post)
+		++run;
+	return run;
+}
+
+/* the streaming launch (wrk_tuner_stream), for the `n_post` post workgroups it keeps resident */
+struct WrStreamTiling {
+	unsigned int min_run;                  /* the shortest runs that give every task a workgroup of its own */
+	unsigned int run, ntiles;              /* what a block goes in while the host is ahead */
+	unsigned int drain_run, drain_ntiles;  /* ... and a host-paced stream's blocks, and a closed stream's last ones */
+	bool long_runs;                        /* `run` started from tasks for half the post workgroups, not from min_run */
+	unsigned int widened;                  /* tiles the small-block rule then added to it */
+};
+
+static inline WrStreamTiling wrp_post_tiling_stream(unsigned int tiles, unsigned int groups, unsigned int n_post)
+{
+	WrStreamTiling t;
+	/* (r06) tasks for HALF the post workgroups, not for all of them: a run's first tile demodulates its 59 rows of overlap a
+	 * second time and reads them a second time, and the launch runs at the package's power limit -- what a block costs is what
+	 * it spends (profiles/r06_power.txt).  C2: runs of 5 tiles (100 tasks a block, 1.15 x the rows) instead of 2 (252, 1.37 x):
+	 * 27.9-28.0 against 29.7 us per block; consecutive blocks' tasks go round the post workgroups (stream_post's `rot`), so two
+	 * blocks' post stages are in flight side by side.  Longer still (8: 28.6, 12: the post stage no longer keeps up) loses. */
+	t.min_run = stream_post_run(tiles, groups, n_post);
+	t.run = t.min_run;
+	t.long_runs = t.min_run >= 2u && n_post >= 8u;          /* (a block with more tiles than post workgroups: the throughput case) */
+	if (t.long_runs)
+		t.run = stream_post_run(tiles, groups, n_post / 2u);
+	/* (r06) small blocks: fewer, longer tasks -- up to four tiles each, down to a quarter of the post workgroups per block --
+	 * so that the post stages of up to four consecutive blocks are in flight on different workgroups (stream_post's `rot`):
+	 * a task's time is latency, and a 64 ms block of BASELINE config 1 is 128 tiles */
+	t.widened = 0;
+	while (t.run < 4u && t.run < tiles && ((tiles + t.run - 1u) / t.run) * groups > n_post / 4u &&
+	       ((tiles + t.run - 1u) / t.run) * groups <= n_post / 2u) {
+		++t.run;
+		++t.widened;
+	}
+	t.ntiles = (tiles + t.run - 1u) / t.run;
+	/* the stream's last blocks (tasks by ticket, the DDC workgroups helping): the shortest runs -- what ends a closed stream is
+	 * the latency of its last tasks (secondary.frontend's launch-per-block mode: 123 against 134 us with the long runs) */
+	t.drain_run = t.min_run < t.run ? t.min_run : t.run;
+	t.drain_ntiles = (tiles + t.drain_run - 1u) / t.drain_run;
+	/* (fewer post-stage tasks than workgroups set aside for them: the rest stay post workgroups -- consecutive blocks' tasks
+	 * go round them -- and do NOT go to the DDC: its waves share the stream's frames evenly and wait for one another at the
+	 * ring's end, so the launch runs at the pace of the fullest SIMD, r05) */
+	return t;
+}
+
+/* ---- the streaming launch ---- */
+
+/* LDS per workgroup: the post stage's stage and tile, or the DDC's NCO tables and window copies -- `nset` per buffer, two
+ * buffers per wave (the block-boundary role inside the post workgroups lays its windows out the same way).  EVERY
+ * workgroup of the launch reserves it (LDS is per kernel, not per role), so an audio filter of `nseg` x 64 taps decides how
+ * many workgroups a CU's 160 KB hold: at D2 = 5, 40 064 / 56 448 / 89 216 B for 64 / 128 / 256 taps */
+static inline size_t stream_lds_bytes(unsigned int d2, unsigned int nset, unsigned int nseg)
+{
+	const size_t post_lds = post_lds_bytes(d2, nseg) + 16u * sizeof(float);     /* (+ stream_post's `sh` words) */
+	const size_t ddc_lds = (size_t)DDC_ROTATE_WAVES * 2u * 512u * nset + 2u * WR_SPLIT_N * 8u;
+	return post_lds > ddc_lds ? post_lds : ddc_lds;
+}
+
+/* Which k_tuner_stream<PD2, NG, TS> a launch takes.  ONE channel filter for the whole tuner and an even number of lane
+ * groups: NG = 2 (two lane groups share a wave's window and its reads).  Otherwise one lane group per wave: TS = 1 while
+ * every lane group has a single channel filter (its own: hlane comes from the wave's lane group), TS = WR_TAPSETS
+ * when a lane group mixes several.  (Two lane groups with different filters do not share a wave: NG = 2 stays the
+ * one-filter shape, the one the headline runs, instruction for instruction.) */
+static inline void stream_shape(unsigned int groups, unsigned int kmax, bool one_filter, unsigned int *ng, unsigned int *ts)
+{
+	*ng = (one_filter && !(groups & 1u)) ? 2u : 1u;
+	*ts = kmax > 1u ? WR_TAPSETS : 1u;
+}
+
+static inline bool stream_nseg_supported(unsigned int d2, unsigned int nseg)
+{
+	return nseg == 1u || nseg == 2u || (nseg == 4u && d2 <= STREAM_NSEG4_MAX_D2);
+}
+
+/* the instance and the LDS request of a streaming launch; `ok` false: this launch shape cannot stream.  `kmax`: the most
+ * channel filters a lane group of the launch mixes; `one_filter`: one for the whole tuner; `nseg`: the audio filter's taps / 64 */
+struct WrStreamPlan {
+	bool ok;
+	unsigned int ng, ts;
+	size_t lds;
+};
+
+static inline WrStreamPlan wrp_stream_plan(unsigned int d2, unsigned int groups, unsigned int kmax, bool one_filter,
+                                           unsigned int nseg)
+{
+	WrStreamPlan p = {false, 0, 0, 0};
+	if (!wrp_post_d2_supported(d2) || !stream_nseg_supported(d2, nseg) || !groups || groups > 16u || !kmax || kmax > WR_TAPSETS)
+		return p;
+	p.ok = true;
+	stream_shape(groups, kmax, one_filter, &p.ng, &p.ts);
+	p.lds = stream_lds_bytes(d2, p.ts == 1u ? 1u : kmax, nseg);
+	return p;
+}
+
+/* How many workgroups of the streaming launch a device holds at once, split into roles.  Every workgroup of the
+ * launch must be resident (they wait for one another): the grid is never larger than what the occupancy query (`per_cu`)
+ * admits, capped at three per CU (what 80 registers and eight waves per workgroup give; the query can be one too
+ * generous near a register-file edge, MI355X_MICROARCH.md "Residency").
+ * An audio filter of 128 taps (and one of 256 up to D2 = 3) leaves a CU's LDS room for TWO workgroups, not three: one DDC
+ * workgroup per CU instead of two, the post stage's slot as before.  Fewer than two: no launch (256 taps from D2 = 4 on),
+ * and none on a device of four CUs or fewer, which has no post workgroup to give. */
+struct WrStreamRoles {
+	unsigned int n_ddc, n_post;            /* both 0: no launch */
+};
+
+static inline WrStreamRoles wrp_stream_roles(int per_cu, int num_cus)
+{
+	WrStreamRoles r = {0, 0};
+	if (per_cu > 3)
+		per_cu = 3;
+	if (per_cu < 2 || num_cus <= 4)
+		return r;
+	/* the same number of DDC workgroups on every CU (see wrk_tuner_stream), one slot per CU for the post stage and the bell */
+	r.n_ddc = (unsigned int)(per_cu - 1) * (unsigned int)num_cus;
+	r.n_post = (unsigned int)num_cus - 4u;                  /* (three workgroup slots of the chip stay free: a copy kernel of the runtime's
+	                                                           finds room without taking a slot the launch's own workgroups wait for) */
+	return r;
+}
+
+/* ---- the per-block DDC, k_tuner_ddc<NCO, UTAPS, PD2, NG>.  Waves per workgroup, persistent workgroups per CU:
+ *   ROTATE, uniform taps : 8 x 4 -- 64 VGPRs, 20 KiB of LDS: 8 waves per SIMD hide the recurrence's
+ *                                  dependent FMAs better than 4 (measured 35.6 -> 34.7 us); NG = 2: 8 x 3
+ *   ROTATE, per-lane taps: 8 x 4 -- one lane group's taps (16 KiB) per workgroup
+ *   SPLIT                : 16 x 1 -- the replicated tables take 128 KiB
+ *   EXACT                : 16 x 2 -- small LDS footprint, two workgroups hide the gather latency ---- */
+struct WrDdcPlan {
+	WrGroupMap map;                        /* ngroups 0: nothing to launch; rest: groups for further launches of their own */
+	unsigned int ng;                       /* lane groups per wave: 2 where the launch allows (see k_tuner_ddc: NG), else 1 */
+	unsigned int waves;                    /* per workgroup (W) */
+	unsigned int kmax;
+	size_t lds;
+	unsigned int wgs_per_cu;               /* persistent DDC workgroups per CU, after the post reserve and the LDS fit */
+	unsigned int post_wgs;                 /* workgroups of the riding post stage */
+	unsigned int kslow, n_bnd;             /* block-boundary frames, and the workgroups that take them */
+	size_t units;                          /* per wave and pass of its loop: NG lane groups */
+	unsigned int wgs;                      /* the persistent ones; the grid is wgs + n_bnd + post_wgs */
+};
+
+/* `pd2`: the audio decimation of the riding post stage of `post_ntiles + 1` workgroups for each of `post_groups` lane groups,
+ * or 0: none rides; `min_passes`: WR_TUNE_DDC_NG2_MIN_PASSES (0 = NG = 2 wherever the launch allows) */
+static inline WrDdcPlan wrp_ddc_plan(int nco, bool utaps, unsigned int pd2, unsigned int slots_used, unsigned long long gsel,
+                                     const unsigned char *nsets, bool one_filter, size_t k1, unsigned int d1, int num_cus,
+                                     size_t min_passes, unsigned int post_ntiles, unsigned int post_groups)
+{
+	WrDdcPlan p;
+	const bool rotate = nco == WR_NCO_ROTATE;
+	const unsigned int W = p.waves = rotate ? DDC_ROTATE_WAVES : DDC_WAVES;
+	p.map = wrp_group_map(slots_used, gsel);
+	const unsigned int ngroups = p.map.ngroups;
+	/* two lane groups per wave where the launch allows: an even number of lane groups, at most 16, all on one and the
+	 * same channel filter ... and enough output frames: a wave of the NG = 2 kernel does twice the work per pass of its
+	 * loop, so with few passes per wave the grid ends ragged (BASELINE config 5: 5 065 frames per chunk, 2.5 passes per
+	 * wave -- 48 us against 43 with one lane group per wave); from four passes on the shared reads win */
+	p.ng = 1u;
+	if (rotate && utaps) {
+		const size_t waves2 = (size_t)num_cus * (DDC_NG2_WAVES_PER_EU * 4u / W - (pd2 ? 1u : 0u)) * W;
+		if (one_filter && !p.map.rest && ngroups >= 2u && (ngroups & 1u) == 0u && k1 * (ngroups / 2u) >= min_passes * waves2)
+			p.ng = 2u;
+	}
+	/* tap sets: SPLIT one, its replicated tables leave no room for more windows */
+	p.kmax = (utaps && rotate) ? wrp_kmax(p.map, nsets) : 1u;
+	p.lds = (nco == WR_NCO_SPLIT) ? DDC_LDS_BYTES
+	        : (W * 2u * 512u * p.kmax) + (rotate ? 2u * WR_SPLIT_N * 8u : 0u) + (rotate && !utaps ? WR_FIR_LENGTH * 64u * 4u : 0u);
+	/* NG = 2: 80 registers, 6 waves per SIMD: three 8-wave workgroups per CU */
+	p.wgs_per_cu = (p.ng == 2u) ? DDC_NG2_WAVES_PER_EU * 4u / W : rotate ? DDC_ROTATE_WGS_PER_CU : (nco == WR_NCO_EXACT) ? 2u : 1u;
+	p.post_wgs = 0;
+	if (pd2 != 0u) {
+		/* the post workgroups' stage + tile set the LDS size of every workgroup of the launch;
+		 * POST_RESERVE workgroup slots per CU are left to them (they come and go, the DDC ones
+		 * persist).  Measured at C2, kernel duration (r02: per-slot turns, priorities by progress,
+		 * post workgroups at priority 3): 1 slot 38.2 us, 2 slots 39.7, 3 slots 49.8 (the DDC
+		 * starves); DDC + post as two launches: 31.3 + 15.2 + gap. */
+		const size_t post_lds = post_lds_bytes(pd2, 1u);
+		if (post_lds > p.lds)
+			p.lds = post_lds;
+		const unsigned int fit = (unsigned int)(WR_CU_LDS_BYTES / p.lds);
+		if (fit < p.wgs_per_cu)
+			p.wgs_per_cu = fit;
+		const unsigned int POST_RESERVE = 1u;
+		p.wgs_per_cu = (p.wgs_per_cu > POST_RESERVE) ? p.wgs_per_cu - POST_RESERVE : 1u;
+		p.post_wgs = (post_ntiles + 1u) * post_groups;
+	}
+	/* launched even for a block too short to yield a channel-rate frame: workgroup 0 still
+	 * advances the NCO (downconverter.cxx:103 runs per input frame) and rolls the histories */
+	/* (roles: ROTATE with folded taps) the first ceil(63 / D1) output frames of the block reach into the previous one: they go
+	 * to n_bnd workgroups of their own, one wave per (lane group, frame), and the persistent waves share the rest */
+	p.kslow = (rotate && utaps) ? wrp_kslow(d1, k1) : 0u;
+	p.n_bnd = (p.kslow * ngroups + W - 1u) / W;
+	p.units = (k1 - p.kslow) * (ngroups / p.ng);
+	p.wgs = (unsigned int)((p.units + W - 1) / W);
+	const unsigned int cap = (unsigned int)num_cus * p.wgs_per_cu;
+	if (p.wgs > cap)
+		p.wgs = cap;                                        /* every slot: the kernel evens the units out (DDC_DEAL_WAYS) */
+	if (rotate && !utaps) {
+		/* per-lane taps live in LDS, one lane group per WORKGROUP: a whole number of
+		 * workgroups per group, at least one */
+		if (ngroups)
+			p.wgs = (p.wgs / ngroups) * ngroups;
+		if (p.wgs < ngroups)
+			p.wgs = ngroups;
+	} else {
+		/* every lane group needs at least one wave of its own (the kernel deals waves to groups) */
+		const unsigned int min_wgs = (ngroups / p.ng + W - 1) / W;
+		if (p.wgs < min_wgs)
+			p.wgs = min_wgs;
+	}
+	return p;
+}
+
+/* ---- the long-filter DDC (wrk_tuner_ddc_long).  `rot`: k_tuner_ddc_long_rot takes every frame and rolls the state
+ * (a tolerance nco mode, one filter per lane group, a block with output frames); else k_tuner_ddc_long and
+ * k_ddc_long_roll ---- */
+struct WrLongPlan {
+	bool rot;
+	bool two;                              /* rot: two lane groups per wave (NG = 2) */
+	unsigned int wgs_r, post_wgs, roll_wgs;/* rot: workgroups per role; the grid is their sum */
+	size_t lds;                            /* rot */
+	unsigned int wgs;                      /* the exact kernel's, 0: not launched */
+	unsigned int rwgs;                     /* the roll kernel's */
+};
+
+/* `ride_d2`: the audio decimation of the riding post stage (as wrp_ddc_plan), or 0 */
+static inline WrLongPlan wrp_long_plan(bool rotate, bool one_filter, size_t k1, unsigned int groups, unsigned int len,
+                                       unsigned int slots, int num_cus, unsigned int ride_d2, unsigned int post_ntiles,
+                                       unsigned int post_groups)
+{
+	WrLongPlan p = {false, false, 0, 0, 0, 0, 0, 0};
+	const size_t roll_total = (size_t)(len - 1u) * slots;
+	p.rot = rotate && k1;
+	if (p.rot) {
+		const size_t units_r = k1 * groups;
+		p.two = one_filter && groups % 2u == 0;
+		p.wgs_r = (unsigned int)(((p.two ? units_r / 2 : units_r) + LONG_ROT_WAVES - 1u) / LONG_ROT_WAVES);
+		/* persistent: 32 waves per CU as before -- or 24 and one workgroup slot per CU left to the post workgroups, which
+		 * come and go beside the DDC ones (as in k_tuner_ddc) instead of queueing up behind them */
+		const unsigned int cap8 = (unsigned int)num_cus * (ride_d2 ? 3u : 4u);
+		if (p.wgs_r > cap8)
+			p.wgs_r = cap8;
+		p.post_wgs = ride_d2 ? (post_ntiles + 1u) * post_groups : 0u;
+		const size_t roll_wgs = (roll_total + LONG_ROT_WAVES * 64u - 1u) / (LONG_ROT_WAVES * 64u);
+		p.roll_wgs = roll_wgs > 256u ? 256u : (unsigned int)roll_wgs;
+		p.lds = LONG_ROT_LDS;
+		if (ride_d2 && post_lds_bytes(ride_d2, 1u) > p.lds)
+			p.lds = post_lds_bytes(ride_d2, 1u);
+		return p;
+	}
+	const size_t units = k1 * groups;
+	p.wgs = (unsigned int)((units + 3) / 4);
+	const unsigned int cap = (unsigned int)num_cus * 8u;
+	if (p.wgs > cap)
+		p.wgs = cap;
+	p.rwgs = (unsigned int)((roll_total + 255) / 256 > 1024 ? 1024 : (roll_total + 255) / 256);
+	return p;
+}
+
+/* ---- the audio filter on its own (wrk_tuner_audio): `len` taps, 64 or 128 / 256 ---- */
+struct WrAudioPlan {
+	unsigned int tk;                       /* output frames per tile: as many as the staged rows allow */
+	unsigned int need;                     /* staged rows */
+	size_t lds;                            /* sized to what this decimation needs, so that two workgroups fit a CU when D2 is small */
+	size_t lds_max;                        /* the most the kernel asks for: 156 KiB of 160 */
+	unsigned int grid_x;                   /* tiles; grid.y is the lane groups */
+};
+
+static inline WrAudioPlan wrp_audio_plan(size_t k2, unsigned int d2, unsigned int len)
+{
+	WrAudioPlan p;
+	p.tk = AUD_TMAX;
+	if (d2 > 1 && (AUD_ROWS - len) / d2 + 1u < p.tk)
+		p.tk = (AUD_ROWS - len) / d2 + 1u;
+	p.need = (p.tk - 1u) * d2 + len;
+	p.lds = ((size_t)p.need * 64u + (size_t)len * 64u + AUD_TMAX * 65u) * sizeof(float);
+	p.lds_max = ((size_t)AUD_ROWS * 64u + (size_t)WR_FIR_FUSED_MAX * 64u + AUD_TMAX * 65u) * sizeof(float);
+	p.grid_x = (unsigned int)((k2 + p.tk - 1) / p.tk);
+	return p;
+}
+
+#endif /* WR_PLAN_H_ */

@@ -855,45 +855,9 @@ k_tuner_stream(const WrStreamArgs S)
 	stream_post<PD2, TS, NSEG>(S, ddc ? blockIdx.x : blockIdx.x - S.n_ddc, lds, ddc);
 }
 
-/* post-stage tiles per workgroup for a launch that may keep `max_post` post workgroups resident */
-static unsigned int stream_post_run(unsigned int tiles, unsigned int groups, unsigned int max_post)
-{
-	unsigned int run = 1;
-	while (run < tiles && ((tiles + run - 1u) / run) * groups > max_post)
-		++run;
-	return run;
-}
+/* (which instance a launch takes, its LDS and its roles: wrp_stream_plan, wrp_stream_roles; its post tiling:
+ * wrp_post_tiling_stream -- wr_plan.h) */
 
-/* LDS per workgroup: the post stage's stage and tile, or the DDC's NCO tables and window copies -- `nset` per buffer, two
- * buffers per wave (the block-boundary role inside the post workgroups lays its windows out the same way).  EVERY
- * workgroup of the launch reserves it (LDS is per kernel, not per role), so an audio filter of `nseg` x 64 taps decides how
- * many workgroups a CU's 160 KB hold: at D2 = 5, 40 064 / 56 448 / 89 216 B for 64 / 128 / 256 taps (DESIGN.md 3.6) */
-static size_t stream_lds_bytes(unsigned int d2, unsigned int nset, unsigned int nseg)
-{
-	const size_t post_lds = post_lds_bytes(d2, nseg) + 16u * sizeof(float);     /* (+ stream_post's `sh` words) */
-	const size_t ddc_lds = (size_t)DDC_ROTATE_WAVES * 2u * 512u * nset + 2u * WR_SPLIT_N * 8u;
-	return post_lds > ddc_lds ? post_lds : ddc_lds;
-}
-
-/* Which k_tuner_stream<PD2, NG, TS> a launch takes.  ONE channel filter for the whole tuner and an even number of lane
- * groups: NG = 2 (two lane groups share a wave's window and its reads).  Otherwise one lane group per wave: TS = 1 while
- * every lane group has a single channel filter (its own: hlane comes from the wave's lane group), TS = WR_TAPSETS
- * when a lane group mixes several.  (Two lane groups with different filters do not share a wave: NG = 2 stays the
- * one-filter shape, the one the headline runs, instruction for instruction.) */
-static void stream_shape(unsigned int groups, unsigned int kmax, bool one_filter, unsigned int *ng, unsigned int *ts)
-{
-	*ng = (one_filter && !(groups & 1u)) ? 2u : 1u;
-	*ts = kmax > 1u ? WR_TAPSETS : 1u;
-}
-
-/* The audio filter lengths a launch is built for, by audio decimation: 64 and 128 taps at every one, 256 taps up to
- * D2 = 3 -- from D2 = 4 on a 256-tap window is 85 KB and more, ONE workgroup per CU, and a launch needs two (a DDC and a post
- * workgroup: wrk_stream_geometry): those tuners keep their launch per block, and no kernel is built for them. */
-#define STREAM_NSEG4_MAX_D2 3u
-static bool stream_nseg_supported(unsigned int d2, unsigned int nseg)
-{
-	return nseg == 1u || nseg == 2u || (nseg == 4u && d2 <= STREAM_NSEG4_MAX_D2);
-}
 /* calls f with the run-time nseg as a compile-time constant; a length the launch is not built for: hipErrorInvalidValue */
 template <unsigned int PD2, class F>
 static hipError_t with_stream_nseg(unsigned int nseg, F &&f)
@@ -906,6 +870,24 @@ static hipError_t with_stream_nseg(unsigned int nseg, F &&f)
 		if (nseg == 4u)
 			return f(std::integral_constant<unsigned int, 4u>());
 	return hipErrorInvalidValue;
+}
+
+/* calls f(StreamInst<PD2, NG, TS, NSEG>()) for the instance the plan `P` of a launch with audio decimation `d2` and `nseg` names */
+template <unsigned int PD2_, unsigned int NG_, unsigned int TS_, unsigned int NSEG_> struct StreamInst {
+	static constexpr unsigned int PD2 = PD2_, NG = NG_, TS = TS_, NSEG = NSEG_;
+};
+template <class F>
+static hipError_t with_stream_instance(const WrStreamPlan &P, unsigned int d2, unsigned int nseg, F &&f)
+{
+	return with_post_d2(d2, [&](auto D2) {
+		constexpr unsigned int PD2 = decltype(D2)::value;
+		return with_stream_nseg<PD2>(nseg, [&](auto NS) {
+			constexpr unsigned int NSEG = decltype(NS)::value;
+			return P.ts != 1u ? f(StreamInst<PD2, 1, WR_TAPSETS, NSEG>())
+			       : P.ng == 1u ? f(StreamInst<PD2, 1, 1, NSEG>())
+			                    : f(StreamInst<PD2, 2, 1, NSEG>());
+		});
+	});
 }
 
 /* An instance's dynamic LDS above 64 KB must be allowed once per device (allow_lds remembers that it has been): the MOST
@@ -921,70 +903,30 @@ static hipError_t stream_allow_lds(size_t lds)
 	return allow_lds((const void *)k_tuner_stream<PD2, NG, TS, NSEG>, stream_lds_bytes(PD2, TS, NSEG), attr_done);
 }
 
-template <unsigned int PD2, unsigned int NG, unsigned int TS, unsigned int NSEG>
-static hipError_t stream_occupancy(size_t lds, int *per_cu)
-{
-	hipError_t e = stream_allow_lds<PD2, NG, TS, NSEG>(lds);
-	if (e != hipSuccess)
-		return e;
-	return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_tuner_stream<PD2, NG, TS, NSEG>, (int)(DDC_ROTATE_WAVES * 64u), lds);
-}
-
-/* How many workgroups of the streaming launch a device holds at once, split into roles.  Every workgroup of the
- * launch must be resident (they wait for one another): the grid is never larger than what the occupancy query
- * admits, capped at three per CU (what 80 registers and eight waves per workgroup give; the query can be one too
- * generous near a register-file edge, MI355X_MICROARCH.md "Residency").  `kmax`: the most channel filters a lane group
- * of the launch mixes; `one_filter`: one for the whole tuner (stream_shape); `nseg`: the audio filter's taps / 64.
- * An audio filter of 128 taps (and one of 256 up to D2 = 3) leaves a CU's LDS room for TWO workgroups, not three: one DDC
- * workgroup per CU instead of two, the post stage's slot as before.  Fewer than two: no launch (256 taps from D2 = 4 on). */
+/* How many workgroups of the streaming launch a device holds at once, split into roles (wrp_stream_roles), by the
+ * occupancy query for the instance the launch takes */
 hipError_t wrk_stream_geometry(unsigned int d2, unsigned int groups, unsigned int kmax, bool one_filter, unsigned int nseg,
                                int num_cus, unsigned int *n_ddc, unsigned int *n_post)
 {
 	*n_ddc = *n_post = 0;
-	if (!wrk_tuner_post_supported(d2) || !stream_nseg_supported(d2, nseg) || !groups || groups > 16u || !kmax ||
-	    kmax > WR_TAPSETS)
+	const WrStreamPlan P = wrp_stream_plan(d2, groups, kmax, one_filter, nseg);
+	if (!P.ok)
 		return hipSuccess;
-	unsigned int ng, ts;
-	stream_shape(groups, kmax, one_filter, &ng, &ts);
-	const size_t lds = stream_lds_bytes(d2, ts == 1u ? 1u : kmax, nseg);
 	int per_cu = 0;
-	hipError_t e = with_post_d2(d2, [&](auto D2) {
-		constexpr unsigned int PD2 = decltype(D2)::value;
-		return with_stream_nseg<PD2>(nseg, [&](auto NS) {
-			constexpr unsigned int NSEG = decltype(NS)::value;
-			return ts != 1u ? stream_occupancy<PD2, 1, WR_TAPSETS, NSEG>(lds, &per_cu)
-			       : ng == 1u ? stream_occupancy<PD2, 1, 1, NSEG>(lds, &per_cu)
-			                  : stream_occupancy<PD2, 2, 1, NSEG>(lds, &per_cu);
-		});
+	hipError_t e = with_stream_instance(P, d2, nseg, [&](auto I) {
+		using K = decltype(I);
+		hipError_t e2 = stream_allow_lds<K::PD2, K::NG, K::TS, K::NSEG>(P.lds);
+		if (e2 != hipSuccess)
+			return e2;
+		return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_tuner_stream<K::PD2, K::NG, K::TS, K::NSEG>,
+		                                                    (int)(DDC_ROTATE_WAVES * 64u), P.lds);
 	});
 	if (e != hipSuccess)
 		return e;
-	if (per_cu > 3)
-		per_cu = 3;
-	if (per_cu < 2)
-		return hipSuccess;
-	/* the same number of DDC workgroups on every CU (see wrk_tuner_stream), one slot per CU for the post stage and the bell */
-	*n_ddc = (unsigned int)(per_cu - 1) * (unsigned int)num_cus;
-	*n_post = (unsigned int)num_cus - 4u;               /* (three workgroup slots of the chip stay free: a copy kernel of the runtime's
-	                                                       finds room without taking a slot the launch's own workgroups wait for) */
+	const WrStreamRoles R = wrp_stream_roles(per_cu, num_cus);
+	*n_ddc = R.n_ddc;
+	*n_post = R.n_post;
 	return hipSuccess;
-}
-
-template <unsigned int PD2, unsigned int NG, unsigned int TS, unsigned int NSEG>
-static hipError_t launch_stream(hipStream_t st, const WrStreamArgs &A, void *ev_start, void *ev_stop)
-{
-	const size_t lds = stream_lds_bytes(PD2, TS == 1u ? 1u : A.kmax, NSEG);
-	hipError_t e = stream_allow_lds<PD2, NG, TS, NSEG>(lds);
-	if (e != hipSuccess)
-		return e;
-	const unsigned int grid = A.n_ddc + A.n_post + 1u;
-	if (ev_start || ev_stop) {
-		hipExtLaunchKernelGGL((k_tuner_stream<PD2, NG, TS, NSEG>), dim3(grid), dim3(DDC_ROTATE_WAVES * 64u), (uint32_t)lds, st,
-		                      (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 0u, A);
-		return hipGetLastError();
-	}
-	k_tuner_stream<PD2, NG, TS, NSEG><<<grid, DDC_ROTATE_WAVES * 64u, lds, st>>>(A);
-	return hipGetLastError();
 }
 
 /* `A.post` comes from wrk_post_args for ONE block of the stream; its tiling is redone here for the post workgroups
@@ -992,50 +934,26 @@ static hipError_t launch_stream(hipStream_t st, const WrStreamArgs &A, void *ev_
 hipError_t wrk_tuner_stream(hipStream_t st, const WrStreamArgs &A0, void *ev_start, void *ev_stop)
 {
 	WrStreamArgs A = A0;
-	if (!A.n_ddc || !A.n_post || !A.groups || A.groups > 16u || !A.k1)
+	if (!A.n_ddc || !A.n_post || !A.k1)
 		return hipErrorInvalidValue;
-	/* (r06) tasks for HALF the post workgroups, not for all of them: a run's first tile demodulates its 59 rows of overlap a
-	 * second time and reads them a second time, and the launch runs at the package's power limit -- what a block costs is what
-	 * it spends (profiles/r06_power.txt).  C2: runs of 5 tiles (100 tasks a block, 1.15 x the rows) instead of 2 (252, 1.37 x):
-	 * 27.9-28.0 against 29.7 us per block; consecutive blocks' tasks go round the post workgroups (stream_post's `rot`), so two
-	 * blocks' post stages are in flight side by side.  Longer still (8: 28.6, 12: the post stage no longer keeps up) loses. */
-	const unsigned int min_run = stream_post_run(A.post.tiles, A.post.groups, A.n_post);
-	A.post.run = min_run;
-	if (min_run >= 2u && A.n_post >= 8u)                    /* (a block with more tiles than post workgroups: the throughput case) */
-		A.post.run = stream_post_run(A.post.tiles, A.post.groups, A.n_post / 2u);
-	/* (r06) small blocks: fewer, longer tasks -- up to four tiles each, down to a quarter of the post workgroups per block --
-	 * so that the post stages of up to four consecutive blocks are in flight on different workgroups (stream_post's `rot`):
-	 * a task's time is latency, and a 64 ms block of BASELINE config 1 is 128 tiles */
-	while (A.post.run < 4u && A.post.run < A.post.tiles &&
-	       ((A.post.tiles + A.post.run - 1u) / A.post.run) * A.post.groups > A.n_post / 4u &&
-	       ((A.post.tiles + A.post.run - 1u) / A.post.run) * A.post.groups <= A.n_post / 2u)
-		++A.post.run;
-	A.post.ntiles = (A.post.tiles + A.post.run - 1u) / A.post.run;
-	/* the stream's last blocks (tasks by ticket, the DDC workgroups helping): the shortest runs -- what ends a closed stream is
-	 * the latency of its last tasks (secondary.frontend's launch-per-block mode: 123 against 134 us with the long runs) */
-	A.drain_run = min_run < A.post.run ? min_run : A.post.run;
-	A.drain_ntiles = (A.post.tiles + A.drain_run - 1u) / A.drain_run;
-	const unsigned int tasks = A.post.ntiles * A.post.groups;
-	/* (fewer post-stage tasks than workgroups set aside for them: the rest stay post workgroups -- consecutive blocks' tasks
-	 * go round them -- and do NOT go to the DDC: its waves share the stream's frames evenly and wait for one another at the
-	 * ring's end, so the launch runs at the pace of the fullest SIMD, r05) */
-	(void)tasks;
-	if (!A.kmax || A.kmax > WR_TAPSETS)
-		return hipErrorInvalidValue;
-	unsigned int ng, ts;
-	stream_shape(A.groups, A.kmax, A.one_filter != 0u, &ng, &ts);
-	if ((size_t)A.n_ddc * DDC_ROTATE_WAVES < A.groups / ng)
+	const WrStreamPlan P = wrp_stream_plan(A.post.d2, A.groups, A.kmax, A.one_filter != 0u, A.post.nseg);
+	if (!P.ok || (size_t)A.n_ddc * DDC_ROTATE_WAVES < A.groups / P.ng)
 		return hipErrorInvalidValue;
 	/* (a block shorter than the audio filter has no L2 - 1 rows of history for the block behind it: wrc_stream_open) */
 	if (A.k1 < WR_FIR_LENGTH * A.post.nseg)
 		return hipErrorInvalidValue;
-	return with_post_d2(A.post.d2, [&](auto D2) {
-		constexpr unsigned int PD2 = decltype(D2)::value;
-		return with_stream_nseg<PD2>(A.post.nseg, [&](auto NS) {
-			constexpr unsigned int NSEG = decltype(NS)::value;
-			return ts != 1u ? launch_stream<PD2, 1, WR_TAPSETS, NSEG>(st, A, ev_start, ev_stop)
-			       : ng == 2u ? launch_stream<PD2, 2, 1, NSEG>(st, A, ev_start, ev_stop)
-			                  : launch_stream<PD2, 1, 1, NSEG>(st, A, ev_start, ev_stop);
-		});
+	const WrStreamTiling T = wrp_post_tiling_stream(A.post.tiles, A.post.groups, A.n_post);
+	A.post.run = T.run;
+	A.post.ntiles = T.ntiles;
+	A.drain_run = T.drain_run;
+	A.drain_ntiles = T.drain_ntiles;
+	return with_stream_instance(P, A.post.d2, A.post.nseg, [&](auto I) {
+		using K = decltype(I);
+		hipError_t e = stream_allow_lds<K::PD2, K::NG, K::TS, K::NSEG>(P.lds);
+		if (e != hipSuccess)
+			return e;
+		launch_stamped(k_tuner_stream<K::PD2, K::NG, K::TS, K::NSEG>, dim3(A.n_ddc + A.n_post + 1u), dim3(DDC_ROTATE_WAVES * 64u), P.lds, st,
+		               ev_start, ev_stop, A);
+		return hipGetLastError();
 	});
 }

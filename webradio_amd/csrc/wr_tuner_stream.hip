@@ -173,10 +173,8 @@ int wrc_stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, bool *
 	const unsigned long long used_mask = (1ull << groups) - 1ull;
 	if ((g->fewsets_mask & used_mask) != used_mask)
 		return WR_OK;
-	unsigned int kmax = 1;
-	for (unsigned int gi = 0; gi < groups; ++gi)
-		if (g->nsets[gi] > kmax)
-			kmax = g->nsets[gi];
+	const WrGroupMap map = wrp_group_map(used, 0);              /* (all of them, groups <= 16: rest = 0) */
+	const unsigned int kmax = wrp_kmax(map, g->nsets);
 	if (int rc = wrc_dev_settle_stream(d))                      /* another tuner's launch in this context */
 		return rc;
 	{
@@ -248,11 +246,9 @@ int wrc_stream_open(wr_tuner *t, const void *iq, size_t nframes, bool u8, bool *
 	A.ext = s.ext ? 1u : 0u;
 	A.slots = g->slots;
 	A.groups = groups;
-	for (unsigned int gi = 0; gi < groups; ++gi)
-		(gi < 8u ? A.gmap0 : A.gmap1) |= (unsigned long long)gi << ((gi & 7u) * 8u);
-	A.kslow = (WR_HIST + g->d1 - 1u) / g->d1;
-	if (A.kslow > k1)
-		A.kslow = (unsigned int)k1;
+	A.gmap0 = map.gmap[0];
+	A.gmap1 = map.gmap[1];
+	A.kslow = wrp_kslow(g->d1, k1);
 	A.hist = L.hist;
 	A.hist_next = L.hist_next;
 	A.phase = g->dev.phase[g->sp];
