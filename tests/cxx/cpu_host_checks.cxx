@@ -249,6 +249,67 @@ extern "C" unsigned int wr_plan_grid_for(unsigned long n, unsigned int block, un
 	return grid_for(n, block, cap);
 }
 
+/* ---- the spectrum launches ---- */
+/* out[7]: points, n1, n2, sub, path, lds_max, real */
+extern "C" void wr_plan_fft_shape(unsigned int n, unsigned int channels, unsigned long long *out)
+{
+	const WrFftShape s = wrp_fft_shape(n, channels);
+	out[0] = s.points;
+	out[1] = s.n1;
+	out[2] = s.n2;
+	out[3] = s.sub;
+	out[4] = s.path;
+	out[5] = s.lds_max;
+	out[6] = s.real;
+}
+
+/* one batch of `batch` frames; out[11]: ct, rt, fpw, lds1, lds2, g1x, g1y, g2x, g2y, g3x, g3y */
+extern "C" void wr_plan_fft_launch(unsigned int n, unsigned int channels, unsigned long batch, unsigned long long *out)
+{
+	const WrFftLaunch l = wrp_fft_launch(wrp_fft_shape(n, channels), batch);
+	out[0] = l.ct;
+	out[1] = l.rt;
+	out[2] = l.fpw;
+	out[3] = l.lds1;
+	out[4] = l.lds2;
+	out[5] = l.g1x;
+	out[6] = l.g1y;
+	out[7] = l.g2x;
+	out[8] = l.g2y;
+	out[9] = l.g3x;
+	out[10] = l.g3y;
+}
+
+extern "C" unsigned long wr_plan_fft_work_frames(unsigned int n, unsigned long have, unsigned long want_frames)
+{
+	return wrp_fft_work_frames(n, have, want_frames);
+}
+
+extern "C" unsigned long wr_plan_fft_chunk(unsigned long remaining, unsigned long work_frames)
+{
+	return wrp_fft_chunk(remaining, work_frames);
+}
+
+extern "C" unsigned long wr_plan_fft_untangle_offset(unsigned long work_frames, unsigned int m)
+{
+	return wrp_fft_untangle_offset(work_frames, m);
+}
+
+extern "C" unsigned int wr_plan_fft_cols_ct(unsigned int n, unsigned int cols, int num_cus)
+{
+	return wrp_fft_cols_ct(n, cols, num_cus);
+}
+
+/* out[5]: FFT_THREADS, FFT_LDS_POINTS, FFT64K_P1_LONG_MIN, FFT_DB_GRID_CAP, FFT_WATERFALL_GRID_CAP */
+extern "C" void wr_plan_fft_constants(unsigned int *out)
+{
+	out[0] = FFT_THREADS;
+	out[1] = FFT_LDS_POINTS;
+	out[2] = FFT64K_P1_LONG_MIN;
+	out[3] = FFT_DB_GRID_CAP;
+	out[4] = FFT_WATERFALL_GRID_CAP;
+}
+
 /* ---- device hand-over bookkeeping of DspBlock (no GPU involved: pointers are just tokens) ---- */
 namespace {
 struct Src : public DspSource {

@@ -1,4 +1,4 @@
-"""The launch plans of the tuner's kernels (webradio_amd/csrc/wr_plan.h) through tests/cxx/libwr_cpu_host_checks.so: plain
+"""The launch plans of the tuner's kernels and of the spectrum launches (webradio_amd/csrc/wr_plan.h) through tests/cxx/libwr_cpu_host_checks.so: plain
 arithmetic, no GPU.  What tests/test_launch_plan.py holds to hand-worked figures, and where a GPU test that has to know which
 branch of a rule a case reaches asks the rule itself."""
 import ctypes as C
@@ -17,6 +17,9 @@ StreamTiling = namedtuple("StreamTiling", "tiles min_run run ntiles drain_run dr
 DdcPlan = namedtuple("DdcPlan", "ngroups rest ng waves kmax lds wgs_per_cu post_wgs kslow n_bnd units wgs")
 LongPlan = namedtuple("LongPlan", "rot two wgs_r post_wgs roll_wgs lds wgs rwgs")
 AudioPlan = namedtuple("AudioPlan", "tk need lds lds_max grid_x")
+FFT_SINGLE, FFT_FOUR_STEP, FFT_REG64K = 0, 1, 2           # WrFftPath
+FftShape = namedtuple("FftShape", "points n1 n2 sub path lds_max real")
+FftLaunch = namedtuple("FftLaunch", "ct rt fpw lds1 lds2 grid1 grid2 grid3")
 
 _lib = None
 
@@ -46,6 +49,13 @@ def lib():
             ("wr_plan_long", None, [i, i, ul, u, u, u, i, u, u, u, pull]),
             ("wr_plan_audio", None, [ul, u, u, pull]),
             ("wr_plan_grid_for", u, [ul, u, u]),
+            ("wr_plan_fft_shape", None, [u, u, pull]),
+            ("wr_plan_fft_launch", None, [u, u, ul, pull]),
+            ("wr_plan_fft_work_frames", ul, [u, ul, ul]),
+            ("wr_plan_fft_chunk", ul, [ul, ul]),
+            ("wr_plan_fft_untangle_offset", ul, [ul, u]),
+            ("wr_plan_fft_cols_ct", u, [u, u, i]),
+            ("wr_plan_fft_constants", None, [pu]),
         ]:
             f = getattr(L, name)
             f.restype, f.argtypes = res, args
@@ -115,3 +125,39 @@ def audio_plan(k2, d2, length):
     out = (C.c_ulonglong * 5)()
     lib().wr_plan_audio(k2, d2, length, out)
     return AudioPlan(*out)
+
+
+def fft_shape(n, real=False):
+    out = (C.c_ulonglong * 7)()
+    lib().wr_plan_fft_shape(n, 1 if real else 2, out)
+    return FftShape(*out[:6], bool(out[6]))
+
+
+def fft_launch(n, batch, real=False):
+    """one batch; the grids as (x, y), (0, 0): no such launch"""
+    o = (C.c_ulonglong * 11)()
+    lib().wr_plan_fft_launch(n, 1 if real else 2, batch, o)
+    return FftLaunch(*o[:5], (o[5], o[6]), (o[7], o[8]), (o[9], o[10]))
+
+
+def fft_work_frames(n, have, want_frames):
+    return lib().wr_plan_fft_work_frames(n, have, want_frames)
+
+
+def fft_chunks(n, frames, have=1):
+    """the batches a call of `frames` frames runs as, after the work area has grown for it"""
+    work, left, got = fft_work_frames(n, have, frames), frames, []
+    while left:
+        got.append(lib().wr_plan_fft_chunk(left, work))
+        left -= got[-1]
+    return got
+
+
+def fft_cols_ct(n, cols, num_cus):
+    return lib().wr_plan_fft_cols_ct(n, cols, num_cus)
+
+
+def fft_constants():
+    out = (C.c_uint * 5)()
+    lib().wr_plan_fft_constants(out)
+    return dict(zip("threads lds_points p1_long_min db_grid_cap waterfall_grid_cap".split(), out))

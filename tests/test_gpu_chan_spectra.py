@@ -9,7 +9,9 @@ import ctypes as C
 
 import numpy as np
 import pytest
+import torch
 
+import launch_plan
 from test_gpu_spectrum_real import _bits, _check_db
 from webradio_amd import capi, synth
 from webradio_amd.device import Spectrum, Tuner
@@ -106,9 +108,11 @@ def test_a_single_receiver(dev, oracle):
 
 @pytest.mark.parametrize("nrx", [449, 961], ids=["512-slots", "1024-slots"])
 def test_more_slots_than_compute_units(dev, oracle, nrx):
-    """Columns share a workgroup only where there are more of them than compute units (256 on an MI355X: two columns per
-    workgroup at 512 slots, four at 1024).  Rows at both ends of the first and of the last tile, and across a lane group."""
+    """Columns share a workgroup only where there are more of them than compute units (wrp_fft_cols_ct; 256 on an MI355X: two
+    columns per workgroup at 512 slots, four at 1024).  Rows at both ends of the first and of the last tile, and across a lane group."""
     n, k1 = 64, 80
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert launch_plan.fft_cols_ct(n, (nrx + 63) // 64 * 64, cus) > 1, "on this device the case does not reach the branch it is about"
     x = dev.upload(_stream(k1 * D1, seed=nrx))
     t = Tuner(dev, FS, nrx, k1 * D1, capi.WR_NCO_ROTATE)
     chans = [t.add_receiver((c % NRX - NRX // 2) * 30_000 + 99, 100_000, CHAN_RATE, capi.WR_FM, 8_000, AUDIO_RATE)

@@ -71,6 +71,23 @@ def test_every_iq_size(dev, oracle, n):
     s.destroy()
 
 
+def test_small_plan_then_large_plan(dev, oracle):
+    """The limit on a kernel's dynamic LDS is raised once per device and kernel and then remembered.  So, in one test on
+    one device, every such kernel first at a size that needs no raised limit and then at its largest LDS: the one order
+    in which a remembered limit could be too small."""
+    for real, small, large in [(False, 8, 8192),            # k_fft_single: 128 B, then 128 KiB
+                               (False, 16384, 262144),      # k_fft_pass1<false> and k_fft_pass2: 32 KiB, then 128 KiB
+                               (True, 16, 16384),           # k_fft_real_single
+                               (True, 32768, 524288)]:      # k_fft_pass1<true>, and k_fft_pass2 again, from a real plan
+        for n in (small, large):
+            x = flat(n if real else 2 * n, seed=900 + n)
+            s = Spectrum(dev, n, real=real)
+            s.push_host(x)
+            assert s.frames_done() == 1
+            _check_newest(s, x if real else x.view(np.complex64), "small then large, %s" % ("real" if real else "IQ"))
+            s.destroy()
+
+
 BATCHES = [
     # k_fft_single
     (8, 3, 300), (512, 128, 70), (8192, 1000, 9),

@@ -1,4 +1,4 @@
-"""The launch geometry of the tuner's kernels (webradio_amd/csrc/wr_plan.h): the arithmetic alone, no GPU.  Every expected
+"""The launch geometry of the tuner's kernels and of the spectrum launches (webradio_amd/csrc/wr_plan.h): the arithmetic alone, no GPU.  Every expected
 figure is worked by hand from the rule as the launch functions had it before the plans were split out of them (the working
 stands beside each), never taken from a run of the code under test."""
 import pytest
@@ -267,3 +267,121 @@ def test_tilings_cover_every_tile_once():
                 assert t.drain_run == t.min_run <= t.run <= tiles, at
                 # every task of the short runs has a post workgroup of its own, unless a lane group's tiles are one task already
                 assert t.drain_ntiles * groups <= n_post or t.min_run == tiles, at
+
+
+# ---- the spectrum launches ------------------------------------------------------------------------------------------------
+# A transform of `points` complex points (the frame's n; a real frame's n / 2 packed ones) is a single pass up to 8192 points --
+# two LDS buffers of 64 KiB -- and n1 x n2 above, n1 = 2^ceil(bits / 2); sub = max(n1, n2).  65536 IQ points: the register path.
+SINGLE, FOUR, REG = lp.FFT_SINGLE, lp.FFT_FOUR_STEP, lp.FFT_REG64K
+KIB = 1024
+
+
+def test_fft_constants():
+    assert lp.fft_constants() == dict(threads=256, lds_points=8192, p1_long_min=96, db_grid_cap=1024, waterfall_grid_cap=4096)
+    # k_bins_to_db strides from 1024 * 256 bins on; k_waterfall_row never does: 2^20 / 256 = 4096 is the widest row there is
+    g = lp.lib().wr_plan_grid_for
+    assert [g(n, 256, 1024) for n in (8, 256, 257, 262144, 524288, 1 << 20)] == [1, 1, 2, 1024, 1024, 1024]
+    assert [g(w, 256, 4096) for w in (1, 512, 65536, 1 << 20)] == [1, 2, 256, 4096]
+
+
+@pytest.mark.parametrize("n,real,n1,n2,path", [
+    (8, False, 8, 1, SINGLE), (8192, False, 8192, 1, SINGLE),
+    (16384, False, 128, 128, FOUR),         # 14 bits: 2^7
+    (32768, False, 256, 128, FOUR),         # 15 bits: 2^8
+    (65536, False, 256, 256, REG),
+    (131072, False, 512, 256, FOUR),        # 17 bits: 2^9
+    (262144, False, 512, 512, FOUR),
+    (524288, False, 1024, 512, FOUR),       # 19 bits: 2^10
+    (1048576, False, 1024, 1024, FOUR),
+    # real: the shape of n / 2 points
+    (8, True, 4, 1, SINGLE), (16384, True, 8192, 1, SINGLE),
+    (32768, True, 128, 128, FOUR), (65536, True, 256, 128, FOUR),
+    (131072, True, 256, 256, FOUR),         # 65536 packed points: the register path is for IQ frames only
+    (1048576, True, 1024, 512, FOUR),
+])
+def test_fft_shape(n, real, n1, n2, path):
+    s = lp.fft_shape(n, real)
+    assert s == (n // 2 if real else n, n1, n2, 0 if n2 == 1 else max(n1, n2), path, 128 * KIB, real)
+
+
+def test_fft_single_pass_launch():
+    # both buffers: 2 * points * 8 bytes; a workgroup per frame
+    assert lp.fft_launch(8192, 5) == (0, 0, 0, 128 * KIB, 0, (5, 1), (0, 0), (0, 0))
+    assert lp.fft_launch(8, 300) == (0, 0, 0, 128, 0, (300, 1), (0, 0), (0, 0))
+    assert lp.fft_launch(16384, 7, real=True) == (0, 0, 0, 128 * KIB, 0, (7, 1), (0, 0), (0, 0))
+    assert lp.fft_launch(16, 1, real=True) == (0, 0, 0, 128, 0, (1, 1), (0, 0), (0, 0))
+
+
+@pytest.mark.parametrize("n,real,want", [
+    # ct = min(16, 8192 / n1), rt = min(16, 8192 / n2); lds = 2 * n1 * ct * 8, 2 * n2 * rt * 8; grids (n2 / ct, 5), (n1 / rt, 5)
+    (16384, False, (16, 16, 0, 32 * KIB, 32 * KIB, (8, 5), (8, 5), (0, 0))),                # 128 x 128
+    (32768, False, (16, 16, 0, 64 * KIB, 32 * KIB, (8, 5), (16, 5), (0, 0))),               # 256 x 128
+    (131072, False, (16, 16, 0, 128 * KIB, 64 * KIB, (16, 5), (32, 5), (0, 0))),            # 512 x 256
+    (262144, False, (16, 16, 0, 128 * KIB, 128 * KIB, (32, 5), (32, 5), (0, 0))),           # 512 x 512
+    (524288, False, (8, 16, 0, 128 * KIB, 128 * KIB, (64, 5), (64, 5), (0, 0))),            # 1024 x 512: 8192 / 1024 = 8 columns
+    (1048576, False, (8, 8, 0, 128 * KIB, 128 * KIB, (128, 5), (128, 5), (0, 0))),          # 1024 x 1024
+    # real: the untangle step's grid (m / 256, 5) behind them
+    (32768, True, (16, 16, 0, 32 * KIB, 32 * KIB, (8, 5), (8, 5), (64, 5))),                # m = 16384: 128 x 128
+    (131072, True, (16, 16, 0, 64 * KIB, 64 * KIB, (16, 5), (16, 5), (256, 5))),            # m = 65536: 256 x 256, generic
+    (1048576, True, (8, 16, 0, 128 * KIB, 128 * KIB, (64, 5), (64, 5), (2048, 5))),         # m = 524288: 1024 x 512
+])
+def test_fft_four_step_launch(n, real, want):
+    assert lp.fft_launch(n, 5, real) == want
+
+
+@pytest.mark.parametrize("batch,fpw,rows", [(1, 1, 1), (95, 1, 95), (96, 4, 24), (97, 4, 25), (256, 4, 64), (259, 4, 65)])
+def test_fft_register_path_launch(batch, fpw, rows):
+    """four frames per pass-1 workgroup from 96 frames on (ceil(batch / 4) rows of 16 workgroups), else one; static LDS"""
+    assert lp.fft_launch(65536, batch) == (0, 0, fpw, 0, 0, (16, rows), (16, batch), (0, 0))
+
+
+def test_fft_lds_and_tiles_at_every_size():
+    for real in (False, True):
+        for bits in range(3, 21):
+            n = 1 << bits
+            s = lp.fft_shape(n, real)
+            assert s.n1 * s.n2 == s.points and s.n1 >= s.n2 and s.lds_max == 128 * KIB, (n, real, s)
+            l = lp.fft_launch(n, 3, real)
+            assert l.lds1 <= s.lds_max and l.lds2 <= s.lds_max, (n, real, l)
+            if s.path == SINGLE:
+                assert s.points <= 8192 and l.lds1 == 16 * s.points, (n, real, l)
+            elif s.path == FOUR:
+                assert s.points > 8192 and 1 <= l.ct <= 16 and 1 <= l.rt <= 16, (n, real, l)
+                assert l.grid1 == (s.n2 // l.ct, 3) and l.grid1[0] * l.ct == s.n2, (n, real, l)
+                assert l.grid2 == (s.n1 // l.rt, 3) and l.grid2[0] * l.rt == s.n1, (n, real, l)
+                assert l.grid3 == ((s.points // 256, 3) if real else (0, 0)), (n, real, l)
+            else:
+                assert (n, real) == (65536, False)
+
+
+def test_fft_work_area():
+    # 128 MB of frames of 8 n bytes (IQ and real alike), the batch at most, one frame at least; it only ever grows
+    assert lp.fft_work_frames(65536, 1, 1000) == 256 and lp.fft_work_frames(1 << 20, 1, 1000) == 16
+    assert lp.fft_work_frames(16384, 1, 7) == 7 and lp.fft_work_frames(16384, 1, 5000) == 1024
+    assert lp.fft_work_frames(65536, 100, 5) == 100 and lp.fft_work_frames(65536, 256, 1000) == 256
+    assert lp.fft_work_frames(65536, 1, 0) == 1 and lp.fft_work_frames(65536, 0, 0) == 0        # nothing asked for: as it was
+    assert lp.fft_work_frames(1 << 25, 0, 5) == 1           # (a frame larger than the cap: one frame)
+    assert lp.fft_chunks(65536, 259) == [256, 3] and lp.fft_chunks(65536, 256) == [256] and lp.fft_chunks(65536, 5) == [5]
+    assert lp.fft_chunks(1 << 20, 17) == [16, 1] and lp.fft_chunks(1 << 20, 33) == [16, 16, 1]
+    assert lp.fft_chunks(32768, 5, have=100) == [5]
+    assert lp.fft_chunks(1 << 20, 3, have=1) == [3] and lp.fft_chunks(1 << 20, 0) == []
+    # a push (one frame) after a batch of 100 still runs as one batch of one
+    assert lp.lib().wr_plan_fft_chunk(1, 100) == 1
+    # real: the packed transform lies behind the intermediates of all the frames in flight: work_frames * m points in
+    assert lp.lib().wr_plan_fft_untangle_offset(16, 524288) == 8_388_608 and lp.lib().wr_plan_fft_untangle_offset(1, 16384) == 16384
+
+
+@pytest.mark.parametrize("n,cols,num_cus,ct", [
+    # min(8192 / n, 8, cols / CUs) rounded down to a power of two, one at least
+    (512, 256, 256, 1),                     # no more columns than compute units
+    (512, 4096, 256, 8),
+    (8192, 64, 256, 1), (8192, 4096, 8, 1), (8192, 4096, 0, 1),     # the LDS holds one
+    (2048, 1024, 256, 4),                   # the LDS holds four
+    (64, 768, 256, 2),                      # three per compute unit: two
+    (64, 64, 256, 1),
+    # num_cus = 0: the rule without the compute units
+    (64, 64, 0, 8), (512, 256, 0, 8), (2048, 64, 0, 4), (4096, 64, 0, 2),
+])
+def test_fft_columns_per_workgroup(n, cols, num_cus, ct):
+    assert lp.fft_cols_ct(n, cols, num_cus) == ct
+    assert 64 % ct == 0 and 2 * n * ct * 8 <= 128 * KIB

@@ -324,7 +324,7 @@ struct wr_resamp : WrRowBank {
 /* wr_dev.hip */
 int        wrc_dev_bind(wr_dev *d);
 int        wrc_dev_settle_stream(wr_dev *d);        /* closes the streaming launch that is open on the device's stream, if any */
-hipError_t wrc_dev_stream_sync(wr_dev *d);          /* ... and waits for the stream */
+/* (wrc_dev_stream_sync -- ... and waits for the stream -- is declared in wr_internal.h: wr_fft.hip needs it too) */
 int        wrc_dev_scratch(wr_dev *d, size_t floats);
 void      *wrc_host_mapped(const void *host, hipError_t *why = nullptr);
 int        wrc_upload_mark_locked(wr_dev *d, hipStream_t st);

@@ -29,8 +29,10 @@
 #include "wr_internal.h"
 
 #include <cstdlib>
+#include <cstring>
+#include <vector>
 
-#define FFT_THREADS 256
+/* (FFT_THREADS, the LDS budget and every other figure of the launches: wr_plan.h) */
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 w)
 {
@@ -464,6 +466,19 @@ k_fft64k_pass1(const float2 *__restrict__ iq, size_t hop, const float *__restric
 	}
 }
 
+/* window_p1 (host): thread (t, c) of column tile T above multiplies rows a*16 + t, a = 0..15, of column T*16 + c: stored as
+ * [T][a / 4][thread][a % 4], a thread takes its 16 values with four 16-byte loads that are contiguous across the threads of
+ * a wave (they were 16 four-byte loads in 64-byte runs: as many memory instructions as the samples) */
+static std::vector<float> fft64k_window_p1(const std::vector<float> &win)
+{
+	std::vector<float> wp(65536);
+	for (unsigned int T = 0; T < 16; ++T)
+		for (unsigned int tid = 0; tid < 256; ++tid)
+			for (unsigned int a = 0; a < 16; ++a)
+				wp[((T * 4 + a / 4) * 256 + tid) * 4 + a % 4] = win[(a * 16 + (tid >> 4)) * 256 + T * 16 + (tid & 15)];
+	return wp;
+}
+
 /* pass 2: 16 adjacent rows k1 of the intermediate; bins X[k1 + 256*k2].  Loads run with t
  * fastest (a row is contiguous), stores with the row index fastest (bins of neighbouring
  * k1 are contiguous).  grid = (16, frames). */
@@ -549,85 +564,96 @@ hipError_t wrk_waterfall_row(hipStream_t st, const float *bins, unsigned int n, 
                              float *db_row, uint8_t *palette)
 {
 	const float scaledb = 20.0f * log10f((float)n);
-	unsigned int grid = (width + 255) / 256;
-	k_waterfall_row<<<grid, 256, 0, st>>>((const float2 *)bins, n, width, hold, scaledb, db_row, palette);
+	k_waterfall_row<<<grid_for(width, 256, FFT_WATERFALL_GRID_CAP), 256, 0, st>>>((const float2 *)bins, n, width, hold, scaledb,
+	                                                                             db_row, palette);
 	return hipGetLastError();
 }
 
 hipError_t wrk_bins_to_db(hipStream_t st, const float *bins, unsigned int n, float *db)
 {
 	const float scaledb = 20.0f * log10f((float)n);
-	unsigned int grid = (n + 255) / 256;
-	if (grid > 1024)
-		grid = 1024;
-	k_bins_to_db<<<grid, 256, 0, st>>>((const float2 *)bins, n, db, scaledb);
+	k_bins_to_db<<<grid_for(n, 256, FFT_DB_GRID_CAP), 256, 0, st>>>((const float2 *)bins, n, db, scaledb);
 	return hipGetLastError();
 }
 
-/* batches of the 65536-point path from this many frames on take four frames per pass-1 workgroup (>= 384 workgroups) */
-#define FFT64K_P1_LONG_MIN 96u
-static int fft64k_p1_fpw(size_t batch)
+/* ---- the plan: the shape (wr_plan.h), the tables the kernels read, the work area between the passes ---- */
+
+void wrk_fft_plan_free(WrFftPlan *P)
 {
-	return batch >= FFT64K_P1_LONG_MIN ? 4 : 1;
+	(void)hipFree(P->tw_n);
+	(void)hipFree(P->tw_sub);
+	(void)hipFree(P->window);
+	(void)hipFree(P->window_p1);
+	(void)hipFree(P->work);
+	memset(P, 0, sizeof(*P));
 }
 
-/* a real plan (P.channels == 1): P.n1 * P.n2 = P.n / 2, the packed transform's shape; `in` and `hop` in floats.  Of
- * P.work's work_frames * n complex values the first half is the intermediate between the passes, the second the packed
- * transform Z that the untangle step reads. */
-static hipError_t fft_frames_real(hipStream_t st, const WrFftPlan &P, const float *in, size_t hop, size_t nframes_fft,
-                                  float *bins_out, float *db_out, float scaledb)
+static hipError_t fft_table(float **dev, const std::vector<float> &host)
 {
-	const unsigned int m = P.n >> 1;
-	hipError_t e;
-	if (P.n2 == 1) {
-		const size_t lds = (size_t)2 * m * sizeof(float2);
-		if (lds > 48 * 1024) {
-			e = hipFuncSetAttribute((const void *)k_fft_real_single, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-			if (e != hipSuccess)
-				return e;
-		}
-		k_fft_real_single<<<(unsigned int)nframes_fft, FFT_THREADS, lds, st>>>(
-			in, hop, P.n, P.window, (const float2 *)P.tw_n, (float2 *)bins_out, db_out, scaledb);
-		return hipGetLastError();
+	hipError_t e = hipMalloc((void **)dev, host.size() * sizeof(float));
+	if (e == hipSuccess)
+		e = hipMemcpy(*dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+	return e;
+}
+
+hipError_t wrk_fft_plan_create(WrFftPlan *P, unsigned int n, unsigned int channels)
+{
+	memset(P, 0, sizeof(*P));
+	P->n = n;
+	P->channels = channels;
+	P->shape = wrp_fft_shape(n, channels);
+	const WrFftShape &S = P->shape;
+	std::vector<float> tw(n), win(n), tws(S.sub ? S.sub : 2);
+	wrd_twiddles(n, tw.data());
+	wrd_spectrum_window(n, win.data());
+	if (S.sub)
+		wrd_twiddles(S.sub, tws.data());
+	hipError_t e = fft_table(&P->tw_n, tw);
+	if (e == hipSuccess)
+		e = fft_table(&P->window, win);
+	if (e == hipSuccess)
+		e = fft_table(&P->tw_sub, tws);
+	if (e == hipSuccess && S.path == WR_FFT_REG64K)
+		e = fft_table(&P->window_p1, fft64k_window_p1(win));
+	if (e == hipSuccess && S.path != WR_FFT_SINGLE) {
+		/* one frame; wrk_fft_plan_reserve grows it */
+		e = hipMalloc((void **)&P->work, (size_t)n * 2 * sizeof(float));
+		if (e == hipSuccess)
+			P->work_frames = 1;
 	}
-	const unsigned int tw_sub_len = P.n1 > P.n2 ? P.n1 : P.n2;
-	unsigned int ct = 8192u / P.n1;
-	if (ct > 16)
-		ct = 16;
-	unsigned int rt = 8192u / P.n2;
-	if (rt > 16)
-		rt = 16;
-	const size_t lds1 = (size_t)2 * P.n1 * ct * sizeof(float2);
-	const size_t lds2 = (size_t)2 * P.n2 * rt * sizeof(float2);
-	e = hipFuncSetAttribute((const void *)k_fft_pass1<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
+	if (e != hipSuccess)
+		wrk_fft_plan_free(P);
+	return e;
+}
+
+hipError_t wrk_fft_plan_reserve(WrFftPlan *P, size_t frames, wr_dev *dev)
+{
+	if (P->shape.path == WR_FFT_SINGLE)
+		return hipSuccess;
+	const size_t want = wrp_fft_work_frames(P->n, P->work_frames, frames);
+	if (want == P->work_frames)
+		return hipSuccess;
+	hipError_t e = wrc_dev_stream_sync(dev);                /* (whatever still uses the old area) */
 	if (e != hipSuccess)
 		return e;
-	e = hipFuncSetAttribute((const void *)k_fft_pass2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-	if (e != hipSuccess)
-		return e;
-	float2 *zbuf = (float2 *)P.work + P.work_frames * m;
-	size_t done = 0;
-	while (done < nframes_fft) {
-		size_t batch = nframes_fft - done;
-		if (batch > P.work_frames)
-			batch = P.work_frames;
-		dim3 g1(P.n2 / ct, (unsigned int)batch);
-		k_fft_pass1<true><<<g1, FFT_THREADS, lds1, st>>>((const float2 *)(in + done * hop), hop, P.n1, P.n2, ct, P.window,
-		                                                 (const float2 *)P.tw_sub, tw_sub_len,
-		                                                 (const float2 *)P.tw_n, (float2 *)P.work);
-		dim3 g2(P.n1 / rt, (unsigned int)batch);
-		k_fft_pass2<<<g2, FFT_THREADS, lds2, st>>>((const float2 *)P.work, P.n1, P.n2, rt, (const float2 *)P.tw_sub,
-		                                           tw_sub_len, zbuf, (float *)nullptr, 0.0f);
-		dim3 g3(m / FFT_THREADS, (unsigned int)batch);
-		k_fft_untangle<<<g3, FFT_THREADS, 0, st>>>(zbuf, P.n, (const float2 *)P.tw_n,
-		                                           bins_out ? (float2 *)(bins_out + 2 * done * P.n) : (float2 *)nullptr,
-		                                           db_out ? db_out + done * P.n : (float *)nullptr, scaledb);
-		e = hipGetLastError();
-		if (e != hipSuccess)
-			return e;
-		done += batch;
-	}
-	return hipSuccess;
+	(void)hipFree(P->work);
+	P->work = nullptr;
+	P->work_frames = 0;
+	e = hipMalloc((void **)&P->work, want * P->n * 2 * sizeof(float));
+	if (e == hipSuccess)
+		P->work_frames = want;
+	return e;
+}
+
+/* ---- the launches: a plan's numbers (wr_plan.h), what only the runtime can give (allow_lds), the launch ---- */
+
+/* every kernel with dynamic LDS may be asked for the whole budget by some plan, and k_fft_pass2 serves plans of every size:
+ * each instance is allowed FFT_LDS_MAX once per device, whatever the first call needs */
+template <auto KERNEL>
+static hipError_t fft_allow_lds(void)
+{
+	static bool done[WR_MAX_DEVICES];
+	return allow_lds((const void *)KERNEL, FFT_LDS_MAX, done);
 }
 
 hipError_t wrk_fft_frames(hipStream_t st, const WrFftPlan &P, const float *iq, size_t hop,
@@ -635,124 +661,71 @@ hipError_t wrk_fft_frames(hipStream_t st, const WrFftPlan &P, const float *iq, s
 {
 	if (!nframes_fft)
 		return hipSuccess;
+	const WrFftShape &S = P.shape;
 	const float scaledb = 20.0f * log10f((float)P.n);   /* spectrumsink.cxx:127 */
+	const float2 *tw_n = (const float2 *)P.tw_n, *tw_sub = (const float2 *)P.tw_sub;
 	hipError_t e;
-	if (P.channels == 1)
-		return fft_frames_real(st, P, iq, hop, nframes_fft, bins_out, db_out, scaledb);
-	if (P.n2 == 1) {
-		const size_t lds = (size_t)2 * P.n * sizeof(float2);
-		if (lds > 48 * 1024) {
-			e = hipFuncSetAttribute((const void *)k_fft_single,
-			                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-			if (e != hipSuccess)
-				return e;
-		}
-		k_fft_single<<<(unsigned int)nframes_fft, FFT_THREADS, lds, st>>>(
-			(const float2 *)iq, hop, P.n, P.window, (const float2 *)P.tw_n, (float2 *)bins_out,
-			db_out, scaledb);
+	if (S.path == WR_FFT_SINGLE) {
+		const WrFftLaunch L = wrp_fft_launch(S, nframes_fft);
+		if ((e = S.real ? fft_allow_lds<k_fft_real_single>() : fft_allow_lds<k_fft_single>()) != hipSuccess)
+			return e;
+		if (S.real)
+			k_fft_real_single<<<L.g1x, FFT_THREADS, L.lds1, st>>>(iq, hop, P.n, P.window, tw_n, (float2 *)bins_out, db_out, scaledb);
+		else
+			k_fft_single<<<L.g1x, FFT_THREADS, L.lds1, st>>>((const float2 *)iq, hop, P.n, P.window, tw_n, (float2 *)bins_out, db_out,
+			                                                 scaledb);
 		return hipGetLastError();
 	}
-	if (P.n1 == 256 && P.n2 == 256) {
-		size_t done = 0;
-		while (done < nframes_fft) {
-			size_t batch = nframes_fft - done;
-			if (batch > P.work_frames)
-				batch = P.work_frames;
-			dim3 grid(16, (unsigned int)batch);
-			const int fpw = fft64k_p1_fpw(batch);
-			if (fpw == 2)
-				k_fft64k_pass1<2u><<<dim3(16, (unsigned int)((batch + 1) / 2)), 256, 0, st>>>(
-					(const float2 *)(iq + 2 * done * hop), hop, P.window, P.window_p1, (const float2 *)P.tw_sub, (const float2 *)P.tw_n,
-					(float2 *)P.work, (unsigned int)batch);
-			else if (fpw == 4)
-				k_fft64k_pass1<4u><<<dim3(16, (unsigned int)((batch + 3) / 4)), 256, 0, st>>>(
-					(const float2 *)(iq + 2 * done * hop), hop, P.window, P.window_p1, (const float2 *)P.tw_sub, (const float2 *)P.tw_n,
-					(float2 *)P.work, (unsigned int)batch);
-			else
-				k_fft64k_pass1<1u><<<grid, 256, 0, st>>>((const float2 *)(iq + 2 * done * hop), hop, P.window, P.window_p1,
-				                                         (const float2 *)P.tw_sub, (const float2 *)P.tw_n, (float2 *)P.work,
-				                                         (unsigned int)batch);
-			k_fft64k_pass2<<<grid, 256, 0, st>>>(
-				(const float2 *)P.work, (const float2 *)P.tw_sub,
-				bins_out ? (float2 *)(bins_out + 2 * done * P.n) : (float2 *)nullptr,
-				db_out ? db_out + done * P.n : (float *)nullptr, scaledb);
-			e = hipGetLastError();
-			if (e != hipSuccess)
-				return e;
-			done += batch;
-		}
-		return hipSuccess;
+	if (S.path == WR_FFT_FOUR_STEP) {
+		if ((e = S.real ? fft_allow_lds<k_fft_pass1<true>>() : fft_allow_lds<k_fft_pass1<false>>()) != hipSuccess)
+			return e;
+		if ((e = fft_allow_lds<k_fft_pass2>()) != hipSuccess)
+			return e;
 	}
-	const unsigned int tw_sub_len = P.n1 > P.n2 ? P.n1 : P.n2;
-	unsigned int ct = 8192u / P.n1;
-	if (ct > 16)
-		ct = 16;
-	unsigned int rt = 8192u / P.n2;
-	if (rt > 16)
-		rt = 16;
-	const size_t lds1 = (size_t)2 * P.n1 * ct * sizeof(float2);
-	const size_t lds2 = (size_t)2 * P.n2 * rt * sizeof(float2);
-	e = hipFuncSetAttribute((const void *)k_fft_pass1<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-	                        (int)lds1);
-	if (e != hipSuccess)
-		return e;
-	e = hipFuncSetAttribute((const void *)k_fft_pass2, hipFuncAttributeMaxDynamicSharedMemorySize,
-	                        (int)lds2);
-	if (e != hipSuccess)
-		return e;
-	size_t done = 0;
-	while (done < nframes_fft) {
-		size_t batch = nframes_fft - done;
-		if (batch > P.work_frames)
-			batch = P.work_frames;
-		const float *src = iq + 2 * done * hop;
-		dim3 g1(P.n2 / ct, (unsigned int)batch);
-		k_fft_pass1<false><<<g1, FFT_THREADS, lds1, st>>>((const float2 *)src, hop, P.n1, P.n2, ct, P.window,
-		                                                  (const float2 *)P.tw_sub, tw_sub_len,
-		                                                  (const float2 *)P.tw_n, (float2 *)P.work);
-		dim3 g2(P.n1 / rt, (unsigned int)batch);
-		k_fft_pass2<<<g2, FFT_THREADS, lds2, st>>>(
-			(const float2 *)P.work, P.n1, P.n2, rt, (const float2 *)P.tw_sub, tw_sub_len,
-			bins_out ? (float2 *)(bins_out + 2 * done * P.n) : (float2 *)nullptr,
-			db_out ? db_out + done * P.n : (float *)nullptr, scaledb);
-		e = hipGetLastError();
-		if (e != hipSuccess)
+	/* two launches per chunk of the work area (real: three -- pass 2 leaves the packed transform in the area's second half
+	 * and k_fft_untangle makes the frame's bins of it) */
+	float2 *work = (float2 *)P.work;
+	float2 *zbuf = S.real ? work + wrp_fft_untangle_offset(P.work_frames, S.points) : nullptr;
+	for (size_t done = 0; done < nframes_fft;) {
+		const size_t batch = wrp_fft_chunk(nframes_fft - done, P.work_frames);
+		const WrFftLaunch L = wrp_fft_launch(S, batch);
+		const float2 *src = (const float2 *)(iq + P.channels * done * hop);
+		float2 *bins = bins_out ? (float2 *)(bins_out + 2 * done * P.n) : (float2 *)nullptr;
+		float *db = db_out ? db_out + done * P.n : (float *)nullptr;
+		const dim3 g1(L.g1x, L.g1y), g2(L.g2x, L.g2y);
+		if (S.path == WR_FFT_REG64K) {
+			if (L.fpw == 4u)
+				k_fft64k_pass1<4u><<<g1, 256, 0, st>>>(src, hop, P.window, P.window_p1, tw_sub, tw_n, work, (unsigned int)batch);
+			else
+				k_fft64k_pass1<1u><<<g1, 256, 0, st>>>(src, hop, P.window, P.window_p1, tw_sub, tw_n, work, (unsigned int)batch);
+			k_fft64k_pass2<<<g2, 256, 0, st>>>(work, tw_sub, bins, db, scaledb);
+		} else {
+			if (S.real)
+				k_fft_pass1<true><<<g1, FFT_THREADS, L.lds1, st>>>(src, hop, S.n1, S.n2, L.ct, P.window, tw_sub, S.sub, tw_n, work);
+			else
+				k_fft_pass1<false><<<g1, FFT_THREADS, L.lds1, st>>>(src, hop, S.n1, S.n2, L.ct, P.window, tw_sub, S.sub, tw_n, work);
+			k_fft_pass2<<<g2, FFT_THREADS, L.lds2, st>>>(work, S.n1, S.n2, L.rt, tw_sub, S.sub, S.real ? zbuf : bins,
+			                                             S.real ? (float *)nullptr : db, S.real ? 0.0f : scaledb);
+			if (S.real)
+				k_fft_untangle<<<dim3(L.g3x, L.g3y), FFT_THREADS, 0, st>>>(zbuf, P.n, tw_n, bins, db, scaledb);
+		}
+		if ((e = hipGetLastError()) != hipSuccess)
 			return e;
 		done += batch;
 	}
 	return hipSuccess;
 }
 
-/* columns per workgroup of k_fft_cols.  Workgroups first: measured at 256 columns (profiles/chan_spectra.txt), one column
- * per workgroup -- 256 workgroups, 8-byte loads a row apart -- takes 5.2 us at n = 512 where 8 columns in 32 workgroups, 64-byte
- * runs per row, take 17.4.  So columns are put side by side only where there are more of them than compute units, and
- * then within what the LDS holds: both buffers within 128 KiB (n * ct <= 8192 points, k_fft_single's budget at 8192), at
- * most 8 (64-byte runs).  A power of two: it divides 64. */
-static unsigned int fft_cols_ct(unsigned int n, unsigned int cols, int num_cus)
-{
-	unsigned int most = 8192u / n;
-	if (most > 8u)
-		most = 8u;
-	if (num_cus > 0 && most > cols / (unsigned int)num_cus)
-		most = cols / (unsigned int)num_cus;
-	unsigned int ct = 1;
-	while (2u * ct <= most)
-		ct *= 2u;
-	return ct;
-}
-
 hipError_t wrk_fft_cols(hipStream_t st, const WrFftPlan &P, const float *iq, unsigned int S, unsigned int cols, size_t first,
                         float *db, int num_cus)
 {
-	if (P.channels != 2 || P.n2 != 1 || P.n < 8 || P.n > 8192 || !cols || cols % 64u || cols > S)
+	if (P.channels != 2 || P.shape.path != WR_FFT_SINGLE || P.n < 8 || P.n > FFT_LDS_POINTS || !cols || cols % 64u || cols > S)
 		return hipErrorInvalidValue;
-	const unsigned int ct = fft_cols_ct(P.n, cols, num_cus);
+	const unsigned int ct = wrp_fft_cols_ct(P.n, cols, num_cus);
 	const size_t lds = (size_t)2 * P.n * ct * sizeof(float2);
-	if (lds > 48 * 1024) {
-		hipError_t e = hipFuncSetAttribute((const void *)k_fft_cols, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		if (e != hipSuccess)
-			return e;
-	}
+	hipError_t e = fft_allow_lds<k_fft_cols>();
+	if (e != hipSuccess)
+		return e;
 	k_fft_cols<<<cols / ct, FFT_THREADS, lds, st>>>((const float2 *)iq, S, cols, first, P.n, ct, P.window, (const float2 *)P.tw_n, db,
 	                                             20.0f * log10f((float)P.n));
 	return hipGetLastError();

@@ -21,6 +21,7 @@
 int         wrc_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));   /* sets wr_last_error() */
 int         wrc_dev_index(const wr_dev *dev);
 hipStream_t wrc_dev_stream(const wr_dev *dev);
+hipError_t  wrc_dev_stream_sync(wr_dev *d);               /* closes the streaming launch that is open on the device's stream, if any, and waits for the stream */
 /* the event the tuner's last launch stamped on completion (wr_tuner_mark_launches), or NULL (wr_ring.hip) */
 int         wrc_tuner_launch_mark(wr_tuner *t, hipEvent_t *ev);
 
@@ -124,6 +125,11 @@ struct WrTunerLaunch {
 };
 
 /* ---- kernel launchers (wr_kernels.hip); all return hipError_t ---- */
+/* hipFuncAttributeMaxDynamicSharedMemorySize is a per-device setting of the loaded code object: a process that drives several
+ * GPUs (the host runtime gives every tuner its own) has to set it once on each.  `done` is the flag array of ONE kernel
+ * instance, `bytes` the MOST that instance ever asks for.  Plain flags: two threads racing on a first call both set the
+ * attribute, to the same value -- what every call did before there were flags. */
+hipError_t allow_lds(const void *fn, size_t bytes, bool (&done)[WR_MAX_DEVICES]);
 hipError_t wrk_mix(hipStream_t st, const float *in, float *out, size_t nframes,
                    unsigned int phase, int step, const float *table_dev);
 hipError_t wrk_fir(hipStream_t st, const float *in, size_t nframes, unsigned int channels,
@@ -316,17 +322,24 @@ hipError_t wrk_tuner_stream(hipStream_t st, const WrStreamArgs &A, void *ev_star
 
 /* ---- FFT (wr_fft.hip) ---- */
 struct WrFftPlan {
-	unsigned int n;             /* transform size */
+	unsigned int n;             /* frame size */
 	unsigned int channels;      /* 2: IQ frames; 1: real samples, transformed as n/2 packed points and untangled */
-	unsigned int n1, n2;        /* n = n1*n2 (real: n/2 = n1*n2); n2 == 1 for single-pass */
-	float *tw_n;                /* [n/2][2] twiddles of the full size (device) */
-	float *tw_sub;              /* [max(n1,n2)/2][2] twiddles of the LDS sub-transforms (device) */
+	WrFftShape shape;           /* wrp_fft_shape(n, channels): the points that are transformed, n1 * n2 of them, and the path */
+	float *tw_n;                /* [n/2][2] twiddles of the frame size (device) */
+	float *tw_sub;              /* [shape.sub/2][2] twiddles of the LDS sub-transforms (device); single-pass: unused */
 	float *window;              /* [n] (device) */
-	float *window_p1;           /* 65536-point path: the window in the order pass 1's threads take it (wr_fft.hip), else NULL */
-	float *work;                /* [n][2] intermediate per frame in flight (device), batch-sized (real: half of it is the
-	                               intermediate, half the packed transform in front of the untangle step) */
-	size_t work_frames;
+	float *window_p1;           /* WR_FFT_REG64K: the window in the order k_fft64k_pass1's threads take it, else NULL */
+	float *work;                /* [work_frames][n][2] (device): the intermediate between the passes of the frames in flight; real:
+	                               half of it is that, half the packed transform in front of the untangle step
+	                               (wrp_fft_untangle_offset).  Single-pass: NULL */
+	size_t work_frames;         /* one from create on, more after wrk_fft_plan_reserve; single-pass: 0 */
 };
+/* the tables and a work area of one frame; on failure the plan is freed again.  Synchronous copies: the caller has settled
+ * the device's stream */
+hipError_t wrk_fft_plan_create(WrFftPlan *P, unsigned int n, unsigned int channels);
+void       wrk_fft_plan_free(WrFftPlan *P);
+/* room in the work area for a call of `frames` frames, as far as wrp_fft_work_frames gives it; growing waits for `dev`'s stream */
+hipError_t wrk_fft_plan_reserve(WrFftPlan *P, size_t frames, wr_dev *dev);
 /* frame f starts `f * hop` frames (of P.channels floats) into `iq` */
 hipError_t wrk_fft_frames(hipStream_t st, const WrFftPlan &P, const float *iq, size_t hop,
                           size_t nframes_fft, float *bins_out /* or NULL */, float *db_out /* or NULL */);

@@ -2129,7 +2129,6 @@ k_tuner_audio(const float *__restrict__ dem, size_t rows_valid, size_t k2, unsig
  * tap read) over them, the sums carried from segment to segment in registers -- the order of additions
  * is the reference's.  (r02-r04: every thread read its 64 taps and 64 rows straight from L2: 20 / 42 / 84 us
  * per C2 block at 64 / 128 / 256 taps.)  blockIdx.x == tiles: the next history (last L - 1 rows). */
-static hipError_t allow_lds(const void *fn, size_t bytes, bool (&done)[WR_MAX_DEVICES]);
 #define IQ2_ROWS 128u           /* staged rows: 128 x 64 x 8 B = 64 KiB; + 16 KiB of taps: two workgroups per CU */
 #define IQ2_B 2u                /* output frames per wave */
 #define IQ2_TKMAX (8u * IQ2_B)
@@ -2263,10 +2262,8 @@ __global__ void k_gather_rows(const float *__restrict__ src, size_t rows, size_t
 /* launchers                                                                   */
 /* ------------------------------------------------------------------------- */
 
-/* hipFuncAttributeMaxDynamicSharedMemorySize is a per-device setting of the loaded code object:
- * a process that drives several GPUs (the host runtime gives every tuner its own) has to set
- * it once on each.  `done` is the call site's own flag array. */
-static hipError_t allow_lds(const void *fn, size_t bytes, bool (&done)[WR_MAX_DEVICES])
+/* (wr_internal.h) */
+hipError_t allow_lds(const void *fn, size_t bytes, bool (&done)[WR_MAX_DEVICES])
 {
 	int dev = 0;
 	hipError_t e = hipGetDevice(&dev);

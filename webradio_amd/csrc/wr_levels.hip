@@ -150,8 +150,9 @@ hipError_t wrk_chan_levels(hipStream_t st, const float *iq, size_t S, unsigned i
 	const dim3 grid((unsigned int)groups, (cols + WR_LANES - 1u) / WR_LANES);
 	if (squelch) {
 		const size_t lds = (size_t)LV_ROWS * WR_LANES * sizeof(float);
-		/* (64 KiB of dynamic LDS is above the default limit of 48) */
-		hipError_t e = hipFuncSetAttribute((const void *)k_levels_part<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		/* (64 KiB of dynamic LDS, all this instance ever asks for, is above the default limit of 48) */
+		static bool attr_done[WR_MAX_DEVICES];
+		hipError_t e = allow_lds((const void *)k_levels_part<true>, lds, attr_done);
 		if (e != hipSuccess)
 			return e;
 		k_levels_part<true><<<grid, LV_THREADS, lds, st>>>((const float2 *)iq, S, cols, k1, d2, k2, squelch, psum, ppeak, pmuted);

@@ -1,11 +1,12 @@
 /*
  * wr_plan.h -- the launch geometry of every tuner launch (the per-block DDC, the long-filter DDC, the post stage, the audio
- * filter, the streaming launch): which kernel instance, how many workgroups per role, how much LDS, the group map, kslow,
- * kmax, the post stage's runs of tiles.  The arithmetic alone, with no HIP call and no environment read, so that a CPU test
- * can hold it to the rule (tests/test_launch_plan.py through tests/cxx/cpu_host_checks.cxx).  The launch functions
- * (wr_kernels.hip, wr_stream_kernel.inc) obtain a plan, ask the runtime for what only it can give (allow_lds, the occupancy
- * query), and launch with the plan's numbers.  The only home of the constants geometry depends on: the kernels use the
- * same names.  Plain C++11.
+ * filter, the streaming launch) and of the spectrum launches (the transform's shape and path, its passes' tiles, grids and
+ * LDS, the work area and its chunks, the columns per workgroup of the channel spectra): which kernel instance, how many
+ * workgroups per role, how much LDS, the group map, kslow, kmax, the post stage's runs of tiles.  The arithmetic alone, with
+ * no HIP call and no environment read, so that a CPU test can hold it to the rule (tests/test_launch_plan.py through
+ * tests/cxx/cpu_host_checks.cxx).  The launch functions (wr_kernels.hip, wr_stream_kernel.inc, wr_fft.hip) obtain a plan,
+ * ask the runtime for what only it can give (allow_lds, the occupancy query), and launch with the plan's numbers.  The only
+ * home of the constants geometry depends on: the kernels use the same names.  Plain C++11.
  */
 #ifndef WR_PLAN_H_
 #define WR_PLAN_H_
@@ -453,6 +454,132 @@ static inline WrAudioPlan wrp_audio_plan(size_t k2, unsigned int d2, unsigned in
 	p.lds_max = ((size_t)AUD_ROWS * 64u + (size_t)WR_FIR_FUSED_MAX * 64u + AUD_TMAX * 65u) * sizeof(float);
 	p.grid_x = (unsigned int)((k2 + p.tk - 1) / p.tk);
 	return p;
+}
+
+/* ---- the spectrum launches (wr_fft.hip): a transform of `points` complex points -- the frame's n, or n / 2 packed points of
+ * a real frame (channels == 1) -- lives in two LDS buffers of at most FFT_LDS_POINTS points each ---- */
+#define FFT_THREADS 256
+#define FFT_LDS_POINTS 8192u               /* per buffer: 64 KiB of float2 */
+#define FFT_LDS_MAX ((size_t)2 * FFT_LDS_POINTS * 8u)   /* the most dynamic LDS an FFT kernel asks for: 128 KiB */
+#define FFT_TILE_MAX 16u                   /* columns (pass 1) or rows (pass 2) of a four-step workgroup */
+#define FFT_COLS_CT_MAX 8u                 /* columns per workgroup of k_fft_cols: 64-byte runs */
+#define FFT_WORK_BYTES ((size_t)128 << 20) /* the work area between the passes: it then still sits in the 256 MB Infinity Cache */
+#define FFT_DB_GRID_CAP 1024u              /* k_bins_to_db strides beyond 262144 bins */
+#define FFT_WATERFALL_GRID_CAP 4096u       /* k_waterfall_row: 2^20 columns, the largest transform's; never reached below it */
+/* batches of the 65536-point path from this many frames on take four frames per pass-1 workgroup (>= 384 workgroups) */
+#define FFT64K_P1_LONG_MIN 96u
+
+enum WrFftPath {
+	WR_FFT_SINGLE = 0,                     /* one workgroup per frame, whole in LDS */
+	WR_FFT_FOUR_STEP,                      /* points = n1 * n2, two launches with the work area between them */
+	WR_FFT_REG64K                          /* 65536 IQ points: 256 x 256 with the sub-transforms in registers */
+};
+
+struct WrFftShape {
+	unsigned int points, n1, n2;           /* n2 == 1: single-pass */
+	unsigned int sub;                      /* length of the sub-transforms' twiddle table, max(n1, n2); 0: single-pass */
+	WrFftPath path;
+	size_t lds_max;
+	bool real;                             /* the packed transform of a real frame: an untangle step follows */
+};
+
+/* up to FFT_LDS_POINTS points a single pass; above, n1 = 2^ceil(bits / 2) */
+static inline WrFftShape wrp_fft_shape(unsigned int n, unsigned int channels)
+{
+	WrFftShape s = {channels == 1u ? n / 2u : n, 0, 1, 0, WR_FFT_SINGLE, FFT_LDS_MAX, channels == 1u};
+	s.n1 = s.points;
+	if (s.points > FFT_LDS_POINTS) {
+		unsigned int bits = 0;
+		while ((1u << bits) < s.points)
+			bits++;
+		s.n1 = 1u << ((bits + 1u) / 2u);
+		s.n2 = s.points / s.n1;
+		s.sub = s.n1 > s.n2 ? s.n1 : s.n2;
+		s.path = (!s.real && s.points == 65536u) ? WR_FFT_REG64K : WR_FFT_FOUR_STEP;
+	}
+	return s;
+}
+
+/* one batch of `batch` frames.  Single-pass: lds1, grid (g1x).  Four-step: ct columns / rt rows per workgroup, as many as
+ * the LDS holds and FFT_TILE_MAX at most, grids (n2 / ct, batch) and (n1 / rt, batch) and, real plans, the untangle step's
+ * (m / FFT_THREADS, batch).  Register path: static LDS, fpw frames per pass-1 workgroup, (16, ceil(batch / fpw)) and (16, batch). */
+struct WrFftLaunch {
+	unsigned int ct, rt, fpw;
+	size_t lds1, lds2;
+	unsigned int g1x, g1y, g2x, g2y, g3x, g3y;     /* 0: no such launch */
+};
+
+static inline WrFftLaunch wrp_fft_launch(const WrFftShape &s, size_t batch)
+{
+	WrFftLaunch l = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	const unsigned int b = (unsigned int)batch;
+	if (s.path == WR_FFT_SINGLE) {
+		l.lds1 = (size_t)2 * s.points * 8u;
+		l.g1x = b;
+		l.g1y = 1;
+	} else if (s.path == WR_FFT_REG64K) {
+		l.fpw = batch >= FFT64K_P1_LONG_MIN ? 4u : 1u;
+		l.g1x = l.g2x = 16;
+		l.g1y = (b + l.fpw - 1u) / l.fpw;
+		l.g2y = b;
+	} else {
+		l.ct = FFT_LDS_POINTS / s.n1 > FFT_TILE_MAX ? FFT_TILE_MAX : FFT_LDS_POINTS / s.n1;
+		l.rt = FFT_LDS_POINTS / s.n2 > FFT_TILE_MAX ? FFT_TILE_MAX : FFT_LDS_POINTS / s.n2;
+		l.lds1 = (size_t)2 * s.n1 * l.ct * 8u;
+		l.lds2 = (size_t)2 * s.n2 * l.rt * 8u;
+		l.g1x = s.n2 / l.ct;
+		l.g2x = s.n1 / l.rt;
+		l.g1y = l.g2y = b;
+		if (s.real) {
+			l.g3x = s.points / FFT_THREADS;
+			l.g3y = b;
+		}
+	}
+	return l;
+}
+
+/* The work area of a two-pass plan of n-point frames (8 n bytes each: a real plan's two halves are n / 2 points): room for
+ * the whole batch, up to FFT_WORK_BYTES, means one pair of launches per call instead of one per 64 frames.  Grows only:
+ * the frames it holds after a call for `want_frames`, `have` before. */
+static inline size_t wrp_fft_work_frames(unsigned int n, size_t have, size_t want_frames)
+{
+	size_t want = FFT_WORK_BYTES / ((size_t)n * 8u);
+	if (want < 1)
+		want = 1;
+	if (want > want_frames)
+		want = want_frames;
+	return want > have ? want : have;
+}
+
+/* a call's frames go through the work area in chunks */
+static inline size_t wrp_fft_chunk(size_t remaining, size_t work_frames)
+{
+	return remaining < work_frames ? remaining : work_frames;
+}
+
+/* a real plan (m = n / 2 packed points): of the work area's work_frames * n complex values the first half is the intermediate
+ * between the passes, the second -- from this offset on -- the packed transform Z that the untangle step reads */
+static inline size_t wrp_fft_untangle_offset(size_t work_frames, unsigned int m)
+{
+	return work_frames * m;
+}
+
+/* columns per workgroup of k_fft_cols.  Workgroups first: measured at 256 columns (profiles/chan_spectra.txt), one column
+ * per workgroup -- 256 workgroups, 8-byte loads a row apart -- takes 5.2 us at n = 512 where 8 columns in 32 workgroups, 64-byte
+ * runs per row, take 17.4.  So columns are put side by side only where there are more of them than compute units, and
+ * then within what the LDS holds: both buffers within 128 KiB (n * ct <= 8192 points, k_fft_single's budget at 8192), at
+ * most 8 (64-byte runs).  A power of two: it divides 64.  (num_cus <= 0: the rule without the compute units.) */
+static inline unsigned int wrp_fft_cols_ct(unsigned int n, unsigned int cols, int num_cus)
+{
+	unsigned int most = FFT_LDS_POINTS / n;
+	if (most > FFT_COLS_CT_MAX)
+		most = FFT_COLS_CT_MAX;
+	if (num_cus > 0 && most > cols / (unsigned int)num_cus)
+		most = cols / (unsigned int)num_cus;
+	unsigned int ct = 1;
+	while (2u * ct <= most)
+		ct *= 2u;
+	return ct;
 }
 
 #endif /* WR_PLAN_H_ */

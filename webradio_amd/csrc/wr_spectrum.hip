@@ -6,16 +6,6 @@
 
 /* --------------------------------------------------------------- spectrum -- */
 
-static void plan_free(WrFftPlan &p)
-{
-	(void)hipFree(p.tw_n);
-	(void)hipFree(p.tw_sub);
-	(void)hipFree(p.window);
-	(void)hipFree(p.window_p1);
-	(void)hipFree(p.work);
-	memset(&p, 0, sizeof(p));
-}
-
 static int spectrum_create(wr_spectrum **spec, wr_dev *dev, unsigned int fft_size, unsigned int hop, unsigned int ch,
                            const char *who)
 {
@@ -45,52 +35,10 @@ static int spectrum_create(wr_spectrum **spec, wr_dev *dev, unsigned int fft_siz
 	s->bins = nullptr;
 	s->frames_done = 0;
 
-	WrFftPlan &p = s->plan;
-	p.n = fft_size;
-	p.channels = ch;
 	/* (real samples: the transform that runs is the packed one of fft_size / 2 points, wr_fft.hip) */
-	const unsigned int points = ch == 1 ? fft_size / 2 : fft_size;
-	if (points <= 8192) {
-		p.n1 = points;
-		p.n2 = 1;
-	} else {
-		unsigned int bits = 0;
-		while ((1u << bits) < points)
-			bits++;
-		p.n1 = 1u << ((bits + 1) / 2);
-		p.n2 = points / p.n1;
-	}
-	const unsigned int sub = (p.n2 == 1) ? 0 : (p.n1 > p.n2 ? p.n1 : p.n2);
-	std::vector<float> tw(fft_size), win(fft_size), tws(sub ? sub : 2);
-	wrd_twiddles(fft_size, tw.data());
-	wrd_spectrum_window(fft_size, win.data());
-	if (sub)
-		wrd_twiddles(sub, tws.data());
-	p.work_frames = (p.n2 == 1) ? 0 : 1;        /* grown on demand by wr_spectrum_batch_db */
-	hipError_t e = hipSuccess;
-	do {
-		if ((e = hipMalloc((void **)&p.tw_n, fft_size * sizeof(float))) != hipSuccess) break;
-		if ((e = hipMalloc((void **)&p.window, fft_size * sizeof(float))) != hipSuccess) break;
-		if ((e = hipMalloc((void **)&p.tw_sub, (sub ? sub : 2) * sizeof(float))) != hipSuccess) break;
-		if (p.work_frames &&
-		    (e = hipMalloc((void **)&p.work, p.work_frames * fft_size * 2 * sizeof(float))) != hipSuccess) break;
-		if ((e = hipMalloc((void **)&s->bins, (size_t)fft_size * 2 * sizeof(float))) != hipSuccess) break;
-		if ((e = hipMemcpy(p.tw_n, tw.data(), fft_size * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
-		if ((e = hipMemcpy(p.window, win.data(), fft_size * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
-		if (p.n1 == 256 && p.n2 == 256) {
-			/* pass 1's thread (t, c) of column tile T multiplies rows a*16 + t, a = 0..15, of column T*16 + c: stored as
-			 * [T][a / 4][thread][a % 4], a thread takes its 16 values with four 16-byte loads that are contiguous across
-			 * the threads of a wave (they were 16 four-byte loads in 64-byte runs: as many memory instructions as the samples) */
-			std::vector<float> wp(fft_size);
-			for (unsigned int T = 0; T < 16; ++T)
-				for (unsigned int tid = 0; tid < 256; ++tid)
-					for (unsigned int a = 0; a < 16; ++a)
-						wp[((T * 4 + a / 4) * 256 + tid) * 4 + a % 4] = win[(a * 16 + (tid >> 4)) * 256 + T * 16 + (tid & 15)];
-			if ((e = hipMalloc((void **)&p.window_p1, fft_size * sizeof(float))) != hipSuccess) break;
-			if ((e = hipMemcpy(p.window_p1, wp.data(), fft_size * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
-		}
-		if (sub && (e = hipMemcpy(p.tw_sub, tws.data(), sub * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) break;
-	} while (0);
+	hipError_t e = wrk_fft_plan_create(&s->plan, fft_size, ch);
+	if (e == hipSuccess)
+		e = hipMalloc((void **)&s->bins, (size_t)fft_size * 2 * sizeof(float));
 	if (e != hipSuccess) {
 		int rc = wrc_fail(WR_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
 		wr_spectrum_destroy(s);
@@ -130,7 +78,7 @@ extern "C" int wr_spectrum_destroy(wr_spectrum *s)
 	if (s->def_ev)
 		(void)hipEventDestroy(s->def_ev);
 	(void)hipHostFree(s->keep_host);
-	plan_free(s->plan);
+	wrk_fft_plan_free(&s->plan);
 	(void)hipFree(s->stage);
 	(void)hipFree(s->bins);
 	delete s;
@@ -435,26 +383,7 @@ static int spectrum_batch(wr_spectrum *s, const float *iq_dev, size_t stride, si
 	if (wrc_dev_bind(s->dev))
 		return WR_ERR_HIP;
 	DEV_SETTLE(s->dev);
-	/* the two-pass transforms keep their intermediate in `work`: room for the whole batch, up
-	 * to 128 MB (it then still sits in the 256 MB Infinity Cache between the passes), means one
-	 * pair of launches per call instead of one per 64 frames */
-	WrFftPlan &p = s->plan;
-	if (p.n2 != 1 && p.work_frames < nframes_fft) {
-		const size_t frame_bytes = (size_t)p.n * 2 * sizeof(float);
-		size_t want = ((size_t)128 << 20) / frame_bytes;
-		if (want < 1)
-			want = 1;
-		if (want > nframes_fft)
-			want = nframes_fft;
-		if (want > p.work_frames) {
-			HIP_TRY(wrc_dev_stream_sync(s->dev));
-			(void)hipFree(p.work);
-			p.work = nullptr;
-			p.work_frames = 0;
-			HIP_TRY(hipMalloc((void **)&p.work, want * frame_bytes));
-			p.work_frames = want;
-		}
-	}
+	HIP_TRY(wrk_fft_plan_reserve(&s->plan, nframes_fft, s->dev));   /* (the two-pass transforms' work area: room for the batch) */
 	HIP_TRY(wrk_fft_frames(s->dev->stream, s->plan, iq_dev, stride, nframes_fft, nullptr, db_dev));
 	return WR_OK;
 }
