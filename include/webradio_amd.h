@@ -60,6 +60,7 @@ extern "C" {
                                                       wr_resamp_info, wr_tuner_resamp_push.
                                     Added to 6 later: wr_dcs_word, wr_dcs_step, wr_dcs_create, wr_dcs_destroy, wr_dcs_reset,
                                                       wr_dcs_seek, wr_dcs_push_rows, wr_tuner_dcs_push, wr_dcs_read, wr_dcs_info.
+                                    Added to 6 later: wr_spectrum_batch_avg, wr_spectrum_rows_waterfall.
                                     Nothing of an earlier version changed or removed */
 #define WR_FIR_LENGTH    64      /* dsp/lowpass.cxx:39  FIR_LENGTH */
 #define WR_TABLE_SIZE    65536   /* dsp/downconverter.cxx:35 LOOKUP_BITS 16 */
@@ -574,6 +575,41 @@ int wr_spectrum_batch_db(wr_spectrum *spec, const float *iq_dev, size_t nframes_
  * launch sequence.  Async; closes an open streaming launch first, like wr_spectrum_batch_db. */
 int wr_spectrum_batch_db_rows(wr_spectrum *spec, const float *in_dev, size_t row_stride, size_t nrows,
                               float *db_dev);
+/* MEAN and PEAK-HOLD spectra over all frames of a block: what a display that polls at 5 Hz (web/waterfallhandler.cxx:56-61)
+ * needs so as not to miss what went by between two polls.  `ngroups` groups of `nframes_fft` frames each: frame f of group
+ * g starts g * group_stride + f * hop frames into in_dev (hop: the spectrum's own; a real spectrum: one float per frame).
+ * ngroups = 1 (any group_stride) is wr_spectrum_batch_db's layout; hop = fft_size, nframes_fft = 1, ngroups = nrows is
+ * wr_spectrum_batch_db_rows'; wr_tuner_audio_dev's pointer with chan_stride as group_stride, on a real spectrum, gives the
+ * averaged audio spectrum of every receiver of a block.  mean_dev and peak_dev each receive ngroups rows of fft_size floats,
+ * fft-shifted as wr_spectrum_get_db shifts; either may be NULL, not both.
+ *   The rule, for bin k of a group, (re_f, im_f) being what the transform of frame f gives there:
+ *     p_f  = fl(fl(re_f * re_f) + fl(im_f * im_f))                       (no fused multiply-add)
+ *     sum  = ((p_0 + p_1) + p_2) + ...      one float accumulator, in frame order
+ *     mean = sum / (float)nframes_fft,      peak = the largest p_f
+ *   linear != 0: the rows hold mean and peak; else 10 * log10f(x) - 20 * log10f(fft_size), wr_spectrum_get_db's expression.
+ * The result does not depend on the launches' grids, on how the call is cut into chunks, or on ngroups.  Non-finite input
+ * gives unspecified values in its group's rows and nothing else.
+ *   Every size and both kinds of spectrum.  The transforms write bins to a scratch area of the spectrum's own (64 MB at
+ * most, freed by wr_spectrum_destroy) and a reduce kernel walks them; longer calls go through it in chunks, over frames
+ * and over groups, with the same bits.  Where one workgroup transforms a frame (IQ up to 8192 points, real up to 16384) a
+ * chunk is two launches however many groups it holds; on the larger sizes the transform is a loop over the groups.
+ *   Async on the device's stream; closes an open streaming launch first, like wr_spectrum_batch_db.  The spectrum's own
+ * frames (wr_spectrum_push, frames_done, get_bins, get_db) are left alone.
+ *   WR_ERR_ARG: spec or in_dev NULL, both outputs NULL, nframes_fft = 0, ngroups > 1 with group_stride < fft_size.
+ * ngroups = 0: WR_OK, nothing written.
+ *   Left out on purpose: an averaging mode of the host runtime's SpectrumSink class, which keeps only the newest frame
+ * beside a streaming launch; an averaged wr_tuner_chan_spectra, whose kernel works on the column layout of channel IQ;
+ * exponential averaging across calls -- a caller blends linear rows. */
+int wr_spectrum_batch_avg(wr_spectrum *spec, const float *in_dev, size_t nframes_fft,
+                          size_t ngroups, size_t group_stride, int linear,
+                          float *mean_dev, float *peak_dev);
+/* Waterfall rows on the device: wr_spectrum_get_waterfall_row's reduction and palette (the last bin or, hold = 1, the
+ * maximum per pixel column; non-finite becomes -10000; the palette expression in double) on `nrows` fft-shifted dB rows of
+ * fft_size floats in device memory -- wr_spectrum_batch_avg's or wr_spectrum_batch_db's.  db_rows_dev[nrows][width] and
+ * palette_dev[nrows][width]: either may be NULL, not both.  `width` <= fft_size, fft_size % width == 0, else WR_ERR_ARG.
+ * One launch, async: a block goes from samples to pixel rows without visiting the host. */
+int wr_spectrum_rows_waterfall(wr_spectrum *spec, const float *db_dev, size_t nrows, unsigned int width, int hold,
+                               float *db_rows_dev, uint8_t *palette_dev);
 
 /* The CHANNEL spectrum of every receiver of a tuner (a SpectrumSink connected to each Receiver's channel filter,
  * io/spectrumsink.cxx:88-142 behind radio.cxx:68-76): for each channel slot the dB row (fft-shifted, wr_spectrum_get_db's

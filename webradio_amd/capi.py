@@ -122,6 +122,8 @@ SIGNATURES = {
     "wr_spectrum_create_real": (C.c_int, [C.POINTER(_vp), _vp, _u32, _u32]),
     "wr_spectrum_channels": (C.c_int, [_vp, C.POINTER(_u32)]),
     "wr_spectrum_batch_db_rows": (C.c_int, [_vp, _vp, _sz, _sz, _vp]),
+    "wr_spectrum_batch_avg": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.c_int, _vp, _vp]),
+    "wr_spectrum_rows_waterfall": (C.c_int, [_vp, _vp, _sz, _u32, C.c_int, _vp, _vp]),
     "wr_tuner_chan_spectra": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(C.c_uint)]),
     "wr_tuner_chan_levels": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(C.c_uint)]),
     "wr_iq_levels": (C.c_int, [_vp, _vp, _sz, C.POINTER(C.c_float), C.POINTER(C.c_float)]),

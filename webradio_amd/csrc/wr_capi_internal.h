@@ -283,6 +283,9 @@ struct wr_spectrum {
 	size_t def_rest = 0;       /* frames behind the deferred frame's hop that belong to the NEXT frame (at stage + 2 * hop) */
 	hipEvent_t def_ev = nullptr;   /* behind that copy */
 	unsigned long long deferred_pushes = 0, resolves = 0;
+	/* wr_spectrum_batch_avg's scratch area (wrp_spec_avg_bytes: a chunk's bins, then the carry): grows only, SPEC_AVG_BYTES at most */
+	float *avg = nullptr;
+	size_t avg_bytes = 0;
 };
 
 /* what the three objects of wr_banks.hip, which keep something per audio row of every receiver, begin with */

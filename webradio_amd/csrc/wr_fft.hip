@@ -22,6 +22,9 @@
  *   n <= 16384 : one workgroup per frame, untangled out of the LDS result buffer.
  *   n  > 16384 : four-step on m, then k_fft_untangle.
  *
+ * Mean and peak hold over the frames of a block (wr_spectrum_batch_avg): the transforms above write bins, k_spec_reduce
+ * walks them frame by frame in one order of operations; k_rows_waterfall reduces dB rows to pixel rows.
+ *
  * The window multiply is the reference's float multiply on the raw sample
  * (spectrumsink.cxx:109-112); the dB expression is the reference's float
  * expression (spectrumsink.cxx:127,137-138).
@@ -76,16 +79,24 @@ __device__ __forceinline__ float to_db(float2 v, float scaledb)
 	return 10.0f * log10f(v.x * v.x + v.y * v.y) - scaledb;
 }
 
-/* whole frame in LDS; grid.x = frame */
+/* where frame `frame` of a launch starts, in frames from the input pointer: frame f of group g at g * gstride + f * hop,
+ * `fpg` frames per group (one group: fpg = the launch's frames, and this is frame * hop) */
+__device__ __forceinline__ size_t frame_start(size_t frame, size_t hop, unsigned int fpg, size_t gstride)
+{
+	const size_t g = frame / fpg;
+	return g * gstride + (frame - g * fpg) * hop;
+}
+
+/* whole frame in LDS; grid.x = frame (group-major: wr_spectrum_batch_avg's groups share one launch) */
 __global__ void __launch_bounds__(FFT_THREADS)
-k_fft_single(const float2 *__restrict__ iq, size_t hop, unsigned int n,
+k_fft_single(const float2 *__restrict__ iq, size_t hop, unsigned int fpg, size_t gstride, unsigned int n,
              const float *__restrict__ window, const float2 *__restrict__ tw,
              float2 *__restrict__ bins, float *__restrict__ db, float scaledb)
 {
 	extern __shared__ float2 lds[];
 	float2 *a = lds, *b = lds + n;
 	const size_t frame = blockIdx.x;
-	const float2 *x = iq + frame * hop;
+	const float2 *x = iq + frame_start(frame, hop, fpg, gstride);
 	for (unsigned int i = threadIdx.x; i < n; i += FFT_THREADS) {
 		const float2 v = x[i];
 		const float w = window[i];
@@ -186,9 +197,10 @@ __device__ __forceinline__ void put_real_bins(float2 *__restrict__ bins, float *
 	}
 }
 
-/* a real frame of n <= 16384 samples whole in LDS (m = n/2 packed points); grid.x = frame, `hop` in floats */
+/* a real frame of n <= 16384 samples whole in LDS (m = n/2 packed points); grid.x = frame (group-major, frame_start),
+ * `hop` and `gstride` in floats */
 __global__ void __launch_bounds__(FFT_THREADS)
-k_fft_real_single(const float *__restrict__ in, size_t hop, unsigned int n,
+k_fft_real_single(const float *__restrict__ in, size_t hop, unsigned int fpg, size_t gstride, unsigned int n,
                   const float *__restrict__ window, const float2 *__restrict__ tw,
                   float2 *__restrict__ bins, float *__restrict__ db, float scaledb)
 {
@@ -196,7 +208,7 @@ k_fft_real_single(const float *__restrict__ in, size_t hop, unsigned int n,
 	const unsigned int m = n >> 1;
 	float2 *a = lds, *b = lds + m;
 	const size_t frame = blockIdx.x;
-	const float *x = in + frame * hop;
+	const float *x = in + frame_start(frame, hop, fpg, gstride);
 	const bool aligned = ((size_t)x & 7u) == 0;
 	for (unsigned int i = threadIdx.x; i < m; i += FFT_THREADS)
 		a[i] = real_pair(x, aligned, window, i);
@@ -533,6 +545,22 @@ __global__ void k_bins_to_db(const float2 *__restrict__ bins, unsigned int n, fl
 		db[(k + (n >> 1)) & (n - 1)] = to_db(bins[k], scaledb);
 }
 
+/* a pixel column's value after dB value `d`, the i-th of the bins that map to it, with `v` so far */
+__device__ __forceinline__ float waterfall_pick(float v, float d, unsigned int i, int hold)
+{
+	if (!isfinite(d))
+		d = -10000.0f;                                            /* waterfallhandler.cxx:65-68 */
+	return (i == 0 || !hold || d > v) ? d : v;                    /* last one wins, or running max */
+}
+
+/* waterfall.js:94-106, in double like JavaScript numbers */
+__device__ __forceinline__ uint8_t waterfall_palette(float v)
+{
+	double c = floor(((double)v + 50.0) / 25.0 * 255.0);
+	c = c < 0.0 ? 0.0 : (c > 255.0 ? 255.0 : c);
+	return (uint8_t)c;
+}
+
 /* waterfall row: dB + fft-shift of the stored bins reduced to `width` pixel columns */
 __global__ void k_waterfall_row(const float2 *__restrict__ bins, unsigned int n, unsigned int width, int hold,
                                 float scaledb, float *__restrict__ db_row, uint8_t *__restrict__ palette)
@@ -543,21 +571,97 @@ __global__ void k_waterfall_row(const float2 *__restrict__ bins, unsigned int n,
 		for (unsigned int i = 0; i < per; ++i) {
 			const unsigned int shifted = x * per + i;                 /* index in the shifted row */
 			const unsigned int k = (shifted + (n >> 1)) & (n - 1);     /* FFTW-order bin */
-			float d = to_db(bins[k], scaledb);
-			if (!isfinite(d))
-				d = -10000.0f;                                        /* waterfallhandler.cxx:65-68 */
-			if (i == 0 || !hold || d > v)
-				v = d;                                                /* last one wins, or running max */
+			v = waterfall_pick(v, to_db(bins[k], scaledb), i, hold);
 		}
 		if (db_row)
 			db_row[x] = v;
-		if (palette) {
-			/* waterfall.js:94-106, in double like JavaScript numbers */
-			double c = floor(((double)v + 50.0) / 25.0 * 255.0);
-			c = c < 0.0 ? 0.0 : (c > 255.0 ? 255.0 : c);
-			palette[x] = (uint8_t)c;
+		if (palette)
+			palette[x] = waterfall_palette(v);
+	}
+}
+
+/* the same reduction on `nrows` shifted dB rows of n floats (wr_spectrum_batch_avg's, wr_spectrum_batch_db's): a thread
+ * per (row, pixel column), the rows' pixel rows back to back */
+__global__ void k_rows_waterfall(const float *__restrict__ db, unsigned int n, size_t nrows, unsigned int width, int hold,
+                                 float *__restrict__ db_rows, uint8_t *__restrict__ palette)
+{
+	const unsigned int per = n / width;
+	const size_t total = nrows * width;
+	for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+		const float *col = db + e * per;                           /* (row * n + x * per: width * per = n) */
+		float v = 0.0f;
+		for (unsigned int i = 0; i < per; ++i)
+			v = waterfall_pick(v, col[i], i, hold);
+		if (db_rows)
+			db_rows[e] = v;
+		if (palette)
+			palette[e] = waterfall_palette(v);
+	}
+}
+
+/* 10*log10f(x) - 20*log10f(N) of a power (to_db's expression behind its sum) */
+__device__ __forceinline__ float power_to_db(float p, float scaledb)
+{
+	return 10.0f * log10f(p) - scaledb;
+}
+
+/* wr_spectrum_batch_avg's reduction over the frames of a chunk: bins[group][frame][n] of `groups` groups, `frames` of each.
+ * One thread per (group, bin k): neighbouring threads load neighbouring bins of one frame.  Per frame the power
+ * p = fl(fl(re*re) + fl(im*im)) (the library is built with -ffp-contract=off), sum = ((p_0 + p_1) + p_2) + ... in ONE float
+ * in frame order, peak the largest p.  `first`: the chunk begins its groups' frames; else sum and peak continue from
+ * carry[group][k] = (sum, peak), so a cut between two chunks leaves no trace in the bits.  `last`: mean = sum / nframes and
+ * peak go out as they are (linear) or in dB, at the fft-shifted position; else (sum, peak) go to the carry. */
+__global__ void __launch_bounds__(SPEC_REDUCE_THREADS)
+k_spec_reduce(const float2 *__restrict__ bins, unsigned int n, size_t groups, size_t frames, int first, int last,
+              float2 *__restrict__ carry, float nframes, int linear, float scaledb,
+              float *__restrict__ mean, float *__restrict__ peak)
+{
+	const size_t e = (size_t)blockIdx.x * SPEC_REDUCE_THREADS + threadIdx.x;
+	if (e >= groups * n)
+		return;
+	const size_t g = e / n;
+	const unsigned int k = (unsigned int)(e - g * n);
+	const float2 *b = bins + g * frames * n + k;
+	float sum, top;
+	size_t f = 0;
+	if (first) {
+		const float2 v = b[0];
+		sum = top = v.x * v.x + v.y * v.y;
+		f = 1;
+	} else {
+		const float2 c = carry[e];
+		sum = c.x;
+		top = c.y;
+	}
+	/* eight frames' loads in flight per thread: the adds wait for one another, the loads need not */
+	for (; f + 8 <= frames; f += 8) {
+		float2 v[8];
+#pragma unroll
+		for (int i = 0; i < 8; ++i)
+			v[i] = b[(f + i) * n];
+#pragma unroll
+		for (int i = 0; i < 8; ++i) {
+			const float p = v[i].x * v[i].x + v[i].y * v[i].y;
+			sum = sum + p;
+			top = p > top ? p : top;
 		}
 	}
+	for (; f < frames; ++f) {
+		const float2 v = b[f * n];
+		const float p = v.x * v.x + v.y * v.y;
+		sum = sum + p;
+		top = p > top ? p : top;
+	}
+	if (!last) {
+		carry[e] = make_float2(sum, top);
+		return;
+	}
+	const float avg = sum / nframes;
+	const size_t o = g * n + ((k + (n >> 1)) & (n - 1u));
+	if (mean)
+		mean[o] = linear ? avg : power_to_db(avg, scaledb);
+	if (peak)
+		peak[o] = linear ? top : power_to_db(top, scaledb);
 }
 
 hipError_t wrk_waterfall_row(hipStream_t st, const float *bins, unsigned int n, unsigned int width, int hold,
@@ -566,6 +670,23 @@ hipError_t wrk_waterfall_row(hipStream_t st, const float *bins, unsigned int n, 
 	const float scaledb = 20.0f * log10f((float)n);
 	k_waterfall_row<<<grid_for(width, 256, FFT_WATERFALL_GRID_CAP), 256, 0, st>>>((const float2 *)bins, n, width, hold, scaledb,
 	                                                                             db_row, palette);
+	return hipGetLastError();
+}
+
+hipError_t wrk_rows_waterfall(hipStream_t st, const float *db, unsigned int n, size_t nrows, unsigned int width, int hold,
+                              float *db_rows, uint8_t *palette)
+{
+	k_rows_waterfall<<<wrp_rows_waterfall_grid(nrows, width), 256, 0, st>>>(db, n, nrows, width, hold, db_rows, palette);
+	return hipGetLastError();
+}
+
+hipError_t wrk_spec_reduce(hipStream_t st, const float *bins, unsigned int n, size_t groups, size_t frames, bool first, bool last,
+                           float *carry, size_t nframes_fft, int linear, float *mean, float *peak)
+{
+	const float scaledb = 20.0f * log10f((float)n);
+	k_spec_reduce<<<wrp_spec_reduce_grid(n, groups), SPEC_REDUCE_THREADS, 0, st>>>((const float2 *)bins, n, groups, frames, first, last,
+	                                                                             (float2 *)carry, (float)nframes_fft, linear, scaledb,
+	                                                                             mean, peak);
 	return hipGetLastError();
 }
 
@@ -659,22 +780,41 @@ static hipError_t fft_allow_lds(void)
 hipError_t wrk_fft_frames(hipStream_t st, const WrFftPlan &P, const float *iq, size_t hop,
                           size_t nframes_fft, float *bins_out, float *db_out)
 {
-	if (!nframes_fft)
+	return wrk_fft_groups(st, P, iq, hop, nframes_fft, 1, 0, bins_out, db_out);
+}
+
+hipError_t wrk_fft_groups(hipStream_t st, const WrFftPlan &P, const float *iq, size_t hop, size_t nframes_fft, size_t ngroups,
+                          size_t gstride, float *bins_out, float *db_out)
+{
+	if (!nframes_fft || !ngroups)
 		return hipSuccess;
 	const WrFftShape &S = P.shape;
 	const float scaledb = 20.0f * log10f((float)P.n);   /* spectrumsink.cxx:127 */
 	const float2 *tw_n = (const float2 *)P.tw_n, *tw_sub = (const float2 *)P.tw_sub;
 	hipError_t e;
 	if (S.path == WR_FFT_SINGLE) {
-		const WrFftLaunch L = wrp_fft_launch(S, nframes_fft);
+		/* every group's frames in one launch */
+		const WrFftLaunch L = wrp_fft_launch(S, nframes_fft * ngroups);
+		const unsigned int fpg = (unsigned int)nframes_fft;
 		if ((e = S.real ? fft_allow_lds<k_fft_real_single>() : fft_allow_lds<k_fft_single>()) != hipSuccess)
 			return e;
 		if (S.real)
-			k_fft_real_single<<<L.g1x, FFT_THREADS, L.lds1, st>>>(iq, hop, P.n, P.window, tw_n, (float2 *)bins_out, db_out, scaledb);
+			k_fft_real_single<<<L.g1x, FFT_THREADS, L.lds1, st>>>(iq, hop, fpg, gstride, P.n, P.window, tw_n, (float2 *)bins_out,
+			                                                      db_out, scaledb);
 		else
-			k_fft_single<<<L.g1x, FFT_THREADS, L.lds1, st>>>((const float2 *)iq, hop, P.n, P.window, tw_n, (float2 *)bins_out, db_out,
-			                                                 scaledb);
+			k_fft_single<<<L.g1x, FFT_THREADS, L.lds1, st>>>((const float2 *)iq, hop, fpg, gstride, P.n, P.window, tw_n,
+			                                                 (float2 *)bins_out, db_out, scaledb);
 		return hipGetLastError();
+	}
+	if (ngroups > 1) {
+		/* the two-pass paths: a loop over the groups */
+		for (size_t g = 0; g < ngroups; ++g) {
+			const size_t row = g * nframes_fft * P.n;
+			if ((e = wrk_fft_groups(st, P, iq + P.channels * g * gstride, hop, nframes_fft, 1, 0, bins_out ? bins_out + 2 * row : nullptr,
+			                        db_out ? db_out + row : nullptr)) != hipSuccess)
+				return e;
+		}
+		return hipSuccess;
 	}
 	if (S.path == WR_FFT_FOUR_STEP) {
 		if ((e = S.real ? fft_allow_lds<k_fft_pass1<true>>() : fft_allow_lds<k_fft_pass1<false>>()) != hipSuccess)

@@ -343,6 +343,17 @@ hipError_t wrk_fft_plan_reserve(WrFftPlan *P, size_t frames, wr_dev *dev);
 /* frame f starts `f * hop` frames (of P.channels floats) into `iq` */
 hipError_t wrk_fft_frames(hipStream_t st, const WrFftPlan &P, const float *iq, size_t hop,
                           size_t nframes_fft, float *bins_out /* or NULL */, float *db_out /* or NULL */);
+/* `ngroups` groups of `nframes_fft` frames: frame f of group g starts `g * gstride + f * hop` frames into `iq`, its row is
+ * row g * nframes_fft + f.  Single-workgroup sizes: one launch for all groups; two-pass sizes: a loop over the groups */
+hipError_t wrk_fft_groups(hipStream_t st, const WrFftPlan &P, const float *iq, size_t hop, size_t nframes_fft, size_t ngroups,
+                          size_t gstride, float *bins_out /* or NULL */, float *db_out /* or NULL */);
+/* wr_spectrum_batch_avg's reduction (k_spec_reduce) of a chunk's bins[groups][frames][n][2]; `carry`: [groups][n][2], read
+ * unless `first`, written unless `last`; `nframes_fft`: the frames of a whole group, the mean's divisor */
+hipError_t wrk_spec_reduce(hipStream_t st, const float *bins, unsigned int n, size_t groups, size_t frames, bool first, bool last,
+                           float *carry, size_t nframes_fft, int linear, float *mean /* or NULL */, float *peak /* or NULL */);
+/* k_waterfall_row's reduction and palette on `nrows` shifted dB rows of n floats in device memory */
+hipError_t wrk_rows_waterfall(hipStream_t st, const float *db, unsigned int n, size_t nrows, unsigned int width, int hold,
+                              float *db_rows /* or NULL */, uint8_t *palette /* or NULL */);
 
 /* the dB row (shifted) of rows [first, first + P.n) of the first `cols` columns of iq[rows][S][2], row of column s at
  * db + s * P.n: IQ plans of at most 8192 points, cols <= S a multiple of 64 */

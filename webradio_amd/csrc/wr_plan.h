@@ -1,7 +1,8 @@
 /*
  * wr_plan.h -- the launch geometry of every tuner launch (the per-block DDC, the long-filter DDC, the post stage, the audio
  * filter, the streaming launch) and of the spectrum launches (the transform's shape and path, its passes' tiles, grids and
- * LDS, the work area and its chunks, the columns per workgroup of the channel spectra): which kernel instance, how many
+ * LDS, the work area and its chunks, the columns per workgroup of the channel spectra, the chunks, scratch cap and launch count
+ * of the averaged spectra): which kernel instance, how many
  * workgroups per role, how much LDS, the group map, kslow, kmax, the post stage's runs of tiles.  The arithmetic alone, with
  * no HIP call and no environment read, so that a CPU test can hold it to the rule (tests/test_launch_plan.py through
  * tests/cxx/cpu_host_checks.cxx).  The launch functions (wr_kernels.hip, wr_stream_kernel.inc, wr_fft.hip) obtain a plan,
@@ -464,6 +465,10 @@ static inline WrAudioPlan wrp_audio_plan(size_t k2, unsigned int d2, unsigned in
 #define FFT_TILE_MAX 16u                   /* columns (pass 1) or rows (pass 2) of a four-step workgroup */
 #define FFT_COLS_CT_MAX 8u                 /* columns per workgroup of k_fft_cols: 64-byte runs */
 #define FFT_WORK_BYTES ((size_t)128 << 20) /* the work area between the passes: it then still sits in the 256 MB Infinity Cache */
+#define SPEC_AVG_BYTES ((size_t)64 << 20)  /* wr_spectrum_batch_avg's scratch (bins and carry): the 127 frames of a BASELINE config 3
+                                              block in one chunk, and with the work area above still inside the Infinity Cache */
+#define SPEC_REDUCE_THREADS 256u           /* k_spec_reduce: one thread per (group, bin) */
+#define SPEC_ROWS_GRID_CAP 4096u           /* k_rows_waterfall strides beyond 2^20 (row, column) pairs */
 #define FFT_DB_GRID_CAP 1024u              /* k_bins_to_db strides beyond 262144 bins */
 #define FFT_WATERFALL_GRID_CAP 4096u       /* k_waterfall_row: 2^20 columns, the largest transform's; never reached below it */
 /* batches of the 65536-point path from this many frames on take four frames per pass-1 workgroup (>= 384 workgroups) */
@@ -580,6 +585,108 @@ static inline unsigned int wrp_fft_cols_ct(unsigned int n, unsigned int cols, in
 	while (2u * ct <= most)
 		ct *= 2u;
 	return ct;
+}
+
+/* ---- wr_spectrum_batch_avg: `G` groups of `F` frames of n points each.  The transforms write bins into a scratch area of
+ * at most SPEC_AVG_BYTES (8 n bytes a frame: 8 frames of 2^20 points, 2^20 frames of 8), k_spec_reduce walks them.  A chunk
+ * is `ng` whole groups of `nf` frames each:
+ *   F frames fit the area : every chunk takes all F frames of as many groups as fit, gchunk at most
+ *   they do not           : one group at a time, fchunk frames per chunk, and one frame's worth of the area is the carry
+ *                           buffer that hands sum and peak from a chunk to the next (carry = 1 group)
+ * Groups are the outer loop, a group's frames go in order. ---- */
+struct WrSpecAvgPlan {
+	size_t fchunk, gchunk;                 /* frames of a group and groups per chunk, at most */
+	size_t carry;                          /* groups the carry buffer holds: 0 where no group's frames are cut */
+};
+
+static inline WrSpecAvgPlan wrp_spec_avg_plan(unsigned int n, size_t F, size_t G)
+{
+	WrSpecAvgPlan p = {0, 0, 0};
+	const size_t room = SPEC_AVG_BYTES / ((size_t)n * 8u);      /* frames; 8 or more */
+	if (!F || !G)
+		return p;
+	if (F <= room) {
+		p.fchunk = F;
+		p.gchunk = room / F < G ? room / F : G;
+	} else {
+		p.fchunk = room - 1u;
+		p.gchunk = 1;
+		p.carry = 1;
+	}
+	return p;
+}
+
+/* the scratch area of a plan: bins [gchunk][fchunk][n][2], then the carry [carry][n][2] (sum, peak) */
+static inline size_t wrp_spec_avg_bytes(unsigned int n, const WrSpecAvgPlan &p)
+{
+	return (p.fchunk * p.gchunk + p.carry) * (size_t)n * 8u;
+}
+
+struct WrSpecAvgChunk {
+	size_t g0, ng, f0, nf;                 /* groups [g0, g0 + ng), of each frames [f0, f0 + nf) */
+};
+
+/* the chunk behind `c` (`start`: the first); false: there is none */
+static inline bool wrp_spec_avg_next(const WrSpecAvgPlan &p, size_t F, size_t G, WrSpecAvgChunk *c, bool start)
+{
+	if (!p.fchunk || !p.gchunk)
+		return false;
+	if (start) {
+		c->g0 = 0;
+		c->f0 = 0;
+	} else if (c->f0 + c->nf < F) {
+		c->f0 += c->nf;
+	} else {
+		c->g0 += c->ng;
+		c->f0 = 0;
+	}
+	if (c->g0 >= G)
+		return false;
+	c->ng = G - c->g0 < p.gchunk ? G - c->g0 : p.gchunk;
+	c->nf = F - c->f0 < p.fchunk ? F - c->f0 : p.fchunk;
+	return true;
+}
+
+/* k_spec_reduce on a chunk of `ng` groups: a thread per (group, bin), no stride (ng * n <= SPEC_AVG_BYTES / 8) */
+static inline unsigned int wrp_spec_reduce_grid(unsigned int n, size_t ng)
+{
+	return (unsigned int)((ng * n + SPEC_REDUCE_THREADS - 1u) / SPEC_REDUCE_THREADS);
+}
+
+/* launches of one chunk.  Single-workgroup sizes: the transform of all its groups' frames and the reduce, however many
+ * groups.  Two-pass sizes: the transform is a loop over the groups, each through the work area (`work_frames` frames) in
+ * pieces of two launches (real: three), and the reduce. */
+static inline size_t wrp_spec_avg_chunk_launches(const WrFftShape &s, size_t ng, size_t nf, size_t work_frames)
+{
+	if (s.path == WR_FFT_SINGLE)
+		return 2;
+	const size_t pieces = (nf + work_frames - 1u) / work_frames;
+	return ng * pieces * (s.real ? 3u : 2u) + 1u;
+}
+
+/* launches of a whole call (closed form of the loop over wrp_spec_avg_next) */
+static inline size_t wrp_spec_avg_launches(unsigned int n, unsigned int channels, size_t F, size_t G, size_t work_frames)
+{
+	const WrFftShape s = wrp_fft_shape(n, channels);
+	const WrSpecAvgPlan p = wrp_spec_avg_plan(n, F, G);
+	if (!p.fchunk)
+		return 0;
+	const size_t gfull = G / p.gchunk, grem = G % p.gchunk, ffull = F / p.fchunk, frem = F % p.fchunk;
+	size_t total = gfull * ffull * wrp_spec_avg_chunk_launches(s, p.gchunk, p.fchunk, work_frames);
+	if (frem)
+		total += gfull * wrp_spec_avg_chunk_launches(s, p.gchunk, frem, work_frames);
+	if (grem) {
+		total += ffull * wrp_spec_avg_chunk_launches(s, grem, p.fchunk, work_frames);
+		if (frem)
+			total += wrp_spec_avg_chunk_launches(s, grem, frem, work_frames);
+	}
+	return total;
+}
+
+/* k_rows_waterfall: a thread per (row, pixel column) */
+static inline unsigned int wrp_rows_waterfall_grid(size_t nrows, unsigned int width)
+{
+	return grid_for(nrows * width, 256, SPEC_ROWS_GRID_CAP);
 }
 
 #endif /* WR_PLAN_H_ */

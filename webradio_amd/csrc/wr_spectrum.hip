@@ -81,6 +81,7 @@ extern "C" int wr_spectrum_destroy(wr_spectrum *s)
 	wrk_fft_plan_free(&s->plan);
 	(void)hipFree(s->stage);
 	(void)hipFree(s->bins);
+	(void)hipFree(s->avg);
 	delete s;
 	return WR_OK;
 }
@@ -402,4 +403,66 @@ extern "C" int wr_spectrum_batch_db_rows(wr_spectrum *s, const float *in_dev, si
 	if (row_stride < s->n)
 		return wrc_fail(WR_ERR_ARG, "wr_spectrum_batch_db_rows: row_stride must not be less than fft_size");
 	return spectrum_batch(s, in_dev, row_stride, nrows, db_dev);
+}
+
+/* room in the averaging scratch area (grows only; wr_spectrum_destroy frees it) */
+static int spectrum_avg_room(wr_spectrum *s, size_t bytes)
+{
+	if (bytes <= s->avg_bytes)
+		return WR_OK;
+	HIP_TRY(wrc_dev_stream_sync(s->dev));                   /* (whatever still uses the old area) */
+	(void)hipFree(s->avg);
+	s->avg = nullptr;
+	s->avg_bytes = 0;
+	HIP_TRY(hipMalloc((void **)&s->avg, bytes));
+	s->avg_bytes = bytes;
+	return WR_OK;
+}
+
+extern "C" int wr_spectrum_batch_avg(wr_spectrum *s, const float *in_dev, size_t nframes_fft, size_t ngroups, size_t group_stride,
+                                     int linear, float *mean_dev, float *peak_dev)
+{
+	if (!s || !in_dev || (!mean_dev && !peak_dev))
+		return wrc_fail(WR_ERR_ARG, "wr_spectrum_batch_avg: bad argument");
+	if (!nframes_fft)
+		return wrc_fail(WR_ERR_ARG, "wr_spectrum_batch_avg: nframes_fft must not be 0");
+	if (ngroups > 1 && group_stride < s->n)
+		return wrc_fail(WR_ERR_ARG, "wr_spectrum_batch_avg: group_stride must not be less than fft_size");
+	if (!ngroups)
+		return WR_OK;
+	wr_dev *d = s->dev;
+	if (wrc_dev_bind(d))
+		return WR_ERR_HIP;
+	DEV_SETTLE(d);
+	const WrSpecAvgPlan plan = wrp_spec_avg_plan(s->n, nframes_fft, ngroups);
+	if (int rc = spectrum_avg_room(s, wrp_spec_avg_bytes(s->n, plan)))
+		return rc;
+	HIP_TRY(wrk_fft_plan_reserve(&s->plan, plan.fchunk, d));
+	float *bins = s->avg, *carry = s->avg + plan.fchunk * plan.gchunk * s->n * 2;
+	WrSpecAvgChunk c;
+	for (bool more = wrp_spec_avg_next(plan, nframes_fft, ngroups, &c, true); more;
+	     more = wrp_spec_avg_next(plan, nframes_fft, ngroups, &c, false)) {
+		const float *src = in_dev + s->ch * (c.g0 * group_stride + c.f0 * s->hop);
+		HIP_TRY(wrk_fft_groups(d->stream, s->plan, src, s->hop, c.nf, c.ng, group_stride, bins, nullptr));
+		HIP_TRY(wrk_spec_reduce(d->stream, bins, s->n, c.ng, c.nf, c.f0 == 0, c.f0 + c.nf == nframes_fft, carry, nframes_fft, linear,
+		                        mean_dev ? mean_dev + c.g0 * s->n : nullptr, peak_dev ? peak_dev + c.g0 * s->n : nullptr));
+	}
+	return WR_OK;
+}
+
+extern "C" int wr_spectrum_rows_waterfall(wr_spectrum *s, const float *db_dev, size_t nrows, unsigned int width, int hold,
+                                          float *db_rows_dev, uint8_t *palette_dev)
+{
+	if (!s || (nrows && !db_dev) || (!db_rows_dev && !palette_dev))
+		return wrc_fail(WR_ERR_ARG, "wr_spectrum_rows_waterfall: bad argument");
+	if (!width || width > s->n || s->n % width)
+		return wrc_fail(WR_ERR_ARG, "wr_spectrum_rows_waterfall: width must divide fft_size");
+	if (!nrows)
+		return WR_OK;
+	wr_dev *d = s->dev;
+	if (wrc_dev_bind(d))
+		return WR_ERR_HIP;
+	DEV_SETTLE(d);
+	HIP_TRY(wrk_rows_waterfall(d->stream, db_dev, s->n, nrows, width, hold, db_rows_dev, palette_dev));
+	return WR_OK;
 }

@@ -590,6 +590,17 @@ class Spectrum:
         """dB rows of the first fft_size frames of `nrows` rows lying `row_stride` frames apart in device memory"""
         check(self.lib.wr_spectrum_batch_db_rows(self.h, ptr(in_dev), row_stride, nrows, ptr(db_dev)))
 
+    def batch_avg(self, in_dev, nframes_fft, mean_dev=None, peak_dev=None, ngroups=1, group_stride=0, linear=False):
+        """mean and peak-hold rows over the `nframes_fft` frames of each of `ngroups` groups lying `group_stride` frames
+        apart in device memory (wr_spectrum_batch_avg): dB, or the powers themselves with `linear`"""
+        check(self.lib.wr_spectrum_batch_avg(self.h, ptr(in_dev), nframes_fft, ngroups, group_stride, int(bool(linear)),
+                                             ptr(mean_dev), ptr(peak_dev)))
+
+    def rows_waterfall(self, db_dev, nrows, width, hold, db_rows_dev=None, palette_dev=None):
+        """`nrows` shifted dB rows in device memory to pixel rows of `width` columns (wr_spectrum_rows_waterfall)"""
+        check(self.lib.wr_spectrum_rows_waterfall(self.h, ptr(db_dev), nrows, width, int(hold), ptr(db_rows_dev),
+                                                  ptr(palette_dev)))
+
     def channels(self):
         c = C.c_uint()
         check(self.lib.wr_spectrum_channels(self.h, C.byref(c)))
