@@ -61,6 +61,7 @@ extern "C" {
                                     Added to 6 later: wr_dcs_word, wr_dcs_step, wr_dcs_create, wr_dcs_destroy, wr_dcs_reset,
                                                       wr_dcs_seek, wr_dcs_push_rows, wr_tuner_dcs_push, wr_dcs_read, wr_dcs_info.
                                     Added to 6 later: wr_spectrum_batch_avg, wr_spectrum_rows_waterfall.
+                                    Added to 6 later: wr_detect_rule_default, wr_spectrum_bin_hz, wr_spectrum_rows_detect.
                                     Nothing of an earlier version changed or removed */
 #define WR_FIR_LENGTH    64      /* dsp/lowpass.cxx:39  FIR_LENGTH */
 #define WR_TABLE_SIZE    65536   /* dsp/downconverter.cxx:35 LOOKUP_BITS 16 */
@@ -610,6 +611,70 @@ int wr_spectrum_batch_avg(wr_spectrum *spec, const float *in_dev, size_t nframes
  * One launch, async: a block goes from samples to pixel rows without visiting the host. */
 int wr_spectrum_rows_waterfall(wr_spectrum *spec, const float *db_dev, size_t nrows, unsigned int width, int hold,
                                float *db_rows_dev, uint8_t *palette_dev);
+
+/* BAND SCAN: the noise floor and the occupied segments of spectrum rows, on the device -- where in the band there is
+ * something to listen to, as a few records of 24 bytes per row instead of the rows themselves.
+ *   Input is `nrows` rows of n = fft_size floats in device memory.  Any rows of that shape are accepted: the fft-shifted dB
+ * rows of wr_spectrum_batch_avg, wr_spectrum_batch_db, wr_spectrum_batch_db_rows and wr_tuner_chan_spectra; with `linear`,
+ * the power rows of wr_spectrum_batch_avg(linear = 1).
+ *   The rule (a wr_detect_rule):
+ *     bin0, nbins   the part of each row that is looked at            bin0 + nbins <= n, nbins >= 8
+ *     span          bins that share one noise floor                   8 <= span, nbins % span == 0
+ *     percent       which order statistic is the floor                0 .. 100
+ *     threshold     float, finite
+ *     linear        int
+ *     max_gap       cold bins a segment bridges                       <= nbins
+ *     min_width     narrowest segment that is kept                    1 .. nbins
+ * (the window bin0 / nbins exists for one half of a real spectrum's symmetric row, and for leaving out band edges or the DC
+ * spike).  Anything outside the limits gives WR_ERR_ARG, with a message that names the call and the field.
+ *   Order of floats.  key(x): with u the float's 32 bits, u ^ 0xFFFFFFFF if the sign bit is set, else u | 0x80000000.  Keys
+ * order -inf < ... < -0 < +0 < ... < +inf.  NaNs never take part (x != x).
+ *   Floor of span j (`span` bins from bin0 + j * span).  Let m be the number of non-NaN values in the span.  The floor is
+ * the value whose key is the rank-th smallest, counting from 0, with rank = ((m - 1) * percent) / 100 in integer division.
+ * Its bits are an input's bits.  m = 0: the floor is NaN (0x7FC00000) and the span has no hot bin.
+ *   Hot bins.  t = fl(floor + threshold), or with `linear` t = fl(floor * threshold): one float32 operation with no fusion.
+ * Bin k is hot iff row[k] >= t, which is false when either side is NaN.
+ *   Segments.  Take the hot bins h_0 < h_1 < ... of the window.  h_i starts a segment iff i = 0 or
+ * h_i - h_{i-1} - 1 > max_gap.  Segments do not wrap round the window's ends and pay no attention to span borders.  A
+ * segment has: first and last, its first and last hot bin; hot, the number of its hot bins; peak_bin, the hot bin with the
+ * largest key, the lowest index on ties; peak = row[peak_bin]; floor, the floor of the span that holds peak_bin.  A segment
+ * is kept iff last - first + 1 >= min_width.
+ *   Records.  Bin indices are the row's own, not relative to bin0.  count_dev[r] is the number of kept segments of row r,
+ * all of them.  det_dev[r * max_det + i] is the i-th kept segment in ascending `first`, for i < min(count, max_det); entries
+ * behind that are not written.  floor_dev[r * (nbins / span) + j] is optional and holds the floors.
+ *   Non-finite input has exactly the meaning above and touches nothing but its own row.  Integers decide, apart from the one
+ * float operation and the one float compare; the result does not depend on grids or on the number of rows. */
+typedef struct {
+	unsigned int bin0, nbins;
+	unsigned int span;
+	unsigned int percent;
+	float threshold;
+	int linear;
+	unsigned int max_gap;
+	unsigned int min_width;
+} wr_detect_rule;
+
+typedef struct { uint32_t first, last, peak_bin, hot; float peak, floor; } wr_detection;
+
+/* The whole row, span = min(fft_size, 1024), percent = 50 (the median), threshold = 10 (dB above it), linear = 0,
+ * max_gap = 1, min_width = 1.  fft_size: a power of two in [8, 1048576], else WR_ERR_ARG.  Needs no device. */
+int wr_detect_rule_default(unsigned int fft_size, wr_detect_rule *rule);
+/* The frequency of (fractional) bin `bin` of a shifted row: *hz = centre_hz + (bin - fft_size / 2) * sample_rate / fft_size
+ * (DC sits at fft_size / 2).  `bin` is a double so that a segment's middle (first + last) / 2 converts too.  WR_ERR_ARG:
+ * fft_size no power of two in [8, 1048576], sample_rate = 0, hz NULL.  Needs no device. */
+int wr_spectrum_bin_hz(unsigned int fft_size, unsigned int sample_rate, double centre_hz, double bin, double *hz);
+/* The rule above on `nrows` rows.  Two launches per chunk of rows: the floors (an exact order statistic by radix select, one
+ * workgroup per span and row), then the segments (forward scans with a carry from tile to tile, one workgroup per row -- a
+ * 2^20-point row is one workgroup's work).  Both kinds of spectrum, every fft_size, any nrows.  Async on the device's stream;
+ * closes an open streaming launch first, like wr_spectrum_rows_waterfall.  max_det = 0 only counts.  Without floor_dev the
+ * floors live in the spectrum's own scratch area (wr_spectrum_batch_avg's, freed by wr_spectrum_destroy), 512 KB of it at
+ * most: more rows than that holds floors for go through it in chunks of rows, with the same result.
+ *   WR_ERR_ARG: spec, rule or count_dev NULL; rows_dev NULL with nrows > 0; det_dev NULL with max_det > 0; a field of the
+ * rule outside its limits.  nrows = 0: WR_OK, nothing written.
+ *   Left out on purpose: tracking detections from block to block, assigning receivers to them, the integrated power of a
+ * segment, detection inside the streaming launch. */
+int wr_spectrum_rows_detect(wr_spectrum *spec, const float *rows_dev, size_t nrows, const wr_detect_rule *rule,
+                            unsigned int max_det, wr_detection *det_dev, unsigned int *count_dev, float *floor_dev);
 
 /* The CHANNEL spectrum of every receiver of a tuner (a SpectrumSink connected to each Receiver's channel filter,
  * io/spectrumsink.cxx:88-142 behind radio.cxx:68-76): for each channel slot the dB row (fft-shifted, wr_spectrum_get_db's

@@ -10,12 +10,12 @@ and bench.py:
   synth   synthetic tuner streams (test and bench inputs)
 """
 __all__ = ["capi", "device", "synth", "CTCSS_HZ", "DCS_CODES", "DcsBank", "dcs_word", "dcs_step", "Resampler", "resamp_design",
-           "resamp_ratio"]
+           "resamp_ratio", "DETECTION"]
 
 
 def __getattr__(name):
-    # the resampler's and the DCS bank's names, from device (imported on first use: importing the package loads no library)
-    if name in ("Resampler", "resamp_design", "resamp_ratio", "DcsBank", "dcs_word", "dcs_step"):
+    # the resampler's, the DCS bank's and the band scan's names, from device (imported on first use: importing the package loads no library)
+    if name in ("Resampler", "resamp_design", "resamp_ratio", "DcsBank", "dcs_word", "dcs_step", "DETECTION"):
         from . import device
         return getattr(device, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

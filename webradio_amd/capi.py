@@ -124,6 +124,9 @@ SIGNATURES = {
     "wr_spectrum_batch_db_rows": (C.c_int, [_vp, _vp, _sz, _sz, _vp]),
     "wr_spectrum_batch_avg": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.c_int, _vp, _vp]),
     "wr_spectrum_rows_waterfall": (C.c_int, [_vp, _vp, _sz, _u32, C.c_int, _vp, _vp]),
+    "wr_detect_rule_default": (C.c_int, [_u32, _vp]),
+    "wr_spectrum_bin_hz": (C.c_int, [_u32, _u32, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    "wr_spectrum_rows_detect": (C.c_int, [_vp, _vp, _sz, _vp, _u32, _vp, _vp, _vp]),
     "wr_tuner_chan_spectra": (C.c_int, [_vp, _vp, _sz, _vp, C.POINTER(C.c_uint)]),
     "wr_tuner_chan_levels": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(C.c_uint)]),
     "wr_iq_levels": (C.c_int, [_vp, _vp, _sz, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -162,6 +165,12 @@ SIGNATURES = {
     "wr_dcs_read": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),
     "wr_dcs_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_ulonglong)]),
 }
+
+
+class DetectRule(C.Structure):
+    """wr_detect_rule (include/webradio_amd.h: the band scan's rule)"""
+    _fields_ = [("bin0", C.c_uint), ("nbins", C.c_uint), ("span", C.c_uint), ("percent", C.c_uint), ("threshold", C.c_float),
+                ("linear", C.c_int), ("max_gap", C.c_uint), ("min_width", C.c_uint)]
 
 
 class WrError(RuntimeError):

@@ -284,6 +284,7 @@ struct wr_spectrum {
 	hipEvent_t def_ev = nullptr;   /* behind that copy */
 	unsigned long long deferred_pushes = 0, resolves = 0;
 	/* wr_spectrum_batch_avg's scratch area (wrp_spec_avg_bytes: a chunk's bins, then the carry): grows only, SPEC_AVG_BYTES at most */
+	/* (wr_spectrum_rows_detect keeps a chunk's floors at its front: DETECT_FLOOR_BYTES at most) */
 	float *avg = nullptr;
 	size_t avg_bytes = 0;
 };

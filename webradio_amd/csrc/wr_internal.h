@@ -354,6 +354,11 @@ hipError_t wrk_spec_reduce(hipStream_t st, const float *bins, unsigned int n, si
 /* k_waterfall_row's reduction and palette on `nrows` shifted dB rows of n floats in device memory */
 hipError_t wrk_rows_waterfall(hipStream_t st, const float *db, unsigned int n, size_t nrows, unsigned int width, int hold,
                               float *db_rows /* or NULL */, uint8_t *palette /* or NULL */);
+/* wr_detect.hip: one chunk of wr_spectrum_rows_detect -- `nrows` (plan.chunk_rows at most) rows of n floats: k_detect_floor into
+ * floors[nrows][plan.nspans], k_detect_segments into det[nrows][max_det] and count[nrows]; `rule` has passed wrp_detect_rule_bad */
+hipError_t wrk_detect_rows(hipStream_t st, const float *rows, unsigned int n, size_t nrows, const wr_detect_rule *rule,
+                           const WrDetectPlan &plan, unsigned int max_det, wr_detection *det /* or NULL: max_det = 0 */,
+                           unsigned int *count, float *floors);
 
 /* the dB row (shifted) of rows [first, first + P.n) of the first `cols` columns of iq[rows][S][2], row of column s at
  * db + s * P.n: IQ plans of at most 8192 points, cols <= S a multiple of 64 */

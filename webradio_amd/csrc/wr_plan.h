@@ -2,7 +2,7 @@
  * wr_plan.h -- the launch geometry of every tuner launch (the per-block DDC, the long-filter DDC, the post stage, the audio
  * filter, the streaming launch) and of the spectrum launches (the transform's shape and path, its passes' tiles, grids and
  * LDS, the work area and its chunks, the columns per workgroup of the channel spectra, the chunks, scratch cap and launch count
- * of the averaged spectra): which kernel instance, how many
+ * of the averaged spectra, the band scan's limits, grids, LDS and chunks of rows): which kernel instance, how many
  * workgroups per role, how much LDS, the group map, kslow, kmax, the post stage's runs of tiles.  The arithmetic alone, with
  * no HIP call and no environment read, so that a CPU test can hold it to the rule (tests/test_launch_plan.py through
  * tests/cxx/cpu_host_checks.cxx).  The launch functions (wr_kernels.hip, wr_stream_kernel.inc, wr_fft.hip) obtain a plan,
@@ -687,6 +687,82 @@ static inline size_t wrp_spec_avg_launches(unsigned int n, unsigned int channels
 static inline unsigned int wrp_rows_waterfall_grid(size_t nrows, unsigned int width)
 {
 	return grid_for(nrows * width, 256, SPEC_ROWS_GRID_CAP);
+}
+
+/* ---- wr_spectrum_rows_detect: two launches per chunk of rows.  k_detect_floor: a workgroup per (row, span), its histogram
+ * and digit hand-off in LDS and, where the span fits, the span's keys behind them.  k_detect_segments: a workgroup per row,
+ * tiles of DETECT_TILE bins, DETECT_PER consecutive bins a thread.  Floors of a chunk: [rows][nspans] floats, within
+ * DETECT_FLOOR_BYTES -- which one row of 2^20 points in spans of 8 fills. ---- */
+#define DETECT_THREADS     256u
+#define DETECT_PER         4u
+#define DETECT_TILE        (DETECT_THREADS * DETECT_PER)
+#define DETECT_WAVES       (DETECT_THREADS / 64u)
+#define DETECT_LDS_KEYS    8192u                   /* a span of up to this many bins keeps its keys in LDS (32 KiB) */
+#define DETECT_FLOOR_HEAD  (256u + 4u)             /* dwords in front of the keys: the histogram, the chosen digit's hand-off */
+#define DETECT_SEG_LDS     (DETECT_WAVES * (2u * 4u + 4u + 24u + 4u))   /* k_detect_segments: the waves' hot flags (two sets), the wave totals of its three scans */
+#define DETECT_FLOOR_BYTES ((size_t)512 << 10)
+#define DETECT_WG_LDS_MAX  (64u * 1024u)           /* what a workgroup may have without asking */
+
+/* the field of the rule that breaks a limit on rows of n floats, or NULL */
+static inline const char *wrp_detect_rule_bad(unsigned int n, const wr_detect_rule *r)
+{
+	if (r->bin0 > n || r->nbins > n - r->bin0)
+		return "bin0";
+	if (r->nbins < 8u)
+		return "nbins";
+	if (r->span < 8u || r->span > r->nbins || r->nbins % r->span)
+		return "span";
+	if (r->percent > 100u)
+		return "percent";
+	if (!(r->threshold - r->threshold == 0.0f))             /* NaN, +-inf */
+		return "threshold";
+	if (r->max_gap > r->nbins)
+		return "max_gap";
+	if (r->min_width < 1u || r->min_width > r->nbins)
+		return "min_width";
+	return NULL;
+}
+
+struct WrDetectPlan {
+	unsigned int nspans;                   /* floors of a row */
+	size_t chunk_rows;                     /* rows of a chunk, at most */
+	size_t floor_bytes;                    /* the floors of the call's largest chunk */
+	bool keys_in_lds;
+	size_t lds_floor, lds_segments;        /* bytes */
+};
+
+/* a valid rule (wrp_detect_rule_bad) */
+static inline WrDetectPlan wrp_detect_plan(const wr_detect_rule *r, size_t nrows)
+{
+	WrDetectPlan p;
+	p.nspans = r->nbins / r->span;
+	p.chunk_rows = DETECT_FLOOR_BYTES / 4u / p.nspans;              /* 1 or more: nspans <= 2^20 / 8 */
+	p.floor_bytes = (nrows < p.chunk_rows ? nrows : p.chunk_rows) * p.nspans * 4u;
+	p.keys_in_lds = r->span <= DETECT_LDS_KEYS;
+	p.lds_floor = (DETECT_FLOOR_HEAD + (p.keys_in_lds ? r->span : 0u)) * 4u;
+	p.lds_segments = DETECT_SEG_LDS;
+	return p;
+}
+
+/* the chunk behind rows [*r0, *r0 + *nr) (`start`: the first); false: there is none */
+static inline bool wrp_detect_next(const WrDetectPlan &p, size_t nrows, size_t *r0, size_t *nr, bool start)
+{
+	*r0 = start ? 0 : *r0 + *nr;
+	if (*r0 >= nrows)
+		return false;
+	*nr = nrows - *r0 < p.chunk_rows ? nrows - *r0 : p.chunk_rows;
+	return true;
+}
+
+/* a chunk's grids: k_detect_floor, a workgroup per (row, span) -- 2^17 at most; k_detect_segments, a workgroup per row */
+static inline unsigned int wrp_detect_floor_grid(const WrDetectPlan &p, size_t rows)
+{
+	return (unsigned int)(rows * p.nspans);
+}
+
+static inline unsigned int wrp_detect_segments_grid(size_t rows)
+{
+	return (unsigned int)rows;
 }
 
 #endif /* WR_PLAN_H_ */

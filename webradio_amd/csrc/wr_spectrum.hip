@@ -466,3 +466,62 @@ extern "C" int wr_spectrum_rows_waterfall(wr_spectrum *s, const float *db_dev, s
 	HIP_TRY(wrk_rows_waterfall(d->stream, db_dev, s->n, nrows, width, hold, db_rows_dev, palette_dev));
 	return WR_OK;
 }
+
+/* --------------------------------------------------------------- band scan -- */
+
+static bool spectrum_size_ok(unsigned int fft_size)
+{
+	return fft_size >= 8 && fft_size <= (1u << 20) && !(fft_size & (fft_size - 1));
+}
+
+extern "C" int wr_detect_rule_default(unsigned int fft_size, wr_detect_rule *rule)
+{
+	if (!rule)
+		return wrc_fail(WR_ERR_ARG, "wr_detect_rule_default: bad argument");
+	if (!spectrum_size_ok(fft_size))
+		return wrc_fail(WR_ERR_ARG, "wr_detect_rule_default: fft_size must be a power of 2 in [8, 1048576]");
+	rule->bin0 = 0;
+	rule->nbins = fft_size;
+	rule->span = fft_size < 1024u ? fft_size : 1024u;
+	rule->percent = 50;
+	rule->threshold = 10.0f;
+	rule->linear = 0;
+	rule->max_gap = 1;
+	rule->min_width = 1;
+	return WR_OK;
+}
+
+extern "C" int wr_spectrum_bin_hz(unsigned int fft_size, unsigned int sample_rate, double centre_hz, double bin, double *hz)
+{
+	if (!hz || !sample_rate)
+		return wrc_fail(WR_ERR_ARG, "wr_spectrum_bin_hz: bad argument");
+	if (!spectrum_size_ok(fft_size))
+		return wrc_fail(WR_ERR_ARG, "wr_spectrum_bin_hz: fft_size must be a power of 2 in [8, 1048576]");
+	*hz = centre_hz + (bin - (double)(fft_size / 2u)) * (double)sample_rate / (double)fft_size;
+	return WR_OK;
+}
+
+extern "C" int wr_spectrum_rows_detect(wr_spectrum *s, const float *rows_dev, size_t nrows, const wr_detect_rule *rule,
+                                       unsigned int max_det, wr_detection *det_dev, unsigned int *count_dev, float *floor_dev)
+{
+	if (!s || !rule || !count_dev || (nrows && !rows_dev) || (max_det && !det_dev))
+		return wrc_fail(WR_ERR_ARG, "wr_spectrum_rows_detect: bad argument");
+	if (const char *field = wrp_detect_rule_bad(s->n, rule))
+		return wrc_fail(WR_ERR_ARG, "wr_spectrum_rows_detect: the rule's %s is outside its limits", field);
+	if (!nrows)
+		return WR_OK;
+	wr_dev *d = s->dev;
+	if (wrc_dev_bind(d))
+		return WR_ERR_HIP;
+	DEV_SETTLE(d);
+	const WrDetectPlan plan = wrp_detect_plan(rule, nrows);
+	if (!floor_dev)
+		if (int rc = spectrum_avg_room(s, plan.floor_bytes))
+			return rc;
+	size_t r0 = 0, nr = 0;
+	for (bool more = wrp_detect_next(plan, nrows, &r0, &nr, true); more; more = wrp_detect_next(plan, nrows, &r0, &nr, false))
+		HIP_TRY(wrk_detect_rows(d->stream, rows_dev + r0 * s->n, s->n, nr, rule, plan, max_det,
+		                        max_det ? det_dev + r0 * max_det : nullptr, count_dev + r0,
+		                        floor_dev ? floor_dev + r0 * plan.nspans : s->avg));
+	return WR_OK;
+}

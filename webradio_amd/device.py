@@ -530,6 +530,18 @@ class DcsBank:
         return n.value, step.value, me.value, frames.value
 
 
+# wr_detection: a record of Spectrum.rows_detect
+DETECTION = np.dtype([("first", np.uint32), ("last", np.uint32), ("peak_bin", np.uint32), ("hot", np.uint32),
+                      ("peak", np.float32), ("floor", np.float32)])
+
+
+def bin_hz(fft_size, sample_rate, centre_hz, bin):
+    """centre_hz + (bin - fft_size / 2) * sample_rate / fft_size (wr_spectrum_bin_hz); needs no device"""
+    hz = C.c_double()
+    check(capi.load().wr_spectrum_bin_hz(fft_size, sample_rate, centre_hz, bin, C.byref(hz)))
+    return hz.value
+
+
 class Spectrum:
     """wr_spectrum: SpectrumSink (io/spectrumsink.h:44-68).  real=True: one float per frame (a receiver's audio),
     wr_spectrum_create_real -- pushes and batches then count samples."""
@@ -605,6 +617,48 @@ class Spectrum:
         c = C.c_uint()
         check(self.lib.wr_spectrum_channels(self.h, C.byref(c)))
         return c.value
+
+    def detect_rule(self, **fields):
+        """wr_detect_rule_default for this spectrum's size, with `fields` (bin0, nbins, span, percent, threshold, linear,
+        max_gap, min_width) set over it; a window given without a span gets one that divides it"""
+        rule = capi.DetectRule()
+        check(self.lib.wr_detect_rule_default(self.n, C.byref(rule)))
+        for k, v in fields.items():
+            if k not in dict(capi.DetectRule._fields_):
+                raise TypeError("wr_detect_rule has no field %r" % k)
+            setattr(rule, k, v)
+        if "nbins" in fields and "span" not in fields and rule.nbins % rule.span:
+            rule.span = rule.nbins
+        return rule
+
+    def rows_detect(self, rows_dev, nrows, rule, max_det, det_dev, count_dev, floor_dev=None):
+        """noise floors and occupied segments of `nrows` rows of fft_size floats in device memory (wr_spectrum_rows_detect):
+        count_dev[nrows], det_dev[nrows][max_det] records of DETECTION, floor_dev[nrows][nbins / span] if given.  Async."""
+        check(self.lib.wr_spectrum_rows_detect(self.h, ptr(rows_dev), nrows, C.byref(rule), max_det, ptr(det_dev),
+                                               ptr(count_dev), ptr(floor_dev)))
+
+    def detect(self, rows_dev, nrows, max_det=64, **rule_fields):
+        """rows_detect with everything allocated, waited for and downloaded: (records, counts, floors) -- a list of one
+        DETECTION array per row, cut to min(count, max_det); the counts [nrows]; the floors [nrows][nbins / span]"""
+        rule = self.detect_rule(**rule_fields)
+        nspans = rule.nbins // rule.span if rule.span else 1     # (a span of 0 is the call's to refuse)
+        dev = self.dev
+        bufs = [dev.malloc(max(1, nrows * max_det) * DETECTION.itemsize), dev.malloc(max(1, nrows) * 4),
+                dev.malloc(max(1, nrows * nspans) * 4)]
+        try:
+            self.rows_detect(rows_dev, nrows, rule, max_det, bufs[0], bufs[1], bufs[2])
+            dev.sync()
+            det = dev.download(bufs[0], nrows * max_det, DETECTION).reshape(nrows, max_det)
+            counts = dev.download(bufs[1], nrows, np.uint32)
+            floors = dev.download(bufs[2], nrows * nspans).reshape(nrows, nspans)
+        finally:
+            for b in bufs:
+                dev.free(b)
+        return [det[r, : min(int(counts[r]), max_det)].copy() for r in range(nrows)], counts, floors
+
+    def bin_hz(self, sample_rate, centre_hz, bin):
+        """the frequency of (fractional) bin `bin` of a shifted row of this size (wr_spectrum_bin_hz)"""
+        return bin_hz(self.n, sample_rate, centre_hz, bin)
 
 
 class Ring:
