@@ -62,6 +62,9 @@ extern "C" {
                                                       wr_dcs_seek, wr_dcs_push_rows, wr_tuner_dcs_push, wr_dcs_read, wr_dcs_info.
                                     Added to 6 later: wr_spectrum_batch_avg, wr_spectrum_rows_waterfall.
                                     Added to 6 later: wr_detect_rule_default, wr_spectrum_bin_hz, wr_spectrum_rows_detect.
+                                    Added to 6 later: wr_voice_design, wr_voice_create, wr_voice_destroy, wr_voice_reset,
+                                                      wr_voice_set_rows, wr_voice_get_rows, wr_voice_push_rows,
+                                                      wr_tuner_voice_push, wr_voice_info.
                                     Nothing of an earlier version changed or removed */
 #define WR_FIR_LENGTH    64      /* dsp/lowpass.cxx:39  FIR_LENGTH */
 #define WR_TABLE_SIZE    65536   /* dsp/downconverter.cxx:35 LOOKUP_BITS 16 */
@@ -110,6 +113,7 @@ typedef struct wr_ring     wr_ring;
 typedef struct wr_tones    wr_tones;
 typedef struct wr_resamp   wr_resamp;
 typedef struct wr_dcs      wr_dcs;
+typedef struct wr_voice    wr_voice;
 
 /* ------------------------------------------------------------------ misc -- */
 int         wr_abi_version(void);
@@ -1000,6 +1004,93 @@ int wr_resamp_info(wr_resamp *rs, unsigned int *L, unsigned int *M, unsigned int
  * submit count).  WR_ERR_ARG: max_rows below the slot count, a bank of another device, out_stride < *n_out. */
 int wr_tuner_resamp_push(wr_tuner *tuner, wr_resamp *rs, float *out_dev, size_t out_stride, size_t *n_out,
                          unsigned int *slots);
+
+/* VOICE BANK: the stage between "decoded" and "listenable" -- per-receiver audio filters and a mute, in one launch.  NFM wants
+ * de-emphasis (FM noise rises 6 dB per octave), the sub-audible tone or DCS word that the tone and DCS banks report is still
+ * in the audio at 10-15 % of full deviation, AM audio carries its carrier as DC and SSB audio has no voice band-pass; the
+ * banks' "it reports, the caller mutes" needs something on the device to mute with.  The reference has nothing of the kind.
+ * A bank is `max_rows` rows, a table of F long FIR filters of ONE length T, and one control word per row that picks the
+ * row's filter and mutes it.  De-emphasis, the tone high-pass and the voice low-pass fold into one linear-phase filter
+ * (wr_voice_design); 512 to 2048 taps at 16 to 50 kHz do the job.  It is deliberately a bank of FIR filters and not of
+ * recursive ones: an output is a fixed-order sum, independent of every other output.
+ *
+ * THE RULE is this library's own definition, as the ones of af_gain, squelch, AGC, the tones and the resampler are.
+ * A bank has max_rows rows, from 1 to 65535; F filters, from 1 to 16; ONE length T for all filters, a multiple of 4 from 8
+ * to 2048; taps c[f][k], finite and |c| <= 16 (wr_voice_create refuses others).  Every row has one 32-bit control word:
+ * bits 0-7 hold the row's filter index, which must be below F; bit 8 is the mute flag; every other bit must be 0; the
+ * default is 0.
+ * A row holds the stream x[n]; x[n] = 0 for n < 0 and for frames before the row's last reset.  Each input is cleaned
+ * exactly as the resampler cleans it:
+ *   x'   = 0.0f if (bits(x) & 0x7fffffff) >= 0x7f800000 (inf, NaN), else min(max(x, -65536.0f), 65536.0f)
+ * (-0.0f stays -0.0f; subnormals are not flushed).  One output frame comes out per input frame; with f the row's filter:
+ *   acc  = +0.0f
+ *   for k = 0 ... T-1 in this order:  acc = acc + c[f][k] * x'[n - k]
+ *   y[n] = mute ? +0.0f : acc
+ * Every product and every sum is rounded to float32 once; nothing is fused, and there is one accumulator.
+ * |acc| <= 2048 * 16 * 65536 = 2^31, so nothing overflows and no NaN arises.  An output has ONE value whatever the grid and
+ * whatever the cut of the stream into pushes; a restatement in float32 numpy is bit-identical.
+ * A muted row's history runs on: un-muting gives the frames the row would have given.  A row's state is its last T - 1
+ * cleaned inputs, so a change of the filter index applies the new taps to the old inputs from the next push on.  A push of
+ * nrows < max_rows clears the histories of the rows it leaves out.  Input and output of a push may not overlap.  A push
+ * takes at most 2^28 frames.  A 64-bit count of the frames pushed since creation or the last reset of every row is kept
+ * (wr_voice_info).
+ * Left out on purpose: recursive filters; per-row filter lengths; filtering inside the streaming launch; a host-side C++
+ * class (the reference has none to mirror); an int16 output; time sharding.
+ * The output is a plain block of rows: it goes straight into wr_resamp_push_rows.  The bank can just as well run BEHIND
+ * the resampler, on its output rows at the lower rate, where a filter of the same sharpness is shorter (512 taps at 16 kHz
+ * for 1024 at 32 kHz): both orders work, and the second is the cheap one.
+ *
+ * wr_voice_design: one filter of T taps for audio at `audio_rate`, computed in double; needs no device.  N = T - 1 taps, an
+ * odd length, symmetric about d = T / 2 - 1, and tap T - 1 = +0: the group delay is exactly d frames, and a unit impulse at
+ * k = d is the "no filter" entry of a table that stays aligned with the filtered rows.  On a grid of G = 32768 points
+ * f_g = g * audio_rate / G:
+ *   band(f) = (highpass_hz == 0 or f >= highpass_hz) and (lowpass_hz == 0 or f <= lowpass_hz)
+ *   de(f)   = 1 if deemph_us == 0, else sqrt((1 + (2 pi 1000 tau)^2) / (1 + (2 pi f tau)^2)), tau = deemph_us * 1e-6
+ *   D(g)    = band(f_g) * de(f_g)                               (de-emphasis has unity gain at 1 kHz)
+ *   h[i]    = (1 / G) [D(0) + 2 sum_{g = 1}^{G / 2 - 1} D(g) cos(2 pi g (i - d) / G) + D(G / 2) cos(pi (i - d))] * kaiser(i)
+ *   kaiser(i) = I0(beta * sqrt(1 - (2 i / (N - 1) - 1)^2)) / I0(beta),   beta = 6,   i = 0 ... N - 1
+ * each tap rounded to float32 once, h[i] and h[N - 1 - i] with the same bits.  The edges are -6 dB points; the transition
+ * half-width on each side is W = (beta / 0.1102 + 8.7 - 8) / (2.285 * 2 pi * (T - 1)) * audio_rate, about
+ * 3.84 * audio_rate / (T - 1).  For 300 .. 3000 Hz (3400 at 8 kHz) with 750 us at 50 kHz / 1024 and 2048 taps and at
+ * 32 kHz / 1024, without de-emphasis at 16 kHz / 512 and 8 kHz / 256, and for the high-pass alone at 50 kHz / 1024: |H| <= -55 dB
+ * from highpass_hz - W down and from lowpass_hz + W up, and |H / D - 1| <= -45 dB between highpass_hz + W and lowpass_hz - W.
+ * Shorter filters with de-emphasis at 50 kHz are not among these: at 512 taps they reach only -40 dB, because the 750 us
+ * response is cut short.  WR_ERR_ARG, and nothing written: a rate of 0; T not a multiple of 4 from 8 to 2048; an edge at or
+ * above audio_rate / 2; both edges given and highpass_hz + W >= lowpass_hz - W; deemph_us > 10000. */
+int wr_voice_design(unsigned int audio_rate, unsigned int T, unsigned int highpass_hz, unsigned int lowpass_hz,
+                    unsigned int deemph_us, float *taps_host /* [T] */);
+/* taps_host[nfilt][T] as wr_voice_design stores them (or the caller's own).  WR_ERR_ARG: a limit above, a tap that is not
+ * finite or whose magnitude exceeds 16. */
+int wr_voice_create(wr_voice **bank, wr_dev *dev, unsigned int max_rows, unsigned int T, unsigned int nfilt,
+                    const float *taps_host /* [nfilt][T] */);
+int wr_voice_destroy(wr_voice *bank);
+/* Clears the row's history: it holds silence before its next frame.  row < 0: every history, and the frame count returns to
+ * 0.  The control words stay.  What a caller does after wr_tuner_seek, wr_chan_reset_history or a retune of the receiver in
+ * that slot: the bank does not watch the tuner.  Asynchronous on the device's stream. */
+int wr_voice_reset(wr_voice *bank, int row);
+/* The control words of rows first ... first + n - 1.  Every word is validated before any changes: WR_ERR_ARG (and no row
+ * changed) for a filter index that is not below F, a bit set beyond bits 0-8, rows that are not the bank's.  Synchronous;
+ * ordered behind the pushes already on the device's stream, it takes effect with the next push. */
+int wr_voice_set_rows(wr_voice *bank, unsigned int first, unsigned int n, const unsigned int *ctl_host);
+/* ... as they were set last.  Host only. */
+int wr_voice_get_rows(wr_voice *bank, unsigned int first, unsigned int n, unsigned int *ctl_host);
+/* The rule on a plain block of rows in device memory: `nrows` rows of `nframes` floats, `row_stride` floats apart; row r of
+ * the call is row r of the bank, and its nframes output frames go to out_dev + r * out_stride.  Consecutive calls continue
+ * the streams whatever the lengths.  Asynchronous on the device's stream; counted by wr_block_kernel_calls.
+ * WR_ERR_ARG: NULL arguments, nrows > max_rows, row_stride < nframes or out_stride < nframes with several rows, more than
+ * 2^28 frames, input and output that overlap. */
+int wr_voice_push_rows(wr_voice *bank, const float *in_dev, size_t row_stride, size_t nrows, size_t nframes, float *out_dev,
+                       size_t out_stride);
+/* Pushes the last submit's audio rows of every channel slot, the rows wr_tuner_resamp_push takes and counted as it counts
+ * them (*slots: whole lane groups of 64); row s yields the submit's audio frames at out_dev + s * out_stride.  Like every
+ * getter it sends held blocks out, launches a pending post stage and closes an open streaming launch; it writes nothing
+ * the tuner reads.  Asynchronous behind that.
+ * WR_ERR_STATE: nothing submitted yet, several rate groups, the same submit pushed twice.  WR_ERR_ARG: max_rows below the
+ * slot count, a bank of another device, a NULL out_dev, out_stride below the frames, an output that overlaps the audio. */
+int wr_tuner_voice_push(wr_tuner *tuner, wr_voice *bank, float *out_dev, size_t out_stride, unsigned int *slots);
+/* The filter length, the filters and the frames pushed since creation or the last reset of every row.  Any pointer may be
+ * NULL.  Host only. */
+int wr_voice_info(wr_voice *bank, unsigned int *T, unsigned int *nfilt, unsigned long long *frames);
 #ifdef __cplusplus
 }
 #endif

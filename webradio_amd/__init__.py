@@ -6,16 +6,17 @@ the reference's DspBlock operator API.  The Python modules here are plumbing for
 and bench.py:
 
   capi    ctypes declarations of the C ABI (fails loudly if the library is not built)
-  device  Device / Tuner / Spectrum / ToneBank / DcsBank / Resampler handles over the C ABI
+  device  Device / Tuner / Spectrum / ToneBank / DcsBank / Resampler / VoiceBank handles over the C ABI
   synth   synthetic tuner streams (test and bench inputs)
 """
 __all__ = ["capi", "device", "synth", "CTCSS_HZ", "DCS_CODES", "DcsBank", "dcs_word", "dcs_step", "Resampler", "resamp_design",
-           "resamp_ratio", "DETECTION"]
+           "resamp_ratio", "DETECTION", "VoiceBank", "voice_design"]
 
 
 def __getattr__(name):
-    # the resampler's, the DCS bank's and the band scan's names, from device (imported on first use: importing the package loads no library)
-    if name in ("Resampler", "resamp_design", "resamp_ratio", "DcsBank", "dcs_word", "dcs_step", "DETECTION"):
+    # the resampler's, the DCS bank's, the band scan's and the voice bank's names, from device (imported on first use: importing the package loads no library)
+    if name in ("Resampler", "resamp_design", "resamp_ratio", "DcsBank", "dcs_word", "dcs_step", "DETECTION", "VoiceBank",
+                "voice_design"):
         from . import device
         return getattr(device, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

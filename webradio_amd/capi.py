@@ -164,6 +164,15 @@ SIGNATURES = {
     "wr_tuner_dcs_push": (C.c_int, [_vp, _vp, C.POINTER(_u32)]),
     "wr_dcs_read": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),
     "wr_dcs_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_ulonglong)]),
+    "wr_voice_design": (C.c_int, [_u32, _u32, _u32, _u32, _u32, _vp]),
+    "wr_voice_create": (C.c_int, [C.POINTER(_vp), _vp, _u32, _u32, _u32, _vp]),
+    "wr_voice_destroy": (C.c_int, [_vp]),
+    "wr_voice_reset": (C.c_int, [_vp, C.c_int]),
+    "wr_voice_set_rows": (C.c_int, [_vp, _u32, _u32, _vp]),
+    "wr_voice_get_rows": (C.c_int, [_vp, _u32, _u32, _vp]),
+    "wr_voice_push_rows": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _vp, _sz]),
+    "wr_tuner_voice_push": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(_u32)]),
+    "wr_voice_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(C.c_ulonglong)]),
 }
 
 

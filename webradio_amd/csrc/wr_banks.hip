@@ -1,8 +1,9 @@
 /*
- * wr_banks.hip -- the three objects that keep something per audio row of every receiver: the tone bank (wr_tones_*, kernels
- * in wr_tones.hip), the DCS bank (wr_dcs_*, kernel in wr_dcs.hip) and the resampler (wr_resamp_*, kernels in wr_resamp.hip).
+ * wr_banks.hip -- the four objects that keep something per audio row of every receiver: the tone bank (wr_tones_*, kernels
+ * in wr_tones.hip), the DCS bank (wr_dcs_*, kernel in wr_dcs.hip), the resampler (wr_resamp_*, kernels in wr_resamp.hip) and
+ * the voice bank (wr_voice_*, kernel in wr_voice.hip).
  * Each takes plain rows (wr_*_push_rows) or the audio rows of a tuner's last submit where they lie (wr_tuner_*_push); what
- * the three share has one copy, up front.
+ * the four share has one copy, up front.
  */
 #include "wr_capi_internal.h"
 
@@ -615,5 +616,213 @@ extern "C" int wr_resamp_info(wr_resamp *r, unsigned int *L, unsigned int *M, un
 		*frames_in = r->frames_in;
 	if (frames_out)
 		*frames_out = r->frames_out;
+	return WR_OK;
+}
+
+/* ------------------------------------------------------------------ voice bank -- */
+
+extern "C" int wr_voice_design(unsigned int audio_rate, unsigned int T, unsigned int highpass_hz, unsigned int lowpass_hz,
+                               unsigned int deemph_us, float *taps_host)
+{
+	if (!taps_host)
+		return wrc_fail(WR_ERR_ARG, "wr_voice_design: taps_host is NULL");
+	if (wrd_voice_design(audio_rate, T, highpass_hz, lowpass_hz, deemph_us, taps_host))
+		return wrc_fail(WR_ERR_ARG, "wr_voice_design: %u taps at %u Hz, %u .. %u Hz, %u us: a rate of 0, T not a multiple of 4 in "
+		                "8 .. 2048, an edge at or above half the rate, edges less than two transition half-widths (each about "
+		                "3.84 rate / (T - 1) Hz) apart, or more than 10000 us", T, audio_rate, highpass_hz, lowpass_hz, deemph_us);
+	return WR_OK;
+}
+
+extern "C" int wr_voice_create(wr_voice **bank, wr_dev *d, unsigned int max_rows, unsigned int T, unsigned int nfilt,
+                               const float *taps_host)
+{
+	if (!bank || !taps_host)
+		return wrc_fail(WR_ERR_ARG, "wr_voice_create: bad argument (NULL bank or taps_host)");
+	if (!max_rows || max_rows > 65535u || !wrp_voice_len_ok(T) || !nfilt || nfilt > VOICE_FILTERS)
+		return wrc_fail(WR_ERR_ARG, "wr_voice_create: %u rows (1 .. 65535), %u taps (a multiple of 4 in 8 .. 2048), %u filters "
+		                "(1 .. 16)", max_rows, T, nfilt);
+	const size_t ntaps = (size_t)nfilt * T, nhist = (size_t)max_rows * (T - 1u);
+	for (size_t i = 0; i < ntaps; ++i) {
+		uint32_t bits;
+		memcpy(&bits, taps_host + i, sizeof(bits));
+		if ((bits & 0x7fffffffu) >= 0x7f800000u || !(fabsf(taps_host[i]) <= 16.0f))
+			return wrc_fail(WR_ERR_ARG, "wr_voice_create: tap [%zu][%zu] = %g is not finite or above 16 in magnitude", i / T, i % T,
+			                (double)taps_host[i]);
+	}
+	if (!d)                                                     /* (behind the limits: those are refused without a device too) */
+		return wrc_fail(WR_ERR_ARG, "wr_voice_create: bad argument (NULL dev)");
+	wr_voice *b;
+	if (int rc = bank_new(&b, "wr_voice_create", d, max_rows))
+		return rc;
+	b->T = T;
+	b->nfilt = nfilt;
+	b->ctl_host = (unsigned int *)calloc(max_rows, sizeof(unsigned int));
+	hipError_t e = b->ctl_host ? hipMalloc((void **)&b->taps, ntaps * sizeof(float)) : hipErrorOutOfMemory;
+	if (e == hipSuccess)
+		e = hipMalloc((void **)&b->ctl, (size_t)max_rows * sizeof(unsigned int));
+	if (e == hipSuccess)
+		e = hipMemsetAsync(b->ctl, 0, (size_t)max_rows * sizeof(unsigned int), d->stream);
+	for (unsigned int s = 0; s < 2u && e == hipSuccess; ++s) {
+		e = hipMalloc((void **)&b->hist[s], nhist * sizeof(float));
+		if (e == hipSuccess)
+			e = hipMemsetAsync(b->hist[s], 0, nhist * sizeof(float), d->stream);
+	}
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(b->taps, taps_host, ntaps * sizeof(float), hipMemcpyHostToDevice, d->stream);
+	return bank_created(bank, b, e, "wr_voice_create", wr_voice_destroy);
+}
+
+extern "C" int wr_voice_destroy(wr_voice *b)
+{
+	if (!b)
+		return WR_OK;
+	(void)hipSetDevice(b->dev->device);
+	(void)wrc_dev_stream_sync(b->dev);
+	(void)hipFree(b->taps);
+	(void)hipFree(b->ctl);
+	(void)hipFree(b->hist[0]);
+	(void)hipFree(b->hist[1]);
+	free(b->ctl_host);
+	delete b;
+	return WR_OK;
+}
+
+extern "C" int wr_voice_reset(wr_voice *b, int row)
+{
+	if (!b)
+		return wrc_fail(WR_ERR_ARG, "wr_voice_reset: bank is NULL");
+	size_t first, n;
+	if (int rc = bank_reset_begin(b, "wr_voice_reset", row, &first, &n))
+		return rc;
+	/* only the set the next push reads matters: that push writes the other one; the control words stay */
+	const size_t H = b->T - 1u;
+	HIP_TRY(hipMemsetAsync(b->hist[b->cur] + first * H, 0, n * H * sizeof(float), b->dev->stream));
+	if (row < 0) {                                              /* all rows: the frame count starts again too */
+		b->zero_from[b->cur] = 0;
+		b->frames = 0;
+	}
+	return WR_OK;
+}
+
+/* rows [first, first + n) are the bank's */
+static int voice_rows_in_range(const wr_voice *b, const char *who, unsigned int first, unsigned int n)
+{
+	if (first > b->max_rows || n > b->max_rows - first)
+		return wrc_fail(WR_ERR_ARG, "%s: rows %u .. %u of a bank of %u", who, first, first + n, b->max_rows);
+	return WR_OK;
+}
+
+extern "C" int wr_voice_set_rows(wr_voice *b, unsigned int first, unsigned int n, const unsigned int *ctl_host)
+{
+	if (!b || !ctl_host)
+		return wrc_fail(WR_ERR_ARG, "wr_voice_set_rows: bad argument (NULL bank or ctl_host)");
+	if (int rc = voice_rows_in_range(b, "wr_voice_set_rows", first, n))
+		return rc;
+	for (unsigned int r = 0; r < n; ++r)                        /* every word, before any changes */
+		if ((ctl_host[r] & ~0x1ffu) || (ctl_host[r] & 0xffu) >= b->nfilt)
+			return wrc_fail(WR_ERR_ARG, "wr_voice_set_rows: row %u: the word 0x%x names filter %u of %u, or has a bit set beyond the "
+			                "filter index (bits 0-7) and mute (bit 8)", first + r, ctl_host[r], ctl_host[r] & 0xffu, b->nfilt);
+	if (!n)
+		return WR_OK;
+	if (int rc = bank_dev_ready(b->dev, false))
+		return rc;
+	/* on the stream, behind the pushes already there, and waited for: the source is the caller's */
+	HIP_TRY(hipMemcpyAsync(b->ctl + first, ctl_host, (size_t)n * sizeof(unsigned int), hipMemcpyHostToDevice, b->dev->stream));
+	HIP_TRY(wrc_dev_stream_sync(b->dev));
+	memcpy(b->ctl_host + first, ctl_host, (size_t)n * sizeof(unsigned int));
+	return WR_OK;
+}
+
+extern "C" int wr_voice_get_rows(wr_voice *b, unsigned int first, unsigned int n, unsigned int *ctl_host)
+{
+	if (!b || !ctl_host)
+		return wrc_fail(WR_ERR_ARG, "wr_voice_get_rows: bad argument (NULL bank or ctl_host)");
+	if (int rc = voice_rows_in_range(b, "wr_voice_get_rows", first, n))
+		return rc;
+	memcpy(ctl_host, b->ctl_host + first, (size_t)n * sizeof(unsigned int));
+	return WR_OK;
+}
+
+/* what both pushes refuse */
+static int voice_check(const wr_voice *b, const char *who, const float *in_dev, size_t row_stride, size_t nrows, size_t nframes,
+                       const float *out_dev, size_t out_stride)
+{
+	if (int rc = bank_rows_refused(b, who, row_stride, nrows, nframes, 28))
+		return rc;
+	if (!nrows || !nframes)
+		return WR_OK;
+	if (!out_dev || (nrows > 1 && out_stride < nframes))
+		return wrc_fail(WR_ERR_ARG, "%s: out_dev is NULL, or rows of %zu output frames overlap at a stride of %zu", who, nframes,
+		                out_stride);
+	const uintptr_t a0 = (uintptr_t)in_dev, a1 = a0 + ((nrows - 1u) * row_stride + nframes) * sizeof(float);
+	const uintptr_t b0 = (uintptr_t)out_dev, b1 = b0 + ((nrows - 1u) * out_stride + nframes) * sizeof(float);
+	if (a0 < b1 && b0 < a1)
+		return wrc_fail(WR_ERR_ARG, "%s: input and output overlap", who);
+	return WR_OK;
+}
+
+/* the push itself, behind voice_check, on a device made ready: the rows it leaves out lose their histories, the count
+ * advances, the history sets change places */
+static int voice_push(wr_voice *b, const float *in_dev, size_t row_stride, size_t nrows, size_t nframes, float *out_dev,
+                      size_t out_stride)
+{
+	if (!nframes)
+		return WR_OK;
+	wr_dev *d = b->dev;
+	const unsigned int from = b->cur, to = from ^ 1u;
+	const size_t H = b->T - 1u;
+	if (nrows < b->zero_from[to])
+		HIP_TRY(hipMemsetAsync(b->hist[to] + nrows * H, 0, (b->zero_from[to] - nrows) * H * sizeof(float), d->stream));
+	const WrVoicePush p = {b->taps, b->T, b->ctl, b->hist[from], b->hist[to]};
+	HIP_TRY(wrk_voice_push(d->stream, in_dev, row_stride, nrows, nframes, p, out_dev, out_stride));
+	b->zero_from[to] = (unsigned int)nrows;
+	b->cur = to;
+	b->frames += nframes;
+	return WR_OK;
+}
+
+extern "C" int wr_voice_push_rows(wr_voice *b, const float *in_dev, size_t row_stride, size_t nrows, size_t nframes, float *out_dev,
+                                  size_t out_stride)
+{
+	if (!b || !in_dev)
+		return wrc_fail(WR_ERR_ARG, "wr_voice_push_rows: bad argument (NULL bank or in_dev)");
+	if (int rc = voice_check(b, "wr_voice_push_rows", in_dev, row_stride, nrows, nframes, out_dev, out_stride))
+		return rc;
+	if (!nframes)
+		return WR_OK;
+	if (int rc = bank_dev_ready(b->dev, true))
+		return rc;
+	return voice_push(b, in_dev, row_stride, nrows, nframes, out_dev, out_stride);
+}
+
+/* the rows wr_tuner_resamp_push takes, through the voice bank: row s yields the submit's audio frames at out_dev + s * out_stride */
+extern "C" int wr_tuner_voice_push(wr_tuner *t, wr_voice *bank, float *out_dev, size_t out_stride, unsigned int *slots)
+{
+	if (!t || !bank)
+		return wrc_fail(WR_ERR_ARG, "wr_tuner_voice_push: bad argument (NULL tuner or bank)");
+	WrLastSubmit v;
+	if (int rc = bank_take_submit(bank, "wr_tuner_voice_push", "bank", t, &v))
+		return rc;
+	const Group *g = v.g;
+	if (int rc = voice_check(bank, "wr_tuner_voice_push", g->dev.audio, g->k2max, v.used, g->last_k2, out_dev, out_stride))
+		return rc;
+	if (int rc = wrc_last_submit_flush(t, &v))
+		return rc;
+	DEV_SETTLE(t->dev);
+	if (int rc = voice_push(bank, g->dev.audio, g->k2max, v.used, g->last_k2, out_dev, out_stride))
+		return rc;
+	return bank_took_submit(bank, t, v, slots);
+}
+
+extern "C" int wr_voice_info(wr_voice *b, unsigned int *T, unsigned int *nfilt, unsigned long long *frames)
+{
+	if (!b)
+		return wrc_fail(WR_ERR_ARG, "wr_voice_info: bank is NULL");
+	if (T)
+		*T = b->T;
+	if (nfilt)
+		*nfilt = b->nfilt;
+	if (frames)
+		*frames = b->frames;
 	return WR_OK;
 }

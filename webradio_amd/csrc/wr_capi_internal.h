@@ -289,11 +289,11 @@ struct wr_spectrum {
 	size_t avg_bytes = 0;
 };
 
-/* what the three objects of wr_banks.hip, which keep something per audio row of every receiver, begin with */
+/* what the four objects of wr_banks.hip, which keep something per audio row of every receiver, begin with */
 struct WrRowBank {
 	wr_dev *dev;
 	unsigned int max_rows;
-	/* wr_tuner_tones_push, wr_tuner_dcs_push, wr_tuner_resamp_push: whose submit, and which, the bank took last -- the same one is not pushed twice */
+	/* wr_tuner_tones_push, wr_tuner_dcs_push, wr_tuner_resamp_push, wr_tuner_voice_push: whose submit, and which, the bank took last -- the same one is not pushed twice */
 	const wr_tuner *last_tuner = nullptr;
 	unsigned long long last_seq = 0;
 };
@@ -321,6 +321,17 @@ struct wr_resamp : WrRowBank {
 	unsigned int zero_from[2] = {0, 0};   /* rows of a set from this one on are known to hold silence */
 	unsigned int nmod = 0;     /* the clock: input frames so far, mod M */
 	unsigned long long frames_in = 0, frames_out = 0;
+};
+
+struct wr_voice : WrRowBank {
+	unsigned int T, nfilt;
+	float *taps;               /* device, [nfilt][T] */
+	unsigned int *ctl;         /* device, [max_rows]: the rows' control words */
+	unsigned int *ctl_host;    /* ... and the host's copy: what wr_voice_get_rows shows */
+	float *hist[2];            /* device, [max_rows][T - 1] each: a push reads set `cur` and writes the other (wr_voice.hip) */
+	unsigned int cur = 0;
+	unsigned int zero_from[2] = {0, 0};   /* rows of a set from this one on are known to hold silence */
+	unsigned long long frames = 0;
 };
 
 /* ------------------------------------------------------------------ helpers that cross files -- */

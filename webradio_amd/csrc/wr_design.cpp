@@ -230,3 +230,60 @@ int wrd_resamp_design(unsigned int in_rate, unsigned int out_rate, unsigned int 
 	*M_out = M;
 	return 0;
 }
+
+/* wr_voice_design (include/webradio_amd.h): the frequency-sampled band-pass with de-emphasis under a Kaiser window, in
+ * double, narrowed once; taps[T] with taps[T - 1] = +0.  The grid has G = 32768 points, so the turn g (i - d) / G is
+ * reduced exactly (mod G, in integers) and the cosine comes from one table of G entries.  The upper half of the N = T - 1
+ * taps is the mirror of the lower one: the same bits.  Non-zero: a limit, or edges too close for the window */
+int wrd_voice_design(unsigned int audio_rate, unsigned int T, unsigned int highpass_hz, unsigned int lowpass_hz,
+                     unsigned int deemph_us, float *taps)
+{
+	const unsigned int G = 32768u;
+	const double beta = 6.0;
+	if (!audio_rate || !wrp_voice_len_ok(T) || deemph_us > 10000u)
+		return 1;
+	const double rate = (double)audio_rate;
+	if (lowpass_hz && 2.0 * (double)lowpass_hz >= rate)
+		return 1;
+	if (highpass_hz && 2.0 * (double)highpass_hz >= rate)          /* (nothing would be left of the band) */
+		return 1;
+	const double W = (beta / 0.1102 + 8.7 - 8.0) / (2.285 * 2.0 * kPi * ((double)T - 1.0)) * rate;
+	if (highpass_hz && lowpass_hz && (double)highpass_hz + W >= (double)lowpass_hz - W)
+		return 1;
+	const unsigned int N = T - 1u, d = T / 2u - 1u;
+	const double tau = (double)deemph_us * 1e-6;
+	const double de1k = 1.0 + (2.0 * kPi * 1000.0 * tau) * (2.0 * kPi * 1000.0 * tau);
+	double *D = new double[G / 2u + 1u];
+	double *cs = new double[G];
+	unsigned int g_lo = G, g_hi = 0;                              /* the grid points where D is not 0 */
+	for (unsigned int g = 0; g <= G / 2u; ++g) {
+		const double f = (double)g * rate / (double)G;
+		const bool band = (!highpass_hz || f >= (double)highpass_hz) && (!lowpass_hz || f <= (double)lowpass_hz);
+		const double w = 2.0 * kPi * f * tau;
+		D[g] = !band ? 0.0 : !deemph_us ? 1.0 : sqrt(de1k / (1.0 + w * w));
+		if (band) {
+			if (g < g_lo)
+				g_lo = g;
+			g_hi = g;
+		}
+	}
+	for (unsigned int q = 0; q < G; ++q)
+		cs[q] = cos(2.0 * kPi * (double)q / (double)G);
+	cs[G / 4u] = cs[3u * G / 4u] = 0.0;                           /* cos(pi / 2): exactly zero, not 6e-17 */
+	const double i0b = bessel_i0(beta);
+	for (unsigned int i = 0; i <= d; ++i) {
+		const unsigned int m = d - i;                                 /* |i - d|: the cosine is even */
+		double acc = 0.0;
+		for (unsigned int g = g_lo; g <= g_hi && g_lo <= g_hi; ++g) {
+			const double term = D[g] * cs[(unsigned int)(((unsigned long long)g * m) & (G - 1u))];
+			acc += (g == 0 || g == G / 2u) ? term : 2.0 * term;
+		}
+		const double u = 2.0 * (double)i / ((double)N - 1.0) - 1.0;
+		const double win = bessel_i0(beta * sqrt(1.0 - u * u > 0.0 ? 1.0 - u * u : 0.0)) / i0b;
+		taps[i] = taps[N - 1u - i] = (float)(acc / (double)G * win);
+	}
+	taps[T - 1u] = 0.0f;
+	delete[] D;
+	delete[] cs;
+	return 0;
+}

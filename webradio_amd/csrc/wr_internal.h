@@ -1,7 +1,7 @@
 /*
  * wr_internal.h -- internal C++ interface between the C ABI (wr_dev.hip, wr_tuner*.hip, wr_spectrum.hip, wr_banks.hip), the host
  * design math (wr_design.cpp) and the kernels (wr_kernels.hip, wr_fft.hip, wr_levels.hip, wr_agc.hip, wr_tones.hip,
- * wr_dcs.hip, wr_resamp.hip).
+ * wr_dcs.hip, wr_resamp.hip, wr_voice.hip).
  * Not installed; the public boundary is include/webradio_amd.h.
  */
 #ifndef WR_INTERNAL_H_
@@ -44,6 +44,9 @@ int      wrd_resamp_ratio(unsigned int in_rate, unsigned int out_rate, unsigned 
 int      wrd_resamp_limits(unsigned int L, unsigned int M, unsigned int P);
 int      wrd_resamp_design(unsigned int in_rate, unsigned int out_rate, unsigned int P, float *taps /* [L][P] */, unsigned int *L,
                            unsigned int *M);
+/* wr_voice_design's arithmetic (in double); non-zero: refused, and nothing written */
+int      wrd_voice_design(unsigned int audio_rate, unsigned int T, unsigned int highpass_hz, unsigned int lowpass_hz,
+                          unsigned int deemph_us, float *taps /* [T] */);
 
 /* ---- per-slot parameter block of one rate group of a tuner, device SoA ---- */
 struct WrGroupDev {
@@ -435,6 +438,21 @@ unsigned long long wrk_resamp_out_frames(unsigned int L, unsigned int M, unsigne
  * yields wrk_resamp_out_frames() frames at out + r * out_stride */
 hipError_t wrk_resamp_push(hipStream_t st, const float *in, size_t row_stride, size_t nrows, size_t nframes, const WrResampPush &p,
                            float *out, size_t out_stride);
+
+/* ---- voice bank (wr_voice.hip) ---- */
+/* what a push is, besides its rows: the bank's filters of T taps each, the rows' control words (bits 0-7: the filter, bit 8:
+ * mute) and the two history sets [rows][T - 1] -- read from hist_old, written (for the `nrows` rows of the push) to hist_new */
+struct WrVoicePush {
+	const float *taps;                 /* device, [nfilt][T]; 16-byte aligned */
+	unsigned int T;
+	const unsigned int *ctl;           /* device, [rows] */
+	const float *hist_old;
+	float       *hist_new;
+};
+/* include/webradio_amd.h's rule (wr_voice_push_rows) on `nrows` rows of `nframes` floats, `row_stride` floats apart: row r
+ * yields `nframes` frames at out + r * out_stride */
+hipError_t wrk_voice_push(hipStream_t st, const float *in, size_t row_stride, size_t nrows, size_t nframes, const WrVoicePush &p,
+                          float *out, size_t out_stride);
 
 hipError_t wrk_bins_to_db(hipStream_t st, const float *bins, unsigned int n, float *db);
 hipError_t wrk_waterfall_row(hipStream_t st, const float *bins, unsigned int n, unsigned int width, int hold,

@@ -2,7 +2,7 @@
  * wr_plan.h -- the launch geometry of every tuner launch (the per-block DDC, the long-filter DDC, the post stage, the audio
  * filter, the streaming launch) and of the spectrum launches (the transform's shape and path, its passes' tiles, grids and
  * LDS, the work area and its chunks, the columns per workgroup of the channel spectra, the chunks, scratch cap and launch count
- * of the averaged spectra, the band scan's limits, grids, LDS and chunks of rows): which kernel instance, how many
+ * of the averaged spectra, the band scan's limits, grids, LDS and chunks of rows) and of the voice bank: which kernel instance, how many
  * workgroups per role, how much LDS, the group map, kslow, kmax, the post stage's runs of tiles.  The arithmetic alone, with
  * no HIP call and no environment read, so that a CPU test can hold it to the rule (tests/test_launch_plan.py through
  * tests/cxx/cpu_host_checks.cxx).  The launch functions (wr_kernels.hip, wr_stream_kernel.inc, wr_fft.hip) obtain a plan,
@@ -763,6 +763,41 @@ static inline unsigned int wrp_detect_floor_grid(const WrDetectPlan &p, size_t r
 static inline unsigned int wrp_detect_segments_grid(size_t rows)
 {
 	return (unsigned int)rows;
+}
+
+/* ---- the voice bank (wr_voice.hip, k_voice_rows): a workgroup is one wave and VOICE_CHUNK consecutive outputs of one row,
+ * VOICE_PER consecutive outputs a thread; its input span of VOICE_CHUNK + T - 1 frames lies in LDS behind four floats that
+ * the last look-ahead read of thread 0 touches.  The grid is (chunks + 1) x rows: the extra workgroup of a row writes its new
+ * history.  One wave per workgroup: a push of 256 rows of 2 000 frames is two thousand waves, two per SIMD of the chip, and
+ * they spread best one at a time (wr_voice.hip: why four outputs a thread and not eight). ---- */
+#define VOICE_THREADS    64u
+#define VOICE_PER        4u
+#define VOICE_CHUNK      256u               /* VOICE_THREADS * VOICE_PER */
+#define VOICE_T_MIN      8u
+#define VOICE_T_MAX      2048u
+#define VOICE_FILTERS    16u
+#define VOICE_LDS_FLOATS (4u + VOICE_CHUNK + VOICE_T_MAX)   /* 9 232 bytes */
+
+/* the header's limits on a filter length */
+static inline bool wrp_voice_len_ok(unsigned int T)
+{
+	return T >= VOICE_T_MIN && T <= VOICE_T_MAX && !(T & 3u);
+}
+
+struct WrVoicePlan {
+	unsigned int chunks;                   /* workgroups of a row that compute outputs */
+	unsigned int grid_x;                   /* ... and the one that writes the row's history; grid.y is the rows */
+	unsigned int threads;
+};
+
+/* a push of `nframes` frames, 1 .. 2^28 */
+static inline WrVoicePlan wrp_voice_plan(size_t nframes)
+{
+	WrVoicePlan p;
+	p.chunks = (unsigned int)((nframes + VOICE_CHUNK - 1u) / VOICE_CHUNK);
+	p.grid_x = p.chunks + 1u;
+	p.threads = VOICE_THREADS;
+	return p;
 }
 
 #endif /* WR_PLAN_H_ */

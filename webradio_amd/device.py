@@ -394,6 +394,14 @@ class Tuner:
             self.dev.free(p)
         return out.reshape(slots.value, stride)[:, : n_out.value].copy()
 
+    def voice_push(self, bank, out, out_stride):
+        """The last submit's audio rows of every channel slot through a VoiceBank (wr_tuner_voice_push); row = Tuner.slot.
+        Row s's frames go to `out` (a device pointer or a torch tensor) + s * out_stride floats.  Returns the rows pushed
+        (whole lane groups of 64).  Asynchronous."""
+        slots = C.c_uint()
+        check(self.lib.wr_tuner_voice_push(self.h, bank.h, ptr(out), out_stride, C.byref(slots)))
+        return slots.value
+
 
 def tone_step(hz, audio_rate):
     """a tone's phase step per audio frame, llround(hz / audio_rate * 2^32) (wr_tone_step); needs no device."""
@@ -774,3 +782,61 @@ class Resampler:
         L, M, P, fi, fo = C.c_uint(), C.c_uint(), C.c_uint(), C.c_ulonglong(), C.c_ulonglong()
         check(self.lib.wr_resamp_info(self.h, C.byref(L), C.byref(M), C.byref(P), C.byref(fi), C.byref(fo)))
         return L.value, M.value, P.value, fi.value, fo.value
+
+
+def voice_design(audio_rate, taps, highpass_hz=300, lowpass_hz=3000, deemph_us=0):
+    """float32 [taps]: the linear-phase voice filter of wr_voice_design -- a band-pass (an edge of 0: none) with de-emphasis
+    (0: none), its group delay taps / 2 - 1 frames; needs no device."""
+    out = np.zeros(max(taps, 1), np.float32)
+    check(capi.load().wr_voice_design(audio_rate, taps, highpass_hz, lowpass_hz, deemph_us, ptr(out)))
+    return out
+
+
+class VoiceBank:
+    """wr_voice: max_rows rows of audio, each through one of up to 16 FIR filters of one length T or muted, the streams
+    running on from push to push (include/webradio_amd.h: VOICE BANK).  A row's control word is its filter index, plus
+    VoiceBank.MUTE."""
+
+    MUTE = 0x100
+
+    def __init__(self, dev, max_rows, taps):
+        """`taps`: [F][T], or [T] for a single filter"""
+        self.dev = dev
+        self.lib = dev.lib
+        self.max_rows = max_rows
+        self.taps = np.atleast_2d(np.ascontiguousarray(taps, dtype=np.float32))
+        assert self.taps.ndim == 2
+        self.F, self.T = self.taps.shape
+        h = C.c_void_p()
+        check(self.lib.wr_voice_create(C.byref(h), dev.h, max_rows, self.T, self.F, ptr(self.taps)))
+        self.h = h
+
+    def destroy(self):
+        if self.h:
+            self.lib.wr_voice_destroy(self.h)
+            self.h = None
+
+    def reset(self, row=-1):
+        """a row's history is cleared (row < 0: every row's, and the frame count returns to 0); the control words stay"""
+        check(self.lib.wr_voice_reset(self.h, row))
+
+    def set_rows(self, first, words):
+        """the control words of rows first, first + 1, ...: all of them or, if one is refused, none"""
+        words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        check(self.lib.wr_voice_set_rows(self.h, first, words.size, ptr(words)))
+
+    def get_rows(self, first=0, n=None):
+        words = np.zeros(self.max_rows - first if n is None else n, np.uint32)
+        check(self.lib.wr_voice_get_rows(self.h, first, words.size, ptr(words)))
+        return words
+
+    def push_rows(self, p, row_stride, nrows, nframes, out_p, out_stride):
+        """nrows rows of nframes floats at device pointer p, row_stride floats apart, continue rows 0 .. nrows-1; row r's
+        nframes output frames go to device pointer out_p + 4 * r * out_stride.  Asynchronous."""
+        check(self.lib.wr_voice_push_rows(self.h, C.c_void_p(p), row_stride, nrows, nframes, C.c_void_p(out_p), out_stride))
+
+    def info(self):
+        """(T, F, frames)"""
+        T, F, frames = C.c_uint(), C.c_uint(), C.c_ulonglong()
+        check(self.lib.wr_voice_info(self.h, C.byref(T), C.byref(F), C.byref(frames)))
+        return T.value, F.value, frames.value
