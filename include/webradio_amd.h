@@ -834,7 +834,10 @@ int wr_tones_reset(wr_tones *bank, int row);
 int wr_tones_push_rows(wr_tones *bank, const float *audio_dev, size_t row_stride, size_t nrows, size_t nframes);
 /* Pushes the last submit's audio rows of every channel slot: WR_STAGE_AUDIO as wr_tuner_audio_dev shows it -- after
  * squelch, AGC, af_gain and scale; row = wr_chan_slot.  Rows are counted as wr_tuner_chan_levels counts them (*slots: whole
- * lane groups of 64); rows of slots that hold no channel carry no meaning.  rho does not depend on af_gain and scale:
+ * lane groups of 64); rows of slots that hold no channel carry no meaning.  The slots are counted when the push is made, not
+ * when the submit was: a receiver removed in between that sat alone in the top lane group makes the push 64 rows shorter, and
+ * a bank that resets the rows a push leaves out (resampler, DCS bank, voice bank; not this one) then resets those.  The same
+ * holds for wr_tuner_dcs_push, wr_tuner_resamp_push and wr_tuner_voice_push.  rho does not depend on af_gain and scale:
  * they multiply I, Q and sqrt(E) alike.  Like every getter it sends held blocks out, launches a pending post stage and
  * closes an open streaming launch; it changes nothing the next block depends on.  Asynchronous behind that.
  * WR_ERR_STATE: nothing submitted yet, several rate groups, the same submit pushed twice (the bank remembers the tuner's

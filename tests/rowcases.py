@@ -1,6 +1,7 @@
 """Case builders the GPU tests of the per-row features share (test_gpu_tones, test_gpu_resamp, test_gpu_agc,
-test_gpu_chan_levels): rows of audio with every awkward float among them, the five-receiver NFM tuner of tones_np with
-its twelve blocks and the audio of its untouched twin, and the keyed-carrier block of the level and AGC tests.
+test_gpu_chan_levels, test_gpu_scripts, test_gpu_bank_limits): rows of audio with every awkward float among them, rows in
+device memory and sentinel-filled outputs, the five-receiver NFM tuner of tones_np with its twelve blocks and the audio of
+its untouched twin, and the keyed-carrier block of the level and AGC tests.
 
 Everything random comes from a seeded numpy Generator through a fixed sequence of calls, so a case is the same floats
 wherever and whenever it is built."""
@@ -23,6 +24,69 @@ def special_rows(nrows, n, seed, max_exp, special):
         for k, at in enumerate(where):
             v[r, at] = np.float32(special[k])
     return v
+
+
+# ---- rows in device memory ------------------------------------------------------------------------------------------------------
+
+SENTINEL = np.array([0x7FC0BEEF], np.uint32).view(np.float32)[0]          # a NaN nobody computes: what a kernel leaves alone
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def upload_rows(dev, v, stride):
+    """the rows `stride` floats apart in device memory, NaN between them: the pointer (the caller frees it)"""
+    nrows, n = v.shape
+    buf = np.full((nrows, stride), np.float32(np.nan), np.float32)
+    buf[:, :n] = v
+    return dev.upload(buf)
+
+
+class OutRows:
+    """nrows rows of `stride` floats in device memory for what a push writes, filled with SENTINEL.  peek(rows, frames)
+    downloads them and checks that nothing but the first `frames` floats of the first `rows` rows was written; arm() fills
+    them again (an upload waits for the device's stream, and so closes an open streaming launch: a caller who wants the push
+    itself to do that arms behind the push, not in front of it); take() is both."""
+
+    def __init__(self, dev, nrows, stride):
+        self.dev, self.nrows, self.stride = dev, nrows, stride
+        self.fill = np.full(nrows * stride, SENTINEL, np.float32)
+        self.p = dev.upload(self.fill)
+
+    def arm(self):
+        capi.check(self.dev.lib.wr_dev_upload(self.dev.h, self.p, capi.ptr(self.fill), self.fill.nbytes))
+
+    def peek(self, nrows, nframes, what=None):
+        assert nrows <= self.nrows and nframes <= self.stride, (what, nrows, nframes)
+        got = self.dev.download(self.p, self.fill.size).reshape(self.nrows, self.stride)
+        for gap in (got[:nrows, nframes:], got[nrows:]):
+            assert np.all(gap.view(np.uint32) == SENTINEL.view(np.uint32)), what
+        return got[:nrows, :nframes].copy()
+
+    def take(self, nrows, nframes, what=None):
+        got = self.peek(nrows, nframes, what)
+        self.arm()
+        return got
+
+    def free(self):
+        self.dev.free(self.p)
+
+
+def dcs_bank(dev, max_rows, words, step, max_errors=0):
+    """a device.DcsBank on a caller's step: its constructor takes an audio rate and asks wr_dcs_step, which refuses rates
+    below two frames per chip; wr_dcs_create itself takes any step in [2^19, 2^28]"""
+    import ctypes as C
+    from webradio_amd.device import DcsBank
+    b = DcsBank.__new__(DcsBank)
+    b.dev, b.lib, b.max_rows, b.step, b.max_errors = dev, dev.lib, max_rows, int(step), max_errors
+    b.words = np.array(words, dtype=np.uint32)
+    b.ncodes = b.words.size
+    h = C.c_void_p()
+    capi.check(dev.lib.wr_dcs_create(C.byref(h), dev.h, max_rows, capi.ptr(b.words), b.ncodes, b.step, max_errors))
+    b.h = h
+    return b
 
 
 # ---- the five NFM receivers of tones_np behind a tuner --------------------------------------------------------------------------

@@ -5,8 +5,14 @@ the CPU model of one (TunerModel: the oracle's receivers and the numpy restateme
   test_script_against_the_model      WR_NCO_EXACT, a launch per block: whatever an operation hands back is the model's
   test_script_in_every_launch_mode   WR_NCO_ROTATE: a launch per block, held blocks and the streaming launch hand back the
                                      same bits, and the first of them is the model's within the ROTATE tolerance
+  test_a_receiver_leaves_between_a_submit_and_its_pushes      the rows of a tuner push are counted when the push is made
+  test_setters_between_a_submit_and_its_pushes                 staged setters wait for the next block, the voice word does not
   test_a_receiver_moves_to_another_rate_group_and_back
   test_caller_designed_taps          wr_chan_set_taps(_n) with taps of full size at every position
+
+The scripts play the resampler, the DCS bank and the voice bank (with a second resampler behind it) as well: GpuPlay pushes
+first and only then downloads the tuner's rows, so that the push is what flushes; every push is compared with the model and,
+on every live row, with the restatement fed the library's own rows.
 
 Tolerances are the suite's own: DB_ATOL on bins within 60 dB of a row's peak (test_gpu_spectrum_real._check_db), FM_ATOL
 and the ROTATE bound through the audio filter's absolute gain (test_gpu_fuzz.py), 1e-6 on ROTATE channel IQ (test_gpu_f4.py)."""
@@ -16,11 +22,12 @@ import numpy as np
 import pytest
 
 import agc_np
+import rowcases
 import tuner_model as tm
 from test_gpu_f4 import OracleChain
 from test_gpu_spectrum import DB_ATOL
 from webradio_amd import capi
-from webradio_amd.device import Spectrum, ToneBank, Tuner
+from webradio_amd.device import Resampler, Spectrum, ToneBank, Tuner, VoiceBank
 
 pytestmark = pytest.mark.gpu
 
@@ -81,10 +88,26 @@ class GpuPlay:
         self.live = {c: c for c in range(s["nrx"])}                       # handle -> slot
         self.pos = 0
         self.cap = s["max_block"] // tm.D1
+        # the row banks (tm.bank_shapes), their outputs a few floats wider than the longest row, and the restatements that are
+        # fed the library's own rows: under WR_NCO_ROTATE, where the model's audio is only close, they hold the banks
+        shapes, k2max = tm.bank_shapes(s), self.cap // s["d2"]
+        self.resamp = Resampler(dev, self.rows, 4, 3, taps=shapes["resamp"][2])
+        self.chain = Resampler(dev, self.rows, 3, 4, taps=shapes["chain"][2])
+        assert (self.resamp.L, self.resamp.M, self.chain.L, self.chain.M) == (3, 4, 4, 3)
+        self.voice = VoiceBank(dev, self.rows, shapes["voice"])
+        self.voice.set_rows(0, np.arange(self.rows) % tm.VOICE_FILTERS)
+        self.dcs = rowcases.dcs_bank(dev, self.rows, shapes["words"], tm.DCS_STEP, tm.DCS_MAX_ERRORS)
+        self.out = {"resamp": rowcases.OutRows(dev, self.rows, (3 * k2max + 3) // 4 + 1 + 5),
+                    "voice": rowcases.OutRows(dev, self.rows, k2max + 3),
+                    "chain": rowcases.OutRows(dev, self.rows, (4 * k2max + 2) // 3 + 1 + 6)}
+        self.rb = tm.RowBanks(s)
+        self.seen = {k: 0 for k in tm.BANK_KINDS}                         # rows held to the restatement, refusals, words set
 
     def close(self):
-        for b in self.banks:
+        for b in self.banks + [self.resamp, self.chain, self.voice, self.dcs]:
             b.destroy()
+        for o in self.out.values():
+            o.free()
         self.chan_spec.destroy()
         self.audio_spec.destroy()
         self.t.destroy()
@@ -93,9 +116,82 @@ class GpuPlay:
         iq, energy, windows, fill = self.banks[b].read()
         return {s: (iq[s].copy(), int(energy[s]), int(windows[s]), int(fill[s])) for s in self.live.values()}
 
+    def _own_rows(self, slots, what):
+        """the library's own rows of the last submit, for the restatements; asked for BEHIND the push, so that the push and
+        not this download is what sends held blocks out and closes an open streaming launch"""
+        rows = self.t.fetch_audio_all()
+        assert rows.shape[0] == slots >= max(self.live.values()) + 1, (what, rows.shape, slots)
+        return rows
+
+    def _held(self, kind, got, want, what):
+        """every live row bit for bit, FM receivers and AGC rows included"""
+        assert got.shape == want.shape, (what, got.shape, want.shape)
+        for s in self.live.values():
+            assert rowcases.same_bits(got[s], want[s]), (what, s)
+        self.seen[kind] += len(self.live)
+
+    def _push(self, kind, what):
+        t, lib = self.t, self.t.lib
+        slots, n_out = C.c_uint(), C.c_size_t()
+        if kind == "resamp":
+            out = self.out["resamp"]
+            capi.check(lib.wr_tuner_resamp_push(t.h, self.resamp.h, C.c_void_p(out.p), out.stride, C.byref(n_out), C.byref(slots)))
+            got = out.take(slots.value, n_out.value, what)
+            self._held(kind, got, self.rb.push_resamp(self._own_rows(slots.value, what)), what)
+            assert self.resamp.info()[3:] == self.rb.counts("resamp"), what
+            return n_out.value, {s: got[s] for s in self.live.values()}
+        if kind == "dcs":
+            capi.check(lib.wr_tuner_dcs_push(t.h, self.dcs.h, C.byref(slots)))
+            got, want = self.dcs.read(), self.rb.push_dcs(self._own_rows(slots.value, what))
+            for s in self.live.values():
+                assert all(np.array_equal(g[s], w[s]) for g, w in zip(got, want)), (what, s, got[3][s], want[3][s])
+            self.seen[kind] += len(self.live)
+            assert self.dcs.info()[3:] == self.rb.counts("dcs"), what
+            return tm.dcs_by_slot(got, self.live.values())
+        out, then = self.out["voice"], self.out["chain"]
+        capi.check(lib.wr_tuner_voice_push(t.h, self.voice.h, C.c_void_p(out.p), out.stride, C.byref(slots)))
+        rows = self._own_rows(slots.value, what)
+        k2 = rows.shape[1]
+        # the output block goes straight on into the second resampler, as a caller chains them
+        n = self.chain.push_rows(out.p, out.stride, slots.value, k2, then.p, then.stride)
+        y, z = out.take(slots.value, k2, what), then.take(slots.value, n, what)
+        want_y, want_z = self.rb.push_voice(rows)
+        self._held(kind, y, want_y, what)
+        self._held(kind, z, want_z, what)
+        assert (self.voice.info()[2],) + self.chain.info()[3:] == self.rb.counts("voice"), what
+        return {s: y[s] for s in self.live.values()}, n, {s: z[s] for s in self.live.values()}
+
+    def _push_again(self, kind, what):
+        """the same submit pushed twice: WR_ERR_STATE, nothing written, nothing counted"""
+        t, lib = self.t, self.t.lib
+        n_out = C.c_size_t()
+        if kind == "resamp":
+            out = self.out["resamp"]
+            rc = lib.wr_tuner_resamp_push(t.h, self.resamp.h, C.c_void_p(out.p), out.stride, C.byref(n_out), None)
+        elif kind == "dcs":
+            rc = lib.wr_tuner_dcs_push(t.h, self.dcs.h, None)
+        else:
+            out = self.out["voice"]
+            rc = lib.wr_tuner_voice_push(t.h, self.voice.h, C.c_void_p(out.p), out.stride, None)
+        assert rc == capi.WR_ERR_STATE and b"already" in lib.wr_last_error(), (what, rc, lib.wr_last_error())
+        self.seen[kind + "_again"] += 1
+        if kind == "dcs":
+            return self.dcs.info()[3:], tm.dcs_by_slot(self.dcs.read(), self.live.values())
+        out.peek(0, 0, what)
+        return self.resamp.info()[3:] if kind == "resamp" else (self.voice.info()[2],) + self.chain.info()[3:]
+
     def do(self, op):
         t, k, lib = self.t, op[0], self.t.lib
-        if k == "submit":
+        what = (self.s["seed"], op)
+        if k in tm.PUSH_KINDS:
+            return self._push(k, what)
+        if k.endswith("_again") and k != "tones_again":
+            return self._push_again(k[:-6], what)
+        if k == "voice_ctl":
+            self.voice.set_rows(op[1], [op[2]])
+            self.rb.voice.set_rows(op[1], [op[2]])
+            self.seen[k] += 1
+        elif k == "submit":
             if op[1] == "host":
                 t.submit_host(self.iq[2 * self.pos: 2 * (self.pos + op[2])])
             else:
@@ -129,8 +225,14 @@ class GpuPlay:
             assert (c, t.slot(c)) == (op[1], op[2]), (op, c, t.slot(c))   # the lowest free handle, the slot that was left
             self.live[c] = op[2]
         elif k == "bank_reset":
-            for b in self.banks:
+            for b in self.banks + [self.resamp, self.chain, self.voice]:
                 b.reset(op[1])
+            if op[1] >= 0 or self.s["seed"] % 2 == 0:
+                self.dcs.reset(op[1])
+            else:                                                         # the bank joins the stream where the seek put it
+                self.dcs.seek(tm.audio_pos(self.s, self.pos))
+            self.rb.reset(op[1], self.pos)
+            assert np.array_equal(self.voice.get_rows(), self.rb.voice.ctl), what     # the control words survive a reset
         elif k == "fetch_audio":
             return t.fetch(op[1], capi.WR_STAGE_AUDIO, self.cap)
         elif k == "fetch_chan":
@@ -213,6 +315,15 @@ def _audio_is_the_models(m, c, got, want, what):
     return 0
 
 
+def _of_slot(result, slot):
+    """what a bank operation's result says of one slot: the {slot: ...} dicts in it cut down to that slot"""
+    if isinstance(result, dict):
+        return result[slot]
+    if isinstance(result, (tuple, list)):
+        return tuple(_of_slot(x, slot) for x in result)
+    return result
+
+
 def _check_exact(play, op, got, want, seen):
     m, k = play.m, op[0]
     by_slot = {r.slot: c for c, r in m.rxs.items()}
@@ -251,6 +362,12 @@ def _check_exact(play, op, got, want, seen):
             if not r.was_fm:
                 assert _same(got[r.slot], want[r.slot]), (what, c, got[r.slot][1:], want[r.slot][1:])
                 seen["latched"] += want[r.slot][2] > 0
+    elif k in tm.BANK_KINDS and k != "voice_ctl":
+        # the rule `tones` uses: bit for bit on every row whose receiver has not run the FM detector; the frame counts always
+        for c, r in m.rxs.items():
+            if not r.was_fm:
+                assert _same(_of_slot(got, r.slot), _of_slot(want, r.slot)), (what, c)
+                seen[k] += 1
     elif k == "get_agc":
         assert _same(got, want), (what, got, want)
         seen["agc"] += bool(want[0])
@@ -263,6 +380,7 @@ def test_script_against_the_model(dev, scripts, seed):
     script, iq, x = scripts(seed)
     model, gpu = tm.ModelPlay(script, iq), GpuPlay(dev, script, iq, x, capi.WR_NCO_EXACT)
     seen = {"exact": 0, "gated": 0, "latched": 0, "agc": 0}
+    seen.update({k: 0 for k in tm.BANK_KINDS if k != "voice_ctl"})
     try:
         for op in script["ops"]:
             got, want = gpu.do(op), model.do(op)
@@ -277,8 +395,9 @@ def test_script_against_the_model(dev, scripts, seed):
         assert gpu.t.agc_info()[0] == model.m.agc_on()
     finally:
         gpu.close()
-    print("seed %d: %s" % (seed, seen))
+    print("seed %d: held to the model %s, to the restatement on the library's rows %s" % (seed, seen, gpu.seen))
     assert seen["exact"] > 0 and seen["latched"] > 0 and seen["gated"] > 0 and seen["agc"] > 0
+    assert not [k for k in tm.PUSH_KINDS if seen[k] < 1 or gpu.seen[k] < 1], (seen, gpu.seen)
 
 
 # ---- 2: a launch per block, held blocks, the streaming launch -------------------------------------------------------------------
@@ -356,6 +475,8 @@ def test_script_in_every_launch_mode(dev, scripts, seed):
                         results.append(got)
                 assert gpu.t.ring_stats() == (0, 0)
                 plays[how] = (results, np.concatenate(ring, axis=1), gpu.t.stream_info(), gpu.t.agc_info())
+                print("seed %d, %s: rows held to the restatement on the library's rows %s" % (seed, how, gpu.seen))
+                assert not [k for k in tm.PUSH_KINDS if gpu.seen[k] < 1], (how, gpu.seen)
             finally:
                 gpu.close()
     finally:
@@ -375,6 +496,171 @@ def test_script_in_every_launch_mode(dev, scripts, seed):
     print("seed %d: stream_info %s, agc_info %s, %d audio rows held to the model" % (seed, plays["stream"][2], agc, held_to_model))
     assert plays["stream"][2][2] >= 3                                     # blocks that did stream
     assert plays["block"][2][2] == 0 and plays["hold"][2][2] == 0
+
+
+# ---- 2a: between a submit and its pushes ------------------------------------------------------------------------------------------
+
+class _FourBanks:
+    """the four row banks of `rows` rows behind a tuner at 1 kHz audio, each with its restatement; push(t) pushes the last
+    submit into all of them, feeds the restatements the library's own rows and compares EVERY row of the banks"""
+
+    def __init__(self, dev, rows, seed=0):
+        script = {"seed": seed, "audio_rate": 1_000, "max_channels": rows, "d2": 5}
+        shapes = tm.bank_shapes(script)
+        self.dev, self.rows, self.rb = dev, rows, tm.RowBanks(script)
+        self.resamp = Resampler(dev, rows, 4, 3, taps=shapes["resamp"][2])
+        self.voice = VoiceBank(dev, rows, shapes["voice"])
+        self.voice.set_rows(0, np.arange(rows) % tm.VOICE_FILTERS)
+        self.dcs = rowcases.dcs_bank(dev, rows, shapes["words"], tm.DCS_STEP, tm.DCS_MAX_ERRORS)
+        self.tones = ToneBank(dev, rows, None, None, 16, steps=tm.bank_steps(1_000)[:2])
+        self.want_tones = tm.tones_np.Bank(rows, tm.bank_steps(1_000)[:2], 16)
+        self.out = {"resamp": rowcases.OutRows(dev, rows, 64), "voice": rowcases.OutRows(dev, rows, 64)}
+
+    def close(self):
+        for b in (self.resamp, self.voice, self.dcs, self.tones):
+            b.destroy()
+        for o in self.out.values():
+            o.free()
+
+    def reset(self, row):
+        for b in (self.resamp, self.voice, self.dcs, self.tones, self.want_tones):
+            b.reset(row)
+        self.rb.reset(row, 0)
+
+    def check(self, y, want_y, v, want_v, what):
+        assert rowcases.same_bits(y, want_y) and rowcases.same_bits(v, want_v), what
+        for g, w in zip(self.dcs.read(), self.rb.read_dcs()):
+            assert np.array_equal(g, w), what
+        for g, w in zip(self.tones.read(), self.want_tones.read()):
+            assert np.array_equal(g, w), what
+
+    def push(self, t, what):
+        """-> (slots, the library's own rows, the resampler's frames, the voice bank's frames)"""
+        lib, slots, n_out, counted = t.lib, C.c_uint(), C.c_size_t(), []
+        o = self.out["resamp"]
+        capi.check(lib.wr_tuner_resamp_push(t.h, self.resamp.h, C.c_void_p(o.p), o.stride, C.byref(n_out), C.byref(slots)))
+        counted.append(slots.value)
+        y = o.take(slots.value, n_out.value, what)
+        o = self.out["voice"]
+        capi.check(lib.wr_tuner_voice_push(t.h, self.voice.h, C.c_void_p(o.p), o.stride, C.byref(slots)))
+        counted.append(slots.value)
+        capi.check(lib.wr_tuner_dcs_push(t.h, self.dcs.h, C.byref(slots)))
+        counted.append(slots.value)
+        counted.append(t.tones_push(self.tones))
+        rows = t.fetch_audio_all()
+        assert counted == [rows.shape[0]] * 4, (what, counted, rows.shape)
+        v = o.take(rows.shape[0], rows.shape[1], what)
+        self.rb.dcs.push(rows)
+        self.want_tones.push(rows)
+        self.check(y, self.rb.push_resamp(rows), v, self.rb.voice.push(rows), what)
+        return rows.shape[0], rows, y, v
+
+    def push_plain(self, v, what):
+        """plain rows into the resampler and the voice bank: what every row's history holds shows in what comes out"""
+        p = rowcases.upload_rows(self.dev, v, v.shape[1] + 3)
+        try:
+            o = self.out["resamp"]
+            n = self.resamp.push_rows(p, v.shape[1] + 3, v.shape[0], v.shape[1], o.p, o.stride)
+            y = o.take(v.shape[0], n, what)
+            o = self.out["voice"]
+            self.voice.push_rows(p, v.shape[1] + 3, v.shape[0], v.shape[1], o.p, o.stride)
+            self.check(y, self.rb.push_resamp(v), o.take(v.shape[0], v.shape[1], what), self.rb.voice.push(v), what)
+        finally:
+            self.dev.free(p)
+
+
+@pytest.mark.parametrize("how", ["block", "hold", "stream"])
+def test_a_receiver_leaves_between_a_submit_and_its_pushes(dev, how):
+    """The rows of a tuner push are counted when the push is made (wr_tuner_tones_push in the header), not when the submit
+    was.  65 receivers: the 65th sits alone in the second lane group.  Two blocks go into all four banks with 128 rows; after
+    the third submit the 65th is removed, and the pushes of that submit count 64 slots: the resampler, the DCS bank and the
+    voice bank reset the rows a push leaves out -- plain rows pushed next come out of empty histories in rows 64 ... -- and
+    the tone bank keeps them.  The receiver then comes back into slot 64, the caller resets that row, and two more blocks
+    agree with the restatements in every row."""
+    nrx, n = 65, 20 * tm.D1 * 5
+    ifs = tm._ifs(nrx)
+    modes = [(tm.AM, tm.USB, tm.LSB)[c % 3] for c in range(nrx)]
+    iq = tm.signal(5 * n, [ifs[3], ifs[64]], seed=11)
+    x = dev.upload(iq)
+    t = Tuner(dev, tm.FS, nrx, 2 * n, capi.WR_NCO_EXACT)
+    banks = _FourBanks(dev, 128)
+    try:
+        for c in range(nrx):
+            assert t.add_receiver(ifs[c], CPB, tm.CHAN_RATE, modes[c], APB, 1_000) == c and t.slot(c) == c
+        if how == "hold":
+            t.blocks_per_launch(2)
+        if how == "stream":
+            t.streaming(True)
+        for b in range(2):
+            t.submit_device(x + 8 * n * b, n)
+            slots, rows, _, _ = banks.push(t, (how, b))
+            assert slots == 128 and float(np.abs(rows[64]).max()) > 0.0
+        kept = [a[64].copy() for a in banks.tones.read()]
+        assert int(kept[2]) == 2 and int(kept[3]) == 8                    # 40 frames: two windows of 16 and 8 in the open one
+        assert int(banks.dcs.read()[3][64]) >= 1
+        t.submit_device(x + 8 * n * 2, n)
+        t.remove_receiver(64)                                             # ... between the submit and its pushes
+        slots, rows, _, _ = banks.push(t, (how, "left"))
+        assert slots == 64 and rows.shape == (64, 20)
+        assert not any(a[64:].any() for a in banks.dcs.read())            # reset: the resampler's convention
+        assert all(np.array_equal(a[64], k) for a, k in zip(banks.tones.read(), kept))     # ... which the tone bank does not have
+        banks.push_plain(rowcases.special_rows(128, 9, 12, 3, [1.0, -0.0]), (how, "plain"))
+        assert t.add_receiver(ifs[64], CPB, tm.CHAN_RATE, modes[64], APB, 1_000) == 64 and t.slot(64) == 64
+        banks.reset(64)
+        for b in (3, 4):
+            t.submit_device(x + 8 * n * b, n)
+            slots, rows, _, _ = banks.push(t, (how, b))
+            assert slots == 128 and float(np.abs(rows[64]).max()) > 0.0
+    finally:
+        banks.close()
+        t.destroy()
+        dev.free(x)
+
+
+def test_setters_between_a_submit_and_its_pushes(dev):
+    """wr_chan_set_af_gain and wr_chan_set_mode issued behind a submit are staged: the pushes of that submit still take its
+    audio, and the next block has the new settings.  wr_voice_set_rows issued there applies with this push, as its header
+    says.  Five receivers, none FM, WR_NCO_EXACT: every row is the model's bit for bit."""
+    nrx, n = 5, 20 * tm.D1 * 5
+    ifs = tm._ifs(nrx)
+    modes = [tm.AM, tm.USB, tm.LSB, tm.AM, tm.USB]
+    iq = tm.signal(3 * n, [ifs[0], ifs[3]], seed=13)
+    t = Tuner(dev, tm.FS, nrx, n, capi.WR_NCO_EXACT)
+    m, twin = tm.TunerModel(tm.FS, 1.0), tm.TunerModel(tm.FS, 1.0)        # twin: no setter ever reaches it
+    banks = _FourBanks(dev, 64, seed=1)
+    want = tm.RowBanks(banks.rb.script)                                   # ... fed the model's rows
+    try:
+        for c in range(nrx):
+            assert t.add_receiver(ifs[c], CPB, tm.CHAN_RATE, modes[c], APB, 1_000) == c
+            for model in (m, twin):
+                model.add(c, c, ifs[c], CPB, tm.CHAN_RATE, modes[c], APB, 1_000)
+        for b in range(3):
+            block = iq[2 * n * b: 2 * n * (b + 1)]
+            t.submit_host(block)
+            m.submit(block)
+            twin.submit(block)
+            if b == 1:                                                    # behind the submit, in front of its pushes
+                t.set_af_gain(0, 6.0)
+                m.set_af_gain(0, 6.0)
+                t.set_mode(1, tm.LSB)
+                m.set_mode(1, tm.LSB)
+                for bank in (banks.voice, banks.rb.voice, want.voice):
+                    bank.set_rows(2, [1 | VoiceBank.MUTE, 1])             # row 2 muted, row 3 on another filter
+            slots, rows, y, v = banks.push(t, b)
+            assert slots == 64
+            for c in range(nrx):
+                assert _same_bits(rows[c], m.audio(c)), (b, c)
+            mine = m.audio_rows(64)
+            assert _same_bits(y[:nrx], want.push_resamp(mine)[:nrx]) and _same_bits(v[:nrx], want.push_voice(mine)[0][:nrx]), b
+            changed = [c for c in range(nrx) if not _same_bits(m.audio(c), twin.audio(c))]
+            assert changed == ([0, 1] if b == 2 else []), (b, changed)    # staged: the next block has them, this one does not
+            if b >= 1:
+                assert not v[2].any() and v[3].any()
+                other = tm.voice_np.Bank(1, banks.voice.taps[0])
+                assert not _same_bits(v[3], other.push(rows[3:4])[0])     # (filter 0 on an empty history would say something else)
+    finally:
+        banks.close()
+        t.destroy()
 
 
 # ---- 3: a receiver moves to another rate group and back -------------------------------------------------------------------------

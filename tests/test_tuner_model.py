@@ -1,6 +1,8 @@
 """Without a GPU: the scripts of tests/tuner_model.py hold what test_gpu_scripts.py relies on, and the model is consistent
 with itself -- so that a script that passes on the GPU has said something, and a model that disagrees with the GPU is not
 simply a model that disagrees with its own parts."""
+import hashlib
+
 import numpy as np
 
 import tuner_model as tm
@@ -16,6 +18,7 @@ def _bits(a):
 def test_every_operation_kind_occurs():
     seeds = list(tm.fuzz_seeds())
     total = {k: 0 for k in tm.ALL_KINDS}
+    first, short = {k: 0 for k in tm.PUSH_KINDS}, {k: 0 for k in tm.BANK_HISTORY}
     for seed in seeds:
         script = tm.make_script(seed)
         assert script == tm.make_script(seed)                            # a pure function of the seed
@@ -31,11 +34,51 @@ def test_every_operation_kind_occurs():
         assert st["reseated_agc"] >= 1, seed
         assert st["reseated_squelch"] >= 1 or seed % 2, seed
         assert st["asked"] >= 1, seed                                     # a setting changed, then asked before the next submit
-        assert len(script["ops"]) <= 100, (seed, len(script["ops"]))
+        assert len([op for op in script["ops"] if op[0] not in tm.BANK_KINDS]) <= 100, (seed, len(script["ops"]))
+        assert len(script["ops"]) <= OPS_WITH_BANKS, (seed, len(script["ops"]))
         assert sum(n for _, n in script["cuts"]) == script["total"]
         assert max(n for _, n in script["cuts"]) <= script["max_block"]
+        # the row banks: every push kind in every seed; a voice_ctl between a submit and its push; a row muted, pushed, and
+        # pushed un-muted again
+        assert not [k for k in tm.PUSH_KINDS if st["kinds"][k] < 1], (seed, st["kinds"])
+        assert st["ctl_pushed"] >= 1 and st["ctl_late"] >= 1 and st["unmuted"] >= 1, (seed, st)
+        for k, n in st["first"].items():
+            first[k] += n
+        for k, n in st["short"].items():
+            short[k] += n
+    print("first after a submit: %s; pushes shorter than the history: %s" % (first, short))
     if len(seeds) >= 8:                                                   # (the kinds take turns over the seeds)
         assert not [k for k, n in total.items() if n < 2], total
+        assert min(first.values()) >= 1, first                            # each push kind is the first getter after a submit
+        assert short["resamp"] >= 1 and short["voice"] >= 1, short        # ... and takes each history writer's short branch
+
+
+OPS_WITH_BANKS = 150          # at most 100 operations of the first pass, and the three banks at up to 14 pushed submits of them
+
+
+def test_the_banks_leave_the_scripts_as_they_were():
+    """the second pass only adds: without its kinds a script's operations are the first pass's, which draws nothing from the
+    second pass's generator -- and everything but the operations is the first pass's too"""
+    for seed in tm.fuzz_seeds():
+        with_banks, without = tm.make_script(seed), tm.make_script(seed, banks=False)
+        assert [op for op in with_banks["ops"] if op[0] not in tm.BANK_KINDS] == without["ops"], seed
+        assert not [op for op in without["ops"] if op[0] in tm.BANK_KINDS], seed
+        assert {k: v for k, v in with_banks.items() if k != "ops"} == {k: v for k, v in without.items() if k != "ops"}, seed
+        if seed in FIRST_PASS:                                            # ... as it was before there was a second pass
+            assert hashlib.sha256(repr(without["ops"]).encode()).hexdigest()[:16] == FIRST_PASS[seed], seed
+
+
+# sha256(repr(ops))[:16] of make_script(seed)["ops"] as the commit before the second pass made them
+FIRST_PASS = {0: "b097297aaf3d4cf0", 1: "6c5638663cc57431", 2: "807f223e6065ba2a", 3: "0f2ec1c02aadbc66",
+              4: "28842b759bca081a", 5: "14016c716da1ad20", 6: "b8977a6c6ad7d31f", 7: "db209ea61d101c23"}
+
+
+def last_submit(ops, i):
+    return max(j for j in range(i) if ops[j][0] == "submit")
+
+
+def next_submit(ops, i):
+    return min([j for j in range(i, len(ops)) if ops[j][0] == "submit"] or [len(ops)])
 
 
 def test_what_a_script_guarantees():
@@ -67,14 +110,53 @@ def test_what_a_script_guarantees():
                 continue
             if op[0] == "submit":
                 pushed, submitted = set(), True
-            elif len(op) > 1 and op[0] not in ("bank_reset", "seek", "spectra", "tones", "tones_again"):
+            elif len(op) > 1 and op[0] not in ("bank_reset", "seek", "spectra", "tones", "tones_again", "voice_ctl"):
                 assert op[1] in live, (seed, i, op)                       # no operation names a receiver that is gone
+            if op[0] in tm.PUSH_KINDS:
+                assert submitted and op[0] not in pushed, (seed, i)       # at most one push per bank and submit ...
+                assert {"tones"} & {o[0] for o in ops[last_submit(ops, i): next_submit(ops, i)]}, (seed, i)   # ... where the tones are pushed
+                pushed.add(op[0])
+            if op[0] in tm.BANK_KINDS and op[0].endswith("_again"):
+                assert op[0][:-6] in pushed, (seed, i)
+            if op[0] == "voice_ctl":
+                assert 0 <= op[1] < tm.slot_rows(script["max_channels"]) and (op[2] & 0xFF) < tm.VOICE_FILTERS and not op[2] >> 9
+                assert i == 0 or ops[i - 1][0] != "submit" or ops[i + 1][0] != "submit", (seed, i)   # never inside a run of blocks
             if op[0] == "tones":
                 assert submitted and op[1] not in pushed, (seed, i)       # at most one push per bank and submit
                 pushed.add(op[1])
             if op[0] == "tones_again":
                 assert op[1] in pushed, (seed, i)
         assert len(live) == script["nrx"]
+
+
+def test_the_banks_say_something_on_the_model():
+    """the scripts played on the model alone: what the GPU plays compare with is not all zeros and not all alike"""
+    zero_out = 0
+    for seed in tm.fuzz_seeds():
+        script = tm.make_script(seed)
+        play = tm.ModelPlay(script, tm.signal(script["total"], script["carriers"], seed))
+        evals, agrees, frames, chained, muted_rows = 0, set(), 0, 0, 0
+        for op in script["ops"]:
+            if op[0] in tm.GETTER_KINDS:                                  # (they change nothing, and tones_np walks rows in Python)
+                continue
+            got = play.do(op)
+            plain =[r.slot for c, r in play.m.rxs.items() if c % 4 != 1]          # receivers that are never FM
+            if op[0] == "resamp":
+                frames += got[0]
+                assert all(got[1][s].shape == (got[0],) for s in got[1])
+            elif op[0] == "dcs":
+                evals = max([evals] + [got[s][3] for s in plain])
+                agrees |= {int(a) for s in plain for a in got[s][0].reshape(-1)}
+            elif op[0] == "voice":
+                chained += got[1]
+                muted_rows += sum(1 for s in plain if play.rb.voice.ctl[s] & tm.voice_np.MUTE and not got[0][s].any())
+                k2 = play.m.audio_rows(play.rows).shape[1]
+                assert all(got[0][s].shape == (k2,) and got[2][s].shape == (got[1],) for s in got[0])
+        # a never-FM row of the DCS bank was evaluated, and the bank does not say the same of every row and code
+        assert evals >= 1 and len(agrees) >= 2, (seed, evals, agrees)
+        assert frames > 0 and chained > 0 and muted_rows >= 1, (seed, frames, chained, muted_rows)
+        zero_out += play.rb.zero_out                                      # (allowed: a push may yield no frame)
+    print("pushes that yielded no frame: %d" % zero_out)
 
 
 # ---- the model ------------------------------------------------------------------------------------------------------------------

@@ -12,6 +12,9 @@ changes (quirk Q7, tests/test_gpu_blocks.py), the oracle copies that and the pro
 another size the model therefore gives the oracle's two filters the buffer length of that size and puts their true last
 L - 1 frames back (wr_oracle.fir_keep_history) -- with the oracle's own wro_fir_process, so that no filter arithmetic is restated here.
 
+Behind the tuner sit the row banks, each as its numpy restatement (RowBanks): tones_np.Bank twice, and resamp_np.Bank,
+dcs_np.Bank and voice_np.Bank with a second resamp_np.Bank behind it, all fed the rows of m.audio_rows().
+
 make_script(seed) is a pure function: the operations, the block cuts and the configuration of one script.  script_stats()
 walks a script without any signal processing and counts what test_tuner_model.py asserts on (the non-vacuity conditions).
 """
@@ -20,8 +23,11 @@ import os
 import numpy as np
 
 import agc_np
+import dcs_np
 import levels_np
+import resamp_np
 import tones_np
+import voice_np
 import wr_oracle as oracle
 
 AM, FM, USB, LSB = range(4)
@@ -34,6 +40,13 @@ AUDIO_SPECTRUM_N = 8                                  # the smallest size wr_spe
 SQUELCH_DBFS = (-46.0, -44.0, -48.0)                  # test_gpu_chan_levels.test_the_gate's thresholds
 GAINS_DB = (6.0, -3.5, -12.5, 0.0)
 AGC_SETTINGS = ((-12.0, 20.0, 60.0), (-6.0, 5.0, 40.0), (-20.0, 60.0, 30.0), (-15.0, 40.0, 60.0))
+# the row banks behind the tuner: a resampler audio_rate -> 3/4 of it, a voice bank whose output block goes on into a second,
+# upsampling resampler (the chain the README recommends), and a DCS bank on a caller's step (wr_dcs_step refuses the scripts'
+# audio rates): just over two frames per chip, an evaluation about every 16 audio frames
+RESAMP_P, CHAIN_P, VOICE_T, VOICE_FILTERS = 32, 8, 64, 3
+DCS_STEP, DCS_MAX_ERRORS = (1 << 28) - 54_321, 1
+DCS_OCTAL = (0o023, 0o047, 0o754, 0o412, 0o131, 0o606)                 # six of DCS_CODES ...
+DCS_OWN_WORDS = (0x2A5A5B, 0x000001)                                  # ... and two words that are nobody's code
 
 
 def fuzz_seeds():
@@ -256,7 +269,13 @@ SETTER_KINDS = ("set_if", "set_mode", "set_filter", "af_gain", "squelch_on", "sq
                 "agc_new", "reset_history", "seek", "remove", "add")
 GETTER_KINDS = ("fetch_audio", "fetch_chan", "fetch_all", "levels", "spectra", "tones", "tones_again", "audio_spectrum",
                 "get_agc", "state", "flush", "drain")
-ALL_KINDS = tuple("submit_" + k for k in SUBMIT_KINDS) + SETTER_KINDS + GETTER_KINDS
+# the row banks behind the tone bank: they enter a script in a pass of their own (_with_banks), so GETTER_KINDS, which the
+# first pass draws from, stays what it was
+PUSH_KINDS = ("resamp", "dcs", "voice")
+BANK_KINDS = PUSH_KINDS + tuple(k + "_again" for k in PUSH_KINDS) + ("voice_ctl",)
+ALL_KINDS = tuple("submit_" + k for k in SUBMIT_KINDS) + SETTER_KINDS + GETTER_KINDS + BANK_KINDS
+# frames of history a bank keeps per row: a push of fewer frames takes the history writers' "nframes < H" branch
+BANK_HISTORY = {"resamp": RESAMP_P - 1, "voice": VOICE_T - 1, "chain": CHAIN_P - 1}
 # getters whose answer is about "the last submit": with wr_tuner_set_blocks_per_launch that is the whole group of held blocks,
 # so a script asks them only where at most one block can be held (a flush goes in front of that block otherwise)
 _LAST_SUBMIT_GETTERS = ("fetch_audio", "fetch_chan", "fetch_all", "levels", "spectra", "tones", "audio_spectrum")
@@ -271,7 +290,7 @@ def _ifs(nrx):
     return [(c - nrx // 2) * spacing + 321 for c in range(nrx)]
 
 
-def make_script(seed):
+def make_script(seed, banks=True):
     """The script of a seed: a dict with the tuner's shape ("nrx", "max_channels", "d2", "audio_rate", "scale", "usual",
     "max_block", "hold", "ifs", "carriers", "total"), the operations "ops" and the block cuts "cuts" [(first frame, frames)].
 
@@ -283,6 +302,10 @@ def make_script(seed):
       ("reset_history", c) ("seek", frame) ("remove", c) ("add", c, slot, hz, mode) ("bank_reset", slot or -1)
       ("fetch_audio", c) ("fetch_chan", c) ("fetch_all",) ("levels",) ("spectra", first_frame) ("tones", bank)
       ("tones_again", bank) ("audio_spectrum",) ("get_agc", c) ("state", c) ("flush",) ("drain",)
+    and, with `banks` (_with_banks: a second pass with a generator of its own; banks=False is the first pass alone):
+      ("resamp",) ("dcs",) ("voice",)   the last submit into the resampler, the DCS bank, the voice bank and on into a second resampler
+      ("resamp_again",) ("dcs_again",) ("voice_again",)   the same submit pushed twice: refused, nothing counted
+      ("voice_ctl", slot, word)         a row's control word: the filter index and the mute bit, from the next push on
     Guarantees: only receivers with c % 4 == 1 are ever FM; an add, a reset_history and a seek are followed by the bank resets
     the header asks of callers; squelch and AGC go to at most 8 receivers each, none of them ever FM, and the squelched ones
     sit on keyed carriers and are never retuned."""
@@ -506,9 +529,80 @@ def make_script(seed):
         getter("tones")
     emit(("flush",))
     emit(("drain",))
-    return {"seed": seed, "nrx": nrx, "max_channels": nrx + 3, "d2": d2, "audio_rate": CHAN_RATE // d2, "frames": frames,
-            "scale": (1.0, 32768.0)[seed % 2], "usual": usual, "max_block": usual * hold + q, "hold": hold, "ifs": ifs,
-            "carriers": carriers, "sq_set": sq_set, "agc_set": agc_set, "ops": ops, "cuts": cuts, "total": st["pos"]}
+    script = {"seed": seed, "nrx": nrx, "max_channels": nrx + 3, "d2": d2, "audio_rate": CHAN_RATE // d2, "frames": frames,
+              "scale": (1.0, 32768.0)[seed % 2], "usual": usual, "max_block": usual * hold + q, "hold": hold, "ifs": ifs,
+              "carriers": carriers, "sq_set": sq_set, "agc_set": agc_set, "ops": ops, "cuts": cuts, "total": st["pos"]}
+    if banks:
+        script["ops"] = _with_banks(script)
+    return script
+
+
+def _with_banks(script):
+    """The operations of `script` with the three row banks played in: with BANK_KINDS filtered out again, the list is the one
+    that came in.  The pushes are "last submit" getters and stand only where the script pushes the tone banks after a submit
+    -- there the flush in front of a held group is in place, and the run of device blocks with nothing between them stays
+    as it is -- in a random order among themselves and among the tone pushes, so each is sometimes the first operation after
+    a submit; now and then a bank skips a submit.  A voice_ctl stands where a setter may stand: in front of a submit that
+    already has something in front of it, or between a submit and its voice push.  In every script one row of a receiver
+    that is never FM and never leaves is muted, pushed, and un-muted again."""
+    seed, base = script["seed"], script["ops"]
+    rng = np.random.default_rng(41_000 + seed)
+    live = {c: c for c in range(script["nrx"])}                           # handle -> slot
+    stays = [c for c in live if c % 4 != 1 and c not in {op[1] for op in base if op[0] == "remove"}]
+    mute_row = int(rng.choice(stays))
+    mute_plan = ["mute", "unmute"]
+    pushed_muted = False
+
+    def ctl(row=None, mute=None):
+        if row is None:
+            row = int(rng.choice(sorted(live.values())))
+        if mute is None:
+            mute = bool(rng.random() < 0.3)
+            if row == mute_row and mute_plan:                             # (the planned row keeps the bit the plan gave it)
+                mute = mute_plan[0] == "unmute"
+        return ("voice_ctl", row, int(rng.integers(0, VOICE_FILTERS)) | (voice_np.MUTE if mute else 0))
+
+    out, i, spans = [], 0, 0
+    total = sum(1 for j, op in enumerate(base) if op[0] == "tones" and base[j - 1][0] != "tones")
+    assert total >= 2, seed
+    while i < len(base):
+        op = base[i]
+        if op[0] == "remove":
+            del live[op[1]]
+        elif op[0] == "add":
+            live[op[1]] = op[2]
+        if op[0] == "submit" and out and out[-1][0] != "submit" and rng.random() < 0.25:
+            out.append(ctl())
+        if op[0] != "tones":
+            out.append(op)
+            i += 1
+            continue
+        seq = []
+        while i < len(base) and base[i][0] == "tones":
+            seq.append(base[i])
+            i += 1
+        last = spans == total - 1
+        new = [k for k in PUSH_KINDS if spans == 0 or rng.random() < 0.85 or (last and k == "voice")]
+        for j in rng.permutation(len(new)):
+            seq.insert(int(rng.integers(0, len(seq) + 1)), (new[int(j)],))
+        if "voice" in new:
+            planned = None
+            if mute_plan and (mute_plan[0] == "mute" or pushed_muted) and (spans == 0 or last or rng.random() < 0.5):
+                planned = ctl(mute_row, mute_plan[0] == "mute")
+                mute_plan.pop(0)
+            elif rng.random() < 0.3:
+                planned = ctl()
+            if planned:
+                seq.insert(int(rng.integers(0, seq.index(("voice",)) + 1)), planned)
+            pushed_muted = pushed_muted or mute_plan == ["unmute"]
+        for n, k in enumerate(PUSH_KINDS):
+            if k in new and (rng.random() < 0.15 or (spans == 0 and n == seed % 3)):
+                seq.insert(int(rng.integers(seq.index((k,)) + 1, len(seq) + 1)), (k + "_again",))
+        out += seq
+        spans += 1
+    assert not mute_plan, (seed, mute_plan)
+    assert [op for op in out if op[0] not in BANK_KINDS] == base
+    return out
 
 
 def script_stats(script):
@@ -517,7 +611,11 @@ def script_stats(script):
     "reseated": adds into a slot that a removed receiver left, "reseated_agc" ("reseated_squelch"): submits in which a receiver
     seated in such a slot has an AGC (a squelch) on, where the receiver that left had run a block with its AGC (squelch) on,
     "asked": getters of a submit's levels or AGC numbers that follow a setter with no submit in between, "latched": per bank
-    the most windows a row completed whose receiver is never FM}"""
+    the most windows a row completed whose receiver is never FM, "first": per push kind of the row banks how often it is the
+    first operation after a submit, "short": per bank ("chain": the second resampler behind the voice bank) the pushes of
+    fewer frames than a row's history, "zero_out": pushes of the resampler that yield no frame, "ctl_pushed": voice pushes
+    behind a voice_ctl, "ctl_late": those whose voice_ctl stands between the submit and its push, "unmuted": live rows
+    pushed un-muted after they were pushed muted}"""
     ops, nrx, d2 = script["ops"], script["nrx"], script["d2"]
     kinds = {k: 0 for k in ALL_KINDS}
     agc, run, best, on, off, reseated = set(), 0, 0, 0, 0, 0
@@ -527,9 +625,35 @@ def script_stats(script):
     fill = [dict() for _ in BANK_WINDOWS]                                 # bank -> slot -> frames since the row's reset
     latched = [0 for _ in BANK_WINDOWS]
     k2 = 0
-    for op in ops:
+    first = {k: 0 for k in PUSH_KINDS}
+    short = {k: 0 for k in BANK_HISTORY}
+    nmod, zero_out, ctl_since, ctl_pushed, ctl_late, was_muted, unmuted, words = 0, 0, None, 0, 0, set(), 0, {}
+    for at, op in enumerate(ops):
         if op[0] != "bank_reset":
             kinds[kind_of(op)] += 1
+        if op[0] in PUSH_KINDS:
+            first[op[0]] += at > 0 and ops[at - 1][0] == "submit"
+        if op[0] == "resamp":
+            short["resamp"] += k2 < BANK_HISTORY["resamp"]
+            zero_out += resamp_np.ceil_div((nmod + k2) * 3, 4) == resamp_np.ceil_div(nmod * 3, 4)
+            nmod = (nmod + k2) % 4
+        elif op[0] == "voice":
+            short["voice"] += k2 < BANK_HISTORY["voice"]
+            short["chain"] += k2 < BANK_HISTORY["chain"]
+            ctl_pushed += ctl_since is not None
+            ctl_late += ctl_since == "late"
+            ctl_since = None
+            for s in slot_of.values():
+                if words.get(s, 0) & voice_np.MUTE:
+                    was_muted.add(s)
+                elif s in was_muted:
+                    was_muted.discard(s)
+                    unmuted += 1
+        elif op[0] == "voice_ctl":
+            words[op[1]] = op[2]
+            ctl_since = "late" if submitted else "early"                  # (late: behind the submit whose push comes next)
+        if op[0] == "bank_reset" and op[1] < 0:
+            nmod = 0
         if op[0] == "submit":
             run = run + 1 if op[1] == "dev" and not agc else 0
             best = max(best, run)
@@ -540,6 +664,8 @@ def script_stats(script):
             re_agc += any(c in agc and "agc" in what for c, what in heirs.items())
             re_sq += any(c in sq and "squelch" in what for c, what in heirs.items())
             staged, submitted = False, True
+            if ctl_since:
+                ctl_since = "early"                                       # (a word set before the submit that is pushed)
             continue
         run = 0
         if op[0] in SETTER_KINDS:
@@ -580,7 +706,8 @@ def script_stats(script):
                     fill[op[1]][s] = fill[op[1]].get(s, 0) + k2
                     latched[op[1]] = max(latched[op[1]], fill[op[1]][s] // BANK_WINDOWS[op[1]])
     return {"kinds": kinds, "run": best, "agc_on": on, "agc_off": off, "reseated": reseated, "reseated_agc": re_agc,
-            "reseated_squelch": re_sq, "asked": asked, "latched": latched}
+            "reseated_squelch": re_sq, "asked": asked, "latched": latched, "first": first, "short": short,
+            "zero_out": zero_out, "ctl_pushed": ctl_pushed, "ctl_late": ctl_late, "unmuted": unmuted}
 
 
 # ---- a script played on the model ---------------------------------------------------------------------------------------------
@@ -595,8 +722,88 @@ def slot_rows(max_channels):
     return (max_channels + 63) // 64 * 64
 
 
+def audio_pos(script, pos):
+    """the stream's position in audio frames at input frame `pos`: where wr_dcs_seek puts a bank that joins there"""
+    return pos // (D1 * script["d2"])
+
+
+def bank_shapes(script):
+    """what a script's row banks are made with: {"resamp": (L, M, taps[L][P]) with wr_resamp_design's taps for audio_rate ->
+    3/4 of it, "chain": (L, M, taps) of the upsampler behind the voice bank, 4/3 with a caller's rough taps of full size,
+    "voice": taps[3][T], two seeded random filters and the unit impulse at T / 2 - 1, "words": the DCS bank's eight}"""
+    from webradio_amd import DCS_CODES
+    from webradio_amd.device import resamp_design
+    rate = script["audio_rate"]
+    taps, L, M = resamp_design(rate, rate * 3 // 4, RESAMP_P)
+    assert (L, M) == (3, 4) and not [c for c in DCS_OCTAL if c not in DCS_CODES]
+    rng = np.random.default_rng(43_000 + script["seed"])
+    chain = rng.uniform(-16.0, 16.0, (4, CHAIN_P)).astype(np.float32)
+    voice = rng.uniform(-1.0, 1.0, (VOICE_FILTERS, VOICE_T)).astype(np.float32)
+    voice[2] = 0.0
+    voice[2, VOICE_T // 2 - 1] = 1.0
+    return {"resamp": (L, M, taps), "chain": (4, 3, chain), "voice": voice,
+            "words": [dcs_np.word(c) for c in DCS_OCTAL] + list(DCS_OWN_WORDS)}
+
+
+class RowBanks:
+    """the restatements of a script's three row banks and of the resampler behind the voice bank, all of slot_rows rows and
+    fed rows[nrows][frames]: the model's rows (ModelPlay) or the library's own (test_gpu_scripts.GpuPlay)"""
+
+    def __init__(self, script):
+        shapes, rows = bank_shapes(script), slot_rows(script["max_channels"])
+        self.script = script
+        self.resamp = resamp_np.Bank(rows, *shapes["resamp"])
+        self.chain = resamp_np.Bank(rows, *shapes["chain"])
+        self.voice = voice_np.Bank(rows, shapes["voice"])
+        self.voice.set_rows(0, np.arange(rows) % VOICE_FILTERS)
+        self.dcs = dcs_np.Bank(rows, shapes["words"], DCS_STEP, DCS_MAX_ERRORS)
+        self.zero_out = 0                                                 # pushes of a resampler that yielded no frame
+
+    def reset(self, row, pos):
+        """what a script's bank_reset does to these banks, at input frame `pos` of the stream"""
+        self.resamp.reset(row)
+        self.chain.reset(row)
+        self.voice.reset(row)
+        if row >= 0 or self.script["seed"] % 2 == 0:
+            self.dcs.reset(row)
+        else:
+            self.dcs.seek(audio_pos(self.script, pos))
+
+    def push_resamp(self, rows):
+        y = self.resamp.push(rows)
+        self.zero_out += y.shape[1] == 0
+        return y
+
+    def push_dcs(self, rows):
+        self.dcs.push(rows)
+        return self.read_dcs()
+
+    def read_dcs(self):
+        return tuple(a.copy() for a in self.dcs.read())
+
+    def push_voice(self, rows):
+        """(the voice bank's frames, the frames of the resampler they go on into)"""
+        y = self.voice.push(rows)
+        z = self.chain.push(y)
+        self.zero_out += z.shape[1] == 0
+        return y, z
+
+    def counts(self, kind):
+        """the frame counts the bank's *_info call shows"""
+        if kind == "resamp":
+            return self.resamp.frames_in, self.resamp.frames_out
+        if kind == "dcs":
+            return (self.dcs.N,)
+        return self.voice.frames, self.chain.frames_in, self.chain.frames_out
+
+
+def dcs_by_slot(read, slots):
+    agree, run, hits, evals = read
+    return {s: (agree[s].copy(), run[s].copy(), hits[s].copy(), int(evals[s])) for s in slots}
+
+
 class ModelPlay:
-    """plays a script's operations on a TunerModel and two tones_np.Banks; do(op) returns what the operation hands back:
+    """plays a script's operations on a TunerModel, two tones_np.Banks and the RowBanks; do(op) returns what the operation hands back:
       fetch_audio / fetch_chan   the array
       fetch_all                  {slot: audio}
       drain                      [(submit number, {slot: audio}, {slot: (bit for bit under WR_NCO_EXACT?, else the FM tolerance
@@ -604,6 +811,11 @@ class ModelPlay:
       levels                     ({handle: (mean, peak, muted)}, frames, audio_frames)
       spectra, audio_spectrum    {handle: dB row}
       tones, tones_again         the bank as {slot: (iq, energy, windows, fill)} for the live receivers
+      resamp                     (output frames, {slot: frames}) for the live receivers
+      dcs                        {slot: (agree, run, hits, evals)}
+      voice                      ({slot: voice frames}, output frames of the second resampler, {slot: its frames})
+      resamp_again, voice_again  the banks' frame counts as wr_resamp_info and wr_voice_info show them
+      dcs_again                  ((frames,), the bank as for dcs)
       get_agc                    (on, target, floor_bits, step, state)
       state                      the NCO phase"""
 
@@ -614,6 +826,7 @@ class ModelPlay:
             self.m.add(c, c, f, CHAN_PASSBANDS[0], CHAN_RATE, c % 4, AUDIO_PASSBAND, script["audio_rate"])
         rows = slot_rows(script["max_channels"])
         self.banks = [tones_np.Bank(rows, bank_steps(script["audio_rate"]), w) for w in BANK_WINDOWS]
+        self.rb = RowBanks(script)
         self.rows = rows
         self.pos = 0
         self.ring = []
@@ -622,6 +835,9 @@ class ModelPlay:
         iq, energy, windows, fill = self.banks[b].read()
         return {r.slot: (iq[r.slot].copy(), int(energy[r.slot]), int(windows[r.slot]), int(fill[r.slot]))
                 for r in self.m.rxs.values()}
+
+    def slots(self):
+        return [r.slot for r in self.m.rxs.values()]
 
     def do(self, op):
         m, k = self.m, op[0]
@@ -659,6 +875,21 @@ class ModelPlay:
         elif k == "bank_reset":
             for b in self.banks:
                 b.reset(op[1])
+            self.rb.reset(op[1], self.pos)
+        elif k == "voice_ctl":
+            self.rb.voice.set_rows(op[1], [op[2]])
+        elif k == "resamp":
+            y = self.rb.push_resamp(m.audio_rows(self.rows))
+            return y.shape[1], {s: y[s] for s in self.slots()}
+        elif k == "dcs":
+            return dcs_by_slot(self.rb.push_dcs(m.audio_rows(self.rows)), self.slots())
+        elif k == "voice":
+            y, z = self.rb.push_voice(m.audio_rows(self.rows))
+            return {s: y[s] for s in self.slots()}, z.shape[1], {s: z[s] for s in self.slots()}
+        elif k == "dcs_again":
+            return self.rb.counts("dcs"), dcs_by_slot(self.rb.read_dcs(), self.slots())
+        elif k in ("resamp_again", "voice_again"):
+            return self.rb.counts(k[:-6])
         elif k == "fetch_audio":
             return m.audio(op[1])
         elif k == "fetch_chan":
