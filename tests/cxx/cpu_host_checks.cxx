@@ -310,6 +310,262 @@ extern "C" void wr_plan_fft_constants(unsigned int *out)
 	out[4] = FFT_WATERFALL_GRID_CAP;
 }
 
+/* ---- wr_spectrum_batch_avg's plan ---- */
+extern "C" size_t spec_avg_cap_bytes(void)
+{
+	return SPEC_AVG_BYTES;
+}
+
+/* fchunk, gchunk, carry and the scratch bytes of a call */
+extern "C" void spec_avg_plan(unsigned int n, size_t F, size_t G, size_t *out4)
+{
+	const WrSpecAvgPlan p = wrp_spec_avg_plan(n, F, G);
+	out4[0] = p.fchunk;
+	out4[1] = p.gchunk;
+	out4[2] = p.carry;
+	out4[3] = wrp_spec_avg_bytes(n, p);
+}
+
+/* the call's chunks in the order the library walks them, `max` at most: rows of (g0, ng, f0, nf); returns how many there are */
+extern "C" size_t spec_avg_chunks(unsigned int n, size_t F, size_t G, size_t max, size_t *rows)
+{
+	const WrSpecAvgPlan p = wrp_spec_avg_plan(n, F, G);
+	WrSpecAvgChunk c;
+	size_t count = 0;
+	for (bool more = wrp_spec_avg_next(p, F, G, &c, true); more; more = wrp_spec_avg_next(p, F, G, &c, false)) {
+		if (count < max) {
+			rows[4 * count] = c.g0;
+			rows[4 * count + 1] = c.ng;
+			rows[4 * count + 2] = c.f0;
+			rows[4 * count + 3] = c.nf;
+		}
+		++count;
+		if (count > max)
+			break;
+	}
+	return count;
+}
+
+/* path (WrFftPath) of a spectrum */
+extern "C" int spec_avg_path(unsigned int n, unsigned int channels)
+{
+	return (int)wrp_fft_shape(n, channels).path;
+}
+
+/* launches of a call whose plan's work area holds what a call for its chunk reserves */
+extern "C" size_t spec_avg_launches(unsigned int n, unsigned int channels, size_t F, size_t G)
+{
+	const WrSpecAvgPlan p = wrp_spec_avg_plan(n, F, G);
+	return wrp_spec_avg_launches(n, channels, F, G, wrp_fft_work_frames(n, 1, p.fchunk));
+}
+
+extern "C" unsigned int spec_avg_reduce_grid(unsigned int n, size_t ng)
+{
+	return wrp_spec_reduce_grid(n, ng);
+}
+
+/* ---- wr_spectrum_rows_detect's plan ---- */
+/* threads, bins of a tile, keys the LDS holds, the cap of a chunk's floors, what a workgroup may have of LDS */
+extern "C" void detect_constants(size_t *out5)
+{
+	out5[0] = DETECT_THREADS;
+	out5[1] = DETECT_TILE;
+	out5[2] = DETECT_LDS_KEYS;
+	out5[3] = DETECT_FLOOR_BYTES;
+	out5[4] = DETECT_WG_LDS_MAX;
+}
+
+/* the field that breaks a limit, or NULL */
+extern "C" const char *detect_rule_bad(unsigned int n, const wr_detect_rule *rule)
+{
+	return wrp_detect_rule_bad(n, rule);
+}
+
+/* nspans, chunk_rows, floor_bytes, keys_in_lds, lds_floor, lds_segments of a call with a valid rule */
+extern "C" void detect_plan(const wr_detect_rule *rule, size_t nrows, size_t *out6)
+{
+	const WrDetectPlan p = wrp_detect_plan(rule, nrows);
+	out6[0] = p.nspans;
+	out6[1] = p.chunk_rows;
+	out6[2] = p.floor_bytes;
+	out6[3] = p.keys_in_lds;
+	out6[4] = p.lds_floor;
+	out6[5] = p.lds_segments;
+}
+
+/* the call's chunks in the order the library walks them, `max` at most: rows of (r0, nr, floor grid, segments grid); returns
+ * how many there are */
+extern "C" size_t detect_chunks(const wr_detect_rule *rule, size_t nrows, size_t max, size_t *rows)
+{
+	const WrDetectPlan p = wrp_detect_plan(rule, nrows);
+	size_t r0 = 0, nr = 0, count = 0;
+	for (bool more = wrp_detect_next(p, nrows, &r0, &nr, true); more; more = wrp_detect_next(p, nrows, &r0, &nr, false)) {
+		if (count < max) {
+			rows[4 * count] = r0;
+			rows[4 * count + 1] = nr;
+			rows[4 * count + 2] = wrp_detect_floor_grid(p, nr);
+			rows[4 * count + 3] = wrp_detect_segments_grid(nr);
+		}
+		++count;
+		if (count > max)
+			break;
+	}
+	return count;
+}
+
+/* ---- the voice bank and the row kernels ---- */
+/* out[9]: VOICE_THREADS, VOICE_PER, VOICE_CHUNK, VOICE_T_MIN, VOICE_T_MAX, VOICE_FILTERS, VOICE_LDS_FLOATS, then of a push of
+ * `nframes` frames chunks, grid_x */
+extern "C" void wr_plan_voice(unsigned long nframes, unsigned int *out)
+{
+	const WrVoicePlan p = wrp_voice_plan(nframes);
+	out[0] = VOICE_THREADS;
+	out[1] = VOICE_PER;
+	out[2] = VOICE_CHUNK;
+	out[3] = VOICE_T_MIN;
+	out[4] = VOICE_T_MAX;
+	out[5] = VOICE_FILTERS;
+	out[6] = VOICE_LDS_FLOATS;
+	out[7] = p.chunks;
+	out[8] = p.grid_x;
+}
+
+extern "C" int wr_plan_voice_len_ok(unsigned int T)
+{
+	return wrp_voice_len_ok(T) ? 1 : 0;
+}
+
+/* out[6]: TN_THREADS, TN_CHUNK, TN_TABLE, then of a push chunks, nq, nr */
+extern "C" void wr_plan_tones(unsigned long nframes, unsigned int window, unsigned long long *out)
+{
+	const WrTonesPlan p = wrp_tones_plan(nframes, window);
+	out[0] = TN_THREADS;
+	out[1] = TN_CHUNK;
+	out[2] = TN_TABLE;
+	out[3] = p.chunks;
+	out[4] = p.nq;
+	out[5] = p.nr;
+}
+
+/* a push of nq * W + nr frames on a row with `fill` frames in its open window; out[6]: a_lo, b_lo, oa, ob, ends, fill_after */
+extern "C" void wr_plan_tones_cut(unsigned int fill, unsigned long long nq, unsigned int nr, unsigned int W, long long *out)
+{
+	const WrTonesCut c = wrp_tones_cut(fill, nq, nr, W);
+	out[0] = c.a_lo;
+	out[1] = c.b_lo;
+	out[2] = c.oa;
+	out[3] = c.ob;
+	out[4] = (long long)c.ends;
+	out[5] = c.fill_after;
+}
+
+/* out[3]: DC_SPAN, DC_THREADS, DC_RING */
+extern "C" void wr_plan_dcs_constants(unsigned int *out)
+{
+	out[0] = DC_SPAN;
+	out[1] = DC_THREADS;
+	out[2] = DC_RING;
+}
+
+extern "C" int wr_plan_dcs_step_ok(unsigned long long step)
+{
+	return wrp_dcs_step_ok(step) ? 1 : 0;
+}
+
+/* the launches of a push of `nframes` frames at clock `first_frame`, `max` at most: rows of (g0, ph0, frames, room); returns
+ * how many there are */
+extern "C" size_t wr_plan_dcs_launches(unsigned long long first_frame, unsigned int step, size_t nframes, size_t max,
+                                       unsigned long long *rows)
+{
+	WrDcsAt at = wrp_dcs_start(first_frame, step);
+	size_t count = 0;
+	for (size_t done = 0, n; done < nframes; done += n, at = wrp_dcs_after(at, step, n)) {
+		n = wrp_dcs_take(at, step, nframes - done);
+		if (count < max) {
+			rows[4 * count] = at.g0;
+			rows[4 * count + 1] = at.ph0;
+			rows[4 * count + 2] = n;
+			rows[4 * count + 3] = wrp_dcs_room(at, step);
+		}
+		++count;
+		if (!n || count > max)
+			break;
+	}
+	return count;
+}
+
+/* out[7]: RS_THREADS, RS_SPAN, RS_L_MAX, RS_RATIO_MAX, RS_P_MIN, RS_P_MAX, RS_TAPS_MAX */
+extern "C" void wr_plan_resamp_constants(unsigned int *out)
+{
+	out[0] = RS_THREADS;
+	out[1] = RS_SPAN;
+	out[2] = RS_L_MAX;
+	out[3] = RS_RATIO_MAX;
+	out[4] = RS_P_MIN;
+	out[5] = RS_P_MAX;
+	out[6] = RS_TAPS_MAX;
+}
+
+extern "C" int wr_plan_resamp_limits_bad(unsigned int L, unsigned int M, unsigned int P)
+{
+	return wrp_resamp_limits_bad(L, M, P);
+}
+
+extern "C" unsigned long long wr_plan_resamp_out_frames(unsigned int L, unsigned int M, unsigned int nmod, unsigned long long nframes)
+{
+	return wrp_resamp_out_frames(L, M, nmod, nframes);
+}
+
+/* out[4]: n_out, j0, chunks, grid_x */
+extern "C" void wr_plan_resamp(unsigned int L, unsigned int M, unsigned int nmod, unsigned long nframes, unsigned long long *out)
+{
+	const WrResampPlan p = wrp_resamp_plan(L, M, nmod, nframes);
+	out[0] = p.n_out;
+	out[1] = p.j0;
+	out[2] = p.chunks;
+	out[3] = p.grid_x;
+}
+
+/* chunk `chunk` of that push; out[6]: i0, base, lo, rem0, cnt, span */
+extern "C" void wr_plan_resamp_chunk(unsigned int L, unsigned int M, unsigned int P, unsigned int nmod, unsigned long nframes,
+                                     unsigned int chunk, long long *out)
+{
+	const WrResampPlan p = wrp_resamp_plan(L, M, nmod, nframes);
+	const WrResampChunk c = wrp_resamp_chunk(L, M, P, nmod, p.j0, p.n_out, chunk);
+	out[0] = (long long)c.i0;
+	out[1] = c.base;
+	out[2] = c.lo;
+	out[3] = c.rem0;
+	out[4] = c.cnt;
+	out[5] = c.span;
+}
+
+/* out[11]: LV_ROWS, LV_THREADS, then groups, grid_y, lds_squelch, sum_grid, psum, ppeak, pmuted, res, work_floats */
+extern "C" void wr_plan_levels(unsigned int cols, unsigned long k1, unsigned long long *out)
+{
+	const WrLevelsPlan p = wrp_levels_plan(cols, k1);
+	out[0] = LV_ROWS;
+	out[1] = LV_THREADS;
+	out[2] = p.groups;
+	out[3] = p.grid_y;
+	out[4] = p.lds_squelch;
+	out[5] = p.sum_grid;
+	out[6] = p.psum;
+	out[7] = p.ppeak;
+	out[8] = p.pmuted;
+	out[9] = p.res;
+	out[10] = p.work_floats;
+}
+
+/* out[4]: AGC_THREADS, AGC_PER, AGC_TILE, AGC_WAVES */
+extern "C" void wr_plan_agc(unsigned int *out)
+{
+	out[0] = AGC_THREADS;
+	out[1] = AGC_PER;
+	out[2] = AGC_TILE;
+	out[3] = AGC_WAVES;
+}
+
 /* ---- device hand-over bookkeeping of DspBlock (no GPU involved: pointers are just tokens) ---- */
 namespace {
 struct Src : public DspSource {

@@ -1,4 +1,5 @@
-"""The launch plans of the tuner's kernels and of the spectrum launches (webradio_amd/csrc/wr_plan.h) through tests/cxx/libwr_cpu_host_checks.so: plain
+"""The launch plans of the tuner's kernels, of the spectrum launches, of the voice bank and of the row kernels
+(webradio_amd/csrc/wr_plan.h) through tests/cxx/libwr_cpu_host_checks.so, the one road by which a test reaches them: plain
 arithmetic, no GPU.  What tests/test_launch_plan.py holds to hand-worked figures, and where a GPU test that has to know which
 branch of a rule a case reaches asks the rule itself."""
 import ctypes as C
@@ -20,6 +21,14 @@ AudioPlan = namedtuple("AudioPlan", "tk need lds lds_max grid_x")
 FFT_SINGLE, FFT_FOUR_STEP, FFT_REG64K = 0, 1, 2           # WrFftPath
 FftShape = namedtuple("FftShape", "points n1 n2 sub path lds_max real")
 FftLaunch = namedtuple("FftLaunch", "ct rt fpw lds1 lds2 grid1 grid2 grid3")
+VoicePlan = namedtuple("VoicePlan", "threads per chunk t_min t_max filters lds_floats chunks grid_x")
+TonesPlan = namedtuple("TonesPlan", "threads chunk table chunks nq nr")
+TonesCut = namedtuple("TonesCut", "a_lo b_lo oa ob ends fill_after")
+DcsLaunch = namedtuple("DcsLaunch", "g0 ph0 frames room")
+ResampPlan = namedtuple("ResampPlan", "n_out j0 chunks grid_x")
+ResampChunk = namedtuple("ResampChunk", "i0 base lo rem0 cnt span")
+LevelsPlan = namedtuple("LevelsPlan", "rows threads groups grid_y lds_squelch sum_grid psum ppeak pmuted res work_floats")
+AgcPlan = namedtuple("AgcPlan", "threads per tile waves")
 
 _lib = None
 
@@ -31,8 +40,10 @@ def lib():
         if not os.path.exists(path):
             subprocess.check_call(["make", "-s", "-C", CXXT, "libwr_cpu_host_checks.so"])
         L = C.CDLL(path)
-        u, ul, ull, i = C.c_uint, C.c_ulong, C.c_ulonglong, C.c_int
-        pu, pull, pb = C.POINTER(u), C.POINTER(ull), C.POINTER(C.c_ubyte)
+        u, ul, ull, i, sz = C.c_uint, C.c_ulong, C.c_ulonglong, C.c_int, C.c_size_t
+        pu, pull, pb, pll, psz = C.POINTER(u), C.POINTER(ull), C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong), C.POINTER(sz)
+        from webradio_amd import capi
+        rule = C.POINTER(capi.DetectRule)
         for name, res, args in [
             ("wr_plan_post_tk", u, []),
             ("wr_plan_group_map", None, [u, ull, pb, pull, pu]),
@@ -56,6 +67,30 @@ def lib():
             ("wr_plan_fft_untangle_offset", ul, [ul, u]),
             ("wr_plan_fft_cols_ct", u, [u, u, i]),
             ("wr_plan_fft_constants", None, [pu]),
+            ("spec_avg_cap_bytes", sz, []),
+            ("spec_avg_plan", None, [u, sz, sz, psz]),
+            ("spec_avg_chunks", sz, [u, sz, sz, sz, psz]),
+            ("spec_avg_path", i, [u, u]),
+            ("spec_avg_launches", sz, [u, u, sz, sz]),
+            ("spec_avg_reduce_grid", u, [u, sz]),
+            ("detect_constants", None, [psz]),
+            ("detect_rule_bad", C.c_char_p, [u, rule]),
+            ("detect_plan", None, [rule, sz, psz]),
+            ("detect_chunks", sz, [rule, sz, sz, psz]),
+            ("wr_plan_voice", None, [ul, pu]),
+            ("wr_plan_voice_len_ok", i, [u]),
+            ("wr_plan_tones", None, [ul, u, pull]),
+            ("wr_plan_tones_cut", None, [u, ull, u, u, pll]),
+            ("wr_plan_dcs_constants", None, [pu]),
+            ("wr_plan_dcs_step_ok", i, [ull]),
+            ("wr_plan_dcs_launches", sz, [ull, u, sz, sz, pull]),
+            ("wr_plan_resamp_constants", None, [pu]),
+            ("wr_plan_resamp_limits_bad", i, [u, u, u]),
+            ("wr_plan_resamp_out_frames", ull, [u, u, u, ull]),
+            ("wr_plan_resamp", None, [u, u, u, ul, pull]),
+            ("wr_plan_resamp_chunk", None, [u, u, u, u, ul, u, pll]),
+            ("wr_plan_levels", None, [u, ul, pull]),
+            ("wr_plan_agc", None, [pu]),
         ]:
             f = getattr(L, name)
             f.restype, f.argtypes = res, args
@@ -161,3 +196,72 @@ def fft_constants():
     out = (C.c_uint * 5)()
     lib().wr_plan_fft_constants(out)
     return dict(zip("threads lds_points p1_long_min db_grid_cap waterfall_grid_cap".split(), out))
+
+
+# ---- the voice bank and the row kernels ------------------------------------------------------------------------------------
+
+def voice_plan(nframes=1):
+    """the constants, and chunks and grid_x of a push of `nframes` frames"""
+    out = (C.c_uint * 9)()
+    lib().wr_plan_voice(nframes, out)
+    return VoicePlan(*out)
+
+
+def tones_plan(nframes, window):
+    out = (C.c_ulonglong * 6)()
+    lib().wr_plan_tones(nframes, window, out)
+    return TonesPlan(*out)
+
+
+def tones_cut(fill, n, W):
+    """a push of n frames on a row with `fill` frames in its open window of W"""
+    out = (C.c_longlong * 6)()
+    lib().wr_plan_tones_cut(fill, n // W, n % W, W, out)
+    return TonesCut(*out)
+
+
+def dcs_constants():
+    out = (C.c_uint * 3)()
+    lib().wr_plan_dcs_constants(out)
+    return dict(zip("span threads ring".split(), out))
+
+
+def dcs_launches(first_frame, step, nframes, most=1 << 20):
+    rows = (C.c_ulonglong * (4 * most))()
+    count = lib().wr_plan_dcs_launches(first_frame, step, nframes, most, rows)
+    assert count <= most, "more launches than the test walks"
+    return [DcsLaunch(*rows[4 * k: 4 * k + 4]) for k in range(count)]
+
+
+def resamp_constants():
+    out = (C.c_uint * 7)()
+    lib().wr_plan_resamp_constants(out)
+    return dict(zip("threads span l_max ratio_max p_min p_max taps_max".split(), out))
+
+
+def resamp_out_frames(L, M, nmod, nframes):
+    return lib().wr_plan_resamp_out_frames(L, M, nmod, nframes)
+
+
+def resamp_plan(L, M, nmod, nframes):
+    out = (C.c_ulonglong * 4)()
+    lib().wr_plan_resamp(L, M, nmod, nframes, out)
+    return ResampPlan(*out)
+
+
+def resamp_chunk(L, M, P, nmod, nframes, chunk):
+    out = (C.c_longlong * 6)()
+    lib().wr_plan_resamp_chunk(L, M, P, nmod, nframes, chunk, out)
+    return ResampChunk(*out)
+
+
+def levels_plan(cols, k1):
+    out = (C.c_ulonglong * 11)()
+    lib().wr_plan_levels(cols, k1, out)
+    return LevelsPlan(*out)
+
+
+def agc_plan():
+    out = (C.c_uint * 4)()
+    lib().wr_plan_agc(out)
+    return AgcPlan(*out)

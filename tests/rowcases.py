@@ -1,13 +1,18 @@
-"""Case builders the GPU tests of the per-row features share (test_gpu_tones, test_gpu_resamp, test_gpu_agc,
+"""Case builders the GPU tests of the per-row features share (test_gpu_tones, test_gpu_resamp, test_gpu_voice, test_gpu_agc,
 test_gpu_chan_levels, test_gpu_scripts, test_gpu_bank_limits): rows of audio with every awkward float among them, rows in
-device memory and sentinel-filled outputs, the five-receiver NFM tuner of tones_np with its twelve blocks and the audio of
-its untouched twin, and the keyed-carrier block of the level and AGC tests.
+device memory -- the layout rule by row count, the push into a sentinel-padded output and its comparison -- and
+sentinel-filled outputs, the five-receiver NFM tuner of tones_np with its twelve blocks (the fm_stream fixture), the audio of
+its untouched twin and a raw wr_tuner_*_push into sentinel-filled rows, and the keyed-carrier block of the level and AGC tests.
 
 Everything random comes from a seeded numpy Generator through a fixed sequence of calls, so a case is the same floats
 wherever and whenever it is built."""
+import ctypes as C
+
 import numpy as np
+import pytest
 
 import tones_np
+from capicases import same_bits  # noqa: F401  (bit-for-bit equality of float32 arrays, as rowcases.same_bits too)
 from webradio_amd import capi
 from webradio_amd.device import Tuner
 
@@ -31,9 +36,50 @@ def special_rows(nrows, n, seed, max_exp, special):
 SENTINEL = np.array([0x7FC0BEEF], np.uint32).view(np.float32)[0]          # a NaN nobody computes: what a kernel leaves alone
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+def row_layout(nrows, n):
+    """(extra, lead) for rows of n floats: one row back to back; three rows an odd stride and a base one float off 16-byte
+    alignment; 64 rows a stride that is a multiple of four and larger than the row; 65 rows odd again"""
+    extra, lead = {1: (0, 0), 3: (5, 1), 64: (8 - n % 4, 0), 65: (7, 1)}.get(nrows, (3, 1))
+    if (n + extra) % 2 == 0 and nrows in (3, 65):
+        extra += 1
+    return extra, lead
+
+
+def upload_laid_out(dev, v):
+    """the rows in device memory behind `lead` floats, `stride` floats apart (row_layout), the gaps NaN -- they are never
+    read: (pointer to free, pointer to row 0, stride)"""
+    nrows, n = v.shape
+    extra, lead = row_layout(nrows, n)
+    stride = n + extra
+    buf = np.full(lead + nrows * stride, np.float32(np.nan), np.float32)
+    for r in range(nrows):
+        buf[lead + r * stride: lead + r * stride + n] = v[r]
+    p = dev.upload(buf)
+    return p, p + 4 * lead, stride
+
+
+def padded_push(dev, nrows, n_out, push, what):
+    """`push(p_out, out_stride)` writes nrows rows of n_out floats into a buffer laid out by row_layout and filled with
+    SENTINEL: (what push returned, check) -- check(ref) holds every output bit to ref[nrows][n_out], then that nothing
+    beside the rows was written"""
+    extra, lead = row_layout(nrows, max(n_out, 1))
+    ostride = n_out + extra
+    obuf = np.full(lead + nrows * ostride + 3, SENTINEL, np.float32)
+    p_out = dev.upload(obuf)
+    try:
+        result = push(p_out + 4 * lead, ostride)
+        got = dev.download(p_out, obuf.size)
+    finally:
+        dev.free(p_out)
+
+    def check(ref):
+        out = got[lead: lead + nrows * ostride].reshape(nrows, ostride)
+        bad = np.argwhere(out[:, :n_out].view(np.uint32) != ref.view(np.uint32))
+        assert bad.size == 0, (what, len(bad), bad[:4], [out[tuple(b)] for b in bad[:4]], [ref[tuple(b)] for b in bad[:4]])
+        gaps = np.concatenate([got[:lead], out[:, n_out:].reshape(-1), got[lead + nrows * ostride:]])
+        assert np.all(gaps.view(np.uint32) == SENTINEL.view(np.uint32)), what
+
+    return result, check
 
 
 def upload_rows(dev, v, stride):
@@ -77,7 +123,6 @@ class OutRows:
 def dcs_bank(dev, max_rows, words, step, max_errors=0):
     """a device.DcsBank on a caller's step: its constructor takes an audio rate and asks wr_dcs_step, which refuses rates
     below two frames per chip; wr_dcs_create itself takes any step in [2^19, 2^28]"""
-    import ctypes as C
     from webradio_amd.device import DcsBank
     b = DcsBank.__new__(DcsBank)
     b.dev, b.lib, b.max_rows, b.step, b.max_errors = dev, dev.lib, max_rows, int(step), max_errors
@@ -101,6 +146,27 @@ def fm_upload(dev):
     return dev.upload(np.concatenate([tones_np.fm_block(BLOCK, b * BLOCK) for b in range(NBLOCKS)]))
 
 
+@pytest.fixture(scope="module")
+def fm_stream(dev):
+    """the twelve blocks in device memory, back to back; uploaded once (a module that uses it imports it)"""
+    p = fm_upload(dev)
+    yield p
+    forget_twins()
+    dev.free(p)
+
+
+def raw_tuner_push(dev, call, stride, out=True):
+    """a wr_tuner_*_push that writes rows: `call(out_dev, out_stride)` -> rc with a buffer of 64 rows of `stride` floats
+    filled with SENTINEL (out False: a NULL out_dev); (rc, the rows downloaded)"""
+    p = dev.upload(np.full(64 * stride, SENTINEL, np.float32))
+    try:
+        rc = call(C.c_void_p(p) if out else None, stride)
+        got = dev.download(p, 64 * stride).reshape(64, stride)
+    finally:
+        dev.free(p)
+    return rc, got
+
+
 def fm_tuner(dev, nco, streaming=False, spare=0):
     t = Tuner(dev, tones_np.FS, len(tones_np.IFS) + spare, BLOCK, nco)
     chans = [t.add_receiver(f, tones_np.CHAN_PASSBAND, tones_np.CHAN_RATE, capi.WR_FM, tones_np.AUDIO_PASSBAND,
@@ -115,14 +181,20 @@ def twin_audio(dev, x, nco, streaming=False):
     mode and way of launching"""
     key = (nco, streaming)
     if key not in _twin_audio:
-        t, chans = fm_tuner(dev, nco, streaming)
-        out = []
-        for b in range(NBLOCKS):
-            t.submit_device(x + 8 * BLOCK * b, BLOCK)
-            out.append([t.fetch(ch, capi.WR_STAGE_AUDIO, K2) for ch in chans])
-        t.destroy()
-        _twin_audio[key] = out
+        _twin_audio[key] = block_audio(fm_tuner(dev, nco, streaming), x, NBLOCKS, BLOCK, K2)
     return _twin_audio[key]
+
+
+def block_audio(tuner, x, nblocks, block, k2):
+    """[block][receiver] audio of `tuner` = (tuner, channels) over `nblocks` blocks of `block` frames at x, a launch and a fetch
+    per block; the tuner is destroyed"""
+    t, chans = tuner
+    out = []
+    for b in range(nblocks):
+        t.submit_device(x + 8 * block * b, block)
+        out.append([t.fetch(ch, capi.WR_STAGE_AUDIO, k2) for ch in chans])
+    t.destroy()
+    return out
 
 
 def forget_twins():

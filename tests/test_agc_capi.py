@@ -2,38 +2,25 @@
 the rule, NULL handles are refused by name, wr_agc_design's numbers are numpy's, and the restatement the GPU tests
 compare bits with (tests/agc_np.py) is held to the rule's plain loop and to the rule's two promises here first."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import capicases
 import agc_np
 from webradio_amd import capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEPS = [0, 1, 2787, 1 << 23, 1 << 31]
-
-
-def _header_args(name):
-    text = open(os.path.join(ROOT, "include", "webradio_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m, "%s is not declared" % name
-    return [a.strip() for a in m.group(1).split(",")]
 
 
 @pytest.mark.parametrize("name, nargs", [("wr_agc_design", 7), ("wr_agc_rows", 9), ("wr_chan_set_agc", 6),
                                          ("wr_chan_get_agc", 7), ("wr_tuner_agc_info", 3)])
 def test_declared_and_bound_with_the_same_arguments(name, nargs):
-    assert len(_header_args(name)) == nargs
-    restype, argtypes = capi.SIGNATURES[name]
-    assert len(argtypes) == nargs
-    assert getattr(capi.load(), name) is not None
+    capicases.declared_and_bound(name, nargs)
 
 
 def test_header_says_the_rule():
-    text = open(os.path.join(ROOT, "include", "webradio_amd.h")).read()
+    text = capicases.header()
     assert "Added to 6 later: wr_agc_design, wr_agc_rows, wr_chan_set_agc, wr_chan_get_agc, wr_tuner_agc_info" in text
     for word in ("0x7f7fffff", "E[m]   = max(L[m], E[m-1] - step, floor)", "g[m]   = target / env[m]", "prefix",
                  "audio filter -> squelch -> AGC -> af_gain -> scale", "0.72 and 1.44", "leaves every bit as it was",

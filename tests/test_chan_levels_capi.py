@@ -1,36 +1,21 @@
 """wr_tuner_chan_levels / wr_iq_levels without a GPU: the header and the binding carry them with the same argument
 counts, NULL handles are refused with a message, and the numpy restatement of the summation rule the GPU tests compare
 bits with (tests/levels_np.py) is held to float64 here first."""
-import os
-import re
-
 import numpy as np
 import pytest
 
+import capicases
 import levels_np
 from webradio_amd import capi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header_args(name):
-    text = open(os.path.join(ROOT, "include", "webradio_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m, "%s is not declared" % name
-    return [a.strip() for a in m.group(1).split(",")]
 
 
 @pytest.mark.parametrize("name, nargs", [("wr_tuner_chan_levels", 7), ("wr_iq_levels", 5)])
 def test_declared_and_bound_with_the_same_arguments(name, nargs):
-    assert len(_header_args(name)) == nargs
-    restype, argtypes = capi.SIGNATURES[name]
-    assert len(argtypes) == nargs
-    assert getattr(capi.load(), name) is not None
+    capicases.declared_and_bound(name, nargs)
 
 
 def test_header_says_the_rule_and_cites_the_reference():
-    text = open(os.path.join(ROOT, "include", "webradio_amd.h")).read()
+    text = capicases.header()
     assert "Added to 6 later: wr_tuner_chan_levels, wr_iq_levels" in text
     for word in ("runs of 16", "groups of 16 runs", "web/receiverhandler.cxx:112,118-119", "dsp/demodulator.cxx:77-115"):
         assert word in text, word

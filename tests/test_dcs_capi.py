@@ -3,43 +3,28 @@ the rule, wr_dcs_word and wr_dcs_step give the rule's numbers (and the restateme
 their limits, the restatement the GPU tests compare bits with agrees with itself across cuts, and the detection conditions
 hold for it on audio from the oracle chain."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
+import capicases
 import dcs_np
 from webradio_amd import DCS_CODES, capi, dcs_step, dcs_word
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [("wr_dcs_word", 2), ("wr_dcs_step", 2), ("wr_dcs_create", 7), ("wr_dcs_destroy", 1), ("wr_dcs_reset", 2),
          ("wr_dcs_seek", 2), ("wr_dcs_push_rows", 5), ("wr_tuner_dcs_push", 3), ("wr_dcs_read", 6), ("wr_dcs_info", 5)]
 PAIRS = [(0o023, 0o047), (0o025, 0o244), (0o026, 0o464), (0o031, 0o627), (0o054, 0o413), (0o072, 0o245), (0o074, 0o174)]
 WORDS = [dcs_np.word(c) for c in DCS_CODES]
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "webradio_amd.h")).read()
-
-
-def _header_args(name):
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m, "%s is not declared" % name
-    return [a.strip() for a in m.group(1).split(",")]
-
-
 @pytest.mark.parametrize("name, nargs", NAMES)
 def test_declared_and_bound_with_the_same_arguments(name, nargs):
-    assert len(_header_args(name)) == nargs
-    restype, argtypes = capi.SIGNATURES[name]
-    assert len(argtypes) == nargs
-    assert getattr(capi.load(), name) is not None
+    capicases.declared_and_bound(name, nargs)
 
 
 def test_header_says_the_rule():
-    text = _header()
+    text = capicases.header()
     assert re.search(r"#define\s+WR_ABI_VERSION\s+6\b", text)
     assert capi.load().wr_abi_version() == 6
     assert re.search(r"Added to 6 later: wr_dcs_word, wr_dcs_step, wr_dcs_create, wr_dcs_destroy, wr_dcs_reset,\s+"

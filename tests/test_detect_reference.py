@@ -5,12 +5,12 @@ keeps its promises."""
 import ctypes as C
 import itertools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import detect_np as dn
+import launch_plan
 import specavg_np as sa
 from flat_spectrum import MASK_OUT_SHARE
 from test_gpu_spectrum import DB_ATOL
@@ -90,19 +90,8 @@ SIZE = C.c_size_t
 
 
 @pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("detect_plan") / "libdetect_plan.so")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-Wall", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "webradio_amd", "csrc"), os.path.join(ROOT, "tests", "cxx", "detect_plan.cxx"),
-                           "-o", so])
-    lib = C.CDLL(so)
-    lib.detect_constants.argtypes = [C.POINTER(SIZE)]
-    lib.detect_rule_bad.restype = C.c_char_p
-    lib.detect_rule_bad.argtypes = [C.c_uint, C.POINTER(capi.DetectRule)]
-    lib.detect_plan.argtypes = [C.POINTER(capi.DetectRule), SIZE, C.POINTER(SIZE)]
-    lib.detect_chunks.restype = SIZE
-    lib.detect_chunks.argtypes = [C.POINTER(capi.DetectRule), SIZE, SIZE, C.POINTER(SIZE)]
-    return lib
+def plan():
+    return launch_plan.lib()
 
 
 def _constants(lib):

@@ -245,13 +245,7 @@ def fm_stream(dev):
 
     def twin(nco):
         if nco not in twins:
-            t, chans = _tuner(dev, nco)
-            out = []
-            for b in range(NBLOCKS):
-                t.submit_device(p + 8 * BLOCK * b, BLOCK)
-                out.append([t.fetch(ch, capi.WR_STAGE_AUDIO, K2) for ch in chans])
-            t.destroy()
-            twins[nco] = out
+            twins[nco] = rowcases.block_audio(_tuner(dev, nco), p, NBLOCKS, BLOCK, K2)
         return twins[nco]
 
     yield p, twin

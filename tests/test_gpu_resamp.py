@@ -16,14 +16,13 @@ import pytest
 import resamp_np
 import rowcases
 import tones_np
-from rowcases import BLOCK, K2, NBLOCKS
+from rowcases import BLOCK, K2, NBLOCKS, SENTINEL, fm_stream  # noqa: F401  (fm_stream: the fixture)
 from webradio_amd import capi
 from webradio_amd.device import Resampler, resamp_design
 
 pytestmark = pytest.mark.gpu
 
 SPECIAL = [np.inf, -np.inf, np.nan, 1e30, -1e30, -0.0, 1e-40, 65536.0]
-SENTINEL = np.array([0x7FC0BEEF], np.uint32).view(np.float32)[0]          # a NaN nobody computes: what the kernel leaves alone
 # (L, M, P) -> the rates wr_resamp_design is asked for; None: it makes no taps for this shape (see above)
 SHAPES = {(3, 2, 4): None, (24, 25, 32): (50_000, 48_000), (24, 125, 64): (250_000, 48_000), (441, 500, 32): (50_000, 44_100),
           (1, 1, 8): None, (8, 1, 16): (6_000, 48_000), (1, 8, 64): None}
@@ -57,36 +56,16 @@ def _frames_for(want, outputs):
     return n
 
 
-def _layout(nrows, n):
-    """(extra, lead): one row back to back; three rows an odd stride and a base one float off 16-byte alignment; 64 rows a
-    stride that is a multiple of four and larger than the row; 65 rows odd again"""
-    extra, lead = {1: (0, 0), 3: (5, 1), 64: (8 - n % 4, 0), 65: (7, 1)}.get(nrows, (3, 1))
-    if (n + extra) % 2 == 0 and nrows in (3, 65):
-        extra += 1
-    return extra, lead
-
-
 def _push(dev, rs, want, p_in, stride, nrows, pos, length, v, what):
     """one push of frames [pos, pos + length) of every row, compared: the count foretold, every output bit, and nothing
     written beside the rows"""
     n_want = want.out_frames(length)
     assert rs.out_frames(length) == n_want, what
-    extra, lead = _layout(nrows, max(n_want, 1))
-    ostride = n_want + extra
-    obuf = np.full(lead + nrows * ostride + 3, SENTINEL, np.float32)
-    p_out = dev.upload(obuf)
-    try:
-        n_out = rs.push_rows(p_in + 4 * pos, stride, nrows, length, p_out + 4 * lead, ostride)
-        got = dev.download(p_out, obuf.size)
-    finally:
-        dev.free(p_out)
+    n_out, check = rowcases.padded_push(dev, nrows, n_want, lambda p_out, ostride: rs.push_rows(p_in + 4 * pos, stride, nrows, length,
+                                                                                            p_out, ostride), what)
     ref = want.push(v[:nrows, pos: pos + length])
     assert n_out == n_want == ref.shape[1], (what, n_out, n_want)
-    out = got[lead: lead + nrows * ostride].reshape(nrows, ostride)
-    bad = np.argwhere(out[:, :n_out].view(np.uint32) != ref.view(np.uint32))
-    assert bad.size == 0, (what, bad[:4], [out[tuple(b)] for b in bad[:4]], [ref[tuple(b)] for b in bad[:4]])
-    gaps = np.concatenate([got[:lead], out[:, n_out:].reshape(-1), got[lead + nrows * ostride:]])
-    assert np.all(gaps.view(np.uint32) == SENTINEL.view(np.uint32)), what
+    check(ref)
     return n_out
 
 
@@ -117,18 +96,13 @@ def test_rows_against_the_restatement(dev, nrows, L, M, P):
         add(_frames_for(plan, outputs))
     add(3000)
     n = sum(lengths)
-    extra, lead = _layout(nrows, n)
-    stride = n + extra
     v = _rows(nrows, n, seed=1000 * nrows + 10 * L + P)
-    buf = np.full(lead + nrows * stride, np.float32(np.nan), np.float32)      # (the gaps between rows are never read)
-    for r in range(nrows):
-        buf[lead + r * stride: lead + r * stride + n] = v[r]
     rs = _bank(dev, nrows, L, M, taps)
-    p = dev.upload(buf)
+    p, p0, stride = rowcases.upload_laid_out(dev, v)
     try:
         pos, counts = 0, []
         for length in lengths:
-            counts.append(_push(dev, rs, want, p + 4 * lead, stride, nrows, pos, length, v, (nrows, L, M, P, pos, length)))
+            counts.append(_push(dev, rs, want, p0, stride, nrows, pos, length, v, (nrows, L, M, P, pos, length)))
             pos += length
         assert 0 in counts or L >= M
         if L <= M:
@@ -200,24 +174,11 @@ def test_reset_and_rows_left_out(dev):
 OUT_RATE, TAPS = 750, 32
 
 
-@pytest.fixture(scope="module")
-def fm_stream(dev):
-    """the twelve blocks in device memory, back to back; uploaded once"""
-    p = rowcases.fm_upload(dev)
-    yield p
-    rowcases.forget_twins()
-    dev.free(p)
-
-
 def _raw_push(dev, t, rs, stride):
     """wr_tuner_resamp_push into a buffer of 64 rows of `stride` floats; (rc, n_out, slots, the rows downloaded)"""
-    p = dev.upload(np.full(64 * stride, SENTINEL, np.float32))
-    try:
-        n_out, slots = C.c_size_t(), C.c_uint()
-        rc = dev.lib.wr_tuner_resamp_push(t.h, rs.h, C.c_void_p(p), stride, C.byref(n_out), C.byref(slots))
-        got = dev.download(p, 64 * stride).reshape(64, stride)
-    finally:
-        dev.free(p)
+    n_out, slots = C.c_size_t(), C.c_uint()
+    rc, got = rowcases.raw_tuner_push(dev, lambda p, s: dev.lib.wr_tuner_resamp_push(t.h, rs.h, p, s, C.byref(n_out), C.byref(slots)),
+                                      stride)
     return rc, n_out.value, slots.value, got
 
 

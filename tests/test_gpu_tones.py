@@ -14,7 +14,7 @@ import pytest
 
 import rowcases
 import tones_np
-from rowcases import BLOCK, K2, NBLOCKS
+from rowcases import BLOCK, K2, NBLOCKS, fm_stream  # noqa: F401  (the fixture)
 from webradio_amd import CTCSS_HZ, capi
 from webradio_amd.device import ToneBank
 
@@ -166,15 +166,6 @@ def test_reset_clears_that_row_alone(dev):
 
 
 # ---- 3: behind a tuner ----------------------------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def fm_stream(dev):
-    """the twelve blocks in device memory, back to back; uploaded once"""
-    p = rowcases.fm_upload(dev)
-    yield p
-    rowcases.forget_twins()
-    dev.free(p)
-
 
 @pytest.mark.parametrize("how", ["per-block", "streaming", "two-per-launch"])
 @pytest.mark.parametrize("nco", [capi.WR_NCO_EXACT, capi.WR_NCO_ROTATE], ids=["exact", "rotate"])

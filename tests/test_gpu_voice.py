@@ -4,45 +4,34 @@ a unit-impulse filter in test_voice_capi.py): every output frame of every row af
 uploaded; a sentinel NaN shows that nothing beside the output rows was written.
 
 The taps are seeded random ones up to +-16 with -0.0, subnormals and 16.0 among them: what is compared is the arithmetic,
-which does not care what the taps mean.  The chunk of outputs a workgroup takes and the outputs a thread takes are read
-from wr_plan.h (every VOICE_CHUNK... and VOICE_PER... value there), and the pushes are cut around them.
+which does not care what the taps mean.  The chunk of outputs a workgroup takes and the outputs a thread takes are the
+plan's (wr_plan.h's VOICE_CHUNK and VOICE_PER through tests/launch_plan.py), and the pushes are cut around them.
 
 The tuner test is the tone bank's: FS 2 MHz, channel rate 5 kHz, audio 1 kHz with five NFM receivers (tones_np.fm_block),
 twelve submits of 100 000 frames = 50 audio frames each, through a bank of 64 rows of 64 taps -- a history longer than a
 block -- and on into a Resampler at 1 000 -> 750 Hz (3 / 4, P = 32)."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import launch_plan
 import resamp_np
 import rowcases
 import tones_np
 import voice_np
-from rowcases import BLOCK, K2, NBLOCKS
+from rowcases import BLOCK, K2, NBLOCKS, SENTINEL, fm_stream  # noqa: F401  (fm_stream: the fixture)
 from voice_np import MUTE
 from webradio_amd import capi
 from webradio_amd.device import Resampler, VoiceBank
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SPECIAL = [np.inf, -np.inf, np.nan, 1e30, -1e30, -0.0, 1e-40, 65536.0]
-SENTINEL = np.array([0x7FC0BEEF], np.uint32).view(np.float32)[0]          # a NaN nobody computes: what the kernel leaves alone
 
 
-def _plan_values(prefix):
-    """every `#define <prefix>... <integer>` of wr_plan.h"""
-    text = open(os.path.join(ROOT, "webradio_amd", "csrc", "wr_plan.h")).read()
-    found = {name: int(value) for name, value in re.findall(r"^#define\s+(%s\w*)\s+(\d+)u?\b" % prefix, text, flags=re.M)}
-    assert found, "wr_plan.h defines no %s..." % prefix
-    return found
-
-
-CHUNKS = sorted(set(_plan_values("VOICE_CHUNK").values()))               # outputs a workgroup takes
-PERS = sorted(set(_plan_values("VOICE_PER").values()))                    # ... and a thread
+CHUNKS = [launch_plan.voice_plan().chunk]                                 # outputs a workgroup takes
+PERS = [launch_plan.voice_plan().per]                                     # ... and a thread
 
 
 def _taps(F, T, seed):
@@ -57,46 +46,13 @@ def _rows(nrows, n, seed):
     return rowcases.special_rows(nrows, n, seed, 7, SPECIAL)
 
 
-def _layout(nrows, n):
-    """(extra, lead): one row back to back; three rows an odd stride and a base one float off 16-byte alignment; 64 rows a
-    stride that is a multiple of four and larger than the row; 65 rows odd again"""
-    extra, lead = {1: (0, 0), 3: (5, 1), 64: (8 - n % 4, 0), 65: (7, 1)}.get(nrows, (3, 1))
-    if (n + extra) % 2 == 0 and nrows in (3, 65):
-        extra += 1
-    return extra, lead
-
-
-def _upload_rows(dev, v):
-    """the rows in device memory behind `lead` floats, `stride` floats apart, the gaps NaN: (pointer to free, pointer to
-    row 0, stride)"""
-    nrows, n = v.shape
-    extra, lead = _layout(nrows, n)
-    stride = n + extra
-    buf = np.full(lead + nrows * stride, np.float32(np.nan), np.float32)
-    for r in range(nrows):
-        buf[lead + r * stride: lead + r * stride + n] = v[r]
-    p = dev.upload(buf)
-    return p, p + 4 * lead, stride
-
-
 def _push(dev, bank, want, p_in, stride, nrows, pos, length, v, what):
     """one push of frames [pos, pos + length) of the first nrows rows, compared: every output bit, and nothing written
     beside the rows"""
-    extra, lead = _layout(nrows, max(length, 1))
-    ostride = length + extra
-    obuf = np.full(lead + nrows * ostride + 3, SENTINEL, np.float32)
-    p_out = dev.upload(obuf)
-    try:
-        bank.push_rows(p_in + 4 * pos, stride, nrows, length, p_out + 4 * lead, ostride)
-        got = dev.download(p_out, obuf.size)
-    finally:
-        dev.free(p_out)
+    _, check = rowcases.padded_push(dev, nrows, length, lambda p_out, ostride: bank.push_rows(p_in + 4 * pos, stride, nrows, length,
+                                                                                          p_out, ostride), what)
     ref = want.push(v[:nrows, pos: pos + length])
-    out = got[lead: lead + nrows * ostride].reshape(nrows, ostride)
-    bad = np.argwhere(out[:, :length].view(np.uint32) != ref.view(np.uint32))
-    assert bad.size == 0, (what, len(bad), bad[:4], [out[tuple(b)] for b in bad[:4]], [ref[tuple(b)] for b in bad[:4]])
-    gaps = np.concatenate([got[:lead], out[:, length:].reshape(-1), got[lead + nrows * ostride:]])
-    assert np.all(gaps.view(np.uint32) == SENTINEL.view(np.uint32)), what
+    check(ref)
     return ref
 
 
@@ -121,7 +77,7 @@ def test_rows_against_the_restatement(dev, T, nrows):
     want = voice_np.Bank(nrows, taps)
     want.set_rows(0, words)
     bank = VoiceBank(dev, nrows, taps)
-    p, p0, stride = _upload_rows(dev, v)
+    p, p0, stride = rowcases.upload_laid_out(dev, v)
     try:
         assert bank.info() == (T, F, 0) and not bank.get_rows().any()
         bank.set_rows(0, words)
@@ -153,7 +109,7 @@ def test_several_chunks_a_row_and_a_rest_of_twelve_taps(dev):
     want = voice_np.Bank(nrows, taps)
     want.set_rows(0, words)
     bank = VoiceBank(dev, nrows, taps)
-    p, p0, stride = _upload_rows(dev, v)
+    p, p0, stride = rowcases.upload_laid_out(dev, v)
     try:
         bank.set_rows(0, words)
         pos = 0
@@ -173,7 +129,7 @@ def test_reset_rows_left_out_and_controls(dev):
     taps = _taps(F, T, seed=5)
     v = _rows(nrows, n, seed=6)
     bank, want = VoiceBank(dev, nrows, taps), voice_np.Bank(nrows, taps)
-    p, p0, stride = _upload_rows(dev, v)
+    p, p0, stride = rowcases.upload_laid_out(dev, v)
     lib = dev.lib
 
     def words(first, w):
@@ -235,24 +191,10 @@ def test_reset_rows_left_out_and_controls(dev):
 OUT_RATE, RS_TAPS, VT = 750, 32, 64
 
 
-@pytest.fixture(scope="module")
-def fm_stream(dev):
-    """the twelve blocks in device memory, back to back; uploaded once"""
-    p = rowcases.fm_upload(dev)
-    yield p
-    rowcases.forget_twins()
-    dev.free(p)
-
-
 def _raw_push(dev, t, bank, stride, out=True):
     """wr_tuner_voice_push into a buffer of 64 rows of `stride` floats (out False: a NULL out_dev); (rc, slots, the rows)"""
-    p = dev.upload(np.full(64 * stride, SENTINEL, np.float32))
-    try:
-        slots = C.c_uint()
-        rc = dev.lib.wr_tuner_voice_push(t.h, bank.h, C.c_void_p(p) if out else None, stride, C.byref(slots))
-        got = dev.download(p, 64 * stride).reshape(64, stride)
-    finally:
-        dev.free(p)
+    slots = C.c_uint()
+    rc, got = rowcases.raw_tuner_push(dev, lambda p, s: dev.lib.wr_tuner_voice_push(t.h, bank.h, p, s, C.byref(slots)), stride, out)
     return rc, slots.value, got
 
 

@@ -385,3 +385,190 @@ def test_fft_work_area():
 def test_fft_columns_per_workgroup(n, cols, num_cus, ct):
     assert lp.fft_cols_ct(n, cols, num_cus) == ct
     assert 64 % ct == 0 and 2 * n * ct * 8 <= 128 * KIB
+
+
+# ==== the voice bank and the row kernels =====================================================================================
+
+def test_voice_plan():
+    # a workgroup is one wave of 64 threads, four outputs each: 256 outputs; one workgroup more per row for its history
+    assert lp.voice_plan(1) == (64, 4, 256, 8, 2048, 16, 4 + 256 + 2048, 1, 2)
+    assert lp.voice_plan(256)[-2:] == (1, 2)
+    assert lp.voice_plan(257)[-2:] == (2, 3)
+    assert [T for T in (4, 6, 8, 10, 12, 2044, 2046, 2048, 2052) if lp.lib().wr_plan_voice_len_ok(T)] == [8, 12, 2044, 2048]
+
+
+def test_agc_plan():
+    # 256 threads of 4 frames: tiles of 1024, four waves (the grid is a workgroup per row: no arithmetic)
+    assert lp.agc_plan() == (256, 4, 1024, 4)
+
+
+# ---- levels: groups of 256 rows; the work area is sums, peaks and muted counts [groups][cols] each, then the result [3][cols]
+@pytest.mark.parametrize("cols,k1,want", [
+    # one row: one group; 5 columns are one lane group, one workgroup of k_levels_sum; 3 * 5 + 3 * 5 floats
+    (5, 1, dict(groups=1, grid_y=1, sum_grid=1, psum=0, ppeak=5, pmuted=10, res=15, work_floats=30)),
+    # 256 rows are still one group; 64 columns still one lane group
+    (64, 256, dict(groups=1, grid_y=1, sum_grid=1, psum=0, ppeak=64, pmuted=128, res=192, work_floats=384)),
+    # 257 rows: a second group of one row; 300 columns: 5 lane groups, 2 workgroups of 256 for the sum; 3 * 600 + 900
+    (300, 257, dict(groups=2, grid_y=5, sum_grid=2, psum=0, ppeak=600, pmuted=1200, res=1800, work_floats=2700)),
+])
+def test_levels_plan(cols, k1, want):
+    p = lp.levels_plan(cols, k1)
+    assert (p.rows, p.threads, p.lds_squelch) == (256, 1024, 256 * 64 * 4)
+    assert {k: getattr(p, k) for k in want} == want
+
+
+# ---- the tone bank ----
+def test_tones_plan():
+    # a workgroup is 4 waves of 128 frames; the push is nq windows and nr frames
+    assert lp.tones_plan(1, 16) == (256, 512, 4096, 1, 0, 1)
+    assert lp.tones_plan(512, 16) == (256, 512, 4096, 1, 32, 0)
+    assert lp.tones_plan(513, 16) == (256, 512, 4096, 2, 32, 1)
+    assert lp.tones_plan(1 << 28, 65536) == (256, 512, 4096, 1 << 19, 4096, 0)
+
+
+# a row with `fill` frames in its open window takes n frames: ends = (fill + n) / W windows end, the last of them at frame
+# e = ends * W - fill of the push; A = [max(e - W, 0), e) counted from oa = e - W, B = [e, n) counted from e; no end: B is
+# the push, counted from -fill
+@pytest.mark.parametrize("fill,n,W,want", [
+    # fill + n < W: no end
+    (5, 10, 16, dict(a_lo=0, b_lo=0, oa=0, ob=-5, ends=0, fill_after=15)),
+    (65000, 500, 65536, dict(a_lo=0, b_lo=0, oa=0, ob=-65000, ends=0, fill_after=65500)),
+    # fill + n == W: e = 16 - 5 = 11 = n, the window began 5 frames before the push
+    (5, 11, 16, dict(a_lo=0, b_lo=11, oa=-5, ob=11, ends=1, fill_after=0)),
+    (0, 16, 16, dict(a_lo=0, b_lo=16, oa=0, ob=16, ends=1, fill_after=0)),
+    (65000, 536, 65536, dict(a_lo=0, b_lo=536, oa=-65000, ob=536, ends=1, fill_after=0)),
+    # one end, fill > 0: oa negative, a_lo = 0; 5 + 20 = 16 + 9
+    (5, 20, 16, dict(a_lo=0, b_lo=11, oa=-5, ob=11, ends=1, fill_after=9)),
+    (1, 65536, 65536, dict(a_lo=0, b_lo=65535, oa=-1, ob=65535, ends=1, fill_after=1)),
+    # several ends: 5 + 45 = 3 * 16 + 2, e = 48 - 5 = 43, the last whole window is [27, 43); the two before it only count
+    (5, 45, 16, dict(a_lo=27, b_lo=43, oa=27, ob=43, ends=3, fill_after=2)),
+    # 65535 + 131073 = 3 * 65536, e = 196608 - 65535 = 131073
+    (65535, 131073, 65536, dict(a_lo=65537, b_lo=131073, oa=65537, ob=131073, ends=3, fill_after=0)),
+    # the longest push: 100 + 2^28 = 4096 * 65536 + 100, e = 2^28 - 100
+    (100, 1 << 28, 65536, dict(a_lo=(1 << 28) - 100 - 65536, b_lo=(1 << 28) - 100, oa=(1 << 28) - 100 - 65536,
+                                ob=(1 << 28) - 100, ends=4096, fill_after=100)),
+])
+def test_tones_cut(fill, n, W, want):
+    assert lp.tones_cut(fill, n, W)._asdict() == want
+
+
+def test_tones_cut_counts_as_the_restatement_does():
+    """every fill < W and n < 3 W at W = 16: windows ended and the fill left are tests/tones_np.py's, and the stretches
+    lie inside the push in order"""
+    import numpy as np
+    import tones_np
+    W = 16
+    for fill in range(W):
+        for n in range(1, 3 * W):
+            bank = tones_np.Bank(1, [1 << 20], W)
+            bank.fill[0] = fill
+            bank.push(np.zeros((1, n), np.float32))
+            c = lp.tones_cut(fill, n, W)
+            assert (c.ends, c.fill_after) == (int(bank.windows[0]), int(bank.fill[0])), (fill, n)
+            assert 0 <= c.a_lo <= c.b_lo <= n and c.oa <= c.a_lo and c.ob <= c.b_lo, (fill, n)
+            assert c.a_lo - c.oa < W and n - c.ob <= W and (c.b_lo - c.oa == W if c.ends else c.b_lo == 0), (fill, n)
+
+
+# ---- the DCS bank: the clock is frames * step in units of 2^-29 chip; a launch may touch DC_SPAN = 256 chips ----
+@pytest.mark.parametrize("first_frame,step,nframes", [
+    (0, 1 << 19, 1 << 28),                  # 1024 frames a chip: 2^18 frames a launch, 1024 launches
+    (12345, 1 << 19, 300_000),
+    (0, 1 << 28, 100_000),                  # 2 frames a chip: 511 frames a launch from a chip's start
+    (7, 1 << 28, 100_000),                  # ... and 510 from its middle
+    ((1 << 46) + 3, 1 << 19, 1 << 20),      # first_frame * step = 2^65 + ...: beyond 64 bits
+    ((1 << 37) + 1, 1 << 28, 5_000),        # 2^65 + 2^28
+    ((1 << 40) + 11, (1 << 28) - 1, 50_000),
+    (3, 1 << 28, 1), (3, 1 << 19, 510),
+])
+def test_dcs_launches(first_frame, step, nframes):
+    span = lp.dcs_constants()["span"]
+    assert span == 256
+    runs = lp.dcs_launches(first_frame, step, nframes)
+    at = first_frame * step                                     # Python's integers do not wrap
+    for g0, ph0, n, room in runs:
+        assert (g0, ph0) == (at >> 29, at & ((1 << 29) - 1))
+        assert 1 <= n <= room and room >= 510
+        assert (ph0 + n * step) >> 29 < span                    # the chip of the frame behind the launch included
+        assert (ph0 + (room + 1) * step) >> 29 >= span          # ... and room is the most that keeps it so
+        at += n * step
+    assert sum(r.frames for r in runs) == nframes
+    assert all(r.frames == r.room for r in runs[:-1])           # only the last launch is short
+
+
+def test_dcs_least_room_is_510():
+    # step 2^28 and a launch that begins half a chip in: (256 * 2^29 - 1 - 2^28) / 2^28 = 511 - 1 / 2^28 -> 510
+    assert [r.room for r in lp.dcs_launches(1, 1 << 28, 2)] == [510]
+    assert [r.room for r in lp.dcs_launches(0, 1 << 28, 2)] == [511]
+    assert [r.room for r in lp.dcs_launches(0, 1 << 19, 2)] == [(1 << 18) - 1]
+    L = lp.lib()
+    assert [s for s in ((1 << 19) - 1, 1 << 19, 1 << 28, (1 << 28) + 1) if L.wr_plan_dcs_step_ok(s)] == [1 << 19, 1 << 28]
+
+
+# ---- the resampler ----
+RESAMP_SHAPES = [(1, 8, 64), (1024, 8192, 4), (1024, 128, 16), (3, 2, 4), (441, 500, 32)]
+
+
+def test_resamp_limits():
+    assert lp.resamp_constants() == dict(threads=256, span=2112, l_max=1024, ratio_max=8, p_min=4, p_max=64, taps_max=16384)
+    bad = lp.lib().wr_plan_resamp_limits_bad
+    assert not any(bad(*s) for s in RESAMP_SHAPES)
+    # L of 0 and above 1024, M above 8 L, L above 8 M, P of 0, above 64, no multiple of 4, L * P above 16384
+    assert all(bad(*s) for s in [(0, 1, 4), (1025, 1025, 4), (1, 9, 4), (9, 1, 4), (1, 1, 0), (1, 1, 68), (1, 1, 6),
+                                 (1024, 1024, 20), (1, 0, 4)])
+
+
+@pytest.mark.parametrize("L,M,P", RESAMP_SHAPES)
+def test_resamp_out_frames_over_cuts_of_a_stream(L, M, P):
+    """however a stream of N frames is cut into pushes, the pushes' output frames sum to ceil(N L / M), each as
+    tests/resamp_np.py has it"""
+    import numpy as np
+    import resamp_np
+    for cuts in ([1] * 40, [M - 1, 1, M, M + 1, 1], [7, 300, 1, 1, 5000, 13], [1 << 28, 1, (1 << 28) - 1]):
+        ref = resamp_np.Bank(1, L, M, np.zeros((L, P), np.float32))
+        nmod = total = 0
+        for n in cuts:
+            got = lp.resamp_out_frames(L, M, nmod, n)
+            assert got == ref.out_frames(n) == lp.resamp_plan(L, M, nmod, n).n_out
+            total += got
+            nmod = ref.nmod = (nmod + n) % M
+        N = sum(cuts)
+        assert total == -(-N * L // M)
+
+
+def _resamp_chunks_hold(L, M, P, nmod, n):
+    """the plan of a push against the closed form: output 256 i of the push is output j0 + 256 i since the clock was last
+    a multiple of M, at t = (j0 + 256 i) M: input frame t / L - nmod of the push, phase t mod L"""
+    p = lp.resamp_plan(L, M, nmod, n)
+    j0 = -(-nmod * L // M)
+    assert p.j0 == j0 and p.chunks == -(-p.n_out // 256) and p.grid_x == p.chunks + 1
+    worst = 0
+    for i in sorted({0, 1, p.chunks // 2, p.chunks - 1} & set(range(p.chunks))):
+        c = lp.resamp_chunk(L, M, P, nmod, n, i)
+        t = (j0 + 256 * i) * M
+        assert (c.i0, c.base, c.rem0, c.lo) == (256 * i, t // L - nmod, t % L, t // L - nmod - (P - 1)), (nmod, n, i)
+        assert c.cnt == min(256, p.n_out - 256 * i) >= 1
+        # the last output of the chunk reads up to frame (t + (cnt - 1) M) / L of the push, the first from P - 1 before base
+        assert c.span == (t + (c.cnt - 1) * M) // L - t // L + P
+        assert 0 <= c.base and c.lo + c.span <= n and c.span <= lp.resamp_constants()["span"]
+        worst = max(worst, c.span)
+    return worst
+
+
+@pytest.mark.parametrize("L,M,P", RESAMP_SHAPES[:4])
+def test_resamp_chunks(L, M, P):
+    worst = max(_resamp_chunks_hold(L, M, P, nmod, n) for nmod in sorted({0, 1, M // 2, M - 1} & set(range(M)))
+                for n in (1, M, 8 * 256 + 1, 100_000))
+    if (L, M, P) == (1, 8, 64):
+        assert worst == 2104                                    # (0 + 255 * 8) / 1 + 64: the longest span there is
+
+
+def test_resamp_chunks_at_every_clock():
+    for nmod in range(500):
+        _resamp_chunks_hold(441, 500, 32, nmod, 3000)
+
+
+def test_resamp_chunk_by_hand():
+    # 3 / 2, P = 4, the clock at 1, 1000 frames: j0 = ceil(3 / 2) = 2, ceil(1001 * 3 / 2) - 2 = 1500 outputs, 6 chunks;
+    # chunk 5: t = (2 + 1280) * 2 = 2564 = 3 * 854 + 2: frame 854 - 1 of the push, phase 2; 220 outputs; (2 + 219 * 2) / 3 + 4
+    assert lp.resamp_plan(3, 2, 1, 1000) == (1500, 2, 6, 7)
+    assert lp.resamp_chunk(3, 2, 4, 1, 1000, 5) == (1280, 853, 850, 2, 220, 150)

@@ -4,16 +4,15 @@ the stated conditions, and the restatement the GPU tests compare bits with (test
 rule written as plain loops (bit for bit, for any cut into pushes) and to an ideal sine delayed by the group delay."""
 import ctypes as C
 import math
-import os
 import re
 
 import numpy as np
 import pytest
 
+import capicases
 import resamp_np
 from webradio_amd import capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [("wr_resamp_ratio", 4), ("wr_resamp_design", 6), ("wr_resamp_create", 7), ("wr_resamp_destroy", 1),
          ("wr_resamp_reset", 2), ("wr_resamp_out_frames", 3), ("wr_resamp_push_rows", 8), ("wr_resamp_info", 6),
          ("wr_tuner_resamp_push", 6)]
@@ -22,27 +21,13 @@ DESIGNS = [(50_000, 48_000, 16), (50_000, 48_000, 32), (50_000, 48_000, 64), (32
 SPECIAL = [np.inf, -np.inf, np.nan, 1e30, -1e30, -0.0, 1e-40, 65536.0]
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "webradio_amd.h")).read()
-
-
-def _header_args(name):
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m, "%s is not declared" % name
-    return [a.strip() for a in m.group(1).split(",")]
-
-
 @pytest.mark.parametrize("name, nargs", NAMES)
 def test_declared_and_bound_with_the_same_arguments(name, nargs):
-    assert len(_header_args(name)) == nargs
-    restype, argtypes = capi.SIGNATURES[name]
-    assert len(argtypes) == nargs
-    assert getattr(capi.load(), name) is not None
+    capicases.declared_and_bound(name, nargs)
 
 
 def test_header_says_the_rule():
-    text = _header()
+    text = capicases.header()
     assert re.search(r"#define\s+WR_ABI_VERSION\s+6\b", text)
     assert re.search(r"Added to 6 later: wr_resamp_ratio, wr_resamp_design, wr_resamp_create, wr_resamp_destroy,\s+"
                      r"wr_resamp_reset, wr_resamp_out_frames, wr_resamp_push_rows,\s+wr_resamp_info, wr_tuner_resamp_push\.", text)
@@ -154,28 +139,13 @@ def test_ratio_refuses_a_rate_of_zero():
 
 # ---- the restatement against the rule as plain loops ---------------------------------------------------------------------------
 
-def _audio(n, seed):
-    """values from 1e-4 to beyond the clamp, both signs, and the non-finite, saturating, signed-zero and subnormal ones"""
-    rng = np.random.default_rng(seed)
-    v = (rng.standard_normal(n) * 10.0 ** rng.integers(-4, 7, n)).astype(np.float32)
-    where = rng.choice(n, size=2 * len(SPECIAL), replace=False)
-    for k, at in enumerate(where):
-        v[at] = np.float32(SPECIAL[k % len(SPECIAL)])
-    return v
-
-
-def _same_bits(a, b):
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 @pytest.mark.parametrize("in_rate, out_rate", [(32_000, 48_000), (50_000, 48_000), (1_000, 750), (50_000, 44_100)],
                          ids=["3/2", "24/25", "3/4", "441/500"])
 def test_the_restatement_is_the_loop(in_rate, out_rate):
     P = 32
     taps, L, M = resamp_np.design(in_rate, out_rate, P)
     n = 400
-    v = _audio(n, seed=L)
+    v = capicases.audio(n, L, SPECIAL, 7)
     bank, loop = resamp_np.Bank(1, L, M, taps), resamp_np.LoopBank(L, M, taps)
     pos, zero_seen = 0, False
 
@@ -185,7 +155,7 @@ def test_the_restatement_is_the_loop(in_rate, out_rate):
         y = bank.push(v[None, pos: pos + length])
         z = loop.push(v[pos: pos + length])
         pos += length
-        assert y.shape == (1, want_n) and _same_bits(y[0], z), (L, M, pos, length)
+        assert y.shape == (1, want_n) and capicases.same_bits(y[0], z), (L, M, pos, length)
         zero_seen = zero_seen or (want_n == 0)
 
     for length in (1, P - 2, P - 1):
@@ -207,22 +177,22 @@ def test_the_restatement_with_rough_taps_and_rows():
     rng = np.random.default_rng(9)
     taps = rng.uniform(-16, 16, (L, P)).astype(np.float32)
     taps[0, 0], taps[1, 3], taps[4, 7], taps[2, 2] = -0.0, 1e-40, -1e-42, 16.0
-    v = np.stack([_audio(120, seed=20 + r) for r in range(3)])
+    v = np.stack([capicases.audio(120, 20 + r, SPECIAL, 7) for r in range(3)])
     bank = resamp_np.Bank(3, L, M, taps)
     loops = [resamp_np.LoopBank(L, M, taps) for _ in range(3)]
     y = bank.push(v[:, :50])
     for r in range(3):
-        assert _same_bits(y[r], loops[r].push(v[r, :50]))
+        assert capicases.same_bits(y[r], loops[r].push(v[r, :50]))
     bank.reset(1)
     loops[1].reset_row()
     y = bank.push(v[:2, 50:53])                                           # row 2 is left out: it saw nothing
     loops[2].reset_row()
     loops[2].push(np.zeros(3, np.float32))
     for r in range(2):
-        assert _same_bits(y[r], loops[r].push(v[r, 50:53]))
+        assert capicases.same_bits(y[r], loops[r].push(v[r, 50:53]))
     y = bank.push(v[:, 53:])
     for r in range(3):
-        assert _same_bits(y[r], loops[r].push(v[r, 53:])), r
+        assert capicases.same_bits(y[r], loops[r].push(v[r, 53:])), r
     assert np.abs(y).max() <= 2.0 ** 26
 
 

@@ -4,11 +4,11 @@ honest, the float32 restatement of the rule agrees with it, the burst has its kn
 import ctypes as C
 import itertools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import launch_plan
 import specavg_np as sa
 import wr_oracle as oracle
 from flat_spectrum import MASK_OUT_SHARE, flat, interleaved
@@ -120,22 +120,8 @@ NS, FS, GS = (8, 8192, 65536, 1048576), (1, 259, 100_000), (1, 256, 65_535)
 
 
 @pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("spec_avg_plan") / "libspec_avg_plan.so")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-Wall", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "webradio_amd", "csrc"), os.path.join(ROOT, "tests", "cxx", "spec_avg_plan.cxx"),
-                           "-o", so])
-    lib = C.CDLL(so)
-    lib.spec_avg_cap_bytes.restype = SIZE
-    lib.spec_avg_plan.argtypes = [C.c_uint, SIZE, SIZE, C.POINTER(SIZE)]
-    lib.spec_avg_chunks.restype = SIZE
-    lib.spec_avg_chunks.argtypes = [C.c_uint, SIZE, SIZE, SIZE, C.POINTER(SIZE)]
-    lib.spec_avg_path.argtypes = [C.c_uint, C.c_uint]
-    lib.spec_avg_launches.restype = SIZE
-    lib.spec_avg_launches.argtypes = [C.c_uint, C.c_uint, SIZE, SIZE]
-    lib.spec_avg_reduce_grid.restype = C.c_uint
-    lib.spec_avg_reduce_grid.argtypes = [C.c_uint, SIZE]
-    return lib
+def plan():
+    return launch_plan.lib()
 
 
 def _plan(lib, n, F, G):

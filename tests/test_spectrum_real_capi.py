@@ -1,21 +1,16 @@
 """The C ABI of the spectrum of real samples (wr_spectrum_create_real, wr_spectrum_channels, wr_spectrum_batch_db_rows):
 declared, exported, bound, and refusing bad arguments.  No GPU needed (and none used)."""
 import ctypes as C
-import os
 import re
 
+import capicases
 from webradio_amd import capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("wr_spectrum_create_real", "wr_spectrum_channels", "wr_spectrum_batch_db_rows")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "webradio_amd.h")).read()
-
-
 def test_header_library_and_binding_have_the_new_functions():
-    code = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    code = re.sub(r"/\*.*?\*/", "", capicases.header(), flags=re.S)
     lib = capi.load()
     for name in NEW:
         assert re.search(r"\bint\s+%s\s*\(" % name, code), name
@@ -26,7 +21,7 @@ def test_header_library_and_binding_have_the_new_functions():
 
 def test_abi_version_is_still_6():
     assert capi.load().wr_abi_version() == capi.WR_ABI_VERSION == 6
-    assert re.search(r"#define\s+WR_ABI_VERSION\s+6\b", _header())
+    assert re.search(r"#define\s+WR_ABI_VERSION\s+6\b", capicases.header())
 
 
 def test_null_handles_are_refused_with_a_message():
@@ -42,4 +37,4 @@ def test_null_handles_are_refused_with_a_message():
 
 
 def test_header_cites_the_reference_s_fixmes():
-    assert "io/spectrumsink.cxx:62-64" in _header()
+    assert "io/spectrumsink.cxx:62-64" in capicases.header()

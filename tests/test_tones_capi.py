@@ -3,40 +3,28 @@ carries the rule, NULL handles are refused by name, wr_tone_step's numbers are n
 compare bits with (tests/tones_np.py) is held here first to the rule written as plain loops (bit for bit), to a float64 DFT
 at the exact phase (within a bound derived below), and to the detection conditions on audio from the oracle chain."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
+import capicases
 import tones_np
 from webradio_amd import CTCSS_HZ, capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [("wr_tone_step", 3), ("wr_tones_create", 6), ("wr_tones_destroy", 1), ("wr_tones_reset", 2),
          ("wr_tones_push_rows", 5), ("wr_tuner_tones_push", 3), ("wr_tones_read", 6)]
 WINDOWS = [16, 17, 500]
 SPECIAL = [np.inf, -np.inf, np.nan, 1e30, -1e30, -0.0, 1e-40, 64.0]
 
 
-def _header_args(name):
-    text = open(os.path.join(ROOT, "include", "webradio_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m, "%s is not declared" % name
-    return [a.strip() for a in m.group(1).split(",")]
-
-
 @pytest.mark.parametrize("name, nargs", NAMES)
 def test_declared_and_bound_with_the_same_arguments(name, nargs):
-    assert len(_header_args(name)) == nargs
-    restype, argtypes = capi.SIGNATURES[name]
-    assert len(argtypes) == nargs
-    assert getattr(capi.load(), name) is not None
+    capicases.declared_and_bound(name, nargs)
 
 
 def test_header_says_the_rule():
-    text = open(os.path.join(ROOT, "include", "webradio_amd.h")).read()
+    text = capicases.header()
     assert re.search(r"#define\s+WR_ABI_VERSION\s+6\b", text)
     assert re.search(r"Added to 6 later: wr_tone_step, wr_tones_create, wr_tones_destroy, wr_tones_reset,\s+"
                      r"wr_tones_push_rows, wr_tuner_tones_push, wr_tones_read\.", text)
@@ -97,17 +85,6 @@ def test_tone_step_refuses(hz, rate):
 
 # ---- the restatement against the rule as plain loops ---------------------------------------------------------------------------
 
-def _audio(n, seed, special=True):
-    """values from 1e-4 to beyond the clamp, both signs; with `special`, the non-finite and saturating values too"""
-    rng = np.random.default_rng(seed)
-    v = (rng.standard_normal(n) * 10.0 ** rng.integers(-4, 3, n)).astype(np.float32)
-    if special:
-        where = rng.choice(n, size=min(n, 2 * len(SPECIAL)), replace=False)
-        for k, at in enumerate(where):
-            v[at] = np.float32(SPECIAL[k % len(SPECIAL)])
-    return v
-
-
 def _loop_bank(v, steps, W):
     """the header's lines, one frame and one tone at a time; returns what wr_tones_read would: (iq, E, windows, fill)"""
     t12 = tones_np.table12()
@@ -139,7 +116,7 @@ def _loop_bank(v, steps, W):
 def test_the_restatement_is_the_loop(W):
     steps = [tones_np.step_of(67.0, 1000), tones_np.step_of(254.1, 1000), (1 << 31) - 1, 1]
     n = 3 * W + W // 3 + 1
-    v = _audio(n, seed=W)
+    v = capicases.audio(n, W, SPECIAL, 3)
     # checked after every push of an uneven cut: a push of one frame, several pushes per window, one that ends exactly on
     # a window end, one with two window ends and two frames behind them
     cuts = [1, W // 2, W, 3 * W + 2, n]
@@ -175,7 +152,7 @@ def test_against_a_float64_dft(W):
     angle and so in cos and sin (their slope is at most 1); the table's float32 entries and the float32 product add a few
     2^-24 relative to |w|, counted as 2^-22; each rint moves a term by at most half a unit, W / 2 in all, counted as W."""
     steps = np.array([tones_np.step_of(hz, 1000) for hz in (67.0, 100.0, 254.1, 499.9)], np.uint64)
-    v = _audio(W, seed=100 + W, special=False)
+    v = capicases.audio(W, 100 + W, None, 3)
     I, Q, _ = tones_np.sums(v, steps, 0)
     vc = tones_np.clean(v).astype(np.float64)
     j = np.arange(W, dtype=np.uint64)

@@ -4,17 +4,16 @@ conditions, and the restatement the GPU tests compare bits with (tests/voice_np.
 as plain loops (bit for bit, for any cut into pushes), to an ideal sine delayed by the group delay and to a unit-impulse
 filter."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
+import capicases
 import voice_np
 from resamp_np import clean
 from webradio_amd import capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [("wr_voice_design", 6), ("wr_voice_create", 6), ("wr_voice_destroy", 1), ("wr_voice_reset", 2), ("wr_voice_set_rows", 4),
          ("wr_voice_get_rows", 4), ("wr_voice_push_rows", 7), ("wr_tuner_voice_push", 5), ("wr_voice_info", 4)]
 # (audio_rate, T, highpass_hz, lowpass_hz, deemph_us)
@@ -24,29 +23,15 @@ SPECIAL = [np.inf, -np.inf, np.nan, 1e30, -1e30, -0.0, 1e-40, 65536.0]
 MUTE = voice_np.MUTE
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "webradio_amd.h")).read()
-
-
-def _header_args(name):
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m, "%s is not declared" % name
-    return [a.strip() for a in m.group(1).split(",")]
-
-
 # ---- 1: declared and bound ------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("name, nargs", NAMES)
 def test_declared_and_bound_with_the_same_arguments(name, nargs):
-    assert len(_header_args(name)) == nargs
-    restype, argtypes = capi.SIGNATURES[name]
-    assert len(argtypes) == nargs
-    assert getattr(capi.load(), name) is not None
+    capicases.declared_and_bound(name, nargs)
 
 
 def test_header_says_the_rule():
-    text = _header()
+    text = capicases.header()
     assert re.search(r"#define\s+WR_ABI_VERSION\s+6\b", text)
     assert re.search(r"Added to 6 later: wr_voice_design, wr_voice_create, wr_voice_destroy, wr_voice_reset,\s+"
                      r"wr_voice_set_rows, wr_voice_get_rows, wr_voice_push_rows,\s+wr_tuner_voice_push, wr_voice_info\.", text)
@@ -178,21 +163,6 @@ def test_design_edges_just_far_enough():
 
 # ---- 5: the restatement against the rule as plain loops -------------------------------------------------------------------------
 
-def _audio(n, seed):
-    """values from 1e-4 to beyond the clamp, both signs, and the non-finite, saturating, signed-zero and subnormal ones"""
-    rng = np.random.default_rng(seed)
-    v = (rng.standard_normal(n) * 10.0 ** rng.integers(-4, 7, n)).astype(np.float32)
-    where = rng.choice(n, size=2 * len(SPECIAL), replace=False)
-    for k, at in enumerate(where):
-        v[at] = np.float32(SPECIAL[k % len(SPECIAL)])
-    return v
-
-
-def _same_bits(a, b):
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def _rough_taps(F, T, seed):
     """random taps in +-16 with -0.0, subnormals and 16.0 among them"""
     taps = np.random.default_rng(seed).uniform(-16.0, 16.0, (F, T)).astype(np.float32)
@@ -207,7 +177,7 @@ def test_the_restatement_is_the_loop(T):
     row against its own loop; and the frames of a row that is not muted equal those of a twin bank that never was."""
     F, n = 3, 3 * T + 200
     taps = _rough_taps(F, T, seed=T)
-    v = np.stack([_audio(n, seed=10 * T + r) for r in range(3)])
+    v = np.stack([capicases.audio(n, 10 * T + r, SPECIAL, 7) for r in range(3)])
     bank, twin = voice_np.Bank(3, taps), voice_np.Bank(3, taps)
     loops = [voice_np.LoopBank(taps) for _ in range(3)]
     pos = 0
@@ -224,11 +194,11 @@ def test_the_restatement_is_the_loop(T):
         z = twin.push(v[:nrows, pos: pos + length])
         assert y.shape == (nrows, length)
         for r in range(nrows):
-            assert _same_bits(y[r], loops[r].push(v[r, pos: pos + length])), (T, r, pos, length)
+            assert capicases.same_bits(y[r], loops[r].push(v[r, pos: pos + length])), (T, r, pos, length)
             if bank.ctl[r] & MUTE:
                 assert not y[r].view(np.uint32).any()                     # +0.0f, every frame
             else:
-                assert _same_bits(y[r], z[r]), (T, r, pos, length)
+                assert capicases.same_bits(y[r], z[r]), (T, r, pos, length)
         for r in range(nrows, 3):                                         # a row left out saw nothing
             loops[r].reset_row()
         pos += length
@@ -288,10 +258,10 @@ def test_a_unit_impulse_filter_delays(T):
     d = T // 2 - 1
     taps = np.zeros(T, np.float32)
     taps[d] = 1.0
-    x = _audio(2 * T + 50, seed=T)
+    x = capicases.audio(2 * T + 50, T, SPECIAL, 7)
     assert np.signbit(x[x == 0]).any()
     bank = voice_np.Bank(1, taps)
     y = np.concatenate([bank.push(x[None, :T - 3])[0], bank.push(x[None, T - 3:])[0]])
     want = np.concatenate([np.zeros(d, np.float32), clean(x)[: x.size - d]])
     want = np.where(want == 0, np.float32(0.0), want)                     # -0.0 -> +0.0
-    assert _same_bits(y, want)
+    assert capicases.same_bits(y, want)

@@ -22,10 +22,7 @@
  */
 #include "wr_internal.h"
 
-#define AGC_THREADS 256u
-#define AGC_PER     4u                          /* consecutive frames of a thread */
-#define AGC_TILE    (AGC_THREADS * AGC_PER)
-#define AGC_WAVES   (AGC_THREADS / WR_LANES)
+/* (AGC_* are wr_plan.h's; the grid is the rows) */
 
 __device__ __forceinline__ unsigned long long agc_max(unsigned long long a, unsigned long long b)
 {

@@ -82,6 +82,14 @@ static int bank_take_submit(const WrRowBank *b, const char *who, const char *nou
 	return WR_OK;
 }
 
+/* ... its middle, behind the bank's own refusals: the submit's audio is there and no streaming launch is open on the device ... */
+static int bank_submit_ready(wr_tuner *t, WrLastSubmit *v)
+{
+	if (int rc = wrc_last_submit_flush(t, v))
+		return rc;
+	return wrc_dev_settle_stream(t->dev);
+}
+
 /* ... and its last, once the push has gone out */
 static int bank_took_submit(WrRowBank *b, const wr_tuner *t, const WrLastSubmit &v, unsigned int *slots)
 {
@@ -90,6 +98,120 @@ static int bank_took_submit(WrRowBank *b, const wr_tuner *t, const WrLastSubmit 
 	if (slots)
 		*slots = v.used;
 	return WR_OK;
+}
+
+/* a destroy's first steps; false: there is no bank */
+static bool bank_destroy_begin(const WrRowBank *b)
+{
+	if (!b)
+		return false;
+	(void)hipSetDevice(b->dev->device);
+	(void)wrc_dev_stream_sync(b->dev);
+	return true;
+}
+
+/* a read's first steps (`any`: the caller gave an array to fill) ... */
+static int bank_read_begin(const WrRowBank *b, const char *who, bool any)
+{
+	if (!b)
+		return wrc_fail(WR_ERR_ARG, "%s: bank is NULL", who);
+	if (!any)
+		return wrc_fail(WR_ERR_ARG, "%s: no array to fill", who);
+	return bank_dev_ready(b->dev, false);
+}
+
+/* ... one member of every row (`width` bytes at `offset` of rows `pitch` bytes apart) into the caller's array, if there is one ... */
+static hipError_t bank_read_column(const WrRowBank *b, void *host, const void *rows, size_t pitch, size_t offset, size_t width)
+{
+	if (!host)
+		return hipSuccess;
+	return hipMemcpy2DAsync(host, width, (const char *)rows + offset, pitch, width, b->max_rows, hipMemcpyDeviceToHost, b->dev->stream);
+}
+
+/* ... and its last */
+static int bank_read_end(const WrRowBank *b, unsigned int *rows)
+{
+	HIP_TRY(wrc_dev_stream_sync(b->dev));
+	if (rows)
+		*rows = b->max_rows;
+	return WR_OK;
+}
+
+/* a filter table [nsets][len] as a create takes it: every tap finite and 16 at most in magnitude */
+static int bank_taps_refused(const char *who, const float *taps_host, size_t nsets, size_t len)
+{
+	for (size_t i = 0; i < nsets * len; ++i) {
+		uint32_t bits;
+		memcpy(&bits, taps_host + i, sizeof(bits));
+		if ((bits & 0x7fffffffu) >= 0x7f800000u || !(fabsf(taps_host[i]) <= 16.0f))
+			return wrc_fail(WR_ERR_ARG, "%s: tap [%zu][%zu] = %g is not finite or above 16 in magnitude", who, i / len, i % len,
+			                (double)taps_host[i]);
+	}
+	return WR_OK;
+}
+
+/* what a push that writes rows of `n_out` frames refuses of its output: none, rows that overlap, rows that overlap the input */
+static int bank_out_refused(const char *who, const float *in_dev, size_t row_stride, size_t nrows, size_t nframes,
+                            const float *out_dev, size_t out_stride, size_t n_out)
+{
+	if (!nrows || !n_out)
+		return WR_OK;
+	if (!out_dev || (nrows > 1 && out_stride < n_out))
+		return wrc_fail(WR_ERR_ARG, "%s: out_dev is NULL, or rows of %zu output frames overlap at a stride of %zu", who, n_out, out_stride);
+	const uintptr_t a0 = (uintptr_t)in_dev, a1 = a0 + ((nrows - 1u) * row_stride + nframes) * sizeof(float);
+	const uintptr_t b0 = (uintptr_t)out_dev, b1 = b0 + ((nrows - 1u) * out_stride + n_out) * sizeof(float);
+	if (a0 < b1 && b0 < a1)
+		return wrc_fail(WR_ERR_ARG, "%s: input and output overlap", who);
+	return WR_OK;
+}
+
+/* ---- the two history sets of the resampler and the voice bank (WrHistSets) ---- */
+
+/* both sets for `rows` rows of `H` frames, silent */
+static hipError_t hist_alloc(WrHistSets *h, size_t rows, size_t H, hipStream_t st)
+{
+	hipError_t e = hipSuccess;
+	h->H = H;
+	for (unsigned int s = 0; s < 2u && e == hipSuccess; ++s) {
+		e = hipMalloc((void **)&h->set[s], rows * H * sizeof(float));
+		if (e == hipSuccess)
+			e = hipMemsetAsync(h->set[s], 0, rows * H * sizeof(float), st);
+	}
+	return e;
+}
+
+static void hist_free(WrHistSets *h)
+{
+	(void)hipFree(h->set[0]);
+	(void)hipFree(h->set[1]);
+}
+
+/* rows [first, first + n) begin their streams (`all`: they are all of the bank's).  Only the set the next push reads
+ * matters: that push writes the other one */
+static hipError_t hist_reset(WrHistSets *h, size_t first, size_t n, bool all, hipStream_t st)
+{
+	const hipError_t e = hipMemsetAsync(h->set[h->cur] + first * h->H, 0, n * h->H * sizeof(float), st);
+	if (e == hipSuccess && all)
+		h->zero_from[h->cur] = 0;
+	return e;
+}
+
+/* a push of `nrows` rows reads *from and writes *to, where the rows it leaves out lose their histories */
+static hipError_t hist_push_begin(WrHistSets *h, size_t nrows, hipStream_t st, const float **from, float **to)
+{
+	const unsigned int w = h->cur ^ 1u;
+	*from = h->set[h->cur];
+	*to = h->set[w];
+	if (nrows >= h->zero_from[w])
+		return hipSuccess;
+	return hipMemsetAsync(h->set[w] + nrows * h->H, 0, (h->zero_from[w] - nrows) * h->H * sizeof(float), st);
+}
+
+/* ... and once it has gone out the sets change places */
+static void hist_push_end(WrHistSets *h, size_t nrows)
+{
+	h->cur ^= 1u;
+	h->zero_from[h->cur] = (unsigned int)nrows;
 }
 
 /* ------------------------------------------------------------------ tone bank -- */
@@ -108,7 +230,7 @@ extern "C" int wr_tones_create(wr_tones **bank, wr_dev *d, unsigned int max_rows
 {
 	if (!bank || !d || !steps_host)
 		return wrc_fail(WR_ERR_ARG, "wr_tones_create: bad argument (NULL bank, dev or steps_host)");
-	if (!max_rows || max_rows > 65535u || !ntones || ntones > WR_LANES || window < 16u || window > 65536u)
+	if (!max_rows || max_rows > 65535u || !ntones || ntones > WR_LANES || window < TN_WINDOW_MIN || window > TN_WINDOW_MAX)
 		return wrc_fail(WR_ERR_ARG, "wr_tones_create: %u rows (1 .. 65535), %u tones (1 .. 64), a window of %u frames "
 		                "(16 .. 65536)", max_rows, ntones, window);
 	unsigned int steps[WR_LANES] = {0};
@@ -117,10 +239,10 @@ extern "C" int wr_tones_create(wr_tones **bank, wr_dev *d, unsigned int max_rows
 			return wrc_fail(WR_ERR_ARG, "wr_tones_create: tone %u: a step of %u is not inside (0, 2^31)", t, steps_host[t]);
 		steps[t] = steps_host[t];
 	}
-	std::vector<float> table(WR_TABLE_SIZE), t12(4096);
+	std::vector<float> table(WR_TABLE_SIZE), t12(TN_TABLE);
 	wrd_sin_table(table.data());
-	for (unsigned int i = 0; i < 4096u; ++i)
-		t12[i] = table[16u * i];
+	for (unsigned int i = 0; i < TN_TABLE; ++i)
+		t12[i] = table[WR_TABLE_SIZE / TN_TABLE * i];
 	wr_tones *b;
 	if (int rc = bank_new(&b, "wr_tones_create", d, max_rows))
 		return rc;
@@ -142,10 +264,8 @@ extern "C" int wr_tones_create(wr_tones **bank, wr_dev *d, unsigned int max_rows
 
 extern "C" int wr_tones_destroy(wr_tones *b)
 {
-	if (!b)
+	if (!bank_destroy_begin(b))
 		return WR_OK;
-	(void)hipSetDevice(b->dev->device);
-	(void)wrc_dev_stream_sync(b->dev);
 	(void)hipFree(b->rows);
 	(void)hipFree(b->t12);
 	(void)hipFree(b->steps);
@@ -188,45 +308,25 @@ extern "C" int wr_tuner_tones_push(wr_tuner *t, wr_tones *bank, unsigned int *sl
 	WrLastSubmit v;
 	if (int rc = bank_take_submit(bank, "wr_tuner_tones_push", "bank", t, &v))
 		return rc;
-	if (int rc = wrc_last_submit_flush(t, &v))
+	if (int rc = bank_submit_ready(t, &v))
 		return rc;
-	DEV_SETTLE(t->dev);
 	const Group *g = v.g;
-	if (v.used && g->last_k2)
-		HIP_TRY(wrk_tones_push(t->dev->stream, g->dev.audio, g->k2max, v.used, g->last_k2, bank->rows, bank->t12, bank->steps,
-		                       bank->ntones, bank->window));
+	HIP_TRY(wrk_tones_push(t->dev->stream, g->dev.audio, g->k2max, v.used, g->last_k2, bank->rows, bank->t12, bank->steps,
+	                       bank->ntones, bank->window));
 	return bank_took_submit(bank, t, v, slots);
 }
 
 extern "C" int wr_tones_read(wr_tones *b, long long *iq_host, long long *energy_host, unsigned long long *windows_host,
                              unsigned int *fill_host, unsigned int *rows)
 {
-	if (!b)
-		return wrc_fail(WR_ERR_ARG, "wr_tones_read: bank is NULL");
-	if (!iq_host && !energy_host && !windows_host && !fill_host)
-		return wrc_fail(WR_ERR_ARG, "wr_tones_read: no array to fill");
-	wr_dev *d = b->dev;
-	if (int rc = bank_dev_ready(d, false))
+	if (int rc = bank_read_begin(b, "wr_tones_read", iq_host || energy_host || windows_host || fill_host))
 		return rc;
-	const char *base = (const char *)b->rows;
-	const size_t pitch = sizeof(WrTonesRow), n = b->max_rows;
-	if (iq_host) {
-		const size_t width = (size_t)b->ntones * 2u * sizeof(long long);
-		HIP_TRY(hipMemcpy2DAsync(iq_host, width, base + offsetof(WrTonesRow, lat), pitch, width, n, hipMemcpyDeviceToHost, d->stream));
-	}
-	if (energy_host)
-		HIP_TRY(hipMemcpy2DAsync(energy_host, sizeof(long long), base + offsetof(WrTonesRow, lat_e), pitch, sizeof(long long), n,
-		                         hipMemcpyDeviceToHost, d->stream));
-	if (windows_host)
-		HIP_TRY(hipMemcpy2DAsync(windows_host, sizeof(unsigned long long), base + offsetof(WrTonesRow, windows), pitch,
-		                         sizeof(unsigned long long), n, hipMemcpyDeviceToHost, d->stream));
-	if (fill_host)
-		HIP_TRY(hipMemcpy2DAsync(fill_host, sizeof(unsigned int), base + offsetof(WrTonesRow, fill), pitch, sizeof(unsigned int), n,
-		                         hipMemcpyDeviceToHost, d->stream));
-	HIP_TRY(wrc_dev_stream_sync(d));
-	if (rows)
-		*rows = b->max_rows;
-	return WR_OK;
+	const size_t pitch = sizeof(WrTonesRow);
+	HIP_TRY(bank_read_column(b, iq_host, b->rows, pitch, offsetof(WrTonesRow, lat), (size_t)b->ntones * 2u * sizeof(long long)));
+	HIP_TRY(bank_read_column(b, energy_host, b->rows, pitch, offsetof(WrTonesRow, lat_e), sizeof(long long)));
+	HIP_TRY(bank_read_column(b, windows_host, b->rows, pitch, offsetof(WrTonesRow, windows), sizeof(unsigned long long)));
+	HIP_TRY(bank_read_column(b, fill_host, b->rows, pitch, offsetof(WrTonesRow, fill), sizeof(unsigned int)));
+	return bank_read_end(b, rows);
 }
 
 /* ------------------------------------------------------------------ DCS bank -- */
@@ -246,18 +346,13 @@ extern "C" int wr_dcs_word(unsigned int code, unsigned int *word)
 	return WR_OK;
 }
 
-static bool dcs_step_ok(unsigned long long step)
-{
-	return step >= (1ull << 19) && step <= (1ull << 28);
-}
-
 extern "C" int wr_dcs_step(unsigned int audio_rate, unsigned int *step)
 {
 	if (!step)
 		return wrc_fail(WR_ERR_ARG, "wr_dcs_step: step is NULL");
 	const unsigned long long den = 5ull * audio_rate;
 	const unsigned long long s = den ? ((672ull << 32) + den / 2u) / den : 0;
-	if (!dcs_step_ok(s))
+	if (!wrp_dcs_step_ok(s))
 		return wrc_fail(WR_ERR_ARG, "wr_dcs_step: at %u Hz a chip (an eighth of a bit at 134.4 bit/s) is not 2 .. 1024 frames: the "
 		                "step would be %llu, outside 2^19 .. 2^28", audio_rate, s);
 	*step = (unsigned int)s;
@@ -269,7 +364,7 @@ extern "C" int wr_dcs_create(wr_dcs **bank, wr_dev *d, unsigned int max_rows, co
 {
 	if (!bank || !words_host)
 		return wrc_fail(WR_ERR_ARG, "wr_dcs_create: bad argument (NULL bank or words_host)");
-	if (!max_rows || max_rows > 65535u || !ncodes || ncodes > WR_DCS_CODES || !dcs_step_ok(step) || max_errors > 3u)
+	if (!max_rows || max_rows > 65535u || !ncodes || ncodes > WR_DCS_CODES || !wrp_dcs_step_ok(step) || max_errors > 3u)
 		return wrc_fail(WR_ERR_ARG, "wr_dcs_create: %u rows (1 .. 65535), %u codes (1 .. 128), a step of %u (2^19 .. 2^28), "
 		                "max_errors %u (0 .. 3)", max_rows, ncodes, step, max_errors);
 	for (unsigned int k = 0; k < ncodes; ++k)
@@ -295,10 +390,8 @@ extern "C" int wr_dcs_create(wr_dcs **bank, wr_dev *d, unsigned int max_rows, co
 
 extern "C" int wr_dcs_destroy(wr_dcs *b)
 {
-	if (!b)
+	if (!bank_destroy_begin(b))
 		return WR_OK;
-	(void)hipSetDevice(b->dev->device);
-	(void)wrc_dev_stream_sync(b->dev);
 	(void)hipFree(b->rows);
 	(void)hipFree(b->words);
 	delete b;
@@ -374,9 +467,8 @@ extern "C" int wr_tuner_dcs_push(wr_tuner *t, wr_dcs *bank, unsigned int *slots)
 	WrLastSubmit v;
 	if (int rc = bank_take_submit(bank, "wr_tuner_dcs_push", "bank", t, &v))
 		return rc;
-	if (int rc = wrc_last_submit_flush(t, &v))
+	if (int rc = bank_submit_ready(t, &v))
 		return rc;
-	DEV_SETTLE(t->dev);
 	const Group *g = v.g;
 	if (int rc = dcs_push(bank, g->dev.audio, g->k2max, v.used, g->last_k2))
 		return rc;
@@ -386,31 +478,14 @@ extern "C" int wr_tuner_dcs_push(wr_tuner *t, wr_dcs *bank, unsigned int *slots)
 extern "C" int wr_dcs_read(wr_dcs *b, unsigned char *agree_host, unsigned int *run_host, unsigned long long *hits_host,
                            unsigned long long *evals_host, unsigned int *rows)
 {
-	if (!b)
-		return wrc_fail(WR_ERR_ARG, "wr_dcs_read: bank is NULL");
-	if (!agree_host && !run_host && !hits_host && !evals_host)
-		return wrc_fail(WR_ERR_ARG, "wr_dcs_read: no array to fill");
-	wr_dev *d = b->dev;
-	if (int rc = bank_dev_ready(d, false))
+	if (int rc = bank_read_begin(b, "wr_dcs_read", agree_host || run_host || hits_host || evals_host))
 		return rc;
-	const char *base = (const char *)b->rows;
-	const size_t pitch = sizeof(WrDcsRow), n = b->max_rows, pairs = (size_t)b->ncodes * 2u;
-	if (agree_host)
-		HIP_TRY(hipMemcpy2DAsync(agree_host, pairs, base + offsetof(WrDcsRow, agree), pitch, pairs, n, hipMemcpyDeviceToHost,
-		                         d->stream));
-	if (run_host)
-		HIP_TRY(hipMemcpy2DAsync(run_host, pairs * sizeof(unsigned int), base + offsetof(WrDcsRow, run), pitch,
-		                         pairs * sizeof(unsigned int), n, hipMemcpyDeviceToHost, d->stream));
-	if (hits_host)
-		HIP_TRY(hipMemcpy2DAsync(hits_host, pairs * sizeof(unsigned long long), base + offsetof(WrDcsRow, hits), pitch,
-		                         pairs * sizeof(unsigned long long), n, hipMemcpyDeviceToHost, d->stream));
-	if (evals_host)
-		HIP_TRY(hipMemcpy2DAsync(evals_host, sizeof(unsigned long long), base + offsetof(WrDcsRow, evals), pitch,
-		                         sizeof(unsigned long long), n, hipMemcpyDeviceToHost, d->stream));
-	HIP_TRY(wrc_dev_stream_sync(d));
-	if (rows)
-		*rows = b->max_rows;
-	return WR_OK;
+	const size_t pitch = sizeof(WrDcsRow), pairs = (size_t)b->ncodes * 2u;
+	HIP_TRY(bank_read_column(b, agree_host, b->rows, pitch, offsetof(WrDcsRow, agree), pairs));
+	HIP_TRY(bank_read_column(b, run_host, b->rows, pitch, offsetof(WrDcsRow, run), pairs * sizeof(unsigned int)));
+	HIP_TRY(bank_read_column(b, hits_host, b->rows, pitch, offsetof(WrDcsRow, hits), pairs * sizeof(unsigned long long)));
+	HIP_TRY(bank_read_column(b, evals_host, b->rows, pitch, offsetof(WrDcsRow, evals), sizeof(unsigned long long)));
+	return bank_read_end(b, rows);
 }
 
 extern "C" int wr_dcs_info(wr_dcs *b, unsigned int *ncodes, unsigned int *step, unsigned int *max_errors, unsigned long long *frames)
@@ -462,14 +537,9 @@ extern "C" int wr_resamp_create(wr_resamp **rs, wr_dev *d, unsigned int max_rows
 	if (!max_rows || max_rows > 65535u || wrd_resamp_limits(L, M, P))
 		return wrc_fail(WR_ERR_ARG, "wr_resamp_create: %u rows (1 .. 65535), L / M = %u / %u (1 <= L <= 1024, M <= 8 L, L <= 8 M), "
 		                "%u taps per phase (a multiple of 4 in 4 .. 64, L * P <= 16384)", max_rows, L, M, P);
-	const size_t ntaps = (size_t)L * P, nhist = (size_t)max_rows * (P - 1u);
-	for (size_t i = 0; i < ntaps; ++i) {
-		uint32_t bits;
-		memcpy(&bits, taps_host + i, sizeof(bits));
-		if ((bits & 0x7fffffffu) >= 0x7f800000u || !(fabsf(taps_host[i]) <= 16.0f))
-			return wrc_fail(WR_ERR_ARG, "wr_resamp_create: tap [%zu][%zu] = %g is not finite or above 16 in magnitude", i / P, i % P,
-			                (double)taps_host[i]);
-	}
+	const size_t ntaps = (size_t)L * P;
+	if (int rc = bank_taps_refused("wr_resamp_create", taps_host, L, P))
+		return rc;
 	wr_resamp *r;
 	if (int rc = bank_new(&r, "wr_resamp_create", d, max_rows))
 		return rc;
@@ -477,11 +547,8 @@ extern "C" int wr_resamp_create(wr_resamp **rs, wr_dev *d, unsigned int max_rows
 	r->M = M;
 	r->P = P;
 	hipError_t e = hipMalloc((void **)&r->taps, ntaps * sizeof(float));
-	for (unsigned int s = 0; s < 2u && e == hipSuccess; ++s) {
-		e = hipMalloc((void **)&r->hist[s], nhist * sizeof(float));
-		if (e == hipSuccess)
-			e = hipMemsetAsync(r->hist[s], 0, nhist * sizeof(float), d->stream);
-	}
+	if (e == hipSuccess)
+		e = hist_alloc(&r->hist, max_rows, P - 1u, d->stream);
 	if (e == hipSuccess)
 		e = hipMemcpyAsync(r->taps, taps_host, ntaps * sizeof(float), hipMemcpyHostToDevice, d->stream);
 	return bank_created(rs, r, e, "wr_resamp_create", wr_resamp_destroy);
@@ -489,13 +556,10 @@ extern "C" int wr_resamp_create(wr_resamp **rs, wr_dev *d, unsigned int max_rows
 
 extern "C" int wr_resamp_destroy(wr_resamp *r)
 {
-	if (!r)
+	if (!bank_destroy_begin(r))
 		return WR_OK;
-	(void)hipSetDevice(r->dev->device);
-	(void)wrc_dev_stream_sync(r->dev);
 	(void)hipFree(r->taps);
-	(void)hipFree(r->hist[0]);
-	(void)hipFree(r->hist[1]);
+	hist_free(&r->hist);
 	delete r;
 	return WR_OK;
 }
@@ -507,11 +571,8 @@ extern "C" int wr_resamp_reset(wr_resamp *r, int row)
 	size_t first, n;
 	if (int rc = bank_reset_begin(r, "wr_resamp_reset", row, &first, &n))
 		return rc;
-	/* only the set the next push reads matters: that push writes the other one */
-	const size_t H = r->P - 1u;
-	HIP_TRY(hipMemsetAsync(r->hist[r->cur] + first * H, 0, n * H * sizeof(float), r->dev->stream));
+	HIP_TRY(hist_reset(&r->hist, first, n, row < 0, r->dev->stream));
 	if (row < 0) {                                              /* all rows: the clock and the counts start again too */
-		r->zero_from[r->cur] = 0;
 		r->nmod = 0;
 		r->frames_in = r->frames_out = 0;
 	}
@@ -532,17 +593,8 @@ static int resamp_check(const wr_resamp *r, const char *who, const float *in_dev
 {
 	if (int rc = bank_rows_refused(r, who, row_stride, nrows, nframes, 28))
 		return rc;
-	const size_t n = (size_t)wrk_resamp_out_frames(r->L, r->M, r->nmod, nframes);
-	*n_out = n;
-	if (!nrows || !n)
-		return WR_OK;
-	if (!out_dev || (nrows > 1 && out_stride < n))
-		return wrc_fail(WR_ERR_ARG, "%s: out_dev is NULL, or rows of %zu output frames overlap at a stride of %zu", who, n, out_stride);
-	const uintptr_t a0 = (uintptr_t)in_dev, a1 = a0 + ((nrows - 1u) * row_stride + nframes) * sizeof(float);
-	const uintptr_t b0 = (uintptr_t)out_dev, b1 = b0 + ((nrows - 1u) * out_stride + n) * sizeof(float);
-	if (a0 < b1 && b0 < a1)
-		return wrc_fail(WR_ERR_ARG, "%s: input and output overlap", who);
-	return WR_OK;
+	*n_out = (size_t)wrk_resamp_out_frames(r->L, r->M, r->nmod, nframes);
+	return bank_out_refused(who, in_dev, row_stride, nrows, nframes, out_dev, out_stride, *n_out);
 }
 
 /* the push itself, behind resamp_check, on a device made ready: the rows it leaves out lose their histories, the clock and
@@ -553,14 +605,10 @@ static int resamp_push(wr_resamp *r, const float *in_dev, size_t row_stride, siz
 	if (!nframes)
 		return WR_OK;
 	wr_dev *d = r->dev;
-	const unsigned int from = r->cur, to = from ^ 1u;
-	const size_t H = r->P - 1u;
-	if (nrows < r->zero_from[to])
-		HIP_TRY(hipMemsetAsync(r->hist[to] + nrows * H, 0, (r->zero_from[to] - nrows) * H * sizeof(float), d->stream));
-	const WrResampPush p = {r->taps, r->L, r->M, r->P, r->nmod, r->hist[from], r->hist[to]};
+	WrResampPush p = {r->taps, r->L, r->M, r->P, r->nmod, nullptr, nullptr};
+	HIP_TRY(hist_push_begin(&r->hist, nrows, d->stream, &p.hist_old, &p.hist_new));
 	HIP_TRY(wrk_resamp_push(d->stream, in_dev, row_stride, nrows, nframes, p, out_dev, out_stride));
-	r->zero_from[to] = (unsigned int)nrows;
-	r->cur = to;
+	hist_push_end(&r->hist, nrows);
 	r->frames_in += nframes;
 	r->frames_out += wrk_resamp_out_frames(r->L, r->M, r->nmod, nframes);
 	r->nmod = (unsigned int)((r->nmod + nframes) % r->M);
@@ -593,9 +641,8 @@ extern "C" int wr_tuner_resamp_push(wr_tuner *t, wr_resamp *rs, float *out_dev, 
 	const Group *g = v.g;
 	if (int rc = resamp_check(rs, "wr_tuner_resamp_push", g->dev.audio, g->k2max, v.used, g->last_k2, out_dev, out_stride, n_out))
 		return rc;
-	if (int rc = wrc_last_submit_flush(t, &v))
+	if (int rc = bank_submit_ready(t, &v))
 		return rc;
-	DEV_SETTLE(t->dev);
 	if (int rc = resamp_push(rs, g->dev.audio, g->k2max, v.used, g->last_k2, out_dev, out_stride))
 		return rc;
 	return bank_took_submit(rs, t, v, slots);
@@ -641,14 +688,9 @@ extern "C" int wr_voice_create(wr_voice **bank, wr_dev *d, unsigned int max_rows
 	if (!max_rows || max_rows > 65535u || !wrp_voice_len_ok(T) || !nfilt || nfilt > VOICE_FILTERS)
 		return wrc_fail(WR_ERR_ARG, "wr_voice_create: %u rows (1 .. 65535), %u taps (a multiple of 4 in 8 .. 2048), %u filters "
 		                "(1 .. 16)", max_rows, T, nfilt);
-	const size_t ntaps = (size_t)nfilt * T, nhist = (size_t)max_rows * (T - 1u);
-	for (size_t i = 0; i < ntaps; ++i) {
-		uint32_t bits;
-		memcpy(&bits, taps_host + i, sizeof(bits));
-		if ((bits & 0x7fffffffu) >= 0x7f800000u || !(fabsf(taps_host[i]) <= 16.0f))
-			return wrc_fail(WR_ERR_ARG, "wr_voice_create: tap [%zu][%zu] = %g is not finite or above 16 in magnitude", i / T, i % T,
-			                (double)taps_host[i]);
-	}
+	const size_t ntaps = (size_t)nfilt * T;
+	if (int rc = bank_taps_refused("wr_voice_create", taps_host, nfilt, T))
+		return rc;
 	if (!d)                                                     /* (behind the limits: those are refused without a device too) */
 		return wrc_fail(WR_ERR_ARG, "wr_voice_create: bad argument (NULL dev)");
 	wr_voice *b;
@@ -662,11 +704,8 @@ extern "C" int wr_voice_create(wr_voice **bank, wr_dev *d, unsigned int max_rows
 		e = hipMalloc((void **)&b->ctl, (size_t)max_rows * sizeof(unsigned int));
 	if (e == hipSuccess)
 		e = hipMemsetAsync(b->ctl, 0, (size_t)max_rows * sizeof(unsigned int), d->stream);
-	for (unsigned int s = 0; s < 2u && e == hipSuccess; ++s) {
-		e = hipMalloc((void **)&b->hist[s], nhist * sizeof(float));
-		if (e == hipSuccess)
-			e = hipMemsetAsync(b->hist[s], 0, nhist * sizeof(float), d->stream);
-	}
+	if (e == hipSuccess)
+		e = hist_alloc(&b->hist, max_rows, T - 1u, d->stream);
 	if (e == hipSuccess)
 		e = hipMemcpyAsync(b->taps, taps_host, ntaps * sizeof(float), hipMemcpyHostToDevice, d->stream);
 	return bank_created(bank, b, e, "wr_voice_create", wr_voice_destroy);
@@ -674,14 +713,11 @@ extern "C" int wr_voice_create(wr_voice **bank, wr_dev *d, unsigned int max_rows
 
 extern "C" int wr_voice_destroy(wr_voice *b)
 {
-	if (!b)
+	if (!bank_destroy_begin(b))
 		return WR_OK;
-	(void)hipSetDevice(b->dev->device);
-	(void)wrc_dev_stream_sync(b->dev);
 	(void)hipFree(b->taps);
 	(void)hipFree(b->ctl);
-	(void)hipFree(b->hist[0]);
-	(void)hipFree(b->hist[1]);
+	hist_free(&b->hist);
 	free(b->ctl_host);
 	delete b;
 	return WR_OK;
@@ -694,13 +730,9 @@ extern "C" int wr_voice_reset(wr_voice *b, int row)
 	size_t first, n;
 	if (int rc = bank_reset_begin(b, "wr_voice_reset", row, &first, &n))
 		return rc;
-	/* only the set the next push reads matters: that push writes the other one; the control words stay */
-	const size_t H = b->T - 1u;
-	HIP_TRY(hipMemsetAsync(b->hist[b->cur] + first * H, 0, n * H * sizeof(float), b->dev->stream));
-	if (row < 0) {                                              /* all rows: the frame count starts again too */
-		b->zero_from[b->cur] = 0;
+	HIP_TRY(hist_reset(&b->hist, first, n, row < 0, b->dev->stream));      /* (the control words stay) */
+	if (row < 0)                                                /* all rows: the frame count starts again too */
 		b->frames = 0;
-	}
 	return WR_OK;
 }
 
@@ -749,16 +781,7 @@ static int voice_check(const wr_voice *b, const char *who, const float *in_dev, 
 {
 	if (int rc = bank_rows_refused(b, who, row_stride, nrows, nframes, 28))
 		return rc;
-	if (!nrows || !nframes)
-		return WR_OK;
-	if (!out_dev || (nrows > 1 && out_stride < nframes))
-		return wrc_fail(WR_ERR_ARG, "%s: out_dev is NULL, or rows of %zu output frames overlap at a stride of %zu", who, nframes,
-		                out_stride);
-	const uintptr_t a0 = (uintptr_t)in_dev, a1 = a0 + ((nrows - 1u) * row_stride + nframes) * sizeof(float);
-	const uintptr_t b0 = (uintptr_t)out_dev, b1 = b0 + ((nrows - 1u) * out_stride + nframes) * sizeof(float);
-	if (a0 < b1 && b0 < a1)
-		return wrc_fail(WR_ERR_ARG, "%s: input and output overlap", who);
-	return WR_OK;
+	return bank_out_refused(who, in_dev, row_stride, nrows, nframes, out_dev, out_stride, nframes);
 }
 
 /* the push itself, behind voice_check, on a device made ready: the rows it leaves out lose their histories, the count
@@ -769,14 +792,10 @@ static int voice_push(wr_voice *b, const float *in_dev, size_t row_stride, size_
 	if (!nframes)
 		return WR_OK;
 	wr_dev *d = b->dev;
-	const unsigned int from = b->cur, to = from ^ 1u;
-	const size_t H = b->T - 1u;
-	if (nrows < b->zero_from[to])
-		HIP_TRY(hipMemsetAsync(b->hist[to] + nrows * H, 0, (b->zero_from[to] - nrows) * H * sizeof(float), d->stream));
-	const WrVoicePush p = {b->taps, b->T, b->ctl, b->hist[from], b->hist[to]};
+	WrVoicePush p = {b->taps, b->T, b->ctl, nullptr, nullptr};
+	HIP_TRY(hist_push_begin(&b->hist, nrows, d->stream, &p.hist_old, &p.hist_new));
 	HIP_TRY(wrk_voice_push(d->stream, in_dev, row_stride, nrows, nframes, p, out_dev, out_stride));
-	b->zero_from[to] = (unsigned int)nrows;
-	b->cur = to;
+	hist_push_end(&b->hist, nrows);
 	b->frames += nframes;
 	return WR_OK;
 }
@@ -806,9 +825,8 @@ extern "C" int wr_tuner_voice_push(wr_tuner *t, wr_voice *bank, float *out_dev, 
 	const Group *g = v.g;
 	if (int rc = voice_check(bank, "wr_tuner_voice_push", g->dev.audio, g->k2max, v.used, g->last_k2, out_dev, out_stride))
 		return rc;
-	if (int rc = wrc_last_submit_flush(t, &v))
+	if (int rc = bank_submit_ready(t, &v))
 		return rc;
-	DEV_SETTLE(t->dev);
 	if (int rc = voice_push(bank, g->dev.audio, g->k2max, v.used, g->last_k2, out_dev, out_stride))
 		return rc;
 	return bank_took_submit(bank, t, v, slots);

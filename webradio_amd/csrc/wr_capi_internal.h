@@ -313,12 +313,19 @@ struct wr_dcs : WrRowBank {
 	unsigned long long frames = 0;     /* the clock: frames since creation, a reset of every row or a seek */
 };
 
+/* the two history sets of a bank that filters its rows (wr_resamp, wr_voice): device, [max_rows][H] floats each.  A push
+ * reads set `cur` and writes the other, so that no workgroup of it reads what another writes (wr_resamp.hip, wr_voice.hip) */
+struct WrHistSets {
+	float *set[2] = {nullptr, nullptr};
+	size_t H = 0;              /* frames of history a row keeps: the filter's length less one */
+	unsigned int cur = 0;
+	unsigned int zero_from[2] = {0, 0};   /* rows of a set from this one on are known to hold silence */
+};
+
 struct wr_resamp : WrRowBank {
 	unsigned int L, M, P;
 	float *taps;               /* device, [L][P] */
-	float *hist[2];            /* device, [max_rows][P - 1] each: a push reads set `cur` and writes the other (wr_resamp.hip) */
-	unsigned int cur = 0;
-	unsigned int zero_from[2] = {0, 0};   /* rows of a set from this one on are known to hold silence */
+	WrHistSets hist;           /* H = P - 1 */
 	unsigned int nmod = 0;     /* the clock: input frames so far, mod M */
 	unsigned long long frames_in = 0, frames_out = 0;
 };
@@ -328,9 +335,7 @@ struct wr_voice : WrRowBank {
 	float *taps;               /* device, [nfilt][T] */
 	unsigned int *ctl;         /* device, [max_rows]: the rows' control words */
 	unsigned int *ctl_host;    /* ... and the host's copy: what wr_voice_get_rows shows */
-	float *hist[2];            /* device, [max_rows][T - 1] each: a push reads set `cur` and writes the other (wr_voice.hip) */
-	unsigned int cur = 0;
-	unsigned int zero_from[2] = {0, 0};   /* rows of a set from this one on are known to hold silence */
+	WrHistSets hist;           /* H = T - 1 */
 	unsigned long long frames = 0;
 };
 

@@ -35,16 +35,10 @@
  * pad word behind every eight chips they start 72 bytes = 18 banks apart and the 23 lanes of a half meet no bank twice.
  */
 #include "wr_internal.h"
+#include "wr_rows.h"
 
-#define DC_THREADS 256u
-#define DC_RING    WR_DCS_RING
-#define DC_SPAN    256u                          /* chips a launch may touch, the chip of the frame behind it included */
-#define DC_BACK    191u                          /* chips an evaluation reaches back from the first it does not use */
-#define DC_CAND    (8u * 23u)
+/* (DC_*, the start of a push and its cut into launches are wr_plan.h's) */
 #define DC_SLOT(p) ((p) + ((p) >> 3))
-
-static_assert(DC_BACK + 1u + DC_SPAN <= DC_RING, "a launch's live chips must fit the ring");
-static_assert((DC_RING & (DC_RING - 1u)) == 0, "the ring is indexed by g mod DC_RING");
 
 __global__ void __launch_bounds__(DC_THREADS)
 k_dcs_push(const float *__restrict__ audio, size_t row_stride, unsigned int nframes, WrDcsRow *__restrict__ rows,
@@ -75,10 +69,7 @@ k_dcs_push(const float *__restrict__ audio, size_t row_stride, unsigned int nfra
 		long long q = 0;
 		unsigned int c = 0xffffffffu;
 		if (valid) {
-			float v = row[k];
-			if ((__float_as_uint(v) & 0x7fffffffu) >= 0x7f800000u)
-				v = 0.0f;
-			q = (long long)(int)rintf(fminf(fmaxf(v, -64.0f), 64.0f) * 16777216.0f);
+			q = (long long)(int)rintf(row_fixed24(row[k]));
 			c = (unsigned int)(((unsigned long long)ph0 + (unsigned long long)k * step) >> 29);
 		}
 #pragma unroll
@@ -184,25 +175,17 @@ hipError_t wrk_dcs_push(hipStream_t st, const float *audio, size_t row_stride, s
 {
 	if (!nrows || !nframes)
 		return hipSuccess;
-	if (!audio || !rows || !words || !ncodes || ncodes > WR_DCS_CODES || step < (1u << 19) || step > (1u << 28) || max_errors > 3u ||
+	if (!audio || !rows || !words || !ncodes || ncodes > WR_DCS_CODES || !wrp_dcs_step_ok(step) || max_errors > 3u ||
 	    nrows > 65535u || nframes > ((size_t)1 << 28) || (nrows > 1 && row_stride < nframes))
 		return hipErrorInvalidValue;
-	const unsigned __int128 at = (unsigned __int128)first_frame * step;           /* may pass 2^64: reduced here */
-	unsigned long long g0 = (unsigned long long)(at >> 29);
-	unsigned int ph0 = (unsigned int)((unsigned long long)at & ((1u << 29) - 1u));
-	for (size_t done = 0; done < nframes;) {
-		/* the most frames n with (ph0 + n * step) >> 29 < DC_SPAN: at least 510, step being 2^28 at most */
-		const size_t room = (size_t)((((unsigned long long)DC_SPAN << 29) - 1u - ph0) / step);
-		const size_t n = nframes - done < room ? nframes - done : room;
+	WrDcsAt at = wrp_dcs_start(first_frame, step);
+	for (size_t done = 0, n; done < nframes; done += n, at = wrp_dcs_after(at, step, n)) {
+		n = wrp_dcs_take(at, step, nframes - done);
 		k_dcs_push<<<(unsigned int)nrows, DC_THREADS, 0, st>>>(audio + done, row_stride, (unsigned int)n, rows, words, ncodes, step,
-		                                                       ph0, g0, max_errors);
+		                                                       at.ph0, at.g0, max_errors);
 		const hipError_t e = hipGetLastError();
 		if (e != hipSuccess)
 			return e;
-		const unsigned long long a = ph0 + (unsigned long long)n * step;
-		g0 += a >> 29;
-		ph0 = (unsigned int)(a & ((1u << 29) - 1u));
-		done += n;
 	}
 	return hipSuccess;
 }

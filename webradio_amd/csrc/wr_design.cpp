@@ -177,7 +177,7 @@ int wrd_resamp_ratio(unsigned int in_rate, unsigned int out_rate, unsigned int *
 /* the header's limits on a resampler's ratio and taps per phase */
 int wrd_resamp_limits(unsigned int L, unsigned int M, unsigned int P)
 {
-	return !L || L > 1024u || !M || M > 8u * L || L > 8u * M || P < 4u || P > 64u || (P & 3u) || L * P > 16384u;
+	return wrp_resamp_limits_bad(L, M, P);
 }
 
 namespace {

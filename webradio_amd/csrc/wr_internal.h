@@ -14,7 +14,6 @@
 #include "webradio_amd.h"
 #include "wr_plan.h"                       /* launch geometry and the constants it depends on (WR_HIST, WR_SPLIT_N, WR_TAPSETS, ...) */
 
-#define WR_LANES     64                    /* wavefront width on gfx950 */
 #define WR_MAX_DEVICES 64                  /* device indices the per-device tables of this library hold */
 
 /* ---- what other translation units need of a wr_dev (wr_dev.hip, wr_tuner_submit.hip) ---- */
@@ -407,8 +406,6 @@ hipError_t wrk_tones_push(hipStream_t st, const float *audio, size_t row_stride,
                           const float *t12, const unsigned int *steps, unsigned int ntones, unsigned int window);
 
 /* ---- DCS bank (wr_dcs.hip) ---- */
-#define WR_DCS_CODES 128                   /* code words a bank holds at most: a lane each, two waves */
-#define WR_DCS_RING  512                   /* chip sums a row keeps, indexed by chip mod 512 (wr_dcs.hip: why that many) */
 struct WrDcsRow {                          /* everything a bank holds of one row; all zero: a row that begins its stream */
 	long long ring[WR_DCS_RING];       /* chip sums; the open chip among them */
 	unsigned long long hits[WR_DCS_CODES][2];

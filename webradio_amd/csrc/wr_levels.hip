@@ -18,10 +18,7 @@
  */
 #include "wr_internal.h"
 
-#define LV_RUN     16u                     /* frames of a run = rows a lane has in flight */
-#define LV_RUNS    16u                     /* runs of a group = waves of a workgroup */
-#define LV_ROWS    (LV_RUN * LV_RUNS)      /* rows of a group */
-#define LV_THREADS (LV_RUNS * WR_LANES)
+/* (LV_*, the grids, the LDS and the work area's layout -- wrp_levels_plan -- are wr_plan.h's) */
 
 /* SQ: count the audio frames the gate mutes.  Then the workgroup keeps its 256 x 64 e values in LDS (64 KiB, dynamic)
  * and adds them again in the gate's own order: audio frame k is this workgroup's when its FIRST row k * d2 lies in the
@@ -113,7 +110,7 @@ k_levels_part(const float2 *__restrict__ iq, size_t S, unsigned int cols, size_t
 }
 
 /* out[0][cols] = sum / (float)k1, out[1][cols] = peak, out[2][cols] = muted (unsigned; 0 without thresholds) */
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(LV_SUM_THREADS)
 k_levels_sum(const float *__restrict__ psum, const float *__restrict__ ppeak, const unsigned int *__restrict__ pmuted,
              size_t groups, unsigned int cols, size_t k1, float *__restrict__ out)
 {
@@ -135,21 +132,20 @@ k_levels_sum(const float *__restrict__ psum, const float *__restrict__ ppeak, co
 
 size_t wrk_chan_levels_work(unsigned int cols, size_t k1)
 {
-	const size_t groups = (k1 + LV_ROWS - 1u) / LV_ROWS;
-	return (groups + 1u) * 3u * cols;
+	return wrp_levels_plan(cols, k1).work_floats;
 }
 
 hipError_t wrk_chan_levels(hipStream_t st, const float *iq, size_t S, unsigned int cols, size_t k1, unsigned int d2, size_t k2,
                            const float *squelch, float *work, const float **out)
 {
-	const size_t groups = (k1 + LV_ROWS - 1u) / LV_ROWS;
-	if (!cols || !k1 || cols > S || groups > 0x7fffffffu || (squelch && !d2))
+	const WrLevelsPlan g = wrp_levels_plan(cols, k1);
+	if (!cols || !k1 || cols > S || g.groups > 0x7fffffffu || (squelch && !d2))
 		return hipErrorInvalidValue;
-	float *psum = work, *ppeak = psum + groups * cols, *res = ppeak + 2u * groups * cols;
-	unsigned int *pmuted = (unsigned int *)(ppeak + groups * cols);
-	const dim3 grid((unsigned int)groups, (cols + WR_LANES - 1u) / WR_LANES);
+	float *psum = work + g.psum, *ppeak = work + g.ppeak, *res = work + g.res;
+	unsigned int *pmuted = (unsigned int *)(work + g.pmuted);
+	const dim3 grid((unsigned int)g.groups, g.grid_y);
 	if (squelch) {
-		const size_t lds = (size_t)LV_ROWS * WR_LANES * sizeof(float);
+		const size_t lds = g.lds_squelch;
 		/* (64 KiB of dynamic LDS, all this instance ever asks for, is above the default limit of 48) */
 		static bool attr_done[WR_MAX_DEVICES];
 		hipError_t e = allow_lds((const void *)k_levels_part<true>, lds, attr_done);
@@ -162,7 +158,7 @@ hipError_t wrk_chan_levels(hipStream_t st, const float *iq, size_t S, unsigned i
 	hipError_t e = hipGetLastError();
 	if (e != hipSuccess)
 		return e;
-	k_levels_sum<<<(cols + 255u) / 256u, 256, 0, st>>>(psum, ppeak, squelch ? pmuted : nullptr, groups, cols, k1, res);
+	k_levels_sum<<<g.sum_grid, LV_SUM_THREADS, 0, st>>>(psum, ppeak, squelch ? pmuted : nullptr, g.groups, cols, k1, res);
 	*out = res;
 	return hipGetLastError();
 }

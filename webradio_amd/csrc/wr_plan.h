@@ -1,11 +1,15 @@
 /*
  * wr_plan.h -- the launch geometry of every tuner launch (the per-block DDC, the long-filter DDC, the post stage, the audio
- * filter, the streaming launch) and of the spectrum launches (the transform's shape and path, its passes' tiles, grids and
+ * filter, the streaming launch), of the spectrum launches (the transform's shape and path, its passes' tiles, grids and
  * LDS, the work area and its chunks, the columns per workgroup of the channel spectra, the chunks, scratch cap and launch count
- * of the averaged spectra, the band scan's limits, grids, LDS and chunks of rows) and of the voice bank: which kernel instance, how many
+ * of the averaged spectra, the band scan's limits, grids, LDS and chunks of rows), of the voice bank and of the row kernels
+ * (tone bank: chunks, grid and the cut of a push into its two summed stretches; DCS bank: the start of a push and its cut
+ * into launches; resampler: the limits on L / M / P, the output frames, grid and input span of a push; levels: groups, grids,
+ * LDS and the work area's layout; AGC: tile): which kernel instance, how many
  * workgroups per role, how much LDS, the group map, kslow, kmax, the post stage's runs of tiles.  The arithmetic alone, with
  * no HIP call and no environment read, so that a CPU test can hold it to the rule (tests/test_launch_plan.py through
- * tests/cxx/cpu_host_checks.cxx).  The launch functions (wr_kernels.hip, wr_stream_kernel.inc, wr_fft.hip) obtain a plan,
+ * tests/cxx/cpu_host_checks.cxx; tests/cxx/plan_sweeps.cxx sweeps it under the host compiler's sanitizers).  The launch
+ * functions (wr_kernels.hip, wr_stream_kernel.inc, wr_fft.hip, the row kernels' files) obtain a plan,
  * ask the runtime for what only it can give (allow_lds, the occupancy query), and launch with the plan's numbers.  The only
  * home of the constants geometry depends on: the kernels use the same names.  Plain C++11.
  */
@@ -16,6 +20,14 @@
 
 #include "webradio_amd.h"
 
+/* what a kernel calls too (WRP_HD): inlined into it by force, and a plain inline function for the host compiler */
+#ifdef __HIPCC__
+#define WRP_HD __host__ __device__ __forceinline__
+#else
+#define WRP_HD static inline
+#endif
+
+#define WR_LANES     64                    /* wavefront width on gfx950 */
 #define WR_HIST      (WR_FIR_LENGTH - 1)   /* 63 frames of FIR history, lowpass.cxx:133 */
 #define WR_SPLIT_N   256                   /* entries of the coarse and of the fine NCO table */
 #define WR_TAPSETS   4                     /* distinct channel filters a lane group may mix in the fast DDC kernel:
@@ -799,5 +811,224 @@ static inline WrVoicePlan wrp_voice_plan(size_t nframes)
 	p.threads = VOICE_THREADS;
 	return p;
 }
+
+/* ================================================================== the row kernels ================================== */
+
+/* ---- the tone bank (wr_tones.hip): k_tones_part, a workgroup of TN_WAVES waves per TN_CHUNK frames of a row, then
+ * k_tones_latch, a workgroup of one wave per row ---- */
+#define TN_THREADS 256u
+#define TN_WAVES   (TN_THREADS / WR_LANES)
+#define TN_RUN     128u                        /* frames a wave walks */
+#define TN_CHUNK   (TN_RUN * TN_WAVES)         /* frames of a workgroup */
+#define TN_TABLE   4096u
+#define TN_WINDOW_MIN 16u
+#define TN_WINDOW_MAX 65536u
+
+struct WrTonesPlan {
+	size_t chunks;                         /* grid.x of k_tones_part (grid.y: the rows); above 2^31 - 1: no launch */
+	unsigned long long nq;                 /* the push is nq * window + nr frames */
+	unsigned int nr;
+};
+
+static inline WrTonesPlan wrp_tones_plan(size_t nframes, unsigned int window)
+{
+	WrTonesPlan p;
+	p.chunks = (nframes + TN_CHUNK - 1u) / TN_CHUNK;
+	p.nq = nframes / window;
+	p.nr = (unsigned int)(nframes % window);
+	return p;
+}
+
+/* the two stretches of a push for a row with `fill` frames in its open window: A = [a_lo, b_lo) counted from frame `oa`
+ * of the push (which may lie in front of it), B = [b_lo, nframes) counted from `ob`; the push is nq * W + nr frames */
+struct WrTonesCut {
+	long long a_lo, b_lo, oa, ob;
+	unsigned long long ends;
+	unsigned int fill_after;
+};
+
+WRP_HD WrTonesCut wrp_tones_cut(unsigned int fill, unsigned long long nq, unsigned int nr, unsigned int W)
+{
+	WrTonesCut c;
+	const bool over = nr + fill >= W;              /* fill < W, nr < W */
+	c.ends = nq + (over ? 1u : 0u);
+	c.fill_after = nr + fill - (over ? W : 0u);
+	if (!c.ends) {
+		c.a_lo = c.b_lo = c.oa = 0;
+		c.ob = -(long long)fill;
+	} else {
+		const long long e = (long long)(c.ends * W) - (long long)fill;
+		c.oa = e - (long long)W;
+		c.a_lo = c.oa > 0 ? c.oa : 0;
+		c.b_lo = c.ob = e;
+	}
+	return c;
+}
+
+/* ---- the DCS bank (wr_dcs.hip): k_dcs_push, a workgroup per row.  The clock is frames * step in units of 2^-29 chip; a
+ * launch takes frames whose chips, the next frame's included, lie within DC_SPAN of its first ---- */
+#define WR_DCS_CODES 128                   /* code words a bank holds at most: a lane each, two waves */
+#define WR_DCS_RING  512                   /* chip sums a row keeps, indexed by chip mod 512 (wr_dcs.hip: why that many) */
+#define DC_THREADS 256u
+#define DC_RING    WR_DCS_RING
+#define DC_SPAN    256u                          /* chips a launch may touch, the chip of the frame behind it included */
+#define DC_BACK    191u                          /* chips an evaluation reaches back from the first it does not use */
+#define DC_CAND    (8u * 23u)
+#define DC_CHIP_BITS 29u                         /* a chip is 2^29 units of the clock: an eighth of a bit of 2^32 */
+#define DC_STEP_MIN (1u << 19)                   /* 1024 frames a chip */
+#define DC_STEP_MAX (1u << 28)                   /* 2 frames a chip */
+
+static_assert(DC_BACK + 1u + DC_SPAN <= DC_RING, "a launch's live chips must fit the ring");
+static_assert((DC_RING & (DC_RING - 1u)) == 0, "the ring is indexed by g mod DC_RING");
+
+static inline bool wrp_dcs_step_ok(unsigned long long step)
+{
+	return step >= DC_STEP_MIN && step <= DC_STEP_MAX;
+}
+
+/* where a launch begins: its first frame's chip and how far into the chip that frame lies */
+struct WrDcsAt {
+	unsigned long long g0;
+	unsigned int ph0;                      /* < 2^29 */
+};
+
+/* the start of a push at clock `first_frame`: the product may pass 2^64 and is reduced here */
+static inline WrDcsAt wrp_dcs_start(unsigned long long first_frame, unsigned int step)
+{
+	const unsigned __int128 at = (unsigned __int128)first_frame * step;
+	const WrDcsAt a = {(unsigned long long)(at >> DC_CHIP_BITS), (unsigned int)((unsigned long long)at & ((1u << DC_CHIP_BITS) - 1u))};
+	return a;
+}
+
+/* the most frames n a launch at `at` may take, (ph0 + n * step) >> 29 < DC_SPAN: 510 or more, step being 2^28 at most */
+static inline size_t wrp_dcs_room(const WrDcsAt &at, unsigned int step)
+{
+	return (size_t)((((unsigned long long)DC_SPAN << DC_CHIP_BITS) - 1u - at.ph0) / step);
+}
+
+/* the frames the launch at `at` takes of the `left` a push still has ... */
+static inline size_t wrp_dcs_take(const WrDcsAt &at, unsigned int step, size_t left)
+{
+	const size_t room = wrp_dcs_room(at, step);
+	return left < room ? left : room;
+}
+
+/* ... and where the launch behind it begins */
+static inline WrDcsAt wrp_dcs_after(const WrDcsAt &at, unsigned int step, size_t n)
+{
+	const unsigned long long a = at.ph0 + (unsigned long long)n * step;
+	const WrDcsAt b = {at.g0 + (a >> DC_CHIP_BITS), (unsigned int)(a & ((1u << DC_CHIP_BITS) - 1u))};
+	return b;
+}
+
+/* ---- the resampler (wr_resamp.hip): k_resamp_rows, a workgroup per RS_THREADS consecutive outputs of a row and one more
+ * per row for its history.  The header's limits on (L, M, P) are what the chunk's input span in LDS rests on ---- */
+#define RS_THREADS   256u
+#define RS_L_MAX     1024u
+#define RS_RATIO_MAX 8u                    /* M <= 8 L and L <= 8 M */
+#define RS_P_MIN     4u
+#define RS_P_MAX     64u                   /* and a multiple of 4 */
+#define RS_TAPS_MAX  16384u                /* L * P: the table is at most 64 KiB */
+#define RS_SPAN      2112u                 /* floats of LDS for a chunk's input span */
+
+/* the worst span: rem0 = L - 1, cnt = RS_THREADS, M = 8 L, P = 64 -- (L - 1 + 255 * 8 L) / L + 64 = 2104 */
+static_assert((RS_L_MAX - 1u + (RS_THREADS - 1u) * RS_RATIO_MAX * RS_L_MAX) / RS_L_MAX + RS_P_MAX == 2104u &&
+              2104u <= RS_SPAN, "RS_SPAN covers the longest input span the limits allow");
+
+/* non-zero: (L, M, P) break the header's limits */
+static inline int wrp_resamp_limits_bad(unsigned int L, unsigned int M, unsigned int P)
+{
+	return !L || L > RS_L_MAX || !M || M > RS_RATIO_MAX * L || L > RS_RATIO_MAX * M || P < RS_P_MIN || P > RS_P_MAX || (P & 3u) ||
+	       L * P > RS_TAPS_MAX;
+}
+
+/* the output frames a push of `nframes` yields at clock `nmod` = N mod M: ceil((nmod + nframes) L / M) - ceil(nmod L / M) */
+static inline unsigned long long wrp_resamp_out_frames(unsigned int L, unsigned int M, unsigned int nmod, unsigned long long nframes)
+{
+	const unsigned long long a = ((unsigned long long)nmod * L + M - 1u) / M;
+	const unsigned long long b = (((unsigned long long)nmod + nframes) * L + M - 1u) / M;
+	return b - a;
+}
+
+struct WrResampPlan {
+	unsigned long long n_out;              /* output frames of a row */
+	unsigned int j0;                       /* ceil(nmod L / M): output i of the push is frame q L + j0 + i of the stream */
+	unsigned int chunks;                   /* workgroups of a row that compute outputs; <= 2^23 */
+	unsigned int grid_x;                   /* ... and the one that writes the row's history; grid.y is the rows */
+};
+
+/* a push of `nframes` frames, 1 .. 2^28, within the limits */
+static inline WrResampPlan wrp_resamp_plan(unsigned int L, unsigned int M, unsigned int nmod, size_t nframes)
+{
+	WrResampPlan p;
+	p.n_out = wrp_resamp_out_frames(L, M, nmod, nframes);
+	p.j0 = (unsigned int)(((unsigned long long)nmod * L + M - 1u) / M);
+	p.chunks = (unsigned int)((p.n_out + RS_THREADS - 1u) / RS_THREADS);
+	p.grid_x = p.chunks + 1u;
+	return p;
+}
+
+/* chunk `chunk` < chunks of a row: outputs [i0, i0 + cnt) of the push.  The first of them reads the push's frame `base`
+ * (n0 - N0 >= 0) at phase rem0 < L; the chunk's inputs are `span` frames from frame lo = base - (P - 1) >= -(P - 1) on */
+struct WrResampChunk {
+	unsigned long long i0;
+	long long base, lo;
+	unsigned int rem0, cnt, span;
+};
+
+WRP_HD WrResampChunk wrp_resamp_chunk(unsigned int L, unsigned int M, unsigned int P, unsigned int nmod, unsigned int j0,
+                                      unsigned long long n_out, unsigned int chunk)
+{
+	WrResampChunk c;
+	c.i0 = (unsigned long long)chunk * RS_THREADS;
+	const unsigned long long u0 = ((unsigned long long)j0 + c.i0) * M;
+	c.base = (long long)(u0 / L) - (long long)nmod;
+	c.rem0 = (unsigned int)(u0 % L);
+	const unsigned long long left = n_out - c.i0;
+	c.cnt = left < RS_THREADS ? (unsigned int)left : RS_THREADS;
+	c.lo = c.base - (long long)(P - 1u);
+	c.span = (c.rem0 + (c.cnt - 1u) * M) / L + P;
+	return c;
+}
+
+/* ---- signal levels (wr_levels.hip): k_levels_part, a workgroup of LV_RUNS waves per group of LV_ROWS rows and lane group of
+ * columns, then k_levels_sum, a thread per column over the groups.  The work area, in floats: the groups' sums, peaks and
+ * muted counts, [groups][cols] each, then the result [3][cols] ---- */
+#define LV_RUN     16u                     /* frames of a run = rows a lane has in flight */
+#define LV_RUNS    16u                     /* runs of a group = waves of a workgroup */
+#define LV_ROWS    (LV_RUN * LV_RUNS)      /* rows of a group */
+#define LV_THREADS (LV_RUNS * WR_LANES)
+#define LV_SUM_THREADS 256u
+
+struct WrLevelsPlan {
+	size_t groups;                         /* grid.x of k_levels_part; above 2^31 - 1: no launch */
+	unsigned int grid_y;                   /* lane groups of columns */
+	size_t lds_squelch;                    /* dynamic LDS of the instance that counts muted frames: a group's e values, 64 KiB */
+	unsigned int sum_grid;                 /* k_levels_sum */
+	size_t psum, ppeak, pmuted, res;       /* offsets into the work area, floats */
+	size_t work_floats;                    /* ... and its size */
+};
+
+static inline WrLevelsPlan wrp_levels_plan(unsigned int cols, size_t k1)
+{
+	WrLevelsPlan p;
+	p.groups = (k1 + LV_ROWS - 1u) / LV_ROWS;
+	p.grid_y = (cols + WR_LANES - 1u) / WR_LANES;
+	p.lds_squelch = (size_t)LV_ROWS * WR_LANES * sizeof(float);
+	p.sum_grid = (cols + LV_SUM_THREADS - 1u) / LV_SUM_THREADS;
+	p.psum = 0;
+	p.ppeak = p.groups * cols;
+	p.pmuted = 2u * p.groups * cols;
+	p.res = 3u * p.groups * cols;
+	p.work_floats = (p.groups + 1u) * 3u * cols;
+	return p;
+}
+
+/* ---- audio AGC (wr_agc.hip): k_agc_rows, a workgroup per row (the grid is the rows) walks it in tiles of AGC_TILE frames,
+ * AGC_PER a thread ---- */
+#define AGC_THREADS 256u
+#define AGC_PER     4u                          /* consecutive frames of a thread */
+#define AGC_TILE    (AGC_THREADS * AGC_PER)
+#define AGC_WAVES   (AGC_THREADS / WR_LANES)
 
 #endif /* WR_PLAN_H_ */

@@ -22,16 +22,9 @@
  * reads what another writes; the host takes the sets in turn.
  */
 #include "wr_internal.h"
+#include "wr_rows.h"
 
-#define RS_THREADS 256u
-#define RS_SPAN    2112u                       /* >= (L - 1 + 255 * 8 L) / L + 64 = 2104 frames */
-
-__device__ __forceinline__ float rs_clean(float x)
-{
-	if ((__float_as_uint(x) & 0x7fffffffu) >= 0x7f800000u)
-		x = 0.0f;
-	return fminf(fmaxf(x, -65536.0f), 65536.0f);
-}
+/* (RS_*, the limits RS_SPAN rests on, the figures of a push and of a chunk -- wrp_resamp_chunk -- are wr_plan.h's) */
 
 __global__ void __launch_bounds__(RS_THREADS)
 k_resamp_rows(const float *__restrict__ in, size_t row_stride, unsigned int nframes, const float *__restrict__ taps,
@@ -46,21 +39,17 @@ k_resamp_rows(const float *__restrict__ in, size_t row_stride, unsigned int nfra
 	if (blockIdx.x == chunks) {                                   /* the row's new history: frames [nframes - H, nframes) */
 		if (tid < H) {
 			const long long n = (long long)nframes - (long long)H + (long long)tid;
-			hist_new[(size_t)blockIdx.y * H + tid] = n < 0 ? ho[(long long)H + n] : rs_clean(row[n]);
+			hist_new[(size_t)blockIdx.y * H + tid] = n < 0 ? ho[(long long)H + n] : row_clean(row[n]);
 		}
 		return;
 	}
-	const unsigned long long i0 = (unsigned long long)blockIdx.x * RS_THREADS;
-	const unsigned long long u0 = ((unsigned long long)j0 + i0) * M;
-	const long long base = (long long)(u0 / L) - (long long)nmod;          /* n0 - N0 of the chunk's first output; >= 0 */
-	const unsigned int rem0 = (unsigned int)(u0 % L);
-	const unsigned long long left = n_out - i0;
-	const unsigned int cnt = left < RS_THREADS ? (unsigned int)left : RS_THREADS;
-	const long long lo = base - (long long)H;                     /* xs[i] is frame lo + i of the push; lo >= -H */
-	const unsigned int span = (rem0 + (cnt - 1u) * M) / L + P;
-	for (unsigned int i = tid; i < span; i += RS_THREADS) {
+	const WrResampChunk ch = wrp_resamp_chunk(L, M, P, nmod, j0, n_out, blockIdx.x);
+	const unsigned long long i0 = ch.i0;
+	const unsigned int rem0 = ch.rem0, cnt = ch.cnt;
+	const long long lo = ch.lo;                                   /* xs[i] is frame lo + i of the push; lo >= -H */
+	for (unsigned int i = tid; i < ch.span; i += RS_THREADS) {
 		const long long n = lo + (long long)i;
-		xs[i] = n < 0 ? ho[(long long)H + n] : n < (long long)nframes ? rs_clean(row[n]) : 0.0f;
+		xs[i] = n < 0 ? ho[(long long)H + n] : n < (long long)nframes ? row_clean(row[n]) : 0.0f;
 	}
 	__syncthreads();
 	if (tid >= cnt)
@@ -82,9 +71,7 @@ k_resamp_rows(const float *__restrict__ in, size_t row_stride, unsigned int nfra
 
 unsigned long long wrk_resamp_out_frames(unsigned int L, unsigned int M, unsigned int nmod, unsigned long long nframes)
 {
-	const unsigned long long a = ((unsigned long long)nmod * L + M - 1u) / M;
-	const unsigned long long b = (((unsigned long long)nmod + nframes) * L + M - 1u) / M;
-	return b - a;
+	return wrp_resamp_out_frames(L, M, nmod, nframes);
 }
 
 hipError_t wrk_resamp_push(hipStream_t st, const float *in, size_t row_stride, size_t nrows, size_t nframes, const WrResampPush &p,
@@ -95,13 +82,11 @@ hipError_t wrk_resamp_push(hipStream_t st, const float *in, size_t row_stride, s
 	if (!in || !p.taps || !p.hist_old || !p.hist_new || p.hist_old == p.hist_new || wrd_resamp_limits(p.L, p.M, p.P) ||
 	    p.nmod >= p.M || nrows > 65535u || nframes > ((size_t)1 << 28) || (nrows > 1 && row_stride < nframes))
 		return hipErrorInvalidValue;
-	const unsigned long long n_out = wrk_resamp_out_frames(p.L, p.M, p.nmod, nframes);
-	if (n_out && (!out || (nrows > 1 && out_stride < n_out)))
+	const WrResampPlan g = wrp_resamp_plan(p.L, p.M, p.nmod, nframes);
+	if (g.n_out && (!out || (nrows > 1 && out_stride < g.n_out)))
 		return hipErrorInvalidValue;
-	const unsigned int j0 = (unsigned int)(((unsigned long long)p.nmod * p.L + p.M - 1u) / p.M);
-	const unsigned int chunks = (unsigned int)((n_out + RS_THREADS - 1u) / RS_THREADS);      /* <= 2^23 */
-	k_resamp_rows<<<dim3(chunks + 1u, (unsigned int)nrows), RS_THREADS, 0, st>>>(in, row_stride, (unsigned int)nframes, p.taps, p.L,
-	                                                                             p.M, p.P, p.hist_old, p.hist_new, p.nmod, j0, n_out,
-	                                                                             chunks, out, out_stride);
+	k_resamp_rows<<<dim3(g.grid_x, (unsigned int)nrows), RS_THREADS, 0, st>>>(in, row_stride, (unsigned int)nframes, p.taps, p.L, p.M,
+	                                                                          p.P, p.hist_old, p.hist_new, p.nmod, g.j0, g.n_out,
+	                                                                          g.chunks, out, out_stride);
 	return hipGetLastError();
 }

@@ -26,38 +26,9 @@
  * at once.  k_tones_latch, a workgroup of 64 lanes per row, latches, carries, counts and leaves `part` zero again.
  */
 #include "wr_internal.h"
+#include "wr_rows.h"
 
-#define TN_THREADS 256u
-#define TN_WAVES   (TN_THREADS / WR_LANES)
-#define TN_RUN     128u                        /* frames a wave walks */
-#define TN_CHUNK   (TN_RUN * TN_WAVES)         /* frames of a workgroup */
-#define TN_TABLE   4096u
-
-/* the two stretches of a push for a row with `fill` frames in its open window: A = [a_lo, b_lo) counted from frame `oa`
- * of the push (which may lie in front of it), B = [b_lo, nframes) counted from `ob`; the push is nq * W + nr frames */
-struct TnCut {
-	long long a_lo, b_lo, oa, ob;
-	unsigned long long ends;
-	unsigned int fill_after;
-};
-
-__device__ __forceinline__ TnCut tn_cut(unsigned int fill, unsigned long long nq, unsigned int nr, unsigned int W)
-{
-	TnCut c;
-	const bool over = nr + fill >= W;              /* fill < W, nr < W */
-	c.ends = nq + (over ? 1u : 0u);
-	c.fill_after = nr + fill - (over ? W : 0u);
-	if (!c.ends) {
-		c.a_lo = c.b_lo = c.oa = 0;
-		c.ob = -(long long)fill;
-	} else {
-		const long long e = (long long)(c.ends * W) - (long long)fill;
-		c.oa = e - (long long)W;
-		c.a_lo = c.oa > 0 ? c.oa : 0;
-		c.b_lo = c.ob = e;
-	}
-	return c;
-}
+/* (TN_*, the launch figures and the cut of a push -- wrp_tones_cut -- are wr_plan.h's) */
 
 __global__ void __launch_bounds__(TN_THREADS)
 k_tones_part(const float *__restrict__ audio, size_t row_stride, size_t nframes, unsigned long long nq, unsigned int nr,
@@ -70,7 +41,7 @@ k_tones_part(const float *__restrict__ audio, size_t row_stride, size_t nframes,
 	__shared__ long long red_e[TN_WAVES][2];
 	const unsigned int tid = threadIdx.x, lane = tid & (WR_LANES - 1u), u = tid / WR_LANES;
 	WrTonesRow *R = rows + blockIdx.y;
-	const TnCut cut = tn_cut(R->fill, nq, nr, W);
+	const WrTonesCut cut = wrp_tones_cut(R->fill, nq, nr, W);
 	const long long k0 = (long long)blockIdx.x * TN_CHUNK;
 	const long long k1 = k0 + TN_CHUNK < (long long)nframes ? k0 + TN_CHUNK : (long long)nframes;
 	if (k1 <= cut.a_lo)                                          /* whole windows in front of the last: only counted */
@@ -83,10 +54,7 @@ k_tones_part(const float *__restrict__ audio, size_t row_stride, size_t nframes,
 		const long long k = k0 + i;
 		if (k >= k1)
 			break;
-		float v = row[k];
-		if ((__float_as_uint(v) & 0x7fffffffu) >= 0x7f800000u)
-			v = 0.0f;
-		const float w = fminf(fmaxf(v, -64.0f), 64.0f) * 16777216.0f;
+		const float w = row_fixed24(row[k]);
 		wv[i] = w;
 		const long long qv = (long long)(int)rintf(w);
 		const long long e = (qv * qv) >> 14;
@@ -156,7 +124,7 @@ k_tones_latch(WrTonesRow *__restrict__ rows, unsigned long long nq, unsigned int
 	const unsigned int t = threadIdx.x;
 	const unsigned int fill = R->fill;
 	__syncthreads();                                              /* (lane 0 is about to change it) */
-	const TnCut cut = tn_cut(fill, nq, nr, W);
+	const WrTonesCut cut = wrp_tones_cut(fill, nq, nr, W);
 	const bool joined = cut.ends == 1u;                           /* (with fill = 0 the carried sums are 0) */
 #pragma unroll
 	for (unsigned int c = 0; c < 2u; ++c) {
@@ -190,17 +158,17 @@ hipError_t wrk_tones_push(hipStream_t st, const float *audio, size_t row_stride,
 {
 	if (!nrows || !nframes)
 		return hipSuccess;
-	const size_t chunks = (nframes + TN_CHUNK - 1u) / TN_CHUNK;
-	if (!audio || !rows || !t12 || !steps || !ntones || ntones > WR_LANES || window < 16u || window > 65536u ||
-	    nrows > 65535u || chunks > 0x7fffffffu || (nrows > 1 && row_stride < nframes))
+	if (!audio || !rows || !t12 || !steps || !ntones || ntones > WR_LANES || window < TN_WINDOW_MIN || window > TN_WINDOW_MAX ||
+	    nrows > 65535u || (nrows > 1 && row_stride < nframes))
 		return hipErrorInvalidValue;
-	const unsigned long long nq = nframes / window;
-	const unsigned int nr = (unsigned int)(nframes % window);
-	k_tones_part<<<dim3((unsigned int)chunks, (unsigned int)nrows), TN_THREADS, 0, st>>>(audio, row_stride, nframes, nq, nr, rows,
-	                                                                                     t12, steps, ntones, window);
+	const WrTonesPlan g = wrp_tones_plan(nframes, window);
+	if (g.chunks > 0x7fffffffu)
+		return hipErrorInvalidValue;
+	k_tones_part<<<dim3((unsigned int)g.chunks, (unsigned int)nrows), TN_THREADS, 0, st>>>(audio, row_stride, nframes, g.nq, g.nr,
+	                                                                                       rows, t12, steps, ntones, window);
 	hipError_t e = hipGetLastError();
 	if (e != hipSuccess)
 		return e;
-	k_tones_latch<<<(unsigned int)nrows, WR_LANES, 0, st>>>(rows, nq, nr, window);
+	k_tones_latch<<<(unsigned int)nrows, WR_LANES, 0, st>>>(rows, g.nq, g.nr, window);
 	return hipGetLastError();
 }

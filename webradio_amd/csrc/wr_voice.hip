@@ -28,18 +28,12 @@
  * sets in turn.  A muted row's chunks store zeros; its history is written like any other's.
  */
 #include "wr_internal.h"
+#include "wr_rows.h"
 
 static_assert(VOICE_CHUNK == VOICE_THREADS * VOICE_PER, "a chunk is every thread's outputs");
 static_assert(VOICE_PER % 4u == 0 && VOICE_PER <= 8u && VOICE_THREADS == WR_LANES,
               "k_voice_rows: lanes read 16-byte aligned, a window of sixteen registers holds at most eight outputs' inputs, a workgroup is one wave");
 constexpr int PER = (int)VOICE_PER;
-
-__device__ __forceinline__ float vo_clean(float x)
-{
-	if ((__float_as_uint(x) & 0x7fffffffu) >= 0x7f800000u)
-		x = 0.0f;
-	return fminf(fmaxf(x, -65536.0f), 65536.0f);
-}
 
 /* dst[i] = src[i] -- CLEAN: cleaned -- for i < n, lane `tid` every VOICE_THREADS-th of them; a lane has eight loads in flight
  * (a workgroup is one wave: nobody else hides a load's latency) */
@@ -55,7 +49,7 @@ template <bool CLEAN> __device__ __forceinline__ void vo_copy(float *dst, const 
 #pragma unroll
 		for (unsigned int j = 0; j < 8u; ++j)
 			if (i + j * VOICE_THREADS < n)
-				dst[i + j * VOICE_THREADS] = CLEAN ? vo_clean(v[j]) : v[j];
+				dst[i + j * VOICE_THREADS] = CLEAN ? row_clean(v[j]) : v[j];
 	}
 }
 
