@@ -19,6 +19,10 @@ from webradio_amd.device import Tuner
 
 # ---- plain rows -----------------------------------------------------------------------------------------------------------------
 
+# the awkward floats of the resampler's and the bank-limit tests' rows: non-finite, saturating, signed zero, subnormal, 2^16
+SPECIAL = [np.inf, -np.inf, np.nan, 1e30, -1e30, -0.0, 1e-40, 65536.0]
+
+
 def special_rows(nrows, n, seed, max_exp, special):
     """[nrows][n] float32: normal deviates times 10^e, e in [-4, max_exp), both signs, and in every row the values of
     `special` (non-finite, saturating, signed-zero, subnormal ...) at places of its own"""

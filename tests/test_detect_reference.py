@@ -13,7 +13,7 @@ import detect_np as dn
 import launch_plan
 import specavg_np as sa
 from flat_spectrum import MASK_OUT_SHARE
-from test_gpu_spectrum import DB_ATOL
+from speccases import DB_ATOL
 from webradio_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

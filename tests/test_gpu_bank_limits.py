@@ -16,7 +16,7 @@ import resamp_np
 import rowcases
 import tones_np
 import voice_np
-from test_gpu_resamp import SPECIAL
+from rowcases import SPECIAL
 from webradio_amd.device import Resampler, ToneBank, VoiceBank
 
 pytestmark = pytest.mark.gpu

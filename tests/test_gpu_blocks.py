@@ -4,13 +4,12 @@ detector depends on a device libm function (atan2f) and gets a stated tolerance.
 import numpy as np
 import pytest
 
+# FM: out = atan2f(..)/pi/2; device atan2f is within a few ulp of glibc's -> <= 4 ulp of
+# the result range [-0.5, 0.5], i.e. 2.4e-7 absolute
+from tunercases import FM_ATOL
 from webradio_amd import capi
 
 pytestmark = pytest.mark.gpu
-
-# FM: out = atan2f(..)/pi/2; device atan2f is within a few ulp of glibc's -> <= 4 ulp of
-# the result range [-0.5, 0.5], i.e. 2.4e-7 absolute
-FM_ATOL = 2.4e-7
 
 
 @pytest.mark.parametrize("if_hz,rate,n", [(100_000, 2_400_000, 102_400), (-39_843_750, 100_000_000, 50_001),

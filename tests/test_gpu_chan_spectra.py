@@ -2,7 +2,7 @@
 each Receiver's channel filter, io/spectrumsink.cxx:88-142 behind radio.cxx:68-76).
 
 The yardstick throughout: oracle.Spectrum(n) fed the channel IQ that wr_chan_fetch(WR_STAGE_CHAN_IQ) returns for that
-receiver, frames [first_frame, first_frame + n); the comparison is test_gpu_spectrum_real._check_db, unchanged (DB_ATOL
+receiver, frames [first_frame, first_frame + n); the comparison is speccases.check_db, unchanged (DB_ATOL
 on bins within 60 dB of the row's peak).  The input carries noise at -50 dBFS so that every receiver's channel IQ is
 non-zero, which is asserted."""
 import ctypes as C
@@ -12,7 +12,8 @@ import pytest
 import torch
 
 import launch_plan
-from test_gpu_spectrum_real import _bits, _check_db
+from speccases import check_db
+from tunercases import bits_f32
 from webradio_amd import capi, synth
 from webradio_amd.device import Spectrum, Tuner
 
@@ -49,7 +50,7 @@ def _check_rows(oracle, t, chans, rows, first, n, k1, what):
         iq = t.fetch(ch, capi.WR_STAGE_CHAN_IQ, 2 * k1)
         assert iq.size == 2 * k1
         assert float(np.abs(iq[2 * first: 2 * (first + n)]).max()) > 0.0
-        _check_db(rows[t.slot(ch)], _oracle_row(oracle, iq, first, n), what)
+        check_db(rows[t.slot(ch)], _oracle_row(oracle, iq, first, n), what)
 
 
 # ---- sizes and offsets: 70 receivers (two lane groups, one ragged), ONE block of K1 = n + 16 channel frames ----------------
@@ -88,7 +89,7 @@ def test_sizes_and_offsets(dev, oracle, sized, n, where):
     assert rows.shape == (128, n)
     for ch, iq in iqs.items():
         assert iq.size == 2 * k1 and float(np.abs(iq[2 * first: 2 * (first + n)]).max()) > 0.0
-        _check_db(rows[t.slot(ch)], _oracle_row(oracle, iq, first, n), "slot %d first %d" % (t.slot(ch), first))
+        check_db(rows[t.slot(ch)], _oracle_row(oracle, iq, first, n), "slot %d first %d" % (t.slot(ch), first))
     assert spec.frames_done() == 0                       # the spectrum's own frame state is left alone
 
 
@@ -153,7 +154,7 @@ def test_after_a_streaming_launch(dev, oracle):
         _check_rows(oracle, t, chans, rows, first, n, k1, "streaming" if stream else "per block")
         got[stream] = rows[[t.slot(ch) for ch in chans]]
         t.destroy()
-    assert np.array_equal(_bits(got[True]), _bits(got[False]))
+    assert np.array_equal(bits_f32(got[True]), bits_f32(got[False]))
     spec.destroy()
     dev.free(x)
 
@@ -211,7 +212,7 @@ def test_db_dev_form_is_the_array_form(dev, oracle):
     assert t.chan_spectra(spec, 9, db_dev=out) == 128
     dev.sync()
     used = [t.slot(ch) for ch in chans]
-    assert np.array_equal(_bits(dev.download(out, 128 * n).reshape(128, n)[used]), _bits(rows[used]))
+    assert np.array_equal(bits_f32(dev.download(out, 128 * n).reshape(128, n)[used]), bits_f32(rows[used]))
     dev.free(out)
     spec.destroy()
     t.destroy()

@@ -13,7 +13,7 @@ import pytest
 import detect_np as dn
 import specavg_np as sa
 from flat_spectrum import flat
-from test_gpu_spectrum import DB_ATOL
+from speccases import DB_ATOL
 from webradio_amd import capi, synth
 from webradio_amd.device import DETECTION, Spectrum, Tuner
 

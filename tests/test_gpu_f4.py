@@ -7,41 +7,12 @@ import os
 import numpy as np
 import pytest
 
+from tunercases import AUDIO_ATOL, IQ_ATOL, LINEAR_ATOL, OracleChain
 from webradio_amd import capi, synth
 from webradio_amd.device import Tuner
 
 pytestmark = pytest.mark.gpu
 MODE_NAMES = {capi.WR_AM: "AM", capi.WR_FM: "FM", capi.WR_USB: "USB", capi.WR_LSB: "LSB"}
-
-
-class OracleChain:
-    """A Receiver chain assembled from the oracle's blocks with explicit filter lengths:
-    mixer -> LowPass(L1, D1) [-> LowPass(L1b, D1b)] -> demodulator -> LowPass(L2, D2).
-    taps: {"channel" / "second" / "audio": coefficients} in place of that stage's LowPass design (wr_chan_set_taps_n)."""
-
-    def __init__(self, oracle, fs, if_hz, l1, pb1, d1, mode, l2, pb2, d2, stage2=None, taps=None):
-        taps = taps or {}
-        self.o, self.mode = oracle, mode
-        self.table = oracle.sin_table()
-        self.step = oracle.phase_step(if_hz, fs)
-        self.phase = 0
-        self.prev = (0.0, 0.0)
-        self.f1 = oracle.Fir(2, d1, taps.get("channel", oracle.lowpass_design(pb1, fs, l1)))
-        r = fs // d1
-        self.f1b = None
-        if stage2:
-            l1b, pb1b, d1b = stage2
-            self.f1b = oracle.Fir(2, d1b, taps.get("second", oracle.lowpass_design(pb1b, r, l1b)))
-            r //= d1b
-        self.f2 = oracle.Fir(1, d2, taps.get("audio", oracle.lowpass_design(pb2, r, l2)))
-
-    def run(self, iq):
-        mixed, self.phase = self.o.mix(self.table, self.phase, self.step, iq)
-        c = self.f1.process(mixed)
-        if self.f1b is not None:
-            c = self.f1b.process(c)
-        d, self.prev = self.o.demod(self.mode, self.prev, c)
-        return self.f2.process(d), c, d
 
 
 @pytest.mark.parametrize("nco", [capi.WR_NCO_EXACT, capi.WR_NCO_ROTATE])
@@ -74,7 +45,7 @@ def test_fir_length_inside_the_fused_path(dev, oracle, nco, lengths):
                     assert np.array_equal(gc.view(np.uint32), wc.view(np.uint32)), (n, c)
                     assert np.array_equal(ga.view(np.uint32), wa.view(np.uint32)), (n, c)
                 else:
-                    assert np.abs(gc - wc).max() <= 1e-6 and np.abs(ga - wa).max() <= 2e-6, (n, c)
+                    assert np.abs(gc - wc).max() <= IQ_ATOL and np.abs(ga - wa).max() <= LINEAR_ATOL, (n, c)
         t.destroy()
     # what the fused path does not take is refused, not silently shortened
     import ctypes as C
@@ -133,15 +104,15 @@ def test_channel_filter_of_128_and_256_taps_inside_the_tuner(dev, oracle, nco, l
                     assert np.array_equal(gc.view(np.uint32), wc.view(np.uint32)), (n, b, c)
                     assert np.array_equal(ga.view(np.uint32), wa.view(np.uint32)), (n, b, c)
                 else:
-                    assert np.abs(gc - wc).max() <= 1e-6, (n, b, c, float(np.abs(gc - wc).max()))
+                    assert np.abs(gc - wc).max() <= IQ_ATOL, (n, b, c, float(np.abs(gc - wc).max()))
                     if wa.size:                            # AM: |.| is 1-Lipschitz, then the linear audio filter
-                        assert np.abs(ga - wa).max() <= 2e-6 * again, (n, b, c)
+                        assert np.abs(ga - wa).max() <= LINEAR_ATOL * again, (n, b, c)
             wa, wc, _ = rxp.run(iq)
             gc = t.fetch(plain, capi.WR_STAGE_CHAN_IQ, 2 * n)
             if nco == capi.WR_NCO_EXACT:
                 assert np.array_equal(gc.view(np.uint32), wc.view(np.uint32)), (n, b)
             else:
-                assert np.abs(gc - wc).max() <= 1e-6, (n, b)
+                assert np.abs(gc - wc).max() <= IQ_ATOL, (n, b)
         assert float(np.abs(t.fetch(chans[0], capi.WR_STAGE_AUDIO, n)).max()) > 1e-3 or n < d1 * d2     # a live channel
         launches, ms = t.profile_read()
         assert launches == 2 * blocks and 0.0 < ms < 50.0, (launches, ms)
@@ -190,7 +161,7 @@ def test_two_stage_channel_filter_through_the_tuner(dev, oracle, nco, fs, d1, pb
                     assert np.array_equal(gc.view(np.uint32), wc.view(np.uint32)), (n, c)
                     assert np.array_equal(ga.view(np.uint32), wa.view(np.uint32)), (n, c)
                 else:
-                    assert np.abs(gc - wc).max() <= 1e-6 and np.abs(ga - wa).max() <= 2e-6, (n, c)
+                    assert np.abs(gc - wc).max() <= IQ_ATOL and np.abs(ga - wa).max() <= LINEAR_ATOL, (n, c)
             live = max(live, float(np.abs(t.fetch(chans[0], capi.WR_STAGE_AUDIO, n)).max()))
         t.destroy()
     assert live > 1e-3                                     # a live channel, not zeros
@@ -260,9 +231,9 @@ def test_audio_filter_and_second_stage_of_128_and_256_taps_inside_the_tuner(dev,
                     elif wa.size:                          # atan2f: ulps per demodulated frame, then the linear filter
                         assert np.abs(ga - wa).max() <= 4.8e-7 * gain2, (n, b, c)
                 else:
-                    assert np.abs(gc - wc).max() <= 1e-6 * gain1b, (n, b, c, float(np.abs(gc - wc).max()))
+                    assert np.abs(gc - wc).max() <= IQ_ATOL * gain1b, (n, b, c, float(np.abs(gc - wc).max()))
                     if wa.size and not fm:                 # |.| and Re/Im sums are 2-Lipschitz, then the linear filter
-                        assert np.abs(ga - wa).max() <= 2e-6 * gain1b * gain2, (n, b, c)
+                        assert np.abs(ga - wa).max() <= LINEAR_ATOL * gain1b * gain2, (n, b, c)
                 if wa.size and c == 0:
                     live = max(live, float(np.abs(ga).max()))
             wa, wc, _ = rxp.run(iq)
@@ -272,7 +243,7 @@ def test_audio_filter_and_second_stage_of_128_and_256_taps_inside_the_tuner(dev,
                 assert np.array_equal(gc.view(np.uint32), wc.view(np.uint32)), (n, b)
                 assert np.array_equal(ga.view(np.uint32), wa.view(np.uint32)), (n, b)
             else:
-                assert np.abs(gc - wc).max() <= 1e-6 and np.abs(ga - wa).max() <= 4e-6, (n, b)
+                assert np.abs(gc - wc).max() <= IQ_ATOL and np.abs(ga - wa).max() <= 4e-6, (n, b)
         assert live > 1e-3, (n, live)                      # a live channel, not zeros
         t.destroy()
     assert dev.lib.wr_block_kernel_calls() == calls0       # nothing left the tuner's own launches
@@ -353,7 +324,7 @@ def test_long_filters_at_c2_full_size(dev, oracle):
     g2 = max(1.0, float(np.abs(oracle.lowpass_design(pb2, r1 // 5, 256)).sum()))
     worst_iq = max(float(np.abs(a[0] - b[0]).max()) for a, b in zip(outs[capi.WR_NCO_EXACT], outs[capi.WR_NCO_ROTATE]))
     worst_au = max(float(np.abs(a[1] - b[1]).max()) for a, b in zip(outs[capi.WR_NCO_EXACT], outs[capi.WR_NCO_ROTATE]))
-    assert worst_iq <= 1e-6 * g1b and worst_au <= 2e-6 * g1b * g2, (worst_iq, worst_au)
+    assert worst_iq <= IQ_ATOL * g1b and worst_au <= LINEAR_ATOL * g1b * g2, (worst_iq, worst_au)
     assert max(float(np.abs(a[1]).max()) for a in outs[capi.WR_NCO_EXACT][::4]) > 1e-3       # the carrier channels are live
     m = 400_000
     xh = x[: 2 * m].cpu().numpy()
@@ -455,7 +426,7 @@ def test_random_f4_configurations(dev, oracle, seed):
                 assert np.array_equal(gc.view(np.uint32), wc.view(np.uint32)), (seed, b, c)
                 assert np.array_equal(ga.view(np.uint32), want.view(np.uint32)), (seed, b, c)
             else:
-                assert np.abs(gc - wc).max() <= 1e-6, (seed, b, c)
+                assert np.abs(gc - wc).max() <= IQ_ATOL, (seed, b, c)
                 g = 10.0 ** (specs[c][2] / 20.0)
                 # a squelch decision may differ where the power sits within 1e-6 of the threshold
                 differ = np.abs(ga - want) > 4e-6 * max(1.0, g)
@@ -505,11 +476,11 @@ def test_fused_post_stage_for_audio_decimations_8_and_10(dev, oracle, d2):
         outs.append(got)
         t.destroy()
     taps2 = oracle.lowpass_design(audio_rate // 2, chan_rate)
-    tol = 2e-6 * max(1.0, float(np.abs(taps2).sum()))
+    tol = LINEAR_ATOL * max(1.0, float(np.abs(taps2).sum()))
     for b in range(len(blocks)):
         assert np.array_equal(outs[0][b].view(np.uint32), outs[1][b].view(np.uint32)), b
         for c in range(nch):
             if c % 4 == 0:                                     # the FM receivers: they sit on the carriers (ifs[::4])
-                assert np.abs(outs[0][b][c] - want[b][c]).max() <= 1e-5, (b, c)
+                assert np.abs(outs[0][b][c] - want[b][c]).max() <= AUDIO_ATOL, (b, c)
             else:
                 assert np.abs(outs[0][b][c] - want[b][c]).max() <= tol, (b, c)

@@ -7,12 +7,12 @@ import os
 import numpy as np
 import pytest
 
+from tunercases import FM_ATOL
 from webradio_amd import capi, synth
 from webradio_amd.device import Tuner
 
 pytestmark = pytest.mark.gpu
 
-FM_ATOL = 2.4e-7
 RATES = [  # (fs, chan_rate, audio_rate): integer related
     (2_000_000, 5_000, 1_000), (2_000_000, 250_000, 50_000), (2_048_000, 256_000, 32_000),
     (240_000, 24_000, 8_000), (1_000_000, 100_000, 100_000), (960_000, 48_000, 48_000),

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import _proc
-from test_gpu_spectrum import DB_ATOL
+from speccases import DB_ATOL
 
 pytestmark = pytest.mark.gpu
 

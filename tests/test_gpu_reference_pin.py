@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import refcases
+from tunercases import hip_chain, hip_chain_stream
 from webradio_amd import capi
 from webradio_amd.device import Tuner, Spectrum
 
@@ -75,65 +76,6 @@ def test_live_mixer(live, oracle, dev, name):
     assert np.array_equal(y.cpu().numpy().view(np.uint32), want.view(np.uint32))
 
 
-def _hip_chain(dev, c, iq, nco):
-    t = Tuner(dev, c["fs"], 1, c["block"], nco)
-    ch = t.add_receiver(c["if_hz"], c["cpb"], c["crate"], c["mode"], c["apb"], c["arate"])
-    t.keep_stages(capi.WR_STAGE_DEMOD)
-    n = c["block"]
-    audio, chan, dem = [], [], []
-    for b in range(c["blocks"]):
-        t.submit_host(iq[2 * n * b: 2 * n * (b + 1)])
-        chan.append(t.fetch(ch, capi.WR_STAGE_CHAN_IQ, 2 * n))
-        dem.append(t.fetch(ch, capi.WR_STAGE_DEMOD, n))
-        audio.append(t.fetch(ch, capi.WR_STAGE_AUDIO, n))
-    t.destroy()
-    return np.concatenate(audio), np.concatenate(chan), np.concatenate(dem)
-
-
-def _stream_cut(c):
-    """The block size a streaming launch takes (wr_tuner_set_streaming: at least 64 channel-rate frames, whole audio
-    frames per block): the case's own where that qualifies, otherwise consecutive blocks merged -- a frame's bits do not
-    depend on where the stream is cut into blocks (lowpass.cxx:138-142 carries the history over)."""
-    d1, d2 = c["fs"] // c["crate"], c["crate"] // c["arate"]
-    for m in range(1, c["blocks"] + 1):
-        n = c["block"] * m
-        if c["blocks"] % m == 0 and n >= 64 * d1 and n % (d1 * d2) == 0:
-            return n
-    raise AssertionError("no cut of this case is eligible for a streaming launch")
-
-
-def _hip_chain_stream(dev, c, iq):
-    """The same Receiver through k_tuner_stream -- the kernel bench.py times: the input resident in device memory,
-    Tuner.streaming(True), one submit_device per block (the first opens the launch, the others ring its doorbell), the
-    audio of EVERY block out of the pinned ring, the last block's channel IQ.  Asserts that the launch was live and took
-    every block (no silent fall-back to a launch per block)."""
-    import torch
-    n = _stream_cut(c)
-    nblk = c["block"] * c["blocks"] // n
-    x = torch.from_numpy(np.ascontiguousarray(iq)).cuda()
-    torch.cuda.synchronize()
-    t = Tuner(dev, c["fs"], 1, n, capi.WR_NCO_ROTATE)
-    ch = t.add_receiver(c["if_hz"], c["cpb"], c["crate"], c["mode"], c["apb"], c["arate"])
-    t.audio_ring(nblk)
-    t.streaming(True)
-    for b in range(nblk):
-        t.submit_device(x[2 * n * b: 2 * n * (b + 1)], n)
-    live, launches, blocks = t.stream_info()
-    assert live and launches == 1 and blocks == nblk, (live, launches, blocks)
-    t.flush()
-    assert t.stream_info()[0] is False
-    slot, audio = t.slot(ch), []
-    for b in range(nblk):
-        a, seq = t.ring_acquire()
-        assert seq == b
-        audio.append(a[slot].copy())
-        t.ring_release()
-    chan_last = t.fetch(ch, capi.WR_STAGE_CHAN_IQ, 2 * n)
-    t.destroy()
-    del x
-    return np.concatenate(audio), chan_last
-
-
 @pytest.mark.parametrize("name", sorted(refcases.CHAINS))
 def test_live_receiver_chain(live, oracle, dev, gold, name):
     """The Receiver chain of radio.cxx:68-83 on the reference's own blocks: channel IQ, demodulator output and
@@ -150,12 +92,12 @@ def test_live_receiver_chain(live, oracle, dev, gold, name):
     for got, want, tol in ((o_chan, w_chan, refcases.CHAN_TOL), (o_dem, w_dem, refcases.AUDIO_TOL), (o_audio, w_audio, refcases.AUDIO_TOL)):
         assert got.shape == want.shape and np.abs(got - want).max() <= tol
     for nco in (capi.WR_NCO_EXACT, capi.WR_NCO_ROTATE):
-        g_audio, g_chan, g_dem = _hip_chain(dev, c, iq, nco)
+        g_audio, g_chan, g_dem = hip_chain(dev, c, iq, nco)
         assert g_chan.shape == w_chan.shape and np.abs(g_chan - w_chan).max() <= refcases.CHAN_TOL, nco
         assert g_audio.shape == w_audio.shape and np.abs(g_audio - w_audio).max() <= refcases.AUDIO_TOL, nco
         assert np.abs(g_dem - w_dem).max() <= refcases.AUDIO_TOL, nco
     # ... and through the streaming launch (k_tuner_stream, what bench.py times), against the reference itself
-    s_audio, s_chan = _hip_chain_stream(dev, c, iq)
+    s_audio, s_chan = hip_chain_stream(dev, c, iq)
     assert s_audio.shape == w_audio.shape and np.abs(s_audio - w_audio).max() <= refcases.AUDIO_TOL
     assert s_chan.size and np.abs(s_chan - w_chan[-s_chan.size:]).max() <= refcases.CHAN_TOL
     if gold is not None:
@@ -284,11 +226,11 @@ def test_hip_path_against_committed_reference_vectors(dev, name):
     c = refcases.CHAINS[name]
     iq = refcases.chain_input(c)
     assert np.array_equal(refcases.sha(iq), g["sha_chain_" + name])
-    audio, chan, dem = _hip_chain(dev, c, iq, capi.WR_NCO_ROTATE)
+    audio, chan, dem = hip_chain(dev, c, iq, capi.WR_NCO_ROTATE)
     assert np.abs(chan - g["chain_%s_chan" % name]).max() <= refcases.CHAN_TOL
     assert np.abs(audio - g["chain_%s_audio" % name]).max() <= refcases.AUDIO_TOL
     # the streaming launch (k_tuner_stream) against the same committed vectors
-    s_audio, s_chan = _hip_chain_stream(dev, c, iq)
+    s_audio, s_chan = hip_chain_stream(dev, c, iq)
     assert s_audio.shape == g["chain_%s_audio" % name].shape
     assert np.abs(s_audio - g["chain_%s_audio" % name]).max() <= refcases.AUDIO_TOL
     assert s_chan.size and np.abs(s_chan - g["chain_%s_chan" % name][-s_chan.size:]).max() <= refcases.CHAN_TOL

@@ -16,13 +16,12 @@ import pytest
 import resamp_np
 import rowcases
 import tones_np
-from rowcases import BLOCK, K2, NBLOCKS, SENTINEL, fm_stream  # noqa: F401  (fm_stream: the fixture)
+from rowcases import BLOCK, K2, NBLOCKS, SENTINEL, SPECIAL, fm_stream  # noqa: F401  (fm_stream: the fixture)
 from webradio_amd import capi
 from webradio_amd.device import Resampler, resamp_design
 
 pytestmark = pytest.mark.gpu
 
-SPECIAL = [np.inf, -np.inf, np.nan, 1e30, -1e30, -0.0, 1e-40, 65536.0]
 # (L, M, P) -> the rates wr_resamp_design is asked for; None: it makes no taps for this shape (see above)
 SHAPES = {(3, 2, 4): None, (24, 25, 32): (50_000, 48_000), (24, 125, 64): (250_000, 48_000), (441, 500, 32): (50_000, 44_100),
           (1, 1, 8): None, (8, 1, 16): (6_000, 48_000), (1, 8, 64): None}

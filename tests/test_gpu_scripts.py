@@ -14,8 +14,8 @@ The scripts play the resampler, the DCS bank and the voice bank (with a second r
 first and only then downloads the tuner's rows, so that the push is what flushes; every push is compared with the model and,
 on every live row, with the restatement fed the library's own rows.
 
-Tolerances are the suite's own: DB_ATOL on bins within 60 dB of a row's peak (test_gpu_spectrum_real._check_db), FM_ATOL
-and the ROTATE bound through the audio filter's absolute gain (test_gpu_fuzz.py), 1e-6 on ROTATE channel IQ (test_gpu_f4.py)."""
+Tolerances are the suite's own: DB_ATOL on bins within 60 dB of a row's peak (speccases.db_error), FM_ATOL and the ROTATE
+bound through the audio filter's absolute gain, IQ_ATOL on ROTATE channel IQ (tunercases.py)."""
 import ctypes as C
 
 import numpy as np
@@ -24,8 +24,8 @@ import pytest
 import agc_np
 import rowcases
 import tuner_model as tm
-from test_gpu_f4 import OracleChain
-from test_gpu_spectrum import DB_ATOL
+from speccases import DB_ATOL, db_error
+from tunercases import IQ_ATOL, LINEAR_ATOL, OracleChain, bits_f32
 from webradio_amd import capi
 from webradio_amd.device import Resampler, Spectrum, ToneBank, Tuner, VoiceBank
 
@@ -35,16 +35,12 @@ CPB, APB = tm.CHAN_PASSBANDS[0], tm.AUDIO_PASSBAND
 WR_TUNE_DDC_NG2_MIN_PASSES = 1                                            # include/webradio_amd.h: enum wr_tunable
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def _same_bits(a, b):
     a, b = np.asarray(a), np.asarray(b)
     if a.shape != b.shape:
         return False
     if a.dtype == np.float32 or b.dtype == np.float32:
-        return np.array_equal(_bits(a), _bits(b))
+        return np.array_equal(bits_f32(a), bits_f32(b))
     return np.array_equal(a, b)
 
 
@@ -57,12 +53,6 @@ def _same(a, b):
     if a is None or b is None:
         return a is b
     return _same_bits(a, b)
-
-
-def _db_close(got, want):
-    """test_gpu_spectrum_real._check_db: DB_ATOL on the bins within 60 dB of the row's peak"""
-    strong = want >= want.max() - 60.0
-    return float(np.abs(got[strong] - want[strong]).max()) <= DB_ATOL
 
 
 class GpuPlay:
@@ -307,7 +297,7 @@ def _audio_is_the_models(m, c, got, want, what):
     r = m.rxs[c]
     assert got.shape == want.shape, what
     if not r.was_fm:
-        bad = np.flatnonzero(_bits(got) != _bits(want))
+        bad = np.flatnonzero(bits_f32(got) != bits_f32(want))
         assert bad.size == 0, (what, c, bad[:4], got[bad[:4]], want[bad[:4]])
         return 1
     if not r.used_agc and want.size:
@@ -352,11 +342,11 @@ def _check_exact(play, op, got, want, seen):
     elif k == "spectra":
         assert got.keys() == want.keys()
         for c in got:
-            assert _db_close(got[c], want[c]), (what, c)
+            assert db_error(got[c], want[c]) <= DB_ATOL, (what, c)
     elif k == "audio_spectrum":
         for c in got:
             if not m.rxs[c].was_fm and float(np.abs(m.audio(c)[: tm.AUDIO_SPECTRUM_N]).max()) > 0.0:
-                assert _db_close(got[c], want[c]), (what, c)
+                assert db_error(got[c], want[c]) <= DB_ATOL, (what, c)
     elif k in ("tones", "tones_again"):
         for c, r in m.rxs.items():
             if not r.was_fm:
@@ -440,7 +430,7 @@ def _check_rotate(model, op, got, want, ring):
         by_slot = {r.slot: c for c, r in m.rxs.items()}
         pairs = [(by_slot[s], got[s], want[s]) for s in want]
     elif k == "fetch_chan":
-        assert float(np.abs(got - want).max()) <= 1e-6, op                # (test_gpu_f4.py: ROTATE channel IQ)
+        assert float(np.abs(got - want).max()) <= IQ_ATOL, op             # (ROTATE channel IQ)
     n = 0
     for c, g, w in pairs:
         r = m.rxs[c]
@@ -491,7 +481,7 @@ def test_script_in_every_launch_mode(dev, scripts, seed):
         for i, (a, b) in enumerate(zip(base, results)):
             assert _same(a, b), (how, i, [op for op in script["ops"] if op[0] != "drain"][i])
         assert other_ring.shape == ring.shape, how
-        assert np.array_equal(_bits(ring)[mask], _bits(other_ring)[mask]), how
+        assert np.array_equal(bits_f32(ring)[mask], bits_f32(other_ring)[mask]), how
         assert other_agc == agc, how
     print("seed %d: stream_info %s, agc_info %s, %d audio rows held to the model" % (seed, plays["stream"][2], agc, held_to_model))
     assert plays["stream"][2][2] >= 3                                     # blocks that did stream
@@ -730,7 +720,7 @@ def test_a_receiver_moves_to_another_rate_group_and_back(dev):
         for c in range(nrx):
             s = t.slot(c)
             assert _same((mean[s], peak[s], int(muted[s])), m.levels(c)), (pos[0] // n, c)
-            assert _db_close(rows[s], m.chan_spectrum(c, 7)), (pos[0] // n, c)
+            assert db_error(rows[s], m.chan_spectrum(c, 7)) <= DB_ATOL, (pos[0] // n, c)
             if modes[c] != tm.FM:
                 for g, w in zip(got_bank, ref_bank):
                     assert np.array_equal(g[s], w[s]), (pos[0] // n, c)
@@ -774,20 +764,6 @@ def test_a_receiver_moves_to_another_rate_group_and_back(dev):
 
 # ---- 4: caller-designed taps ----------------------------------------------------------------------------------------------------
 
-class _Chain(OracleChain):
-    """OracleChain over blocks of several sizes: its filters keep their true histories (wr_oracle.fir_keep_history; quirk Q7)"""
-
-    def run(self, iq):
-        n = np.asarray(iq).size // 2
-        tm.oracle.fir_keep_history(self.f1.s, 2 * n)
-        k = n // self.f1.decimation
-        if self.f1b is not None:
-            tm.oracle.fir_keep_history(self.f1b.s, 2 * k)
-            k //= self.f1b.decimation
-        tm.oracle.fir_keep_history(self.f2.s, k)
-        return OracleChain.run(self, iq)
-
-
 STAGES = {"channel": 0, "audio": 1, "second": 2}                          # WR_FILTER_CHANNEL, WR_FILTER_AUDIO, WR_FILTER_CHANNEL2
 
 
@@ -824,8 +800,9 @@ def test_caller_designed_taps(dev, oracle, stage, length, nco):
                 capi.check(lib.wr_chan_set_taps(t.h, ch, STAGES[stage], capi.ptr(taps), decim))     # the 64-tap entry
             else:
                 capi.check(lib.wr_chan_set_taps_n(t.h, ch, STAGES[stage], capi.ptr(taps), length, decim))
-        rxs = {c: _Chain(oracle, fs, ifs[c], 64, pb1, d1, modes[c % 3], 64, pb2, d2, stage2=(64, pb1b, d1b) if two else None,
-                         taps={stage: sets[c in own]}) for c in probe}
+        # (blocks of several sizes: the oracle's filters keep their true histories, quirk Q7)
+        rxs = {c: OracleChain(oracle, fs, ifs[c], 64, pb1, d1, modes[c % 3], 64, pb2, d2, stage2=(64, pb1b, d1b) if two else None,
+                              taps={stage: sets[c in own]}, keep_history=True) for c in probe}
         gain = {s: max(1.0, float(np.abs(sets[s]).sum())) for s in (0, 1)}
         gain2 = max(1.0, float(np.abs(oracle.lowpass_design(pb2, r_dem)).sum()))
         pos, live = 0, 0.0
@@ -840,13 +817,13 @@ def test_caller_designed_taps(dev, oracle, stage, length, nco):
                 ga = t.fetch(c, capi.WR_STAGE_AUDIO, n)
                 assert gc.size == wc.size == 2 * (n // d1 // d1b) and ga.size == wa.size == n // d1 // d1b // d2, (n, c)
                 if nco == capi.WR_NCO_EXACT:
-                    assert np.array_equal(_bits(gc), _bits(wc)), (n, c)
-                    assert np.array_equal(_bits(ga), _bits(wa)), (n, c)
+                    assert np.array_equal(bits_f32(gc), bits_f32(wc)), (n, c)
+                    assert np.array_equal(bits_f32(ga), bits_f32(wa)), (n, c)
                 else:
                     g = gain[c in own]
-                    assert float(np.abs(gc - wc).max()) <= 1e-6, (n, c, float(np.abs(gc - wc).max()))      # (test_gpu_f4.py)
-                    # |.| and the sums of Re and Im are 2-Lipschitz, then the linear audio filter (test_gpu_f4.py)
-                    assert float(np.abs(ga - wa).max()) <= 2e-6 * (g if stage == "audio" else gain2), (n, c)
+                    assert float(np.abs(gc - wc).max()) <= IQ_ATOL, (n, c, float(np.abs(gc - wc).max()))
+                    # |.| and the sums of Re and Im are 2-Lipschitz, then the linear audio filter (tunercases.py)
+                    assert float(np.abs(ga - wa).max()) <= LINEAR_ATOL * (g if stage == "audio" else gain2), (n, c)
                 live = max(live, float(np.abs(ga).max()))
         assert live > 1e-4                                                # a live channel, not zeros
         count = C.c_int()

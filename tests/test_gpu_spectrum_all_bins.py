@@ -7,7 +7,7 @@ of bins -- asserted on every frame: at most MASK_OUT_SHARE of them are left out 
 at.  The reference is oracle.spectrum_np (float32 window and product, float64 FFT), which
 tests/test_spectrum_flat_reference.py holds to oracle.Spectrum.
 
-Tolerances: BIN_RTOL and DB_ATOL of tests/test_gpu_spectrum.py, unchanged.  A float32 radix-2 Stockham restatement of
+Tolerances: BIN_RTOL and DB_ATOL of tests/speccases.py, unchanged.  A float32 radix-2 Stockham restatement of
 one frame of this input in numpy stays within 1.9e-7 * peak and 4e-4 dB up to 2^20 points: tenfold room.
 Every check prints the figures it then asserts on (the lines that start with "all-bins:")."""
 import numpy as np
@@ -15,7 +15,7 @@ import pytest
 
 import wr_oracle
 from flat_spectrum import MASK_OUT_SHARE, bin_error, db_error, flat, frames_of, interleaved, rows_db_error
-from test_gpu_spectrum import BIN_RTOL, DB_ATOL
+from speccases import BIN_RTOL, DB_ATOL
 from webradio_amd.device import Spectrum
 
 pytestmark = pytest.mark.gpu

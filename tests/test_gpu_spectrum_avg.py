@@ -3,7 +3,7 @@
 Two yardsticks (tests/specavg_np.py).  To the bit, with linear rows, on the sizes one workgroup transforms: the rule
 restated in float32 numpy on the bins a second Spectrum gives for each frame pushed on its own.  In dB, on every path and
 every bin: the float64 reference -- oracle.spectrum_np per frame, averaged or maximised as powers -- under the mask and
-share check of tests/test_gpu_spectrum_all_bins.py with DB_ATOL of tests/test_gpu_spectrum.py, unchanged: every frame's row
+share check of tests/test_gpu_spectrum_all_bins.py with DB_ATOL of tests/speccases.py, unchanged: every frame's row
 is held to it already, a mean of such rows is no further off, and the order of summation adds under 1e-4 dB at 259
 frames (tests/test_spectrum_avg_reference.py prints that figure).  Every check prints the figures it then asserts on."""
 import ctypes as C
@@ -13,7 +13,8 @@ import pytest
 
 import specavg_np as sa
 from flat_spectrum import MASK_OUT_SHARE
-from test_gpu_spectrum import DB_ATOL
+from speccases import DB_ATOL
+from tunercases import bits_f32
 from webradio_amd import capi, synth
 from webradio_amd.device import Spectrum, Tuner
 
@@ -23,10 +24,6 @@ pytestmark = pytest.mark.gpu
 def _say(what, n, **figures):
     print("spectrum-avg: %-30s n=%-8d %s" % (what, n, "  ".join(("%s=%d" if isinstance(v, int) else "%s=%.3g") % (k, v)
                                                                 for k, v in figures.items())))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _avg(dev, spec, stream, F, groups=1, stride=0, linear=False, want=("mean", "peak")):
@@ -73,11 +70,11 @@ def test_the_rule_to_the_bit(dev, oracle, real, n, hop):
         mean, peak = _avg(dev, s, stream, F, linear=True)
         s.destroy()
         want_mean, want_peak = sa.restate_linear(_frame_bins(dev, sa.group_frames(stream, real, n, hop, F), real))
-        same = (int((_bits(mean[0]) != _bits(want_mean)).sum()), int((_bits(peak[0]) != _bits(want_peak)).sum()))
+        same = (int((bits_f32(mean[0]) != bits_f32(want_mean)).sum()), int((bits_f32(peak[0]) != bits_f32(want_peak)).sum()))
         _say("rule to the bit, %s" % ("real" if real else "IQ"), n, hop=hop, frames=F, mean_differ=same[0], peak_differ=same[1])
         assert same == (0, 0)
         if F == 1:
-            assert np.array_equal(_bits(mean), _bits(peak))
+            assert np.array_equal(bits_f32(mean), bits_f32(peak))
 
 
 # ---- 2. every path, every bin, in dB ------------------------------------------------------------------------------------------
@@ -102,7 +99,7 @@ def test_one_output_alone_is_the_same_row(dev, oracle):
     only_mean = _avg(dev, s, stream, F, want=("mean",))[0]
     only_peak = _avg(dev, s, stream, F, want=("peak",))[1]
     s.destroy()
-    assert np.array_equal(_bits(only_mean), _bits(mean)) and np.array_equal(_bits(only_peak), _bits(peak))
+    assert np.array_equal(bits_f32(only_mean), bits_f32(mean)) and np.array_equal(bits_f32(only_peak), bits_f32(peak))
 
 
 # ---- 3. groups ------------------------------------------------------------------------------------------------------------------
@@ -121,7 +118,7 @@ def test_groups(dev, oracle, real, n, hop, F, groups, stride):
         differ = 0
         for g in range(groups):
             wm, wp = sa.restate_linear(_frame_bins(dev, sa.group_frames(stream, real, n, hop, F, g, stride), real))
-            differ += int((_bits(lin_mean[g]) != _bits(wm)).sum()) + int((_bits(lin_peak[g]) != _bits(wp)).sum())
+            differ += int((bits_f32(lin_mean[g]) != bits_f32(wm)).sum()) + int((bits_f32(lin_peak[g]) != bits_f32(wp)).sum())
         _say("groups to the bit", n, groups=groups, differ=differ)
         assert differ == 0
     # G calls with one group each: dB and linear
@@ -138,7 +135,7 @@ def test_groups(dev, oracle, real, n, hop, F, groups, stride):
     dev.free(p)
     s.destroy()
     for a, b in zip(single, (mean, peak, lin_mean, lin_peak)):
-        assert np.array_equal(_bits(a), _bits(b))
+        assert np.array_equal(bits_f32(a), bits_f32(b))
 
 
 def test_a_cut_between_chunks_leaves_no_trace(dev, oracle):
@@ -151,7 +148,7 @@ def test_a_cut_between_chunks_leaves_no_trace(dev, oracle):
     mean, peak = _avg(dev, s, stream, F, linear=True)
     s.destroy()
     wm, wp = sa.restate_linear(_frame_bins(dev, sa.group_frames(stream, real, n, hop, F), real))
-    differ = (int((_bits(mean[0]) != _bits(wm)).sum()), int((_bits(peak[0]) != _bits(wp)).sum()))
+    differ = (int((bits_f32(mean[0]) != bits_f32(wm)).sum()), int((bits_f32(peak[0]) != bits_f32(wp)).sum()))
     _say("three chunks to the bit", n, frames=F, mean_differ=differ[0], peak_differ=differ[1])
     assert differ == (0, 0)
 
@@ -251,7 +248,7 @@ def test_averaged_audio_spectra_of_a_tuner(dev, oracle):
     a, stride, frames = t.audio_dev()
     srows2 = _audio_avg(dev, t, spec, a, stride, audio.shape[0], F)
     assert [t.slot(ch) for ch in chans] == used
-    assert np.array_equal(_bits(srows2[:, used]), _bits(rows2[:, used]))
+    assert np.array_equal(bits_f32(srows2[:, used]), bits_f32(rows2[:, used]))
     t.destroy()
     spec.destroy()
     dev.free(x)
@@ -284,7 +281,7 @@ def test_rows_waterfall_is_its_restatement(dev, oracle):
             gdb = dev.download(odb, nrows * width).reshape(nrows, width)
             gpal = dev.download(opal, nrows * width, np.uint8).reshape(nrows, width)
             wdb, wpal = sa.rows_waterfall(rows, width, hold)
-            assert np.array_equal(_bits(gdb), _bits(wdb)), (width, hold)
+            assert np.array_equal(bits_f32(gdb), bits_f32(wdb)), (width, hold)
             assert np.array_equal(gpal, wpal), (width, hold)
             assert np.all(gdb[groups] == -10000.0) and np.all(gpal[groups] == 0)
             inside = max(inside, float(((wpal > 0) & (wpal < 255)).mean()))
@@ -292,7 +289,7 @@ def test_rows_waterfall_is_its_restatement(dev, oracle):
             s.rows_waterfall(db, nrows, width, hold, odb, None)
             s.rows_waterfall(db, nrows, width, hold, None, opal)
             dev.sync()
-            assert np.array_equal(_bits(dev.download(odb, nrows * width)), _bits(wdb.ravel()))
+            assert np.array_equal(bits_f32(dev.download(odb, nrows * width)), bits_f32(wdb.ravel()))
             dev.free(odb)
             dev.free(opal)
     _say("rows_waterfall", n, rows=nrows, inside_palette=inside)
@@ -303,8 +300,8 @@ def test_rows_waterfall_is_its_restatement(dev, oracle):
     o = dev.malloc(F * 8 * 4)
     s.rows_waterfall(bdb, F, 8, 1, o, None)
     dev.sync()
-    assert np.array_equal(_bits(dev.download(o, F * 8).reshape(F, 8)),
-                          _bits(sa.rows_waterfall(dev.download(bdb, F * n).reshape(F, n), 8, 1)[0]))
+    assert np.array_equal(bits_f32(dev.download(o, F * 8).reshape(F, 8)),
+                          bits_f32(sa.rows_waterfall(dev.download(bdb, F * n).reshape(F, n), 8, 1)[0]))
     for q in (db, p, bdb, o):
         dev.free(q)
     s.destroy()
@@ -326,7 +323,7 @@ def test_the_spectrum_s_own_frames_are_left_alone(dev, oracle, real, n, hop, F):
     _avg(dev, s, other, F)
     after = (s.frames_done(), s.get_bins(), s.get_db())
     assert after[0] == before[0]
-    assert np.array_equal(_bits(after[1]), _bits(before[1])) and np.array_equal(_bits(after[2]), _bits(before[2]))
+    assert np.array_equal(bits_f32(after[1]), bits_f32(before[1])) and np.array_equal(bits_f32(after[2]), bits_f32(before[2]))
     s.push_host(other[: ch * hop])                        # ... and the next push completes the next frame as ever
     assert s.frames_done() == 3
     s.destroy()

@@ -1,7 +1,7 @@
 """-m gpu: the spectrum of REAL samples (wr_spectrum_create_real; the reference's FIXMEs at io/spectrumsink.cxx:62-64).
 
 The definition: what the IQ sink gives for the frames (x[n], 0) -- so the oracle is oracle.Spectrum(n) fed (x, 0)
-interleaved, and the tolerances are those of tests/test_gpu_spectrum.py, unchanged: BIN_RTOL * the frame's peak bin on
+interleaved, and the tolerances are those of tests/speccases.py, unchanged: BIN_RTOL * the frame's peak bin on
 all n complex bins, DB_ATOL on bins within 60 dB of the peak.  (A float32 emulation of this formulation -- radix-2
 transform of n/2 packed points, untangle step, twiddles rounded from double -- stays within 1.2e-7 * peak of a float64
 FFT for n = 8 ... 2^20: the bound has tenfold room.)  Every check prints the figures it then asserts on."""
@@ -10,7 +10,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_spectrum import BIN_RTOL, DB_ATOL
+from speccases import BIN_RTOL, check_db
+from tunercases import bits_f32
 from webradio_amd import capi, synth
 from webradio_amd.device import Spectrum, Tuner
 
@@ -45,13 +46,6 @@ def _oracle_frame(oracle, x):
     return _want[key]
 
 
-def _check_db(got_db, want_db, what=""):
-    strong = want_db >= want_db.max() - 60.0
-    err = float(np.abs(got_db[strong] - want_db[strong]).max())
-    print("%s n=%d dB error on strong bins %.3g (bound %.3g)" % (what, want_db.size, err, DB_ATOL))
-    assert err <= DB_ATOL
-
-
 def _check(spec, want, what=""):
     want_db, want_bins = want
     got_bins = spec.get_bins()
@@ -59,11 +53,7 @@ def _check(spec, want, what=""):
     err = float(np.abs(got_bins - want_bins).max())
     print("%s n=%d bin error %.3g x peak (bound %.3g)" % (what, want_db.size, err / peak, BIN_RTOL))
     assert err <= BIN_RTOL * peak
-    _check_db(spec.get_db(), want_db, what)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+    check_db(spec.get_db(), want_db, what)
 
 
 def _assert_symmetric(spec):
@@ -71,12 +61,12 @@ def _assert_symmetric(spec):
     z = spec.get_bins()
     re, im = z[0::2], z[1::2]
     k = np.arange(1, n // 2)
-    assert np.array_equal(_bits(re[n - k]), _bits(re[k]))
-    assert np.array_equal(_bits(im[n - k]), _bits(-im[k]))
-    assert _bits(im[:1])[0] == 0 and _bits(im[n // 2: n // 2 + 1])[0] == 0      # exactly +0
+    assert np.array_equal(bits_f32(re[n - k]), bits_f32(re[k]))
+    assert np.array_equal(bits_f32(im[n - k]), bits_f32(-im[k]))
+    assert bits_f32(im[:1])[0] == 0 and bits_f32(im[n // 2: n // 2 + 1])[0] == 0      # exactly +0
     db = spec.get_db()
     j = np.arange(1, n // 2)
-    assert np.array_equal(_bits(db[n // 2 + j]), _bits(db[n // 2 - j]))
+    assert np.array_equal(bits_f32(db[n // 2 + j]), bits_f32(db[n // 2 - j]))
 
 
 # 8: a 4-point packed transform; 16384: the largest in one pass; 32768: the smallest with the untangle kernel;
@@ -217,9 +207,9 @@ def test_batch_db_rows(dev, oracle, n, rows, pad):
     s = Spectrum(dev, n, real=True)
     got = _rows_dev(dev, s, x, stride, rows)
     for r in range(rows):
-        _check_db(got[r], _oracle_frame(oracle, x[r * stride: r * stride + n])[0], "rows")
+        check_db(got[r], _oracle_frame(oracle, x[r * stride: r * stride + n])[0], "rows")
         j = np.arange(1, n // 2)
-        assert np.array_equal(_bits(got[r][n // 2 + j]), _bits(got[r][n // 2 - j]))
+        assert np.array_equal(bits_f32(got[r][n // 2 + j]), bits_f32(got[r][n // 2 - j]))
     s.destroy()
 
 
@@ -229,7 +219,7 @@ def test_batch_db_reads_frames_a_hop_of_floats_apart(dev, oracle, n, hop, frames
     s = Spectrum(dev, n, hop, real=True)
     got = _rows_dev(dev, s, x, hop, frames, how="hop")
     for f in range(frames):
-        _check_db(got[f], _oracle_frame(oracle, x[f * hop: f * hop + n])[0], "batch_db")
+        check_db(got[f], _oracle_frame(oracle, x[f * hop: f * hop + n])[0], "batch_db")
     s.destroy()
 
 
@@ -241,7 +231,7 @@ def test_rows_of_an_iq_spectrum_are_batch_db_s(dev, n, rows):
     assert s.channels() == 2
     a = _rows_dev(dev, s, iq, n, rows, how="hop")
     b = _rows_dev(dev, s, iq, n, rows, how="rows")
-    assert np.array_equal(_bits(a), _bits(b))
+    assert np.array_equal(bits_f32(a), bits_f32(b))
     s.destroy()
 
 
@@ -299,7 +289,7 @@ def test_audio_spectra_of_every_receiver_of_a_tuner(dev, oracle):
         audio = t.fetch(ch, capi.WR_STAGE_AUDIO, K2)
         assert audio.size == K2
         if float(np.abs(audio).max()) > 0.0:
-            _check_db(rows[t.slot(ch)], _oracle_frame(oracle, audio)[0], "tuner")
+            check_db(rows[t.slot(ch)], _oracle_frame(oracle, audio)[0], "tuner")
     assert any(float(np.abs(t.fetch(ch, capi.WR_STAGE_AUDIO, K2)).max()) > 0.0 for ch in chans)
     t.submit_device(x + 8 * K2 * 50, K2 * 50)
     rows2 = _audio_rows(dev, t, spec)
@@ -318,7 +308,7 @@ def test_audio_spectra_of_every_receiver_of_a_tuner(dev, oracle):
     dev.free(out)
     srows2 = _audio_rows(dev, t, spec)
     used = [t.slot(ch) for ch in chans]
-    assert np.array_equal(_bits(srows2[used]), _bits(rows2[used]))
+    assert np.array_equal(bits_f32(srows2[used]), bits_f32(rows2[used]))
     t.destroy()
     spec.destroy()
     dev.free(x)

@@ -11,7 +11,9 @@ import time
 import numpy as np
 import pytest
 
-import launch_plan
+import streamcases as sc
+from streamcases import DECIMATION_RATES, LANE_CASES, MODES
+from tunercases import AUDIO_ATOL, IQ_ATOL, bits, drain
 from webradio_amd import capi, synth
 from webradio_amd.device import Tuner
 
@@ -38,19 +40,6 @@ def _stream_dev(nblk, nch, n=N, seed=0):
     return x
 
 
-def _drain(t, count):
-    out = []
-    for b in range(count):
-        audio, seq = t.ring_acquire()
-        out.append((seq, audio.copy()))
-        t.ring_release()
-    return out
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 @pytest.mark.parametrize("nch", [8, 70, 200])
 def test_streamed_blocks_give_the_same_bits(dev, nch):
     """nblk consecutive blocks through one launch per block and through ONE streaming launch: the audio of every
@@ -70,12 +59,12 @@ def test_streamed_blocks_give_the_same_bits(dev, nch):
             assert live and launches == 1 and blocks == nblk
         t.flush()
         assert t.stream_info()[0] is False
-        got = _drain(t, nblk)
+        got = drain(t, nblk)
         # the tuner's DEVICE audio array behind the stream is the LAST block's (two blocks' post stages can run
         # side by side in the drain; they store into two arrays by turns) -- by wr_tuner_fetch_audio_all and per channel
         last_dev = t.fetch_audio_all()
-        assert np.array_equal(_bits(last_dev[:nch]), _bits(got[-1][1][:nch]))
-        assert np.array_equal(_bits(t.fetch(chans[-1], capi.WR_STAGE_AUDIO, N)), _bits(got[-1][1][t.slot(chans[-1])]))
+        assert np.array_equal(bits(last_dev[:nch]), bits(got[-1][1][:nch]))
+        assert np.array_equal(bits(t.fetch(chans[-1], capi.WR_STAGE_AUDIO, N)), bits(got[-1][1][t.slot(chans[-1])]))
         iq = np.stack([t.fetch(c, capi.WR_STAGE_CHAN_IQ, 2 * N) for c in chans[::3]])
         state = [t.state(c) for c in chans]
         t.streaming(False)
@@ -83,7 +72,7 @@ def test_streamed_blocks_give_the_same_bits(dev, nch):
         for b in range(nblk, nblk + 2):
             t.submit_device(x[2 * N * b: 2 * N * (b + 1)], N)
         t.flush()
-        got += _drain(t, 2)
+        got += drain(t, 2)
         t.destroy()
         return got, iq, state
 
@@ -92,11 +81,11 @@ def test_streamed_blocks_give_the_same_bits(dev, nch):
     assert [s for s, _ in one] == [s for s, _ in many] == list(range(nblk + 2))
     for (_, a), (_, b) in zip(one, many):
         assert a.shape == b.shape
-        assert np.array_equal(_bits(a[:nch]), _bits(b[:nch]))
+        assert np.array_equal(bits(a[:nch]), bits(b[:nch]))
     assert float(np.abs(one[-1][1]).max()) > 0.0
-    assert np.array_equal(_bits(iq1), _bits(iq2))
+    assert np.array_equal(bits(iq1), bits(iq2))
     for (p1, v1), (p2, v2) in zip(st1, st2):
-        assert p1 == p2 and np.array_equal(_bits(np.asarray(v1, np.float32)), _bits(np.asarray(v2, np.float32)))
+        assert p1 == p2 and np.array_equal(bits(np.asarray(v1, np.float32)), bits(np.asarray(v2, np.float32)))
 
 
 def test_whatever_touches_the_tuner_closes_the_launch(dev):
@@ -143,7 +132,7 @@ def test_whatever_touches_the_tuner_closes_the_launch(dev):
     b, info = run(True)
     assert info[1] >= 4 and info[2] >= 8                          # launches opened, blocks they took
     for u, v in zip(a, b):
-        assert u.shape == v.shape and np.array_equal(_bits(u), _bits(v))
+        assert u.shape == v.shape and np.array_equal(bits(u), bits(v))
 
 
 def test_two_tuners_on_one_device_both_asked_to_stream(dev):
@@ -165,12 +154,12 @@ def test_two_tuners_on_one_device_both_asked_to_stream(dev):
             tb.submit_device(x[2 * N * (nblk + b): 2 * N * (nblk + b + 1)], N)
         ta.flush()
         tb.flush()
-        oa, ob = _drain(ta, nblk), _drain(tb, nblk)
+        oa, ob = drain(ta, nblk), drain(tb, nblk)
         ia, ib = ta.stream_info(), tb.stream_info()
         for b in range(3):                                        # b alone: one launch for the three
             tb.submit_device(x[2 * N * b: 2 * N * (b + 1)], N)
         tb.flush()
-        ob += _drain(tb, 3)
+        ob += drain(tb, 3)
         ib2 = tb.stream_info()
         ta.destroy()
         tb.destroy()
@@ -183,7 +172,7 @@ def test_two_tuners_on_one_device_both_asked_to_stream(dev):
     for want, got in ((pa, sa), (pb, sb)):
         assert [q for q, _ in want] == [q for q, _ in got]
         for (_, u), (_, v) in zip(want, got):
-            assert u.shape == v.shape and np.array_equal(_bits(u), _bits(v))
+            assert u.shape == v.shape and np.array_equal(bits(u), bits(v))
 
 
 def test_a_second_context_on_the_same_gpu_goes_the_ordinary_way(dev):
@@ -214,7 +203,7 @@ def test_a_second_context_on_the_same_gpu_goes_the_ordinary_way(dev):
             want_a, want_b = got_a, got_b
         else:
             assert ia[2] >= nblk - 1 and ib[1] == 0 and ib[2] == 0, (ia, ib)
-            assert np.array_equal(_bits(got_a), _bits(want_a)) and np.array_equal(_bits(got_b), _bits(want_b))
+            assert np.array_equal(bits(got_a), bits(want_a)) and np.array_equal(bits(got_b), bits(want_b))
 
 
 def test_a_blocks_audio_arrives_without_a_flush(dev):
@@ -235,7 +224,7 @@ def test_a_blocks_audio_arrives_without_a_flush(dev):
     for b in range(nblk):
         t.submit_device(x[2 * N * b: 2 * N * (b + 1)], N)
         audio, seq = t.ring_acquire()                             # waits for the block's audio, not for the stream
-        assert seq == b and np.array_equal(_bits(audio), _bits(want[b]))
+        assert seq == b and np.array_equal(bits(audio), bits(want[b]))
         t.ring_release()
         assert t.stream_info() == (True, 1, b + 1)               # still the same launch
     t.destroy()                                                   # closes it
@@ -268,8 +257,8 @@ def test_an_idle_launch_ends_by_itself_and_the_host_knows(dev):
     t.submit_device(x[4 * N: 6 * N], N)
     assert t.stream_info()[1] == 3
     t.flush()
-    for b, (seq, audio) in enumerate(_drain(t, nblk)):
-        assert seq == b and np.array_equal(_bits(audio), _bits(want[b]))
+    for b, (seq, audio) in enumerate(drain(t, nblk)):
+        assert seq == b and np.array_equal(bits(audio), bits(want[b]))
     t.destroy()
 
 
@@ -289,12 +278,12 @@ def test_u8_blocks_stream_too(dev):
         for b in range(nblk):
             t.submit_u8_device(x[2 * N * b: 2 * N * (b + 1)], N)
         t.flush()
-        got = _drain(t, nblk)
+        got = drain(t, nblk)
         t.destroy()
         return got
 
     for (s1, a), (s2, b) in zip(run(False), run(True)):
-        assert s1 == s2 and np.array_equal(_bits(a), _bits(b))
+        assert s1 == s2 and np.array_equal(bits(a), bits(b))
 
 
 @pytest.mark.parametrize("on_time", [False, True], ids=["ahead", "on-time"])
@@ -316,7 +305,7 @@ def test_byte_blocks_out_of_page_locked_host_memory_stream(dev, page_locked, on_
     for b in range(nblk):
         t.submit_u8_device(x[2 * N * b: 2 * N * (b + 1)], N)
     t.flush()
-    want = _drain(t, nblk)
+    want = drain(t, nblk)
     t.destroy()
 
     bufs = [page_locked(2 * N) for _ in range(4)]
@@ -338,18 +327,18 @@ def test_byte_blocks_out_of_page_locked_host_memory_stream(dev, page_locked, on_
         t.submit_u8_host(h)
         assert t.last_staging() == 3 and t.stream_info()[0], (b, t.last_staging(), t.stream_info())
         if on_time:
-            got += _drain(t, 1)
+            got += drain(t, 1)
             assert t.stream_info()[0]                       # (taking a block's audio needs no flush: WrStreamCtl::done)
     live, launches, blocks = t.stream_info()
     assert launches == 1 and blocks == nblk and t.stream_host_blocks() == nblk
     t.flush()
     if not on_time:
-        got = _drain(t, nblk)
+        got = drain(t, nblk)
     st = t.state(chans[3])
     t.destroy()
     assert [s for s, _ in got] == [s for s, _ in want] == list(range(nblk))
     for (_, a), (_, b) in zip(want, got):
-        assert np.array_equal(_bits(a[:nch]), _bits(b[:nch]))
+        assert np.array_equal(bits(a[:nch]), bits(b[:nch]))
     assert float(np.abs(want[-1][1]).max()) > 0.0 and st is not None
     # pageable memory: not streamed (the runtime would stage the copy synchronously), the same bits all the same
     t, _ = _tuner(dev, nch)
@@ -358,9 +347,9 @@ def test_byte_blocks_out_of_page_locked_host_memory_stream(dev, page_locked, on_
     t.submit_u8_host(raw[: 2 * N].copy())
     assert t.last_staging() != 3 and t.stream_host_blocks() == 0
     t.flush()
-    a0 = _drain(t, 1)[0][1]
+    a0 = drain(t, 1)[0][1]
     t.destroy()
-    assert np.array_equal(_bits(a0[:nch]), _bits(want[0][1][:nch]))
+    assert np.array_equal(bits(a0[:nch]), bits(want[0][1][:nch]))
 
 
 @pytest.mark.parametrize("paced,mixed", [(False, False), (True, False), (False, True)], ids=["host-ahead", "host-paced", "host-ahead-all-modes"])
@@ -400,9 +389,9 @@ def test_streaming_at_c2_size(dev, paced, mixed):
                 if paced and stream:
                     time.sleep(0.002)                           # (a block takes the launch 30 us: it idles till the next ring)
             t.flush()
-            out += [a for _, a in _drain(t, nblk - 1)]
+            out += [a for _, a in drain(t, nblk - 1)]
         #  the device audio array after the close holds the LAST streamed block's audio, all 256 rows
-        assert np.array_equal(_bits(t.fetch_audio_all()), _bits(out[-1]))
+        assert np.array_equal(bits(t.fetch_audio_all()), bits(out[-1]))
         t.streaming(False)
         t.submit_device(x[2 * n * (nblk - 1): 2 * n * nblk], n)
         out.append(t.fetch_audio_all().copy())
@@ -416,7 +405,7 @@ def test_streaming_at_c2_size(dev, paced, mixed):
     # nine blocks rung at once: all but the last two (the drain) find two further blocks rung; paced, none does
     assert (info[3] == 0) if paced else (nblk - 3 <= info[3] <= 2 * (nblk - 3)), info
     assert one.shape == many.shape == (256, (2 * nblk - 1) * n // 400 // 5)
-    assert np.array_equal(_bits(one), _bits(many))
+    assert np.array_equal(bits(one), bits(many))
     assert float(np.abs(one[::4]).max()) > 0.0                  # the carrier channels carry audio (every 4th: AM in `all-modes`)
     assert not mixed or float(np.abs(one[1::4]).max()) > 0.0
 
@@ -513,7 +502,7 @@ def test_random_streams_with_streaming(dev, seed):
     many, st2, info = play(True)
     assert one.shape == many.shape and one.shape[1] > 0
     assert st1 == st2
-    assert np.array_equal(_bits(one), _bits(many)), (seed, info)
+    assert np.array_equal(bits(one), bits(many)), (seed, info)
     if seed % 3 != 2:
         assert info[2] >= 3, info                           # blocks that did go through streaming launches
 
@@ -533,7 +522,6 @@ def test_c2_full_size_stream_against_the_oracle(dev, oracle):
       - the phases behind the stream equal the closed form (downconverter.cxx:103)."""
     import torch
     import fm_bound
-    IQ_ATOL, AUDIO_ATOL = 1e-6, 1e-5
     c2 = synth.C2
     fs, n = c2["input_rate"], c2["block_frames"]
     ifs = synth.c2_ifs()
@@ -557,7 +545,7 @@ def test_c2_full_size_stream_against_the_oracle(dev, oracle):
     live, launches, blocks = t.stream_info()
     assert live and launches == 1 and blocks == nblk, (live, launches, blocks)
     t.flush()
-    s_audio = np.concatenate([a for _, a in _drain(t, nblk)], axis=1)            # [slot][frames of the whole stream]
+    s_audio = np.concatenate([a for _, a in drain(t, nblk)], axis=1)            # [slot][frames of the whole stream]
     assert s_audio.shape == (256, nblk * k2)
     slots = [t.slot(ch) for ch in chans]
     s_iq_last = [t.fetch(ch, capi.WR_STAGE_CHAN_IQ, 2 * k1) for ch in chans]
@@ -640,7 +628,7 @@ def test_c1_capture_streams_against_the_reference_vectors(dev, oracle):
             (t.submit_u8_device if as_bytes else t.submit_device)(x[2 * n * b: 2 * n * (b + 1)], n)
         assert t.stream_info() == (True, 1, nblk)
         t.flush()
-        audio = np.concatenate([a[t.slot(ch)] for _, a in _drain(t, nblk)])
+        audio = np.concatenate([a[t.slot(ch)] for _, a in drain(t, nblk)])
         chan = t.fetch(ch, capi.WR_STAGE_CHAN_IQ, 2 * n)
         t.destroy()
         assert audio.shape == g["audio"].shape
@@ -648,7 +636,7 @@ def test_c1_capture_streams_against_the_reference_vectors(dev, oracle):
         assert chan.size and np.abs(chan - g["chan_iq"][-chan.size:]).max() <= 1e-6
         assert float(np.abs(g["audio"]).max()) > 1e-3
         outs.append((audio, chan))
-    assert np.array_equal(_bits(outs[0][0]), _bits(outs[1][0])) and np.array_equal(_bits(outs[0][1]), _bits(outs[1][1]))
+    assert np.array_equal(bits(outs[0][0]), bits(outs[1][0])) and np.array_equal(bits(outs[0][1]), bits(outs[1][1]))
 
 
 @pytest.mark.parametrize("nfft,hop", [(512, 0), (4096, 2048)])
@@ -678,7 +666,7 @@ def test_a_front_ends_spectrum_sink_beside_the_stream(dev, nfft, hop):
                 polls.append((sp.get_db().copy(), sp.get_bins().copy(), sp.frames_done()))
                 launches_at_poll.append(t.stream_info()[1])
         t.flush()
-        audio = _drain(t, nblk)
+        audio = drain(t, nblk)
         info, lazy = t.stream_info(), sp.lazy_info()
         sp.destroy()
         t.destroy()
@@ -691,141 +679,21 @@ def test_a_front_ends_spectrum_sink_beside_the_stream(dev, nfft, hop):
     assert info2[1] == 1 + nblk // poll_every and lp == [1, 2]      # a poll closes the launch; the next block opens the next
     assert info2[2] == nblk                                 # ... and every block went through a streaming launch
     for (s1, u), (s2, v) in zip(a1, a2):
-        assert s1 == s2 and np.array_equal(_bits(u[:nch]), _bits(v[:nch]))
+        assert s1 == s2 and np.array_equal(bits(u[:nch]), bits(v[:nch]))
     assert len(p1) == len(p2) == nblk // poll_every
     for (d1, b1, f1), (d2, b2, f2) in zip(p1, p2):
-        assert f1 == f2 and np.array_equal(_bits(b1), _bits(b2)) and np.array_equal(_bits(d1), _bits(d2))
+        assert f1 == f2 and np.array_equal(bits(b1), bits(b2)) and np.array_equal(bits(d1), bits(d2))
 
 
 # ---- every k_tuner_stream<PD2, NG> instance, the block-size and tiling edges, the WR_STREAM_MAX_BLOCKS rollover and host byte
 #      blocks at the smallest size -- each against the ORACLE on probe receivers and against one launch per block, bit for bit,
 #      on every receiver --------------------------------------------------------------------------------------------------------
 
-IQ_ATOL, AUDIO_ATOL = 1e-6, 1e-5              # test_c2_full_size_stream_against_the_oracle's
-MODES = (capi.WR_FM, capi.WR_USB, capi.WR_AM, capi.WR_LSB)     # receiver c demodulates MODES[c % 4]
-
-
-def _lane_groups(nch):
-    return (nch + 63) // 64
-
-
-def _ng(groups):
-    """wrk_tuner_stream: k_tuner_stream<PD2, 1> for an odd lane-group count, <PD2, 2> for an even one"""
-    return 1 if groups & 1 else 2
-
-
-def _post_tiling(k2, groups, n_post):
-    """wrk_tuner_stream's cut of one block's post stage, from the rule itself (wr_plan.h: wrp_post_tiling_stream, which says
-    which of its branches it took): (min_run, run, drain_run, how run was chosen)"""
-    t = launch_plan.stream_tiling(k2, groups, n_post)
-    return t.min_run, t.run, t.drain_run, ("long" if t.long_runs else "min") + "+loop" * t.widened
-
-
-def _n_post():
-    """post workgroups of a streaming launch on this device (wr_plan.h: wrp_stream_roles: one slot per CU, less four, whether
-    the launch has two or three workgroups per CU -- two, the fewest a launch exists with, is what is asked here)"""
-    import torch
-    return launch_plan.stream_roles(2, torch.cuda.get_device_properties(0).multi_processor_count)[1]
-
-
-def _passbands(fs, crate, arate):
-    """(channel, audio) passband.  The reference's 64-tap LowPass keeps the frequency bins below passband * 32 / rate
-    (lowpass_maxbin): a channel passband of fs / 16 keeps two at every input rate, arate / 3 at least one up to D2 = 10."""
-    return fs // 16, arate // 3
-
-
-def _spread_ifs(fs, nch):
-    step = int(0.9 * fs / nch)
-    return [(c - nch // 2) * step + 37 for c in range(nch)]
-
-
-def _fm_probes(nch):
-    """the FM receivers that carry a carrier: the first, and the last FM one, in the ragged last lane group"""
-    return [0, (nch - 1) // 4 * 4]
-
-
-def _probes(nch):
-    """receivers 0-3 (every mode), an AM / USB / LSB one in every lane group, the FM probes and the last receiver.  (Only the FM
-    probes have a carrier of their own, far from each other: FM's arctangent is well conditioned only where one carrier
-    dominates the channel; the other demodulators are linear or 1-Lipschitz in the channel IQ.)"""
-    per_group = {64 * g + 1 + (g % 3) for g in range(_lane_groups(nch))}
-    return sorted({0, 1, 2, 3, nch - 1} | {c for c in per_group if c < nch} | set(_fm_probes(nch)))
-
-
-def _carriers(ifs):
-    return [ifs[c] for c in _fm_probes(len(ifs))]
-
-
-def _play(dev, fs, crate, arate, ifs, blocks, stream, submit, between=None, ring=None, take_every=None, before=None):
-    """Submit `blocks` ((offset, frames) into the stream) to a fresh tuner, streaming or with one launch per block, taking every
-    block's audio out of the ring.  between(t, chans, b): called before block b is submitted, returns the ring entries it took;
-    before(): called once, right before the first submit.  Returns a dict: the ring entries
-    (seq, audio), the slots, the last block's channel IQ and every receiver's state after a flush, stream_info before it and the
-    long-run count after it."""
+def _against_the_oracle(oracle, fs, crate, arate, ifs, host_blocks, run, check_blocks=None):
+    """streamcases.probes -- every lane group, every demodulator -- against oracle.Receiver with the common passbands"""
     nch = len(ifs)
-    t = Tuner(dev, fs, nch, max(n for _, n in blocks), capi.WR_NCO_ROTATE)
-    cpb, apb = _passbands(fs, crate, arate)
-    chans = [t.add_receiver(f, cpb, crate, MODES[c % 4], apb, arate) for c, f in enumerate(ifs)]
-    t.audio_ring(ring or len(blocks))
-    t.streaming(stream)
-    got = []
-    if before is not None:
-        before()
-    for b, (off, n) in enumerate(blocks):
-        if between is not None:
-            got += between(t, chans, b)
-        submit(t, b, off, n)
-        if take_every and t.ring_stats()[0] >= take_every:
-            got += _drain(t, t.ring_stats()[0])
-    info = t.stream_info()
-    t.flush()
-    got += _drain(t, len(blocks) - len(got))
-    k1 = blocks[-1][1] * crate // fs
-    out = dict(got=got, info=info, host=t.stream_host_blocks(), slots=[t.slot(c) for c in chans],
-               iq=[t.fetch(c, capi.WR_STAGE_CHAN_IQ, 2 * k1) for c in chans],
-               state=[t.state(c) for c in chans])
-    out["long"] = t.stream_long_blocks()           # (counted when the closed launch is checked: the state reads waited for it)
-    t.destroy()
-    return out
-
-
-def _same_bits(one, many):
-    """the streamed run against the launch-per-block run: every block's audio on EVERY receiver, the last block's channel IQ
-    and every receiver's state"""
-    assert [s for s, _ in one["got"]] == [s for s, _ in many["got"]] == list(range(len(one["got"])))
-    assert one["slots"] == many["slots"]
-    rows = one["slots"]
-    for b, ((_, u), (_, v)) in enumerate(zip(one["got"], many["got"])):
-        assert u.shape == v.shape and np.array_equal(_bits(u[rows]), _bits(v[rows])), b
-    for c, (u, v) in enumerate(zip(one["iq"], many["iq"])):
-        assert u.size and np.array_equal(_bits(u), _bits(v)), c
-    for c, ((p1, v1), (p2, v2)) in enumerate(zip(one["state"], many["state"])):
-        assert p1 == p2 and np.array_equal(_bits(np.asarray(v1, np.float32)), _bits(np.asarray(v2, np.float32))), c
-
-
-def _against_the_oracle(oracle, fs, crate, arate, ifs, host_blocks, run, probes, check_blocks=None):
-    """the probe receivers' audio of every block (or of `check_blocks`) and the last block's channel IQ against oracle.Receiver
-    on the same input; at least one probe carries a carrier"""
-    nch = len(ifs)
-    assert {run["slots"][c] // 64 for c in probes} == set(range(_lane_groups(nch)))     # every lane group, the ragged last too
-    assert {c % 4 for c in probes} == {0, 1, 2, 3}                                       # every demodulator
-    cpb, apb = _passbands(fs, crate, arate)
-    assert oracle.lowpass_maxbin(cpb, fs) >= 1 and oracle.lowpass_maxbin(apb, crate) >= 1     # (filters that pass something)
-    loudest = 0.0
-    for c in probes:
-        rx = oracle.Receiver(fs, ifs[c], cpb, crate, MODES[c % 4], apb, arate)
-        if MODES[c % 4] == capi.WR_FM:     # the audio filter's gain over the demodulator's differences (test_random_post_stage_runs)
-            tol = AUDIO_ATOL * max(1.0, float(np.abs(oracle.lowpass_design(apb, crate)).sum()))
-        else:
-            tol = AUDIO_ATOL
-        for b, iq in enumerate(host_blocks):
-            wa, wc, _ = rx.run(iq)
-            if check_blocks is None or b in check_blocks:
-                ga = run["got"][b][1][run["slots"][c]]
-                assert ga.shape == wa.shape and np.abs(ga - wa).max() <= tol, (c, b, float(np.abs(ga - wa).max()))
-                loudest = max(loudest, float(np.abs(wa).max()))
-        assert run["iq"][c].shape == wc.shape and np.abs(run["iq"][c] - wc).max() <= IQ_ATOL, c
-    assert loudest > 1e-3, loudest
+    sc.against_oracle(sc.ProbeOracle(oracle, fs, crate, arate, ifs), host_blocks, run, sc.probes(nch),
+                      sc.covers_groups_and_modes(nch), check_blocks)
 
 
 def _oracle_vs_stream(dev, oracle, fs, crate, arate, nch, n, nblk, expect_launches=1, amp=0.1, host_ahead=False):
@@ -836,18 +704,10 @@ def _oracle_vs_stream(dev, oracle, fs, crate, arate, nch, n, nblk, expect_launch
     finds every one of them rung when it starts.  Returns the streamed run."""
     import torch
     from webradio_amd.device import Device
-    ifs = _spread_ifs(fs, nch)
-    probes = _probes(nch)
+    ifs = sc.spread_ifs(fs, nch)
     first = 1 if host_ahead else 0
-    iq = synth.fm_stream((first + nblk) * n, fs, _carriers(ifs), amp=amp)
-    x = torch.from_numpy(iq).cuda()
-    torch.cuda.synchronize()
-    blocks = [(b * n, n) for b in range(first + nblk)]
-    views = [x[2 * off: 2 * (off + m)] for off, m in blocks]            # (sliced ahead: the submits go back to back)
+    host_blocks, blocks, submit = sc.device_stream(fs, ifs, n, first + nblk, amp=amp)
     side = torch.cuda.Stream()
-
-    def submit(t, b, off, m):
-        t.submit_device(views[b], m)
 
     def between(t, chans, b):
         if first and b == first:
@@ -857,10 +717,10 @@ def _oracle_vs_stream(dev, oracle, fs, crate, arate, nch, n, nblk, expect_launch
                     torch.cuda._sleep(20_000_000)   # (core clock cycles: ~10 ms, far below WR_STREAM_STALE_MS)
         return []
 
-    one = _play(dev, fs, crate, arate, ifs, blocks, False, submit, between=between)
+    one = sc.play(dev, fs, crate, arate, ifs, blocks, False, submit, between=between)
     held = Device(0, stream=side.cuda_stream)      # (a context on a stream of the test's own: the hold goes on it)
     try:
-        many = _play(held, fs, crate, arate, ifs, blocks, True, submit, between=between)
+        many = sc.play(held, fs, crate, arate, ifs, blocks, True, submit, between=between)
     finally:
         held.close()
     assert one["info"][1:] == (0, 0)
@@ -869,63 +729,42 @@ def _oracle_vs_stream(dev, oracle, fs, crate, arate, nch, n, nblk, expect_launch
         assert live and launches == first + expect_launches and taken == first + nblk, many["info"]   # not a silent launch per block
     else:
         assert not live and launches == 0 and taken == 0, many["info"]
-    _same_bits(one, many)
-    _against_the_oracle(oracle, fs, crate, arate, ifs, [iq[2 * off: 2 * (off + m)] for off, m in blocks], many, probes)
+    sc.same_bits(one, many)
+    _against_the_oracle(oracle, fs, crate, arate, ifs, host_blocks, many)
     return many
 
 
-# (fs, chan_rate) per audio decimation: D1 = 10, 12, 20, 8, 16, 8, 16, 5
-DECIMATION_RATES = {1: (2_400_000, 240_000), 2: (2_400_000, 200_000), 3: (2_400_000, 120_000), 4: (2_048_000, 256_000),
-                    5: (2_400_000, 150_000), 6: (1_920_000, 240_000), 8: (2_048_000, 128_000), 10: (2_400_000, 480_000)}
-LANE_CASES = {"odd": 130, "even": 70}         # 3 and 2 lane groups of 64, the last one ragged
 INSTANCES = [(pd2, lanes) for pd2 in sorted(DECIMATION_RATES) for lanes in LANE_CASES]
 
 
 @pytest.mark.parametrize("pd2,lanes", INSTANCES,
-                         ids=[f"PD2={p}-NG={_ng(_lane_groups(LANE_CASES[l]))}" for p, l in INSTANCES])
+                         ids=[f"PD2={p}-NG={sc.ng(sc.lane_groups(LANE_CASES[l]))}" for p, l in INSTANCES])
 def test_stream_at_every_audio_decimation(dev, oracle, pd2, lanes):
     """launch_stream_d2 instantiates k_tuner_stream<PD2, NG> for PD2 in {1..6, 8, 10} and NG in {1, 2}: every one of the 16
     takes six blocks through one launch here, against the oracle and against a launch per block."""
     fs, crate = DECIMATION_RATES[pd2]
     nch = LANE_CASES[lanes]
-    assert _ng(_lane_groups(nch)) == (1 if lanes == "odd" else 2)
+    assert sc.ng(sc.lane_groups(nch)) == (1 if lanes == "odd" else 2)
     d1 = fs // crate
     k2 = -(-64 // pd2) + 37                    # >= 64 channel-rate frames; the tiles' count and the ragged last differ by PD2
     _oracle_vs_stream(dev, oracle, fs, crate, crate // pd2, nch, k2 * pd2 * d1, 6)
 
 
-# id: (fs, chan_rate, audio_rate, receivers, audio frames per block or None for the smallest block a launch takes,
-#      (min_run, run, drain_run, how) wrk_tuner_stream picks for n_post = 252 (MI355X: 256 CUs) or None)
-EDGE_CASES = {
-    "smallest-D1=1": (240_000, 240_000, 48_000, 70, None, None),            # 65 frames, k2 = 13: under one tile
-    "smallest-D1=2": (480_000, 240_000, 80_000, 130, None, None),           # 132 frames, k2 = 22: a ragged second tile
-    "smallest-D1=3": (720_000, 240_000, 60_000, 70, None, None),            # 192 frames, k2 = 16: exactly one tile
-    "under-one-tile": (2_400_000, 240_000, 30_000, 130, 9, None),
-    "run-1-ragged": (2_400_000, 240_000, 48_000, 40, 60, (1, 1, 1, "min")),
-    "run-2": (2_400_000, 240_000, 80_000, 100, 790, (1, 2, 1, "min+loop")),
-    "run-3": (2_048_000, 256_000, 64_000, 300, 393, (1, 3, 1, "min+loop+loop")),
-    "run-4": (2_400_000, 60_000, 60_000, 40, 4790, (2, 4, 2, "long+loop")),
-    "long-runs": (2_400_000, 60_000, 30_000, 100, 3595, (2, 4, 2, "long")),
-    "16-groups": (2_400_000, 240_000, 48_000, 1000, 100, None),
-    "17-groups": (2_400_000, 240_000, 48_000, 1025, 100, None),
-}
-
-
-@pytest.mark.parametrize("case", list(EDGE_CASES))
+@pytest.mark.parametrize("case", list(sc.BLOCK_EDGE_CASES))
 def test_stream_block_edges(dev, oracle, case):
     """The edges wrk_tuner_stream's formulas have: the smallest block a launch takes (64 x D1 frames, whole audio frames) at
     D1 = 1, 2, 3, where a channel filter window reaches into the block before; fewer audio frames than one post tile; a ragged
     last tile; every way the post stage is cut into runs of tiles (restated here, so a case that stops reaching its branch
     fails); 16 lane groups with a ragged last -- and 17, which must NOT stream."""
-    fs, crate, arate, nch, k2, tiling = EDGE_CASES[case]
+    fs, crate, arate, nch, k2, tiling = sc.BLOCK_EDGE_CASES[case]
     d1, d2 = fs // crate, crate // arate
     if k2 is None:                                 # 64 x D1 frames, rounded up to whole audio frames
         k2 = -(-64 // d2)
         assert d1 <= 3 and k2 * d2 >= 64 > (k2 - 1) * d2
     n = k2 * d2 * d1
-    groups = _lane_groups(nch)
-    n_post = _n_post()
-    min_run, run, drain_run, how = _post_tiling(k2, groups, n_post)
+    groups = sc.lane_groups(nch)
+    n_post = sc.n_post()
+    min_run, run, drain_run, how = sc.post_tiling(k2, groups, n_post)
     if tiling is not None:
         assert (min_run, run, drain_run, how) == tiling, (case, n_post, (min_run, run, drain_run, how))
     nblk = 6
@@ -942,27 +781,17 @@ def test_stream_past_max_blocks(dev, oracle):
     """WR_STREAM_MAX_BLOCKS + 9 smallest blocks: the launch takes 512 and the next submit opens a second one.  The audio is
     taken as it comes, out of a ring smaller than the stream; sequence numbers run on; the same bits as a launch per block on
     every receiver, and the probes against the oracle from both launches' blocks and around the boundary."""
-    import torch
     fs, crate, arate, nch = 2_400_000, 240_000, 60_000, 70
     n = 64 * (fs // crate)                             # k1 = 64, k2 = 16
     nblk = capi.WR_STREAM_MAX_BLOCKS + 9
-    ifs = _spread_ifs(fs, nch)
-    probes = _probes(nch)
-    iq = synth.fm_stream(nblk * n, fs, _carriers(ifs), amp=0.1)
-    x = torch.from_numpy(iq).cuda()
-    torch.cuda.synchronize()
-    blocks = [(b * n, n) for b in range(nblk)]
-    views = [x[2 * off: 2 * (off + m)] for off, m in blocks]
-
-    def submit(t, b, off, m):
-        t.submit_device(views[b], m)
-
-    one = _play(dev, fs, crate, arate, ifs, blocks, False, submit, ring=16, take_every=8)
-    many = _play(dev, fs, crate, arate, ifs, blocks, True, submit, ring=16, take_every=8)
+    ifs = sc.spread_ifs(fs, nch)
+    host_blocks, blocks, submit = sc.device_stream(fs, ifs, n, nblk)
+    one = sc.play(dev, fs, crate, arate, ifs, blocks, False, submit, ring=16, take_every=8)
+    many = sc.play(dev, fs, crate, arate, ifs, blocks, True, submit, ring=16, take_every=8)
     assert many["info"] == (True, 2, nblk), many["info"]
-    _same_bits(one, many)
+    sc.same_bits(one, many)
     edge = capi.WR_STREAM_MAX_BLOCKS
-    _against_the_oracle(oracle, fs, crate, arate, ifs, [iq[2 * off: 2 * (off + m)] for off, m in blocks], many, probes,
+    _against_the_oracle(oracle, fs, crate, arate, ifs, host_blocks, many,
                         check_blocks=set(range(0, 4)) | set(range(edge - 3, nblk)))
 
 
@@ -985,9 +814,8 @@ def test_host_byte_stream_submit_ahead_without_flush(dev, oracle, page_locked):
     offs = np.cumsum([0] + sizes[:-1]).tolist()
     blocks = list(zip(offs, sizes))
     total = sum(sizes)
-    ifs = _spread_ifs(fs, nch)
-    probes = _probes(nch)
-    z = synth.fm_stream(total, fs, _carriers(ifs), amp=0.1).astype(np.float64)
+    ifs = sc.spread_ifs(fs, nch)
+    z = synth.fm_stream(total, fs, sc.carriers(ifs), amp=0.1).astype(np.float64)
     raw = np.clip(np.round(127.5 + 127.0 * z), 0, 255).astype(np.uint8)     # io/rtlsdrtuner.cxx:106's format
     x = torch.from_numpy(raw).cuda()
     torch.cuda.synchronize()
@@ -1005,7 +833,7 @@ def test_host_byte_stream_submit_ahead_without_flush(dev, oracle, page_locked):
             if b in take_at:
                 if not stream:
                     t.flush()                      # (the ordinary path queues a block's ring entry with its post stage)
-                got = _drain(t, take_at[b])
+                got = drain(t, take_at[b])
                 if stream:
                     assert t.stream_info() == (True, 1, b), (b, t.stream_info())     # taking audio closed nothing
             if b == 20:
@@ -1018,18 +846,18 @@ def test_host_byte_stream_submit_ahead_without_flush(dev, oracle, page_locked):
                 assert t.last_staging() == 3, (b, t.last_staging())
             else:
                 t.submit_u8_device(views[b], m)
-        return _play(dev, fs, crate, arate, ifs, blocks, 2 if stream else False, submit, between=between)
+        return sc.play(dev, fs, crate, arate, ifs, blocks, 2 if stream else False, submit, between=between)
 
     one = play(False)
     many = play(True)
     # blocks 0-12 one launch; 13 (another size) its own; 14-19 one; 20-23, behind the setter, one
     assert many["info"] == (True, 4, len(blocks)) and many["host"] == len(blocks), (many["info"], many["host"])
-    _same_bits(one, many)
+    sc.same_bits(one, many)
     host_f = oracle.u8_to_float(raw)
     # (the oracle only where the block size did not change: at a change the reference's LowPass history is not the true
-    # one -- quirk Q7, which the product deliberately does not copy, tests/test_gpu_blocks.py; _same_bits covers those two)
+    # one -- quirk Q7, which the product deliberately does not copy, tests/test_gpu_blocks.py; same_bits covers those two)
     same_size = {b for b in range(len(blocks)) if b == 0 or sizes[b] == sizes[b - 1]}
-    _against_the_oracle(oracle, fs, crate, arate, ifs, [host_f[2 * off: 2 * (off + m)] for off, m in blocks], many, probes,
+    _against_the_oracle(oracle, fs, crate, arate, ifs, [host_f[2 * off: 2 * (off + m)] for off, m in blocks], many,
                         check_blocks=same_size)
 
     # 64 channel-rate frames: a launch takes such a block out of device memory, but not out of host memory
@@ -1039,7 +867,7 @@ def test_host_byte_stream_submit_ahead_without_flush(dev, oracle, page_locked):
     outs = []
     for stream in (False, True):
         t = Tuner(dev, fs, nch, small, capi.WR_NCO_ROTATE)
-        cpb, apb = _passbands(fs, crate, arate)
+        cpb, apb = sc.passbands(fs, crate, arate)
         for c, f in enumerate(ifs):
             t.add_receiver(f, cpb, crate, MODES[c % 4], apb, arate)
         t.audio_ring(1)
@@ -1050,6 +878,6 @@ def test_host_byte_stream_submit_ahead_without_flush(dev, oracle, page_locked):
         else:
             t.submit_u8_device(x[: 2 * small], small)
         t.flush()
-        outs.append(_drain(t, 1)[0][1])
+        outs.append(drain(t, 1)[0][1])
         t.destroy()
-    assert np.array_equal(_bits(outs[0][:nch]), _bits(outs[1][:nch])) and float(np.abs(outs[0]).max()) > 1e-3
+    assert np.array_equal(bits(outs[0][:nch]), bits(outs[1][:nch])) and float(np.abs(outs[0]).max()) > 1e-3

@@ -10,23 +10,19 @@ history for the block behind it and the frame in front of them.
 Every case asserts the exact stream_info() tuple (a silent fall-back to a launch per block fails), the SAME BITS as one
 launch per block on a fresh tuner (every block's audio on every receiver, the last block's channel IQ, every receiver's
 state), and holds probe receivers of all four demodulators in every lane group to the oracle's chain with an L2-tap audio
-filter (test_gpu_f4.OracleChain), within that file's ROTATE bounds: channel IQ 1e-6; audio 2e-6 x sum|h2| for AM, USB
-and LSB (|.| and the Re / Im sums are 2-Lipschitz in the channel IQ, then the linear filter), AUDIO_ATOL x sum|h2| for FM
-as the stream tests have it."""
+filter (tunercases.OracleChain), within tunercases' ROTATE bounds: channel IQ IQ_ATOL; audio LINEAR_ATOL x sum|h2| for AM,
+USB and LSB (|.| and the Re / Im sums are 2-Lipschitz in the channel IQ, then the linear filter), AUDIO_ATOL x sum|h2| for
+FM as the stream tests have it (streamcases.ProbeOracle)."""
 import numpy as np
 import pytest
 
 import launch_plan
-from webradio_amd import capi, synth
-from webradio_amd.device import Tuner
-from test_gpu_f4 import OracleChain
-from test_gpu_stream import (AUDIO_ATOL, DECIMATION_RATES, IQ_ATOL, MODES, _carriers, _drain, _lane_groups,
-                             _passbands, _probes, _same_bits, _spread_ifs)
+import streamcases as sc
+from streamcases import DECIMATION_RATES, LANE_CASES, pb, sets_per_group, spread, staggered
+from webradio_amd import capi
 
 pytestmark = pytest.mark.gpu
 
-LINEAR_ATOL = 2e-6                            # test_gpu_f4.py's ROTATE bound for AM / USB / LSB audio, per unit of sum|h2|
-LANE_CASES = {"odd": 130, "even": 70}         # 3 and 2 lane groups of 64, the last one ragged
 # the audio decimations a launch must take, by audio filter length (wr_stream_kernel.inc: with_stream_nseg)
 STREAMED_D2 = {128: sorted(DECIMATION_RATES), 256: [1, 2, 3]}
 
@@ -36,113 +32,17 @@ def _k2_for(l2, d2, k2=100):
     return max(k2, -(-l2 // d2) + 5)
 
 
-def _play_long(dev, fs, crate, arate, ifs, l2, blocks, stream, submit, between=None, apbs=None, cpbs=None):
-    """test_gpu_stream._play with an audio filter of l2 taps on every receiver (fir_lengths=(64, l2)) and, with `apbs` /
-    `cpbs`, an audio / a channel passband per receiver; `stream` may be a callable(t, b) that says per block whether to
-    stream it (the state hand-over case).  Returns _play's dict."""
-    nch = len(ifs)
-    t = Tuner(dev, fs, nch, max(n for _, n in blocks), capi.WR_NCO_ROTATE)
-    cpb, apb = _passbands(fs, crate, arate)
-    chans = [t.add_receiver(f, cpbs[c] if cpbs else cpb, crate, MODES[c % 4], apbs[c] if apbs else apb, arate,
-                            fir_lengths=(64, l2))
-             for c, f in enumerate(ifs)]
-    t.audio_ring(len(blocks))
-    if not callable(stream):
-        t.streaming(stream)
-    got = []
-    for b, (off, n) in enumerate(blocks):
-        if between is not None:
-            got += between(t, chans, b)
-        if callable(stream):
-            stream(t, b)
-        submit(t, b, off, n)
-    info = t.stream_info()
-    t.flush()
-    got += _drain(t, len(blocks) - len(got))
-    k1 = blocks[-1][1] * crate // fs
-    out = dict(got=got, info=info, slots=[t.slot(c) for c in chans],
-               iq=[t.fetch(c, capi.WR_STAGE_CHAN_IQ, 2 * k1) for c in chans], state=[t.state(c) for c in chans])
-    t.destroy()
-    return out
-
-
-def _against_the_chain(oracle, fs, crate, arate, ifs, l2, host_blocks, run, probes, apbs=None, every_group=True,
-                       cpbs=None):
-    """the probes' audio of every block and the last block's channel IQ against the oracle's mixer -> LowPass(64, D1) ->
-    demodulator -> LowPass(l2, D2) chain; every demodulator is probed in every lane group, and a carrier is heard"""
-    nch = len(ifs)
-    d1, d2 = fs // crate, crate // arate
-    omode = {capi.WR_FM: oracle.FM, capi.WR_USB: oracle.USB, capi.WR_AM: oracle.AM, capi.WR_LSB: oracle.LSB}
-    if every_group:
-        # (receiver c sits in slot c; a ragged last lane group may be too short to hold all four)
-        assert run["slots"] == list(range(nch))
-        assert {(c // 64, c % 4) for c in probes} == {(c // 64, c % 4) for c in range(nch)}
-    cpb_all, apb = _passbands(fs, crate, arate)
-    loudest = 0.0
-    for c in probes:
-        pb2 = apbs[c] if apbs else apb
-        cpb = cpbs[c] if cpbs else cpb_all
-        assert oracle.lowpass_maxbin(cpb, fs) >= 1 and oracle.lowpass_maxbin_n(l2, pb2, crate) >= 1     # (filters that pass something)
-        rx = OracleChain(oracle, fs, ifs[c], 64, cpb, d1, omode[MODES[c % 4]], l2, pb2, d2)
-        gain2 = max(1.0, float(np.abs(oracle.lowpass_design(pb2, crate, l2)).sum()))
-        tol = (AUDIO_ATOL if MODES[c % 4] == capi.WR_FM else LINEAR_ATOL) * gain2
-        wc = None
-        for b, iq in enumerate(host_blocks):
-            wa, wc, _ = rx.run(iq)
-            ga = run["got"][b][1][run["slots"][c]]
-            err = float(np.abs(ga - wa).max()) if ga.shape == wa.shape else None
-            assert err is not None and err <= tol, (c, b, err, tol)
-            loudest = max(loudest, float(np.abs(wa).max()))
-        err = float(np.abs(run["iq"][c] - wc).max()) if run["iq"][c].shape == wc.shape else None
-        assert err is not None and err <= IQ_ATOL, (c, err)
-    assert loudest > 1e-3, loudest
-
-
-def _group_probes(nch):
-    """all four demodulators in every lane group (the ragged last one too), and test_gpu_stream's probes: the FM ones carry
-    the carriers"""
-    out = set(_probes(nch))
-    for g in range(_lane_groups(nch)):
-        top = min(64 * g + 63, nch - 1)
-        for m in range(4):
-            mine = [c for c in range(64 * g, top + 1) if c % 4 == m]
-            if mine:
-                out.add(mine[len(mine) // 2])
-    return sorted(out)
+def _play_long(dev, fs, crate, arate, ifs, l2, blocks, stream, submit, **more):
+    """streamcases.play with an audio filter of l2 taps on every receiver"""
+    return sc.play(dev, fs, crate, arate, ifs, blocks, stream, submit, fir_lengths=(64, l2), **more)
 
 
 def _stream_vs_blocks(dev, oracle, l2, fs, crate, arate, nch, n, nblk, expect, u8=False):
-    """nblk blocks of n frames out of device memory, streamed and with a launch per block: the exact stream_info() tuple
-    (`expect`: one tuple, or a set of admissible ones), the same bits, the probes against the oracle.  Returns the streamed
-    run."""
-    import torch
-    ifs = _spread_ifs(fs, nch)
-    iq = synth.fm_stream(nblk * n, fs, _carriers(ifs), amp=0.1)
-    if u8:
-        raw = np.clip(np.rint(iq * 128.0 + 128.0), 0, 255).astype(np.uint8)
-        iq = oracle.u8_to_float(raw)                       # what the tuner sees (io/rtlsdrtuner.cxx:106)
-        x = torch.from_numpy(raw).cuda()
-    else:
-        x = torch.from_numpy(iq).cuda()
-    torch.cuda.synchronize()
-    blocks = [(b * n, n) for b in range(nblk)]
-    views = [x[2 * off: 2 * (off + m)] for off, m in blocks]
-
-    def submit(t, b, off, m):
-        (t.submit_u8_device if u8 else t.submit_device)(views[b], m)
-
-    one = _play_long(dev, fs, crate, arate, ifs, l2, blocks, False, submit)
-    many = _play_long(dev, fs, crate, arate, ifs, l2, blocks, True, submit)
-    assert one["info"] == (False, 0, 0)
-    print("stream_info", l2, crate // arate, nch, n, many["info"])
-    if isinstance(expect, tuple):
-        assert many["info"] == expect, many["info"]
-    else:
-        assert many["info"] in expect, many["info"]
-    _same_bits(one, many)
-    _against_the_chain(oracle, fs, crate, arate, ifs, l2, [iq[2 * off: 2 * (off + m)] for off, m in blocks], many,
-                       _group_probes(nch))
-    return many
+    """streamcases.stream_vs_blocks with an audio filter of l2 taps on every receiver: every demodulator is probed in every
+    lane group (streamcases.group_probes) against the oracle's chain"""
+    ifs = sc.spread_ifs(fs, nch)
+    return sc.stream_vs_blocks(dev, sc.ProbeOracle(oracle, fs, crate, arate, ifs, l2), fs, crate, arate, ifs, n, nblk, expect,
+                               sc.group_probes(nch), sc.covers_modes_in_groups(nch), u8=u8, fir_lengths=(64, l2))
 
 
 INSTANCES = [(l2, pd2, lanes) for l2 in sorted(STREAMED_D2) for pd2 in STREAMED_D2[l2] for lanes in LANE_CASES]
@@ -213,20 +113,12 @@ def test_long_audio_filter_state_goes_both_ways(dev, oracle, l2, pd2):
     against five blocks with a launch each.  The stream's block 0 takes its L2 - 1 rows of history from the tuner's state
     (dem_hist), its second block from the channel-IQ ring (chan_prev), and the closing state task leaves L2 - 1 rows and
     the last channel frame for the launch behind it."""
-    import torch
     fs, crate = DECIMATION_RATES[pd2]
     arate, nch, nblk = crate // pd2, 130, 5
     n = _k2_for(l2, pd2, 60) * pd2 * (fs // crate)
-    ifs = _spread_ifs(fs, nch)
-    iq = synth.fm_stream(nblk * n, fs, _carriers(ifs), amp=0.1)
-    x = torch.from_numpy(iq).cuda()
-    torch.cuda.synchronize()
-    blocks = [(b * n, n) for b in range(nblk)]
-    views = [x[2 * off: 2 * (off + m)] for off, m in blocks]
+    ifs = sc.spread_ifs(fs, nch)
+    host_blocks, blocks, submit = sc.device_stream(fs, ifs, n, nblk)
     seen = {}
-
-    def submit(t, b, off, m):
-        t.submit_device(views[b], m)
 
     def phases(t, b):
         if b in (2, 4):
@@ -240,9 +132,9 @@ def test_long_audio_filter_state_goes_both_ways(dev, oracle, l2, pd2):
     assert one["info"] == (False, 0, 0)
     assert seen["streamed"] == (True, 1, 2), seen
     assert many["info"] == (False, 1, 2), many["info"]
-    _same_bits(one, many)
-    _against_the_chain(oracle, fs, crate, arate, ifs, l2, [iq[2 * off: 2 * (off + m)] for off, m in blocks], many,
-                       _group_probes(nch))
+    sc.same_bits(one, many)
+    sc.against_oracle(sc.ProbeOracle(oracle, fs, crate, arate, ifs, l2), host_blocks, many,
+                      sc.group_probes(nch), sc.covers_modes_in_groups(nch))
 
 
 @pytest.mark.parametrize("l2,pd2", [(128, 5), (256, 2)])
@@ -251,24 +143,16 @@ def test_an_audio_passband_per_receiver_and_setters_between_blocks(dev, oracle, 
     lane groups 1 and 2 share one filter each and read it through the scalar cache (uni2 set).  A retune and a change of
     mode between blocks close the launch at their block boundary, and the next block opens another -- the counts of
     test_gpu_stream_filters.test_filter_setters_mid_stream."""
-    import torch
     fs, crate = DECIMATION_RATES[pd2]
     arate, nch, nblk = crate // pd2, 130, 6
     n = _k2_for(l2, pd2, 60) * pd2 * (fs // crate)
-    ifs = _spread_ifs(fs, nch)
-    _, apb = _passbands(fs, crate, arate)
+    ifs = sc.spread_ifs(fs, nch)
+    _, apb = sc.passbands(fs, crate, arate)
     apbs = [apb // 2 if c < 32 else apb for c in range(nch)]
     assert oracle.lowpass_maxbin_n(l2, apb // 2, crate) >= 1
     assert not np.array_equal(oracle.lowpass_design(apb // 2, crate, l2), oracle.lowpass_design(apb, crate, l2))
     retuned, remoded = 70, 9                     # lane group 1 (shared filter) and lane group 0 (per-lane taps)
-    iq = synth.fm_stream(nblk * n, fs, _carriers(ifs), amp=0.1)
-    x = torch.from_numpy(iq).cuda()
-    torch.cuda.synchronize()
-    blocks = [(b * n, n) for b in range(nblk)]
-    views = [x[2 * off: 2 * (off + m)] for off, m in blocks]
-
-    def submit(t, b, off, m):
-        t.submit_device(views[b], m)
+    host_blocks, blocks, submit = sc.device_stream(fs, ifs, n, nblk)
 
     def run(stream):
         seen = {}
@@ -290,11 +174,12 @@ def test_an_audio_passband_per_receiver_and_setters_between_blocks(dev, oracle, 
     assert seen[2] == (True, 1, 2), seen            # blocks 0, 1: one launch
     assert seen[4] == (True, 2, 4), seen            # blocks 2, 3: the retune closed it, block 2 opened the second
     assert many["info"] == (True, 3, 6), many["info"]   # blocks 4, 5: behind the change of mode, a third
-    _same_bits(one, many)
-    probes = [c for c in _group_probes(nch) if c not in (retuned, remoded)]
+    sc.same_bits(one, many)
+    probes = [c for c in sc.group_probes(nch) if c not in (retuned, remoded)]
     assert {apbs[c] for c in probes} == {apb // 2, apb}
-    _against_the_chain(oracle, fs, crate, arate, ifs, l2, [iq[2 * off: 2 * (off + m)] for off, m in blocks], many, probes,
-                       apbs=apbs, every_group=False)
+    # (no coverage condition beyond the one above: the two receivers left out were their lane group's probes of a demodulator)
+    sc.against_oracle(sc.ProbeOracle(oracle, fs, crate, arate, ifs, l2, apbs=apbs),
+                      host_blocks, many, probes)
 
 
 def test_long_audio_filter_streams_byte_blocks(dev, oracle):
@@ -304,10 +189,7 @@ def test_long_audio_filter_streams_byte_blocks(dev, oracle):
     _stream_vs_blocks(dev, oracle, 128, fs, crate, crate // 8, 70, 100 * 8 * (fs // crate), 4, (True, 1, 4), u8=True)
 
 
-# audio taps: (audio decimation, receivers, distinct channel passbands per lane group, how they are laid out)
-MIXED_CHANNEL_FILTERS = {128: [(5, 130, 4, "spread"), (10, 70, 3, "staggered"), (1, 200, 2, "spread")],
-                         256: [(3, 130, 4, "staggered"), (1, 70, 2, "spread"), (2, 200, 3, "spread")]}
-MIXED_CASES = [(l2,) + c for l2 in sorted(MIXED_CHANNEL_FILTERS) for c in MIXED_CHANNEL_FILTERS[l2]]
+MIXED_CASES = [(l2,) + c for l2 in sorted(sc.LONG_MIXED_FILTERS) for c in sc.LONG_MIXED_FILTERS[l2]]
 
 
 @pytest.mark.parametrize("l2,pd2,nch,k,layout", MIXED_CASES, ids=[f"L2={c[0]}-PD2={c[1]}-{c[3]}-filters" for c in MIXED_CASES])
@@ -316,34 +198,25 @@ def test_long_audio_filter_with_channel_passbands_per_receiver(dev, oracle, l2, 
     (receiverhandler.cxx:130-137; tests/test_gpu_stream_filters.py's layouts) on a tuner whose audio filters have 128 or
     256 taps -- a window copy per channel filter in the DDC waves, the long window in the post stage.  One launch, the
     bits of a launch per block, every distinct channel passband probed against the oracle's chain."""
-    import torch
-    from test_gpu_stream_filters import _pb, _sets_per_group, _spread, _staggered
     fs, crate = DECIMATION_RATES[pd2]
     arate, nblk = crate // pd2, 4
-    bins = (_spread if layout == "spread" else _staggered)(nch, k)
-    sets = _sets_per_group(bins)
+    bins = (spread if layout == "spread" else staggered)(nch, k)
+    sets = sets_per_group(bins)
     assert max(sets) == k > 1 and (layout == "spread" or len(set(sets)) > 1), sets
-    cpbs = [_pb(fs, m) for m in bins]
+    cpbs = [pb(fs, m) for m in bins]
     n = _k2_for(l2, pd2, 60) * pd2 * (fs // crate)
-    ifs = _spread_ifs(fs, nch)
-    iq = synth.fm_stream(nblk * n, fs, _carriers(ifs), amp=0.1)
-    x = torch.from_numpy(iq).cuda()
-    torch.cuda.synchronize()
-    blocks = [(b * n, n) for b in range(nblk)]
-    views = [x[2 * off: 2 * (off + m)] for off, m in blocks]
-
-    def submit(t, b, off, m):
-        t.submit_device(views[b], m)
+    ifs = sc.spread_ifs(fs, nch)
+    host_blocks, blocks, submit = sc.device_stream(fs, ifs, n, nblk)
 
     one = _play_long(dev, fs, crate, arate, ifs, l2, blocks, False, submit, cpbs=cpbs)
     many = _play_long(dev, fs, crate, arate, ifs, l2, blocks, True, submit, cpbs=cpbs)
     assert one["info"] == (False, 0, 0)
     assert many["info"] == (True, 1, nblk), many["info"]
-    _same_bits(one, many)
-    probes = _group_probes(nch)
+    sc.same_bits(one, many)
+    probes = sc.group_probes(nch)
     for m in sorted(set(bins)):                        # every distinct channel passband, by a linear demodulator too
         probes += [c for c in range(nch) if bins[c] == m and c % 4 != 0][:1]
     probes = sorted(set(probes))
     assert {bins[c] for c in probes} == set(bins)
-    _against_the_chain(oracle, fs, crate, arate, ifs, l2, [iq[2 * off: 2 * (off + m)] for off, m in blocks], many, probes,
-                       cpbs=cpbs)
+    sc.against_oracle(sc.ProbeOracle(oracle, fs, crate, arate, ifs, l2, cpbs=cpbs),
+                      host_blocks, many, probes, sc.covers_modes_in_groups(nch))

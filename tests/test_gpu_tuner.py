@@ -1,22 +1,6 @@
 """-m gpu: the fused per-tuner path (wr_tuner_*) against the oracle's Receiver chains.
 
-Tolerances (float32, |x| <= 1):
-  WR_NCO_EXACT  channel-filter IQ is BIT-EXACT (same table, same unfused operations in the
-                same order); AM/USB/LSB demod and audio bit-exact; FM within FM_ATOL.
-  WR_NCO_SPLIT  the LO comes from the two-level table: it differs from the reference's
-                table entry by <= 3.5e-7 (the reference table itself carries 2.4e-7 of
-                argument-rounding noise) and the taps are accumulated with FMAs, so
-                channel IQ is within IQ_ATOL = 1e-6 absolute; FM audio on channels
-                that hold a carrier within AUDIO_ATOL = 1e-5, and on EVERY channel -- noise-only
-                ones too, where FM is ill-conditioned -- within what the channel's
-                own IQ difference allows: per demod frame 1.25 * (|dz[k]|/|z[k]| + |dz[k-1]|/|z[k-1]|)
-                / (2 pi) + 2.4e-7 cycles, through the audio filter's |taps| (tests/fm_bound.py;
-                the bound itself is tested on the CPU in tests/test_fm_bound.py).
-  WR_NCO_ROTATE (default) the same table index per frame; each LO value is the anchor's turned
-                by a product of correctly rounded turns (Horner recurrence): same tolerances as
-                SPLIT, measured 1.3e-7 on channel IQ.
-In every mode the integer NCO phase is exact and a frame's bits do not depend on how the stream
-is cut into blocks.
+The tolerances (FM_ATOL, IQ_ATOL, AUDIO_ATOL) and their derivation per NCO mode: tests/tunercases.py.
 """
 import numpy as np
 import pytest
@@ -24,12 +8,9 @@ import pytest
 from webradio_amd import capi, synth
 from webradio_amd.device import Tuner
 import fm_bound
+from tunercases import AUDIO_ATOL, FM_ATOL, IQ_ATOL
 
 pytestmark = pytest.mark.gpu
-
-FM_ATOL = 2.4e-7
-IQ_ATOL = 1e-6
-AUDIO_ATOL = 1e-5
 
 MODES = [capi.WR_AM, capi.WR_FM, capi.WR_USB, capi.WR_LSB]
 

@@ -12,7 +12,7 @@ import launch_plan
 import specavg_np as sa
 import wr_oracle as oracle
 from flat_spectrum import MASK_OUT_SHARE, flat, interleaved
-from test_gpu_spectrum import DB_ATOL
+from speccases import DB_ATOL
 from webradio_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

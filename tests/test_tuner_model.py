@@ -7,10 +7,7 @@ import numpy as np
 
 import tuner_model as tm
 from tuner_model import AM, FM, LSB, USB
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+from tunercases import bits_f32
 
 
 # ---- the scripts ----------------------------------------------------------------------------------------------------------------
@@ -216,7 +213,7 @@ def test_cut_invariance_of_the_model():
     for cuts in ([5, 11, 7, 9, 16], [16, 3, 13, 2, 1, 13], [1, 15, 16, 10, 6]):
         parts, m = _play_cuts(cuts, iq)
         for c in (0, 2, 3, 4):
-            assert np.array_equal(_bits(parts[c]), _bits(whole[c])), (cuts, c)
+            assert np.array_equal(bits_f32(parts[c]), bits_f32(whole[c])), (cuts, c)
         assert np.abs(parts[1] - whole[1]).max() <= m.fm_tolerance(1)
         for c in range(5):
             assert m.phase(c) == m0.phase(c) and m.get_agc(c) == m0.get_agc(c)
@@ -237,9 +234,9 @@ def test_reset_equals_fresh():
         rx.s.phase = phases[c]
         rx.s.prev_i, rx.s.prev_q = prevs[c]
         wa, wc, _ = rx.run(iq[2 * 20 * Q:])
-        assert np.array_equal(_bits(m.chan_iq(c)), _bits(wc)), c
+        assert np.array_equal(bits_f32(m.chan_iq(c)), bits_f32(wc)), c
         if c in (1, 4):                                                   # no squelch, af_gain or AGC: the scale alone
-            assert np.array_equal(_bits(m.audio(c)), _bits(wa * np.float32(32768.0))), c
+            assert np.array_equal(bits_f32(m.audio(c)), bits_f32(wa * np.float32(32768.0))), c
     # ... and the whole receiver, squelch, AGC (from floor again) and af_gain included, is a fresh model's given the same two
     m2 = _model()
     for c in range(5):
@@ -247,7 +244,7 @@ def test_reset_equals_fresh():
         m2.rxs[c].rx.s.prev_i, m2.rxs[c].rx.s.prev_q = prevs[c]
     m2.submit(iq[2 * 20 * Q:])
     for c in range(5):
-        assert np.array_equal(_bits(m.audio(c)), _bits(m2.audio(c))), c
+        assert np.array_equal(bits_f32(m.audio(c)), bits_f32(m2.audio(c))), c
         assert m.get_agc(c) == m2.get_agc(c)
     assert m.get_agc(2)[0] is True and m.get_agc(0)[0] is True
 
@@ -257,10 +254,10 @@ def test_agc_off_changes_nothing():
     with_agc, m = _play_cuts([16, 16, 16], iq, agc=True)
     without, _ = _play_cuts([16, 16, 16], iq, agc=False)
     for c in (1, 3, 4):                                                   # never had an AGC
-        assert np.array_equal(_bits(with_agc[c]), _bits(without[c])), c
-    assert not np.array_equal(_bits(with_agc[2]), _bits(without[2]))      # the AGC did something
-    assert not np.array_equal(_bits(with_agc[0][:32]), _bits(without[0][:32]))
-    assert np.array_equal(_bits(with_agc[0][32:]), _bits(without[0][32:]))   # off from frame 32: the plain receiver's bits
+        assert np.array_equal(bits_f32(with_agc[c]), bits_f32(without[c])), c
+    assert not np.array_equal(bits_f32(with_agc[2]), bits_f32(without[2]))      # the AGC did something
+    assert not np.array_equal(bits_f32(with_agc[0][:32]), bits_f32(without[0][:32]))
+    assert np.array_equal(bits_f32(with_agc[0][32:]), bits_f32(without[0][32:]))   # off from frame 32: the plain receiver's bits
     assert m.get_agc(0)[0] is False and m.get_agc(2)[0] is True
 
 
@@ -271,11 +268,11 @@ def test_the_model_mends_what_a_change_of_block_size_breaks():
     whole = rx.run(iq)[0]
     rx = tm.oracle.Receiver(tm.FS, IFS[2], 128_000, tm.CHAN_RATE, USB, tm.AUDIO_PASSBAND, tm.CHAN_RATE // D2)
     bare = np.concatenate([rx.run(iq[: 2 * 20 * Q])[0], rx.run(iq[2 * 20 * Q:])[0]])
-    assert not np.array_equal(_bits(bare), _bits(whole))
+    assert not np.array_equal(bits_f32(bare), bits_f32(whole))
     m = tm.TunerModel(tm.FS, 1.0)
     m.add(0, 0, IFS[2], 128_000, tm.CHAN_RATE, USB, tm.AUDIO_PASSBAND, tm.CHAN_RATE // D2)
     got = []
     for a, b in ((0, 20), (20, 32)):
         m.submit(iq[2 * a * Q: 2 * b * Q])
         got.append(m.audio(0))
-    assert np.array_equal(_bits(np.concatenate(got)), _bits(whole))
+    assert np.array_equal(bits_f32(np.concatenate(got)), bits_f32(whole))

@@ -16,6 +16,7 @@ os.environ.setdefault("WEBRADIO_QUIET", "1")
 
 import wr_oracle as o  # noqa: E402
 import refcases  # noqa: E402
+import tunercases  # noqa: E402
 from webradio_amd import capi  # noqa: E402
 from webradio_amd.device import Device, Tuner, Spectrum  # noqa: E402
 
@@ -61,22 +62,10 @@ def main():
         parts = [rx.run(iq[2 * n * b: 2 * n * (b + 1)]) for b in range(c["blocks"])]
         rows = [[np.concatenate([p[i] for p in parts]) for i in range(3)]]
         for nco in (capi.WR_NCO_EXACT, capi.WR_NCO_ROTATE):
-            t = Tuner(dev, c["fs"], 1, n, nco)
-            ch = t.add_receiver(c["if_hz"], c["cpb"], c["crate"], c["mode"], c["apb"], c["arate"])
-            t.keep_stages(capi.WR_STAGE_DEMOD)
-            a, z, d = [], [], []
-            for b in range(c["blocks"]):
-                t.submit_host(iq[2 * n * b: 2 * n * (b + 1)])
-                z.append(t.fetch(ch, capi.WR_STAGE_CHAN_IQ, 2 * n))
-                d.append(t.fetch(ch, capi.WR_STAGE_DEMOD, n))
-                a.append(t.fetch(ch, capi.WR_STAGE_AUDIO, n))
-            t.destroy()
-            rows.append([np.concatenate(a), np.concatenate(z), np.concatenate(d)])
-        sys.path.insert(0, os.path.join(ROOT, "tests"))
-        import test_gpu_reference_pin as pin
-        s_audio, s_chan = pin._hip_chain_stream(dev, c, iq)
+            rows.append(list(tunercases.hip_chain(dev, c, iq, nco)))
+        s_audio, s_chan = tunercases.hip_chain_stream(dev, c, iq)
         stream_txt = "stream (k_tuner_stream, blocks of %d): last block's IQ %.1e, audio %.1e" % (
-            pin._stream_cut(c), np.abs(s_chan - w[1][-s_chan.size:]).max(), np.abs(s_audio - w[0]).max())
+            tunercases.stream_cut(c), np.abs(s_chan - w[1][-s_chan.size:]).max(), np.abs(s_audio - w[0]).max())
         txt = "; ".join("%.1e / %.1e / %.1e" % (np.abs(r[1] - w[1]).max(), np.abs(r[2] - w[2]).max(), np.abs(r[0] - w[0]).max())
                         for r in rows)
         print("  %-6s %s   max|audio| %.3f\n         %s" % (name, txt, np.abs(w[0]).max(), stream_txt))
